@@ -12,13 +12,17 @@ independent volumes (weak scaling, no data-path collective); value = all volumes
 Arithmetic of the timed region (`--precision`, default "split"): fp32 tensors, fp32 accumulation, every convolution
 product formed from an EXACT three-way bf16 split of both fp32 operands (six bf16 MFMA products per fp32 product, dropped
 terms <= 2^-24 relative): fp32-equivalent arithmetic on the bf16 matrix pipe; full-size parity under the fp32 bound in
-tests/test_gpu_parity.py::test_full_config3_inverse_vs_oracle.  The same step on the plain fp32 MFMA kernels is measured
-after the timed region and stays on the line as `fp32_mfma`.
+tests/test_gpu_parity.py::test_full_config3_inverse_vs_oracle.  With `--full` the same step on the plain fp32 MFMA kernels
+is measured after the timed region and stays on the line as `fp32_mfma`.
 
-Extra objects on the JSON line: `roofline` / `roofline_second` (the two conv kernels with the largest time share, HIP
-events on the launch stream), `roofline_dwt` (the in-path fused chain kernel that holds the inverse Haar; the standalone
-Haar kernel as a secondary field), `forward_nll` (BASELINE.json configs[3]: batch 4 per GPU, four flow steps + condition
-nets, one all-reduce of the NLL sums at N > 1), `fp32_mfma`, `bf16` (configs[4]), `experiment_train_step`,
+A plain run sets up, warms up, times `--steps` steps and prints the headline line (`value`, `ms_per_step`, ...).
+`--dump-outputs DIR` writes the volume the last timed step reconstructed to DIR/volume.npy (float32; above 8 Mi elements a
+fixed, seeded sample of them in flat-index order), the same array from run to run for the same arguments.
+
+Extra objects on the JSON line, `--full` only: `roofline` / `roofline_second` (the two conv kernels with the largest time
+share, HIP events on the launch stream), `roofline_dwt` (the in-path fused chain kernel that holds the inverse Haar; the
+standalone Haar kernel as a secondary field), `forward_nll` (BASELINE.json configs[3]: batch 4 per GPU, four flow steps +
+condition nets, one all-reduce of the NLL sums at N > 1), `fp32_mfma`, `bf16` (configs[4]), `experiment_train_step`,
 `cpu_baseline` (the CPU oracle timed on this host, rank 0, N = 1 only).
 """
 import argparse
@@ -38,6 +42,9 @@ PEAK_FP32_MFMA_TFLOPS = 157.3
 PEAK_BF16_MFMA_TFLOPS = 2500.0     # dense (AMD's 5 PF headline includes 2:1 sparsity)
 PEAK_HBM_GBS = 8000.0
 SPLIT_PRODUCTS = 6                 # bf16 MFMA products issued per fp32 product in "split" precision
+DUMP_MAX_ELEMS = 1 << 23           # --dump-outputs: at most 8 Mi float32 values (32 MB) per array
+LAST_STEP_SEED = 1234              # device RNG seed of the last timed step (the LRNN's dropout draws): its output does not
+                                   # depend on how many steps ran before it
 
 WINO2D_MIN = 512      # the library's "winograd_2d" default (ops.WINOGRAD_2D_DEFAULT); --wino2d overrides both
 
@@ -185,6 +192,19 @@ def roofline_of(fam, t_ms, n, flops, shapes, products, share=None, all_conv_ms=N
     return r
 
 
+def dump_outputs(path, arrays):
+    """`--dump-outputs`: every array as path/<name>.npy in float32.  An array of more than DUMP_MAX_ELEMS values is written
+    as the fixed sample of DUMP_MAX_ELEMS of them (flat indices from a seeded permutation, in ascending order), so the
+    files of two runs or two builds with the same arguments can be compared value for value."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def launch_command(n, argv, port=None):
     """The command `python bench.py --gpus N ...` turns itself into when it is started without a launcher: the same launch the
     driver uses (one process per GPU, rendezvous on 127.0.0.1 -- the container hostname may not resolve)."""
@@ -220,11 +240,14 @@ def main():
     ap.add_argument("--block-type", default="CAT", choices=("CAT", "GLOW", "AI1", "RNVP", "GIN"),
                     help="coupling block of the flow steps (main.py --INN_block_type; CAT is the reference's default and the "
                          "headline configuration)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-full", action="store_true", help="the complete SURVEY 8d protocol on the full volume "
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure: kernel selection "
+                    "pass and roofline objects, forward NLL leg, the other precisions, training step, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--cpu-baseline-full", action="store_true", help="(--full) the complete SURVEY 8d protocol on the full volume "
                     "(warm-up + median of 3, all cores and 8 threads): several minutes")
     ap.add_argument("--no-lrnn", action="store_true", help="(diagnostic) flows + condition nets only")
-    ap.add_argument("--no-experiment", action="store_true", help="skip the extra measurements after the timed region")
+    ap.add_argument("--no-experiment", action="store_true", help="(--full) skip the extra measurements after the timed region")
     ap.add_argument("--split3x3-min", type=int, default=None, help="(tuning) smallest output-channel count of a 3x3 bank that takes "
                     "the split-bf16 kernel in split / bf16 precision (library default: ops.SPLIT_3X3_MIN_COUT)")
     ap.add_argument("--no-couple-epilogue", action="store_true", help="(ablation, block types other than CAT) sub-networks write "
@@ -242,6 +265,8 @@ def main():
     ap.add_argument("--no-merge-omega", action="store_true", help="(ablation) every condition net runs its own conv1 / downsample launches")
     ap.add_argument("--wino2d", type=int, default=None, help="(tuning) override the 2-D Winograd output-channel threshold (0 = off)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started without a launcher: become the launcher (one rank per GPU over RCCL) BEFORE anything touches the GPU in
@@ -332,23 +357,29 @@ def main():
 
     out = step()                                             # cold pass: weight packing, allocator
     assert out.shape == (B, a.depths, a.side, a.side) and bool(torch.isfinite(out).all())
-    # selection pass: which conv kernels dominate?
-    sel = ops.conv_event_sink = ConvEvents()
-    step()
-    torch.cuda.synchronize()
-    tot = sel.totals()
-    all_conv_ms = sum(t[0] for t in tot.values())
-    ranked = sorted(tot, key=lambda k: -tot[k][0])
-    dom = ranked[0]                                          # the kernel (one instantiation) with the largest time share
-    ops.conv_event_sink = None
-    for _ in range(max(a.warmup - 2, 0)):
+    if a.full:
+        # selection pass: which conv kernels dominate?
+        sel = ops.conv_event_sink = ConvEvents()
         step()
+        torch.cuda.synchronize()
+        tot = sel.totals()
+        all_conv_ms = sum(t[0] for t in tot.values())
+        ranked = sorted(tot, key=lambda k: -tot[k][0])
+        dom = ranked[0]                                      # the kernel (one instantiation) with the largest time share
+        ops.conv_event_sink = None
+        for _ in range(max(a.warmup - 2, 0)):
+            step()
+        sink = ops.conv_event_sink = ConvEvents(only={dom})  # only the dominant kernel carries events in the timed region
+    else:
+        for _ in range(max(a.warmup, 2) - 1):               # as many passes before the timed region as --full makes
+            step()
 
-    sink = ops.conv_event_sink = ConvEvents(only={dom})      # only the dominant kernel carries events in the timed region
     sync_all()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    for _ in range(a.steps - 1):
         step()
+    torch.cuda.manual_seed(LAST_STEP_SEED + rank)
+    last = step()
     sync_all()
     elapsed = time.perf_counter() - t0
     ops.conv_event_sink = None
@@ -356,10 +387,13 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"volume": last})
+    del last
 
     # BASELINE.json configs[3] / the metric's second half: forward NLL, batch-sharded, one all-reduce of the NLL sums
     fwd = None
-    if not a.no_experiment and not a.no_lrnn:
+    if a.full and not a.no_experiment and not a.no_lrnn:
         try:
             fwd = forward_nll_leg(CWFA, ops, conv_inn, cond_nets, a, dev, rank, world, sync_all, products)
         except Exception as exc:                    # noqa: BLE001  (after the timed region; must not cost the line)
@@ -367,7 +401,6 @@ def main():
 
     res = None
     if rank == 0:
-        t_dom, n_dom, f_dom, shapes, shape_ms = sink.totals()[dom]
         baseline = json.load(open(os.path.join(ROOT, "BASELINE.json")))
         dtype = {"split": "f32 (storage, accumulation, wavelets, couplings); convolution products on the bf16 matrix cores from an "
                           "exact three-way bf16 split of both fp32 operands, six products per fp32 product: fp32-equivalent; "
@@ -385,61 +418,64 @@ def main():
                             "bf16": "bf16 conv operands (BASELINE.json configs[4]), NOT the fp32 headline"}[a.precision],
             "multi_gpu": ("this line is N = 1; the 1/2/4/8-GPU half of the metric and the RCCL NLL all-reduce are UNMEASURED on hardware "
                           "so far (builders cannot launch multi-GPU runs; `python bench.py --gpus N` starts its own ranks)") if world == 1 else
-                         f"{world} ranks, one per GPU, {'gloo on ONE card (rehearsal)' if rehearse else 'RCCL'}; see forward_nll.nll_check",
+                         f"{world} ranks, one per GPU, {'gloo on ONE card (rehearsal)' if rehearse else 'RCCL'}" +
+                         ("; see forward_nll.nll_check" if a.full else ""),
             "config": {"workload": f"{a.side}x{a.side}x{a.depths} volume, 4-scale CWFA ({a.block_type} blocks, 64 ch) + "
                                    f"{'LRNN' if not a.no_lrnn else 'synthetic low-res (NO LRNN: diagnostic)'} inverse, z=0, "
                                    f"batch {B}/GPU, random-init weights (BASELINE.json configs[2])",
                        "precision": a.precision,
                        "parallelism": f"replicated x{world} (independent volumes per GPU, no collective)"},
-            "roofline": roofline_of(dom, t_dom, n_dom, f_dom, shapes, products, tot[dom][0] / all_conv_ms, all_conv_ms, shape_ms),
             "reference_readme": {"volumes_per_s": 6.25, "note": "README.md:29, unstated CUDA GPU, fp16 autocast; not "
                                  "this fp32 metric, hence vs_baseline is null"},
         }
-        res["roofline"]["traffic"], res["roofline"]["traffic_detail"] = pmc_traffic(dom, a)
-        if len(ranked) > 1:                                        # the runner-up kernel, same definitions, timed in three
-            sink2 = ops.conv_event_sink = ConvEvents(only={ranked[1]})   # extra steps AFTER the timed region (its many small
-            for _ in range(3):                                     # launches would otherwise put event gaps into `value`)
-                step()
-            torch.cuda.synchronize()
-            ops.conv_event_sink = None
-            t2, n2, f2, sh2, sm2 = sink2.totals()[ranked[1]]
-            res["roofline_second"] = roofline_of(ranked[1], t2, n2, f2, sh2, products, tot[ranked[1]][0] / all_conv_ms, shape_ms=sm2)
-            res["roofline_second"]["traffic"], _ = pmc_traffic(ranked[1], a)
-        res["roofline_dwt"] = dwt_roofline(ops, step, a, dev)
-        if fwd is not None:
-            res["forward_nll"] = fwd
-        if world == 1 and not a.no_lrnn and not a.no_experiment:
-            for name, mode in (("fp32_mfma", "fp32"), ("bf16", "bf16"), ("split", "split")):
-                if mode == a.precision:
-                    continue
-                try:                                          # never let a side measurement cost the headline line
-                    ops.set_precision(PREC[mode])
-                    dt = timed(step, max(a.steps // 2, 3))
-                    roof = None
-                    if mode == "bf16":                        # configs[4] carries its own roofline object: dominant kernel of THIS mode
-                        roof = mode_roofline(ops, step, "bf16")
-                    res[name] = {"value": B / dt, "unit": "volumes/s", "ms_per_step": 1e3 * dt, "steps": max(a.steps // 2, 3),
-                                 "note": {"fp32": "the same step on the plain fp32 MFMA kernels (Winograd F(2,3) / F(2x2,3x3)), after the timed region",
-                                          "bf16": "BASELINE.json configs[4]: bf16 conv operands, fp32 accumulation; parity max-rel <= 1e-2, "
-                                                  "L2-rel <= 5e-3 vs the fp32 oracle (tests/test_gpu_parity.py::test_full_config3_inverse_vs_oracle)",
-                                          "split": "fp32-equivalent split-bf16 arithmetic (see --precision)"}[mode]}
-                    if roof is not None:
-                        res[name]["roofline"] = roof
-                except Exception as exc:                      # noqa: BLE001
-                    res[name] = {"error": repr(exc)[:300]}
+        if a.full:
+            t_dom, n_dom, f_dom, shapes, shape_ms = sink.totals()[dom]
+            res["roofline"] = roofline_of(dom, t_dom, n_dom, f_dom, shapes, products, tot[dom][0] / all_conv_ms, all_conv_ms, shape_ms)
+            res["roofline"]["traffic"], res["roofline"]["traffic_detail"] = pmc_traffic(dom, a)
+            if len(ranked) > 1:                                        # the runner-up kernel, same definitions, timed in three
+                sink2 = ops.conv_event_sink = ConvEvents(only={ranked[1]})   # extra steps AFTER the timed region (its many small
+                for _ in range(3):                                     # launches would otherwise put event gaps into `value`)
+                    step()
+                torch.cuda.synchronize()
+                ops.conv_event_sink = None
+                t2, n2, f2, sh2, sm2 = sink2.totals()[ranked[1]]
+                res["roofline_second"] = roofline_of(ranked[1], t2, n2, f2, sh2, products, tot[ranked[1]][0] / all_conv_ms, shape_ms=sm2)
+                res["roofline_second"]["traffic"], _ = pmc_traffic(ranked[1], a)
+            res["roofline_dwt"] = dwt_roofline(ops, step, a, dev)
+            if fwd is not None:
+                res["forward_nll"] = fwd
+            if world == 1 and not a.no_lrnn and not a.no_experiment:
+                for name, mode in (("fp32_mfma", "fp32"), ("bf16", "bf16"), ("split", "split")):
+                    if mode == a.precision:
+                        continue
+                    try:                                          # never let a side measurement cost the headline line
+                        ops.set_precision(PREC[mode])
+                        dt = timed(step, max(a.steps // 2, 3))
+                        roof = None
+                        if mode == "bf16":                        # configs[4] carries its own roofline object: dominant kernel of THIS mode
+                            roof = mode_roofline(ops, step, "bf16")
+                        res[name] = {"value": B / dt, "unit": "volumes/s", "ms_per_step": 1e3 * dt, "steps": max(a.steps // 2, 3),
+                                     "note": {"fp32": "the same step on the plain fp32 MFMA kernels (Winograd F(2,3) / F(2x2,3x3)), after the timed region",
+                                              "bf16": "BASELINE.json configs[4]: bf16 conv operands, fp32 accumulation; parity max-rel <= 1e-2, "
+                                                      "L2-rel <= 5e-3 vs the fp32 oracle (tests/test_gpu_parity.py::test_full_config3_inverse_vs_oracle)",
+                                              "split": "fp32-equivalent split-bf16 arithmetic (see --precision)"}[mode]}
+                        if roof is not None:
+                            res[name]["roofline"] = roof
+                    except Exception as exc:                      # noqa: BLE001
+                        res[name] = {"error": repr(exc)[:300]}
+                    finally:
+                        ops.set_precision(PREC[a.precision])
+                try:
+                    res["experiment_train_step"] = train_experiment(conv_inn, cond_nets, dev, a, max(a.steps // 4, 3), ops)
+                except Exception as exc:                          # noqa: BLE001
+                    res["experiment_train_step"] = {"error": repr(exc)[:300]}
                 finally:
                     ops.set_precision(PREC[a.precision])
-            try:
-                res["experiment_train_step"] = train_experiment(conv_inn, cond_nets, dev, a, max(a.steps // 4, 3), ops)
-            except Exception as exc:                          # noqa: BLE001
-                res["experiment_train_step"] = {"error": repr(exc)[:300]}
-            finally:
-                ops.set_precision(PREC[a.precision])
-        if world == 1 and not a.no_cpu_baseline and not a.no_lrnn and a.block_type == "CAT":
-            try:
-                res["cpu_baseline"] = cpu_baseline(conv_inn, cond_nets, cond_input, mean_cache, a.cpu_baseline_full)
-            except Exception as exc:                          # noqa: BLE001  (host trouble must not lose the GPU measurement)
-                res["cpu_baseline"] = {"value": None, "unit": "volumes/s", "cores": 0, "kind": "port", "sample": "failed: " + repr(exc)[:200]}
+            if world == 1 and not a.no_cpu_baseline and not a.no_lrnn and a.block_type == "CAT":
+                try:
+                    res["cpu_baseline"] = cpu_baseline(conv_inn, cond_nets, cond_input, mean_cache, a.cpu_baseline_full)
+                except Exception as exc:                          # noqa: BLE001  (host trouble must not lose the GPU measurement)
+                    res["cpu_baseline"] = {"value": None, "unit": "volumes/s", "cores": 0, "kind": "port", "sample": "failed: " + repr(exc)[:200]}
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()

@@ -43,7 +43,7 @@ import numpy as np
 
 warnings.filterwarnings("ignore")
 REF = "/root/reference"
-# CWFA_GOLDEN_OUT: write somewhere else (tests/test_make_golden.py regenerates into a temp dir and compares)
+# CWFA_GOLDEN_OUT: write somewhere else (regenerate into a temp dir and compare with tests/golden)
 OUT = os.environ.get("CWFA_GOLDEN_OUT") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
 
 

@@ -1866,7 +1866,7 @@ def test_bench_line_contract_at_a_small_size(extra):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-lrnn", "--side", "128", "--depths", "32", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-experiment", *extra], capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-experiment", *extra], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -1879,6 +1879,37 @@ def test_bench_line_contract_at_a_small_size(extra):
     rf = d["roofline"]
     assert rf["bound"] == "mfma" and 0 < rf["frac"] <= 1.0 and rf["unit"] == "TFLOP/s" and rf["achieved"] / rf["peak"] == pytest.approx(rf["frac"])
     assert d["roofline_dwt"]["bound"] == "hbm" and 0 < d["roofline_dwt"]["frac"] <= 1.0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) prints the headline line alone, runs exactly --steps timed steps and, with
+    --dump-outputs, writes the volume of its last timed step: float32, the workload's shape, finite, and the same values as
+    the last timed step of a --full run of the same arguments (the extra passes of --full do not change what is dumped)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    args = [sys.executable, os.path.join(root, "bench.py"), "--no-lrnn", "--side", "128", "--depths", "32", "--steps", "3", "--warmup", "2"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-experiment"])):
+        r = subprocess.run([*args, *extra, "--dump-outputs", str(tmp_path / mode)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        js = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(js) == 1, r.stdout[-2000:]
+        lines[mode] = json.loads(js[0])
+    d = lines["plain"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["unit"] == "volumes/s" and d["higher_is_better"] is True
+    assert d["value"] == pytest.approx(1e3 / d["ms_per_step"])
+    for k in ("roofline", "roofline_second", "roofline_dwt", "forward_nll", "fp32_mfma", "bf16", "experiment_train_step", "cpu_baseline"):
+        assert k not in d, k
+    assert "roofline" in lines["full"] and "roofline_dwt" in lines["full"]
+    assert sorted(os.listdir(tmp_path / "plain")) == ["volume.npy"]
+    v = np.load(tmp_path / "plain" / "volume.npy")
+    assert v.dtype == np.float32 and v.shape == (1, 32, 128, 128) and np.isfinite(v).all()
+    assert_close(torch.from_numpy(v), torch.from_numpy(np.load(tmp_path / "full" / "volume.npy")), 1e-6, "plain vs --full dump")
 
 
 # ------------------------------------------------------------------------------------------------ API surface not on the plan path

@@ -277,3 +277,23 @@ def test_bench_self_launch_plumbing(monkeypatch, tmp_path):
         bench.main()
     except SystemExit as e:
         assert "must agree" in str(e.code) and not seen
+
+
+def test_bench_dump_outputs_is_float32_bounded_and_seeded(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: a small array is written whole in float32; an array above the cap becomes the same fixed
+    sample (ascending flat indices of a seeded permutation) on every call, so two runs can be compared value for value."""
+    import importlib
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    small = torch.arange(24, dtype=torch.float64).reshape(2, 3, 4)
+    big = torch.randn(3, 20, 30, generator=torch.Generator().manual_seed(2))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "volume": big})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (2, 3, 4) and np.array_equal(s, small.numpy().astype(np.float32))
+    v = np.load(tmp_path / "a" / "volume.npy")
+    assert v.dtype == np.float32 and v.shape == (1000,)
+    assert np.array_equal(v, np.load(tmp_path / "b" / "volume.npy"))
+    flat = big.reshape(-1).numpy()
+    idx =torch.randperm(big.numel(), generator=torch.Generator().manual_seed(0))[:1000].sort().values.numpy()
+    assert np.array_equal(v, flat[idx])

@@ -72,7 +72,7 @@ def main():
         return read_smi()
 
     idle = [sample() for _ in range(5)]
-    child = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-experiment", "--steps", "500",
+    child = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-experiment", "--steps", "500",
                               "--warmup", "5", *sys.argv[1:]], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
     rows, t0 = [], time.time()
     while child.poll() is None:

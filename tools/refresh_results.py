@@ -39,7 +39,7 @@ CPU baseline (oracle, torch CPU): {cb['value']:.4f} volumes/s on {cb['cores']} t
 
 Dominant kernel traffic (`profiles/{TAG}_pmc_traffic.json`): {(r['traffic'] or 0) / 1e6:.0f} MB per launch HBM-side (FETCH_SIZE×2 + WRITE_SIZE) vs {r['algorithmic_bytes_per_launch'] / 1e6:.0f} MB algorithmic (input once + output once) -- 805 MB before the XCD-aware block order: what is left is the first read of an input tile by the XCD that owns it plus the 10/8 × 34/32 halo where it misses that L2; the layer kernel {(r2['traffic'] or 0) / 1e6:.0f} MB vs {r2['algorithmic_bytes_per_launch'] / 1e6:.0f} MB.  `avg_launch_ms` of `{dom_name}`: {r['avg_launch_ms']:.3f} (HIP events inside bench.py's timed region) vs {avg_dom:.3f} (rocprofv3 `AverageNs` of the same kernel name over the whole profiled run); of `{r2['kernel'].split(' (')[0]}` (all map-layout instantiations): {r2['avg_launch_ms']:.4f} vs {avg_r2:.4f}.
 
-Per-kernel time per volume (rocprofv3 `--kernel-trace --stats` over `bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-experiment`, `profiles/{TAG}_bench_kernel_stats.csv`; {steps} volumes in the trace):
+Per-kernel time per volume (rocprofv3 `--kernel-trace --stats` over `bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-experiment`, `profiles/{TAG}_bench_kernel_stats.csv`; {steps} volumes in the trace):
 {table}
 <!-- RESULTS:END -->"""
 p = os.path.join(ROOT, "DESIGN.md")
