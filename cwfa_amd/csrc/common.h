@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <utility>
 #include "cwfa_hip.h"
 
 void cwfa_set_error(const char* fmt, ...);
@@ -22,6 +23,14 @@ void cwfa_set_error(const char* fmt, ...);
             return CWFA_E_HIP;                                               \
         }                                                                    \
     } while (0)
+
+// vector types of the kernels; lds_ptr: an LDS address (the LDS-DMA destination of __builtin_amdgcn_raw_ptr_buffer_load_lds)
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) void* lds_ptr;
 
 static inline bool cwfa_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -52,12 +61,18 @@ __device__ __forceinline__ float cwfa_row16_sum(float v) {
     return v;
 }
 
+// Buffer descriptor of `bytes` bytes from `base` (stride 0: raw byte offsets, range-checked against `bytes`; out-of-range
+// loads return 0).  Word 3 = 0x00020000: DATA_FORMAT (bits 18:15) = 4, 32-bit, no swizzle, no index stride -- the
+// buffer-descriptor recipe of the CDNA HIP programming guide (T8, T20).  Build it from wave-uniform values only.  (A macro:
+// behind an inline function the compiler orders the scalar setup of some descriptors differently.)
+#define CWFA_RSRC(base, bytes) \
+    __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(static_cast<const void*>(base)), 0, (bytes), 0x00020000)
+
 // 16-byte buffer store with an SGPR offset.  gfx950: the store keeps reading its data registers after issue, also in this
 // addressing form, which LLVM's hazard rule exempts ("only if soffset is not a register"): a VALU write into the tuple right
 // behind it corrupted the stored data.  EVERY 16-byte buffer store of the library goes through
 // this helper, which carries the wait states and keeps the scheduler from moving anything across.
-typedef unsigned cwfa_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void cwfa_buffer_store_b128(cwfa_u32x4 data, __amdgpu_buffer_rsrc_t rsrc, unsigned voffset, int soffset) {
+__device__ __forceinline__ void cwfa_buffer_store_b128(u32x4 data, __amdgpu_buffer_rsrc_t rsrc, unsigned voffset, int soffset) {
     __builtin_amdgcn_raw_buffer_store_b128(data, rsrc, voffset, soffset, 0);
     asm volatile("s_nop 1");
     __builtin_amdgcn_sched_barrier(0);
@@ -133,3 +148,57 @@ __device__ __forceinline__ float cwfa_act(float v, int act, float alpha) {
         default: return v;
     }
 }
+
+// compile-time activation (the epilogues specialised per activation); same cases as cwfa_act
+template <int ACT>
+__device__ __forceinline__ float cwfa_act_ct(float v, float alpha) {
+    if constexpr (ACT == CWFA_ACT_ELU) return cwfa_elu(v);
+    if constexpr (ACT == CWFA_ACT_PRELU) return v > 0.f ? v : alpha * v;
+    if constexpr (ACT == CWFA_ACT_GELU) return cwfa_gelu(v);
+    if constexpr (ACT == CWFA_ACT_RELU) return v > 0.f ? v : 0.f;
+    return v;
+}
+
+// the soft clamp of the coupling blocks (coupling_layers.py:50-60): the affine apply / chain kernels (elementwise.hip) and the
+// coupling epilogue of the split 3x3 (conv_split3x3.hip) both go through this one definition -- their parity rests on it
+__device__ __forceinline__ float cwfa_soft_clamp(float a, int kind, float clamp) {
+    switch (kind) {
+        case CWFA_CLAMP_ATAN: return clamp * (0.636f * cwfa_atan(a));
+        case CWFA_CLAMP_TANH: return clamp * cwfa_tanh(a);
+        case CWFA_CLAMP_SIGMOID: return clamp * (2.f * (1.f / (1.f + expf(-a)) - 0.5f));
+        default: return clamp * a;
+    }
+}
+
+// a compile-time int argument (read as decltype(k)::value), and f(cwfa_ic<i>{}) for i = 0 .. N-1 unrolled at compile time
+template <int K>
+using cwfa_ic = std::integral_constant<int, K>;
+template <class F, int... I>
+__device__ __forceinline__ void cwfa_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+    (f(cwfa_ic<I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void cwfa_static_for(F&& f) {
+    cwfa_static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// channel held by accumulator register r of a 32x32 fp32 MFMA tile in lane half kh (C/D layout of v_mfma_f32_32x32x2_f32)
+__device__ __forceinline__ int cwfa_acc_row(int r, int kh) { return (r & 3) + 8 * (r >> 2) + 4 * kh; }
+
+// The three-way bf16 split of the fp32-equivalent kernels: v = a1 + a2 + a3 EXACTLY (24 significand bits; each difference is
+// exact: the subtrahend is the minuend rounded to 8 significant bits).  SIX = false: the leading piece only (plain bf16
+// operands, `split_products` = 1); a2 and a3 are then not written.
+template <bool SIX>
+__device__ __forceinline__ void cwfa_split3(float v, __bf16& a1, __bf16& a2, __bf16& a3) {
+    a1 = (__bf16)v;
+    if constexpr (SIX) {
+        const float r1 = v - (float)a1;
+        a2 = (__bf16)r1;
+        const float r2 = r1 - (float)a2;
+        a3 = (__bf16)r2;
+    }
+}
+
+// c += a . b on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16), and a scheduling barrier no instruction is moved across
+#define CWFA_MFMA(a, b, c) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
+#define CWFA_FENCE() __builtin_amdgcn_sched_barrier(0)

@@ -20,33 +20,6 @@
 
 #include <string.h>
 #include <type_traits>
-#include <utility>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// tuning knobs (defaults = shipped configuration; tools/conv_tune.py builds variants with -D overrides)
-#ifndef CWFA_MINW
-#define CWFA_MINW 1
-#endif
-#ifndef CWFA_PREFETCH
-#define CWFA_PREFETCH 1
-#endif
-#ifndef CWFA_WN64
-#define CWFA_WN64 8
-#endif
-#ifndef CWFA_WM128
-#define CWFA_WM128 2
-#endif
-#ifndef CWFA_WN128
-#define CWFA_WN128 4
-#endif
-#ifndef CWFA_CK3
-#define CWFA_CK3 8
-#endif
-#ifndef CWFA_CK1
-#define CWFA_CK1 16
-#endif
 
 namespace {
 
@@ -117,17 +90,6 @@ __device__ __forceinline__ Tile make_tile(const ConvParams& p) {
 // by the last MFMAs of chunk c.  Global reads go through buffer descriptors: the per-lane byte offset is computed once,
 // the per-chunk part is the scalar soffset, and padding (outside the image, channels >= Cin) is an out-of-range offset
 // that the hardware range check returns as 0.0.
-template <int K>
-using sc_int = std::integral_constant<int, K>;
-template <class F, int... S>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, S...>) {
-    (f(sc_int<S>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 template <class C, bool PRO>
 __device__ __forceinline__ void conv_mainloop(const ConvParams& p, const Tile& t, float* smem, f32x16 (&acc)[C::MT][C::NT]) {
     const int tid = threadIdx.x;
@@ -159,17 +121,12 @@ __device__ __forceinline__ void conv_mainloop(const ConvParams& p, const Tile& t
     const bool cat = !PRO && p.o.in_cat != nullptr;
     const int n1 = cat ? p.o.in_cat_from / C::CK : p.nchunks;
     const int xbytes = (int)((int64_t)(cat ? p.o.in_cat_c1 : p.Cin) * HW * 4);
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (int64_t)t.b * p.x_bs), 0, xbytes, 0x00020000);
-    const auto rx2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(cat ? p.o.in_cat + (int64_t)t.b * p.o.in_cat_bs : p.x), 0,
-                                                       cat ? (int)((int64_t)(p.Cin - p.o.in_cat_from) * HW * 4) : 0, 0x00020000);
-    const auto ra = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(has_add ? p.o.in_add + (int64_t)t.b * p.o.in_add_bs : p.x), 0, has_add ? xbytes : 0, 0x00020000);
-    const auto rsc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(has_aff ? p.o.in_scale + (int64_t)t.b * p.o.in_affine_bs : p.x), 0, has_aff ? p.Cin * 4 : 0, 0x00020000);
-    const auto rsh = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(has_aff ? p.o.in_shift + (int64_t)t.b * p.o.in_affine_bs : p.x), 0, has_aff ? p.Cin * 4 : 0, 0x00020000);
-    const auto rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wp + (int64_t)t.ct * p.nchunks * C::WS), 0,
-                                                      p.nchunks * C::WS * 4, 0x00020000);
+    const auto rx = CWFA_RSRC(p.x + (int64_t)t.b * p.x_bs, xbytes);
+    const auto rx2 = CWFA_RSRC(cat ? p.o.in_cat + (int64_t)t.b * p.o.in_cat_bs : p.x, cat ? (int)((int64_t)(p.Cin - p.o.in_cat_from) * HW * 4) : 0);
+    const auto ra = CWFA_RSRC(has_add ? p.o.in_add + (int64_t)t.b * p.o.in_add_bs : p.x, has_add ? xbytes : 0);
+    const auto rsc = CWFA_RSRC(has_aff ? p.o.in_scale + (int64_t)t.b * p.o.in_affine_bs : p.x, has_aff ? p.Cin * 4 : 0);
+    const auto rsh = CWFA_RSRC(has_aff ? p.o.in_shift + (int64_t)t.b * p.o.in_affine_bs : p.x, has_aff ? p.Cin * 4 : 0);
+    const auto rw = CWFA_RSRC(p.wp + (int64_t)t.ct * p.nchunks * C::WS, p.nchunks * C::WS * 4);
     const int chunk_bytes = (int)(C::CK * HW * 4);
     auto ldf = [](decltype(rx) r, unsigned vo, int so) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0)); };
     auto ldx = [&](decltype(rx) r, unsigned vo, int so) {
@@ -263,7 +220,7 @@ __device__ __forceinline__ void conv_mainloop(const ConvParams& p, const Tile& t
     auto chunk_body = [&](int cur, int chunk, auto morec, auto pfc) {
         constexpr bool more = decltype(morec)::value, pf = decltype(pfc)::value;
         constexpr int ring0 = 0;
-        static_for<NSTEP>([&](auto sc) {
+        cwfa_static_for<NSTEP>([&](auto sc) {
             constexpr int s = decltype(sc)::value;
             if constexpr (s == NSLOT && more) __syncthreads();
             if constexpr (s + DEPTH < NSTEP) {
@@ -279,18 +236,18 @@ __device__ __forceinline__ void conv_mainloop(const ConvParams& p, const Tile& t
             if constexpr (s < NSLOT) {
                 // items [k0, k1) are staged after this step: NITEM items spread evenly over the NSLOT steps
                 constexpr int k0 = s * NITEM / NSLOT, k1 = (s + 1) * NITEM / NSLOT;
-                static_for<k1 - k0>([&](auto jc) {
+                cwfa_static_for<k1 - k0>([&](auto jc) {
                     constexpr int k = k0 + decltype(jc)::value;
-                    if constexpr (more) store_item(sc_int<k>{}, cur ^ 1);
-                    if constexpr (pf) load_item(sc_int<k>{}, chunk + 2);
+                    if constexpr (more) store_item(cwfa_ic<k>{}, cur ^ 1);
+                    if constexpr (pf) load_item(cwfa_ic<k>{}, chunk + 2);
                 });
             }
             __builtin_amdgcn_sched_barrier(0);
         });
     };
 
-    static_for<NITEM>([&](auto kc) { load_item(kc, 0); });
-    static_for<NITEM>([&](auto kc) {
+    cwfa_static_for<NITEM>([&](auto kc) { load_item(kc, 0); });
+    cwfa_static_for<NITEM>([&](auto kc) {
         store_item(kc, 0);
         if (1 < p.nchunks) load_item(kc, 1);
     });
@@ -320,9 +277,6 @@ __device__ __forceinline__ void stg_off(float* base, unsigned byte_off, float v)
     *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_off) = v;
 }
 
-// channel held by accumulator register r of a 32x32 tile in lane half kh (C/D layout of the 32x32 MFMAs)
-__device__ __forceinline__ int acc_row(int r, int kh) { return (r & 3) + 8 * (r >> 2) + 4 * kh; }
-
 // ------------------------------------------------------------------------------------------------ epilogues
 enum { EPI_GENERIC = 0, EPI_NONE, EPI_ELU, EPI_RES_ELU, EPI_PRELU, EPI_RES_PRELU, EPI_GELU_RES, EPI_UP, EPI_NONE_BLK8, EPI_COUNT };
 
@@ -334,15 +288,6 @@ struct EpiTraits {
     static constexpr int ACT2 = EPI == EPI_RES_ELU ? CWFA_ACT_ELU : EPI == EPI_RES_PRELU ? CWFA_ACT_PRELU : CWFA_ACT_NONE;
     static constexpr bool UP = EPI == EPI_UP;
 };
-
-template <int ACT>
-__device__ __forceinline__ float act_ct(float v, float alpha) {
-    if constexpr (ACT == CWFA_ACT_ELU) return cwfa_elu(v);
-    if constexpr (ACT == CWFA_ACT_PRELU) return v > 0.f ? v : alpha * v;
-    if constexpr (ACT == CWFA_ACT_GELU) return cwfa_gelu(v);
-    if constexpr (ACT == CWFA_ACT_RELU) return v > 0.f ? v : 0.f;
-    return v;
-}
 
 template <class C, int EPI>
 __device__ __forceinline__ void epilogue(const ConvParams& p, const Tile& t, f32x16 (&acc)[C::MT][C::NT]) {
@@ -369,7 +314,7 @@ __device__ __forceinline__ void epilogue(const ConvParams& p, const Tile& t, f32
                         }
                 const int row = t.row0 + t.wn * C::NT + n;
                 for (int r = 0; r < 16; ++r) {
-                    const int co = t.ct * C::CT + (t.wm * C::MT + m) * 32 + acc_row(r, t.kh);
+                    const int co = t.ct * C::CT + (t.wm * C::MT + m) * 32 + cwfa_acc_row(r, t.kh);
                     if (co >= p.Cout || row >= p.H || col >= p.W) continue;
                     const int cb = p.o.upshuffle2 ? co >> 2 : co;
                     int64_t o;
@@ -446,7 +391,7 @@ __device__ __forceinline__ void epilogue(const ConvParams& p, const Tile& t, f32
             for (int m = 0; m < C::MT; ++m)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    int co = t.ct * C::CT + (t.wm * C::MT + m) * 32 + acc_row(r, t.kh);
+                    int co = t.ct * C::CT + (t.wm * C::MT + m) * 32 + cwfa_acc_row(r, t.kh);
                     co = co < p.Cout ? co : p.Cout - 1;
                     bias[m][r] = p.o.bias ? p.o.bias[co] : 0.f;
                 }
@@ -454,16 +399,16 @@ __device__ __forceinline__ void epilogue(const ConvParams& p, const Tile& t, f32
             for (int m = 0; m < C::MT; ++m) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int co = t.ct * C::CT + (t.wm * C::MT + m) * 32 + acc_row(r, t.kh);
+                    const int co = t.ct * C::CT + (t.wm * C::MT + m) * 32 + cwfa_acc_row(r, t.kh);
                     if (co >= p.Cout) continue;
 #pragma unroll
                     for (int n = 0; n < C::NT; ++n) {
                         const int row = t.row0 + t.wn * C::NT + n;
                         if (row >= p.H || col >= p.W) continue;
                         const int64_t o = (int64_t)co * HW + (int64_t)row * p.W + col;
-                        float v = act_ct<E::ACT1>(acc[m][n][r] + bias[m][r], alpha);
+                        float v = cwfa_act_ct<E::ACT1>(acc[m][n][r] + bias[m][r], alpha);
                         if constexpr (E::RES) v += rb[o];
-                        yb[o] = act_ct<E::ACT2>(v, alpha);
+                        yb[o] = cwfa_act_ct<E::ACT2>(v, alpha);
                     }
                 }
             }
@@ -472,7 +417,7 @@ __device__ __forceinline__ void epilogue(const ConvParams& p, const Tile& t, f32
 }
 
 template <class C, int EPI, bool PRO>
-__global__ __launch_bounds__(C::NTHREADS, CWFA_MINW) void conv2d_mfma_kernel(ConvParams p) {
+__global__ __launch_bounds__(C::NTHREADS, 1) void conv2d_mfma_kernel(ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const Tile t = make_tile<C>(p);
     f32x16 acc[C::MT][C::NT];
@@ -523,7 +468,7 @@ __global__ __launch_bounds__(CL::NTHREADS, 1) void subnet_layer_kernel(ConvParam
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             // channel = (mo*32 + rc) + 4*kh with rc compile-time: scalar K*HW4 + one per-lane base (oo already has 4*kh)
-            const unsigned K = (unsigned)(mo * 32 + acc_row(r, 0));
+            const unsigned K = (unsigned)(mo * 32 + cwfa_acc_row(r, 0));
             res[r] = ldg_off(xb, K * HW4 + oo[n]) + ldg_off(p.b1x1, K * 4u + (unsigned)t.kh * 16u);
         }
     };
@@ -532,7 +477,7 @@ __global__ __launch_bounds__(CL::NTHREADS, 1) void subnet_layer_kernel(ConvParam
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) b3v[m][r] = ldg_off(p.o.bias, (unsigned)(m * 32 + acc_row(r, 0)) * 4u + (unsigned)t.kh * 16u);
+        for (int r = 0; r < 16; ++r) b3v[m][r] = ldg_off(p.o.bias, (unsigned)(m * 32 + cwfa_acc_row(r, 0)) * 4u + (unsigned)t.kh * 16u);
 
     // stage the 1x1 panel (4096 floats) where the 3x3 weight panel was
     __syncthreads();
@@ -568,7 +513,7 @@ __global__ __launch_bounds__(CL::NTHREADS, 1) void subnet_layer_kernel(ConvParam
                 }
                 if (q > 0 && (j & 1)) {                                 // element j/2 of the previous quarter
                     const int pq = q > 0 ? q - 1 : 0, pmo = pq >> 1, pn = pq & 1, rr = j >> 1;
-                    const unsigned K = (unsigned)(pmo * 32 + acc_row(rr, 0));
+                    const unsigned K = (unsigned)(pmo * 32 + cwfa_acc_row(rr, 0));
                     if (ok[pn]) stg_off(yb, K * HW4 + oo[pn], cwfa_elu(yq[pq][rr] + rq[pq][rr]));
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -576,7 +521,7 @@ __global__ __launch_bounds__(CL::NTHREADS, 1) void subnet_layer_kernel(ConvParam
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {                                      // tail: the last quarter (mo = 1, n = 1)
-        const unsigned K = (unsigned)(32 + acc_row(r, 0));
+        const unsigned K = (unsigned)(32 + cwfa_acc_row(r, 0));
         if (ok[1]) stg_off(yb, K * HW4 + oo[1], cwfa_elu(yq[3][r] + rq[3][r]));
     }
 }
@@ -586,7 +531,7 @@ __global__ __launch_bounds__(256) void pack1x1_kernel(const float* __restrict__ 
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 4096) return;
     const int lane = i & 63, mo = (i >> 6) & 1, kr = i >> 7, m = kr >> 4, r = kr & 15;
-    out[i] = w[(32 * mo + (lane & 31)) * 64 + 32 * m + acc_row(r, lane >> 5)];
+    out[i] = w[(32 * mo + (lane & 31)) * 64 + 32 * m + cwfa_acc_row(r, lane >> 5)];
 }
 
 // ---- weight repack: torch [Cout][Cin][ks][ks] -> [cout tile][chunk][tap][ck][CT]   (zeros beyond Cout / Cin)
@@ -614,15 +559,15 @@ __global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ w, 
 }
 
 // ---- configuration table.  One entry per (ks, Cout class); pack and launch MUST agree, hence one selector.
-typedef Cfg<3, CWFA_CK3, 1, 4, 1, 4> C3_32;                        // Cout <= 32 : 32 ch x 16 rows x 32 cols
-typedef Cfg<3, CWFA_CK3, 2, 2, 1, CWFA_WN64> C3_64;                // Cout <= 64 : 64 ch x 2*WN rows x 32 cols
-typedef Cfg<3, CWFA_CK3, 2, 2, CWFA_WM128, CWFA_WN128> C3_128;     // Cout  > 64 : 64*WM ch x 2*WN rows x 32 cols
-typedef Cfg<1, CWFA_CK1, 1, 4, 1, 4> C1_32;
-typedef Cfg<1, CWFA_CK1, 2, 2, 1, CWFA_WN64> C1_64;
-typedef Cfg<1, CWFA_CK1, 2, 2, CWFA_WM128, CWFA_WN128> C1_128;
-typedef Cfg<1, CWFA_CK1, 1, 4, 1, 4, 4> C1v_32;                           // the same tiles staged 16 bytes per lane
-typedef Cfg<1, CWFA_CK1, 2, 2, 1, CWFA_WN64, 4> C1v_64;
-typedef Cfg<1, CWFA_CK1, 2, 2, CWFA_WM128, CWFA_WN128, 4> C1v_128;
+typedef Cfg<3, 8, 1, 4, 1, 4> C3_32;            // Cout <= 32 : 32 ch x 16 rows x 32 cols
+typedef Cfg<3, 8, 2, 2, 1, 8> C3_64;            // Cout <= 64 : 64 ch x 16 rows x 32 cols
+typedef Cfg<3, 8, 2, 2, 2, 4> C3_128;           // Cout  > 64 : 128 ch x 8 rows x 32 cols
+typedef Cfg<1, 16, 1, 4, 1, 4> C1_32;
+typedef Cfg<1, 16, 2, 2, 1, 8> C1_64;
+typedef Cfg<1, 16, 2, 2, 2, 4> C1_128;
+typedef Cfg<1, 16, 1, 4, 1, 4, 4> C1v_32;       // the same tiles staged 16 bytes per lane
+typedef Cfg<1, 16, 2, 2, 1, 8, 4> C1v_64;
+typedef Cfg<1, 16, 2, 2, 2, 4, 4> C1v_128;
 typedef Cfg<7, 4, 1, 4, 1, 4> C7_32;
 typedef Cfg<7, 4, 2, 2, 1, 8> C7_64;
 
@@ -753,10 +698,10 @@ int fill_params(ConvParams& p, const char* name, const float* x, const float* w_
 //   * weights are split at pack time into [cout tile][chunk of 16 ci][piece][k half][256 cout][8];
 //   * the GEMM kernel moves both with LDS-DMA (buffer_load ... lds, no staging registers, two chunks ahead, three LDS
 //     buffers), block = 256 cout x 8 rows x 32 px, 8 waves of 2 x 4 accumulator tiles, the epilogues of the fp32 path.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef Cfg<1, 16, 2, 4, 4, 2> CS;     // 256 ch x 8 rows x 32 cols, 512 threads (geometry only: staging is its own)
 constexpr int CS_XB = 3 * 2 * 8 * 32 * 16, CS_WB = 3 * 2 * 256 * 16, CS_BUFB = CS_XB + CS_WB;    // bytes per LDS buffer
 
+// cwfa_split3 with the pieces as raw bits (kept apart: on top of cwfa_split3 the two pack kernels compile differently)
 __device__ __forceinline__ void split3(float v, unsigned short (&o)[3]) {
     const __bf16 a1 = (__bf16)v;
     const float r1 = v - (float)a1;
@@ -860,12 +805,9 @@ __global__ __launch_bounds__(512, 1) void conv1x1_split_kernel(SplitParams sp) {
         const int gr = t.row0 + row, gc = t.col0 + px;
         xoff[i] = (gr < p.H && gc < p.W) ? (unsigned)((((int64_t)piece * sp.CG2 + h) * HW + (int64_t)gr * p.W + gc) * 16) : OOB;
     }
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(sp.ws) + (int64_t)t.b * sp.ws_bs),
-                                                      0, (int)sp.ws_bs, 0x00020000);
-    const auto rw = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(p.wp) + (int64_t)t.ct * p.nchunks * CS_WB), 0, p.nchunks * CS_WB, 0x00020000);
+    const auto rx = CWFA_RSRC(reinterpret_cast<const char*>(sp.ws) + (int64_t)t.b * sp.ws_bs, (int)sp.ws_bs);
+    const auto rw = CWFA_RSRC(reinterpret_cast<const char*>(p.wp) + (int64_t)t.ct * p.nchunks * CS_WB, p.nchunks * CS_WB);
     const int xchunk = (int)(2 * HW * 16);
-    typedef __attribute__((address_space(3))) void* lds_ptr;
     auto dma = [&](int chunk, int buf) {          // chunks past the end: out of range, zeros, never read
         char* base = lds + buf * CS_BUFB + wave * 1024;
 #pragma unroll

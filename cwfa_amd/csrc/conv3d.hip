@@ -133,9 +133,6 @@ struct C3M {
     static constexpr int PS = 4, PH = HT + 4, PW = 36, OS = PS * PH * PW;
 };
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4_c3 __attribute__((ext_vector_type(4)));
-
 // batch of tap t in the scatter (found by exhaustive search: 10 of the 12 two-tap registers keep both halves together)
 __host__ __device__ constexpr int c3m_batch(int t) {
     constexpr int F[9] = {0, 2, 1, 2, 1, 1, 2, 1, 0};
@@ -174,7 +171,7 @@ __global__ __launch_bounds__(256) void conv3d_1k1_mfma_kernel(const float* __res
         for (int i = 0; i < NI; ++i)
             if (tid + i * C::NTHREADS < C::XS) Xs[tid + i * C::NTHREADS] = v[i];
     }
-    for (int e = tid; e < C::NWAVES * C::OS / 4; e += C::NTHREADS) reinterpret_cast<f32x4_c3*>(Os)[e] = f32x4_c3{0.f, 0.f, 0.f, 0.f};
+    for (int e = tid; e < C::NWAVES * C::OS / 4; e += C::NTHREADS) reinterpret_cast<f32x4*>(Os)[e] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // operand panels, resident in registers for the whole block.  conv1's bias rides on the unused 28th tap
     // (MFMA 13, k-slot 1: A = b1[k], B = 1).  relp[r] = where accumulator register r of this lane scatters to, relative

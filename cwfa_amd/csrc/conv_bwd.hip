@@ -12,21 +12,9 @@
 // Strips are double-buffered: the next strip's global loads are issued before the 32 k-steps of the current one and
 // stored to the other buffer after them.  Every pixel worker writes its partial filter bank; a second kernel sums the
 // partials in a fixed order, so the result is deterministic (no float atomics).
-#include <type_traits>
 #include "common.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-template <int N, class F, int I = 0>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<N, F, I + 1>(static_cast<F&&>(f));
-    }
-}
-__device__ __forceinline__ int acc_row(int r, int kh) { return (r & 3) + 8 * (r >> 2) + 4 * kh; }
 
 struct WgParams {
     const float* x;
@@ -73,10 +61,8 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_kernel(WgParams p) {
     auto issue = [&](int strip) {
         const int b = strip / (p.sy * p.sx), rem = strip - b * (p.sy * p.sx);
         const int r0 = (rem / p.sx) * 2, c0 = (rem % p.sx) * 32;
-        const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (int64_t)b * p.x_bs + (int64_t)ci0 * HW), 0,
-                                                          (int)((unsigned)min(64, p.Cin - ci0) * HW4), 0x00020000);
-        const auto rd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dy + (int64_t)b * p.dy_bs + (int64_t)co0 * HW), 0,
-                                                          (int)((unsigned)min(64, p.Cout - co0) * HW4), 0x00020000);
+        const auto rx = CWFA_RSRC(p.x + (int64_t)b * p.x_bs + (int64_t)ci0 * HW, (int)((unsigned)min(64, p.Cin - ci0) * HW4));
+        const auto rd = CWFA_RSRC(p.dy + (int64_t)b * p.dy_bs + (int64_t)co0 * HW, (int)((unsigned)min(64, p.Cout - co0) * HW4));
         {   // x, core columns: pair q = sq + 8 j -> ci = q / XR, row = q % XR.  8 is a multiple of XR, so the row (and with it
             // the validity) is the same for every j and the channel advances by 8 / XR: one compare, then one add per load
             // (the out-of-range marker survives the adds: 64 * HW4 < 2^31)
@@ -163,8 +149,8 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_kernel(WgParams p) {
 #pragma unroll
             for (int i = 0; i < C::TAPS; ++i) bv[s & 1][i] = xs[((row + i / KW) * C::XC + col + i % KW) * WG_CHP];
         };
-        fetch(std::integral_constant<int, 0>{});
-        static_for<32>([&](auto sc) {
+        fetch(cwfa_ic<0>{});
+        cwfa_static_for<32>([&](auto sc) {
             constexpr int s = decltype(sc)::value;
             // one operand read of step s + 1 after every MFMA of step s: a burst of reads between two steps would hold the
             // issue port longer than the last MFMA keeps the matrix pipe busy
@@ -198,7 +184,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_kernel(WgParams p) {
     if (ci < p.Cin) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int co = co0 + mt * 32 + acc_row(r, kh);
+            const int co = co0 + mt * 32 + cwfa_acc_row(r, kh);
             if (co < p.Cout) {
 #pragma unroll
                 for (int i = 0; i < C::TAPS; ++i) out[((int64_t)co * p.Cin + ci) * C::TAPS + i] = acc[i][r];
@@ -312,7 +298,6 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_rows_kernel(WgParams p) {
     using namespace wr;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     char* lds = reinterpret_cast<char*>(smem);
-    typedef __attribute__((address_space(3))) void* lds_ptr;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, kh = lane >> 5;
     const int mt = wave & 1, cit = wave >> 1;
     const int co0 = blockIdx.y * 64, ci0 = blockIdx.z * 64;
@@ -340,10 +325,8 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_rows_kernel(WgParams p) {
     auto issue = [&](int strip, int buf) {
         const int b = strip / (p.sy * p.sx), rem = strip - b * (p.sy * p.sx);
         const int r0 = (rem / p.sx) * 2, c0 = (rem % p.sx) * 32;
-        const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (int64_t)b * p.x_bs + (int64_t)ci0 * HW), 0,
-                                                          (int)((unsigned)min(64, p.Cin - ci0) * HW4), 0x00020000);
-        const auto rd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.dy + (int64_t)b * p.dy_bs + (int64_t)co0 * HW), 0,
-                                                          (int)((unsigned)min(64, p.Cout - co0) * HW4), 0x00020000);
+        const auto rx = CWFA_RSRC(p.x + (int64_t)b * p.x_bs + (int64_t)ci0 * HW, (int)((unsigned)min(64, p.Cin - ci0) * HW4));
+        const auto rd = CWFA_RSRC(p.dy + (int64_t)b * p.dy_bs + (int64_t)co0 * HW, (int)((unsigned)min(64, p.Cout - co0) * HW4));
         const unsigned origin = (unsigned)((r0 * p.W + c0) * 4);
         // tile rows r0-1 .. r0+2 and column chunks c0-4+4cc: which of them lie inside the image
         const int rmin = r0 == 0 ? 1 : 0, rmax = min(3, p.H - r0), cmin = c0 == 0 ? 1 : 0, cmax = min(XCH - 1, (p.W - c0) / 4);
@@ -393,7 +376,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_rows_kernel(WgParams p) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) win[ky][c] = bp[ky * XCH + c];
         av = ap[0];
-        static_for<8>([&](auto jc) {
+        cwfa_static_for<8>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -440,7 +423,7 @@ __global__ __launch_bounds__(256, 1) void conv_wgrad_rows_kernel(WgParams p) {
     if (ci < p.Cin) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int co = co0 + mt * 32 + acc_row(r, kh);
+            const int co = co0 + mt * 32 + cwfa_acc_row(r, kh);
             if (co < p.Cout) {
 #pragma unroll
                 for (int i = 0; i < 9; ++i) out[((int64_t)co * p.Cin + ci) * 9 + i] = acc[i][r];
@@ -476,19 +459,6 @@ constexpr int XPLANE = 64 * XROW, XBUF = 3 * XPLANE;
 constexpr int LDS_BYTES = 2 * DYBUF + XBUF;   // 144 384
 }  // namespace ws
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-template <bool SIX>
-__device__ __forceinline__ void wsplit3(float v, __bf16& a1, __bf16& a2, __bf16& a3) {
-    a1 = (__bf16)v;
-    a2 = a3 = (__bf16)0.f;
-    if constexpr (SIX) {
-        const float r1 = v - (float)a1;
-        a2 = (__bf16)r1;
-        a3 = (__bf16)(r1 - (float)a2);
-    }
-}
-
 // KS = 3, or 1: the 1x1 weight gradient as the same walk with one tap (one dy copy, one x row in use)
 template <bool SIX, int KS = 3>
 __global__ __launch_bounds__(512, 1) void conv_wgrad_split_kernel(WgParams p) {
@@ -519,7 +489,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_split_kernel(WgParams p) {
         // this thread's staging source: dy threads read channel co0 + ch of dy, x threads channel ci0 + ch of x
         const int cvalid = is_dy ? min(64, p.Cout - co0) : min(64, p.Cin - ci0);
         const float* src = is_dy ? p.dy + (int64_t)b * p.dy_bs + (int64_t)co0 * HW : p.x + (int64_t)b * p.x_bs + (int64_t)ci0 * HW;
-        const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src), 0, cvalid * HW * 4, 0x00020000);
+        const auto rs = CWFA_RSRC(src, cvalid * HW * 4);
         const int px = c0 + grp * 8;
         float e[10];                                           // [0] = pixel px - 1, [1..8] = px .. px + 7, [9] = px + 8 (dy only)
         auto load_row = [&](int y) {
@@ -540,9 +510,9 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_split_kernel(WgParams p) {
         // split the loaded row and store it: x -> ring slot `slot`; dy -> buffer `buf`, three shifted copies; `count`: add to the bias sum
         auto store_row = [&](int slot, int buf, bool count) {
             if (is_dy) {
-                __bf16 pc[3][10];
+                __bf16 pc[3][10] = {};
 #pragma unroll
-                for (int i = (KS > 1 ? 0 : 1); i < (KS > 1 ? 10 : 9); ++i) wsplit3<SIX>(e[i], pc[0][i], pc[1][i], pc[2][i]);
+                for (int i = (KS > 1 ? 0 : 1); i < (KS > 1 ? 10 : 9); ++i) cwfa_split3<SIX>(e[i], pc[0][i], pc[1][i], pc[2][i]);
                 if (count) {
 #pragma unroll
                     for (int i = 1; i <= 8; ++i) bsum += e[i];
@@ -558,9 +528,9 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_split_kernel(WgParams p) {
                         *reinterpret_cast<bf16x8*>(dst + (s * 3 + q) * DYPLANE) = v;
                     }
             } else {
-                __bf16 pc[3][8];
+                __bf16 pc[3][8] = {};
 #pragma unroll
-                for (int i = 0; i < 8; ++i) wsplit3<SIX>(e[1 + i], pc[0][i], pc[1][i], pc[2][i]);
+                for (int i = 0; i < 8; ++i) cwfa_split3<SIX>(e[1 + i], pc[0][i], pc[1][i], pc[2][i]);
                 char* dst = lds + 2 * DYBUF + ch * XROW + slot * 64 + grp * 16;
 #pragma unroll
                 for (int q = 0; q < NQ; ++q) {
@@ -866,7 +836,7 @@ __global__ __launch_bounds__(256) void conv3d_hidden_fwd_kernel(const float* __r
     const Vox v{(int)(i / ((int64_t)H * W)), (int)((i / W) % H), (int)(i % W)};
     unsigned off[27];
     tap_offsets(v, D, H, W, +1, off);
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x + (int64_t)b * vol), 0, (int)(vol * 4), 0x00020000);
+    const auto rx = CWFA_RSRC(x + (int64_t)b * vol, (int)(vol * 4));
     float nb[27];
 #pragma unroll
     for (int t = 0; t < 27; ++t) nb[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, off[t], 0, 0));
@@ -893,7 +863,7 @@ __global__ __launch_bounds__(256) void conv3d_hidden_bwd_kernel(const float* __r
         const Vox v{(int)(i / ((int64_t)H * W)), (int)((i / W) % H), (int)(i % W)};
         unsigned off[27];
         tap_offsets(v, D, H, W, -1, off);
-        const auto rd = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dy + (int64_t)b * vol), 0, (int)(vol * 4), 0x00020000);
+        const auto rd = CWFA_RSRC(dy + (int64_t)b * vol, (int)(vol * 4));
         float nb[27];
 #pragma unroll
         for (int t = 0; t < 27; ++t) nb[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rd, off[t], 0, 0));
@@ -990,8 +960,7 @@ __global__ __launch_bounds__(256) void conv3d_input_bwd_kernel(const float* __re
     tap_offsets(v, D, H, W, -1, off);
     // one descriptor over the K hidden volumes of this sample (< 2 GiB, checked by the host); the channel moves through the
     // scalar offset and the padding marker 0x80000000 is out of range whichever way the offsets are summed
-    const auto rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(m + (int64_t)b * K * vol), 0, (int)((int64_t)K * vol * 4),
-                                                      0x00020000);
+    const auto rm = CWFA_RSRC(m + (int64_t)b * K * vol, (int)((int64_t)K * vol * 4));
     float acc = 0.f;
     for (int k = 0; k < K; ++k) {
         const int so = (int)((int64_t)k * vol * 4);
@@ -1026,8 +995,7 @@ __global__ __launch_bounds__(256) void conv3d_input_bwd4_kernel(const float* __r
         ol[l] = ok && x0 > 0 ? base - 4u : OOB;
         orr[l] = ok && x0 + 4 < W ? base + 16u : OOB;
     }
-    const auto rm = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(m + (int64_t)b * K * vol), 0, (int)((int64_t)K * vol * 4),
-                                                      0x00020000);
+    const auto rm = CWFA_RSRC(m + (int64_t)b * K * vol, (int)((int64_t)K * vol * 4));
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < K; ++k) {
         const int so = (int)((int64_t)k * vol * 4);
@@ -1097,7 +1065,7 @@ __global__ __launch_bounds__(256) void conv3d_wgrad_kernel(const float* __restri
     }
     float* out = part + (int64_t)wave * 1024;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) out[acc_row(r, kh) * 32 + l31] = acc[r];
+    for (int r = 0; r < 16; ++r) out[cwfa_acc_row(r, kh) * 32 + l31] = acc[r];
 }
 
 // The same GEMM for 16-byte aligned rows (W % 4 == 0): the MFMA k index pairs the two HALVES of a 64-voxel run (lane half
@@ -1159,7 +1127,7 @@ __global__ __launch_bounds__(256) void conv3d_wgrad4_kernel(const float* __restr
     }
     float* out = part + (int64_t)wave * 1024;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) out[acc_row(r, kh) * 32 + l31] = acc[r];
+    for (int r = 0; r < 16; ++r) out[cwfa_acc_row(r, kh) * 32 + l31] = acc[r];
 }
 
 // PReLU backward from the layer's OUTPUT o = PReLU(q), single alpha > 0:  y = g * (o > 0 ? 1 : alpha),

@@ -22,11 +22,6 @@
 //   step before, verified at its end; one barrier per step.
 #include "conv_internal.h"
 
-#include <utility>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 extern int g_cwfa_split_products;       // conv2d.hip ("split_products" option: 6 or 1)
 extern int g_cwfa_split_xcd_map;        // conv2d.hip ("split3x3_xcd_map" option)
 extern int g_cwfa_split_rows16;         // conv2d.hip ("split3x3_rows16" option: 16-row tiles for the 64-channel tiling)
@@ -76,57 +71,11 @@ struct SParams {
     cwfa_couple cp;             // EPI_COUPLE only
 };
 
-template <int K>
-struct ic {
-    static constexpr int value = K;
-};
-template <class F, int... S>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, S...>) {
-    (f(ic<S>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) {
-    sfor_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-template <bool SIX>
-__device__ __forceinline__ void split3(float v, __bf16& a1, __bf16& a2, __bf16& a3) {
-    a1 = (__bf16)v;
-    if constexpr (SIX) {
-        const float r1 = v - (float)a1;
-        a2 = (__bf16)r1;
-        const float r2 = r1 - (float)a2;
-        a3 = (__bf16)r2;
-    }
-}
-
-template <int ACT>
-__device__ __forceinline__ float act_of(float v, float alpha) {
-    if constexpr (ACT == CWFA_ACT_ELU) return cwfa_elu(v);
-    if constexpr (ACT == CWFA_ACT_PRELU) return v > 0.f ? v : alpha * v;
-    if constexpr (ACT == CWFA_ACT_GELU) return cwfa_gelu(v);
-    if constexpr (ACT == CWFA_ACT_RELU) return v > 0.f ? v : 0.f;
-    return v;
-}
-
-#define MFMA(a, b, c) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
-#define FENCE() __builtin_amdgcn_sched_barrier(0)
-
 // byte offset of the B fragments of tap t in buffer `buf`, relative to the lane base
 template <int KS, int RPW>
 __host__ __device__ constexpr int tap_off(int buf, int tap) { return buf * XG<KS, RPW>::XB + ((tap / KS) * XG<KS, RPW>::XC + tap % KS) * 16; }
 
 enum { EPI_RUNTIME = -1, EPI_COUPLE = -2 };
-
-// the soft clamp of the coupling blocks (coupling_layers.py:50-60; same expressions as csrc/elementwise.hip)
-__device__ __forceinline__ float soft_clamp(float a, int kind, float clamp) {
-    switch (kind) {
-        case CWFA_CLAMP_ATAN: return clamp * (0.636f * cwfa_atan(a));
-        case CWFA_CLAMP_TANH: return clamp * cwfa_tanh(a);
-        case CWFA_CLAMP_SIGMOID: return clamp * (2.f * (1.f / (1.f + expf(-a)) - 0.5f));
-        default: return clamp * a;
-    }
-}
 
 // ADD: a second tensor is added on load (UNet skip); ACT1: compile-time activation of the common epilogues (bias -> ACT1),
 // EPI_RUNTIME = whatever cwfa_conv_opts says (bias -> act -> + residual -> act2)
@@ -154,7 +103,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
     constexpr unsigned OOB = 0x80000000u;
     constexpr int NQ = SIX ? 3 : 1;
     constexpr int OFF_W = 2 * XB;
-    typedef __attribute__((address_space(3))) void* lds_ptr;
     // XCD-aware block -> (spatial tile, cout tile) map.  Workgroups are dealt round-robin over the 8 XCDs (blocks L and L + 8 share
     // an L2): XCD x works through its own contiguous band of spatial tiles (row-major: halo rows are re-read from that L2) with the
     // cout tiles of one spatial tile in consecutive slots, so the second .. fourth read of an input tile hits L2, not the fabric.
@@ -202,9 +150,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
         if constexpr (!SPECIAL) fo[k] = !fok[k] ? OOB : fo[k] + (unsigned)(ekh[k] * 8) * (unsigned)plane;    // (either layout: 8 planes)
     }
     const int xbytes = p.Cin * plane;                   // channels >= Cin: out of range, 0.0
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (int64_t)b * p.x_bs), 0, xbytes, 0x00020000);
-    const auto ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ADD ? p.o.in_add + (int64_t)b * p.o.in_add_bs : p.x), 0,
-                                                      ADD ? xbytes : 0, 0x00020000);
+    const auto rx = CWFA_RSRC(p.x + (int64_t)b * p.x_bs, xbytes);
+    const auto ra = CWFA_RSRC(ADD ? p.o.in_add + (int64_t)b * p.o.in_add_bs : p.x, ADD ? xbytes : 0);
     const bool has_aff = p.o.in_scale != nullptr;
     // the load-side affine tables are read through the SCALAR cache (constant address space; they were written by an
     // earlier kernel and the channel index is uniform over a wave): as vector loads each cost a full memory round trip
@@ -254,7 +201,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
             if (has_aff) v = fok[k] ? v * scv[j] + shv[j] : 0.f;       // padding stays zero
             if constexpr (ADD) v += av[j];
             __bf16 a1, a2 = (__bf16)0.f, a3 = (__bf16)0.f;
-            split3<SIX>(v, a1, a2, a3);
+            cwfa_split3<SIX>(v, a1, a2, a3);
             pc[0][j] = a1; pc[1][j] = a2; pc[2][j] = a3;
         }
         char* dst = lds + buf * XB + ekh[k] * KHB + eidx[k] * 16;
@@ -270,9 +217,9 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
     constexpr int NPC = (SIX ? WSL : WSL / 3) / 1024;
     const int64_t wtile = (int64_t)ct * p.nsteps * WSL;
     const char* wbase = reinterpret_cast<const char*>(p.wp) + wtile;
-    const auto rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(static_cast<const void*>(wbase)), 0, p.nsteps * WSL, 0x00020000);
+    const auto rw = CWFA_RSRC(wbase, p.nsteps * WSL);
     auto dma_w = [&](int slice, int slot) {              // slices past the end: out of range, zeros, never read
-        sfor<(NPC + 7) / 8>([&](auto ic_) {
+        cwfa_static_for<(NPC + 7) / 8>([&](auto ic_) {
             constexpr int i = decltype(ic_)::value;
             const int piece = i * 8 + wave;
             if (piece < NPC) {                           // wave-uniform
@@ -308,20 +255,20 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
     };
     auto mfma6 = [&](f32x4& c, const bf16x8 (&a)[3], const bf16x8 (&bb)[3]) {
         if constexpr (SIX) {
-            MFMA(a[2], bb[0], c);
-            MFMA(a[1], bb[1], c);
-            MFMA(a[0], bb[2], c);
-            MFMA(a[1], bb[0], c);
-            MFMA(a[0], bb[1], c);
+            CWFA_MFMA(a[2], bb[0], c);
+            CWFA_MFMA(a[1], bb[1], c);
+            CWFA_MFMA(a[0], bb[2], c);
+            CWFA_MFMA(a[1], bb[0], c);
+            CWFA_MFMA(a[0], bb[1], c);
         }
-        MFMA(a[0], bb[0], c);
+        CWFA_MFMA(a[0], bb[0], c);
     };
 
     // ---------------------------------------------------------------------------------------------- prologue
-    sfor<NEK>([&](auto kc) { load_entry(kc, xa[decltype(kc)::value], aa[decltype(kc)::value], 0); });
-    sfor<NEK>([&](auto kc) { load_entry(kc, xb[decltype(kc)::value], ab[decltype(kc)::value], 1); });
+    cwfa_static_for<NEK>([&](auto kc) { load_entry(kc, xa[decltype(kc)::value], aa[decltype(kc)::value], 0); });
+    cwfa_static_for<NEK>([&](auto kc) { load_entry(kc, xb[decltype(kc)::value], ab[decltype(kc)::value], 1); });
     dma_w(0, 0);
-    sfor<NEK>([&](auto kc) { store_entry(kc, xa[decltype(kc)::value], aa[decltype(kc)::value], 0, 0); });
+    cwfa_static_for<NEK>([&](auto kc) { store_entry(kc, xa[decltype(kc)::value], aa[decltype(kc)::value], 0, 0); });
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
 
@@ -346,37 +293,37 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
         // its own DMA and loads, when everything older has long landed (after them it cost 2 - 9 thousand cycles per step).
         // the vector-heavy part of staging: split + LDS stores of one entry of the chunk after next
         // (written out per entry: behind a generic lambda the staged-entry arrays stopped being promoted to registers)
-        if (P == SB) store_entry(ic<0>{}, xb[0], ab[0], co, 1);
-        if (P == SB + 1) store_entry(ic<1>{}, xb[1], ab[1], co, 1);
+        if (P == SB) store_entry(cwfa_ic<0>{}, xb[0], ab[0], co, 1);
+        if (P == SB + 1) store_entry(cwfa_ic<1>{}, xb[1], ab[1], co, 1);
         if constexpr (NEK > 2) {
-            if (P == SB + 2) store_entry(ic<NEK - 1>{}, xb[NEK - 1], ab[NEK - 1], co, 1);
+            if (P == SB + 2) store_entry(cwfa_ic<NEK - 1>{}, xb[NEK - 1], ab[NEK - 1], co, 1);
         }
-        if (P == SA) store_entry(ic<0>{}, xa[0], aa[0], ce + 2, 0);
-        if (P == SA + 1) store_entry(ic<1>{}, xa[1], aa[1], ce + 2, 0);
+        if (P == SA) store_entry(cwfa_ic<0>{}, xa[0], aa[0], ce + 2, 0);
+        if (P == SA + 1) store_entry(cwfa_ic<1>{}, xa[1], aa[1], ce + 2, 0);
         if constexpr (NEK > 2) {
-            if (P == SA + 2) store_entry(ic<NEK - 1>{}, xa[NEK - 1], aa[NEK - 1], ce + 2, 0);
+            if (P == SA + 2) store_entry(cwfa_ic<NEK - 1>{}, xa[NEK - 1], aa[NEK - 1], ce + 2, 0);
         }
-        FENCE();
+        CWFA_FENCE();
         // first A fragments (the step's first B fragments were requested before the barrier of the step before)
         const int abase = alane + sl * WSL;
         const int bbase = blane + (sel ? offB : offA);
         read_a(abase, 0);
-        FENCE();
+        CWFA_FENCE();
 #pragma unroll
         for (int m0 = 0; m0 < MPW; m0 += MH) {
             if (m0 > 0) {
                 read_a(abase, m0);
                 read_b(0, bbase, 0);
-                FENCE();
+                CWFA_FENCE();
             }
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 if (nt + 1 < NT) read_b((nt + 1) & 1, bbase, nt + 1);
-                FENCE();
+                CWFA_FENCE();
 #pragma unroll
                 for (int mt = 0; mt < MH; ++mt) {
                     mfma6(acc[m0 + mt][nt], A[mt], Bq[nt & 1]);
-                    FENCE();                 // keep the six products of a tile back to back (accumulator forwarding)
+                    CWFA_FENCE();                 // keep the six products of a tile back to back (accumulator forwarding)
                 }
                 // this step's staging loads and the next weight slice are issued from INSIDE the MFMA stream (after the first
                 // n-tiles): issued in a burst right behind the barrier, all eight waves stood in their issue cost (~100 cycles per
@@ -384,21 +331,21 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
                 // the DMA: they overwrite loop-carried registers, so the compiler waits for every older vector-memory
                 // operation first -- which must not include a DMA issued a moment ago.
                 if (m0 == 0 && nt == 0) {
-                    if (P == LA) load_entry(ic<0>{}, xa[0], aa[0], ce + 2);
-                    if (P == LA + 1) load_entry(ic<1>{}, xa[1], aa[1], ce + 2);
+                    if (P == LA) load_entry(cwfa_ic<0>{}, xa[0], aa[0], ce + 2);
+                    if (P == LA + 1) load_entry(cwfa_ic<1>{}, xa[1], aa[1], ce + 2);
                     if constexpr (NEK > 2) {
-                        if (P == LA + 2) load_entry(ic<NEK - 1>{}, xa[NEK - 1], aa[NEK - 1], ce + 2);
+                        if (P == LA + 2) load_entry(cwfa_ic<NEK - 1>{}, xa[NEK - 1], aa[NEK - 1], ce + 2);
                     }
-                    if (P == LB) load_entry(ic<0>{}, xb[0], ab[0], co + 2);
-                    if (P == LB + 1) load_entry(ic<1>{}, xb[1], ab[1], co + 2);
+                    if (P == LB) load_entry(cwfa_ic<0>{}, xb[0], ab[0], co + 2);
+                    if (P == LB + 1) load_entry(cwfa_ic<1>{}, xb[1], ab[1], co + 2);
                     if constexpr (NEK > 2) {
-                        if (P == LB + 2) load_entry(ic<NEK - 1>{}, xb[NEK - 1], ab[NEK - 1], co + 2);
+                        if (P == LB + 2) load_entry(cwfa_ic<NEK - 1>{}, xb[NEK - 1], ab[NEK - 1], co + 2);
                     }
-                    FENCE();
+                    CWFA_FENCE();
                 }
                 if (m0 == 0 && nt == 1) {
                     dma_w(step + 1, sl ^ 1);
-                    FENCE();
+                    CWFA_FENCE();
                 }
             }
         }
@@ -409,7 +356,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
             const int nbufA = nA >= NTAP, ntA = nA - NTAP * nbufA, nbufB = nB >= NTAP, ntB = nB - NTAP * nbufB;
             const int noffA = nbufA * XB + ((ntA / KS) * XC + ntA % KS) * 16, noffB = nbufB * XB + ((ntB / KS) * XC + ntB % KS) * 16;
             read_b(0, blane + (sel ? noffB : noffA), 0);
-            FENCE();
+            CWFA_FENCE();
         }
         // the next slice (the youngest vector-memory operation of the step) has landed
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -428,13 +375,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
     // ---------------------------------------------------------------------------------------------- epilogue
     // accumulator register r of tile (mt, nt): channel ct*CT + (wm*MPW + mt)*16 + 4g + r, pixel (row0 + 4*wn + nt/2, col0 + 16*(nt&1) + c16).
     // Buffer stores: the descriptor ends at channel Cout and a pixel outside the image carries an out-of-range offset.
-    const auto ry = __builtin_amdgcn_make_buffer_rsrc(p.y + (int64_t)b * p.y_bs, 0, p.Cout * plane, 0x00020000);
-    const auto rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.o.residual ? p.o.residual + (int64_t)b * p.o.res_bs : p.y), 0,
-                                                      p.o.residual ? p.Cout * plane : 0, 0x00020000);
-    const auto rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.o.bias ? p.o.bias : p.y), 0, p.o.bias ? p.Cout * 4 : 0, 0x00020000);
+    const auto ry = CWFA_RSRC(p.y + (int64_t)b * p.y_bs, p.Cout * plane);
+    const auto rr = CWFA_RSRC(p.o.residual ? p.o.residual + (int64_t)b * p.o.res_bs : p.y, p.o.residual ? p.Cout * plane : 0);
+    const auto rb = CWFA_RSRC(p.o.bias ? p.o.bias : p.y, p.o.bias ? p.Cout * 4 : 0);
     const bool alpha_pc = p.o.prelu_per_channel != 0;          // (uniform) one PReLU slope per output channel
     const float alpha = (p.o.prelu_alpha && !alpha_pc) ? *p.o.prelu_alpha : 0.f;
-    const auto rpa = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(alpha_pc ? p.o.prelu_alpha : p.y), 0, alpha_pc ? p.Cout * 4 : 0, 0x00020000);
+    const auto rpa = CWFA_RSRC(alpha_pc ? p.o.prelu_alpha : p.y, alpha_pc ? p.Cout * 4 : 0);
     const int cwave = ct * CT + wm * MPW * 16;      // uniform: rides in the scalar offset
     const unsigned glane = (unsigned)(4 * g) * (unsigned)plane;                           // the lane group's channel offset
     if constexpr (ACT1 == EPI_COUPLE) {
@@ -445,8 +391,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
         static_assert(MPW <= 2 && !ADD, "coupling epilogue: narrow tilings only");
         constexpr int NP = MPW == 1 ? 2 : 4;                                       // pairs per lane and n-tile
         const cwfa_couple& cp = p.cp;
-        const auto cx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(cp.x + (int64_t)b * cp.x_bs), 0, cp.n * plane, 0x00020000);
-        const auto cy = __builtin_amdgcn_make_buffer_rsrc(cp.y + (int64_t)b * cp.y_bs, 0, cp.n * plane, 0x00020000);
+        const auto cx = CWFA_RSRC(cp.x + (int64_t)b * cp.x_bs, cp.n * plane);
+        const auto cy = CWFA_RSRC(cp.y + (int64_t)b * cp.y_bs, cp.n * plane);
         const unsigned jlane = (unsigned)((MPW == 1 ? 2 : 4) * g) * (unsigned)plane;
         const int jwave = wm * (MPW == 1 ? 8 : 16);
         float bs[NP], bt[NP];
@@ -471,13 +417,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
                 float tr;
                 if constexpr (MPW == 1) tr = acc[0][nt][k + 2] + bt[k];
                 else tr = acc[MPW - 1][nt][k] + bt[k];
-                const float sv = soft_clamp(sr * cp.pre_scale, cp.clamp_kind, cp.clamp);
+                const float sv = cwfa_soft_clamp(sr * cp.pre_scale, cp.clamp_kind, cp.clamp);
                 const float tv = tr * cp.pre_scale;
                 const float yv = cp.rev ? (xv[k] - tv) * __expf(-sv) : __expf(sv) * xv[k] + tv;     // |s| <= clamp: v_exp_f32, rel. error ~2e-7
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, yv), cy, po, (jwave + k) * plane, 0);
                 ssum += ok ? sv : 0.f;
             }
-            FENCE();
+            CWFA_FENCE();
         }
         if (cp.logdet) {                                  // block sum -> one float64 atomic per block
             const double ws = cwfa_wave_sum((double)ssum);
@@ -533,22 +479,22 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
 #pragma unroll
                 for (int nt = 0; nt < RLA; ++nt) load_res(nt);
             }
-            FENCE();
+            CWFA_FENCE();
         }
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const int row = row0 + wn * RW + (nt >> 1), col = col0 + 16 * (nt & 1) + c16;
             if constexpr (ACT1 == EPI_RUNTIME) {
                 if (nt + RLA < NT && p.o.residual) load_res(nt + RLA);
-                FENCE();
+                CWFA_FENCE();
             }
             if constexpr (ACT1 != EPI_RUNTIME) {
                 if (outb) {
                     f32x4 o4;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) o4[r] = act_of<ACT1>(acc[mt][nt][r] + bias[r], al[r]);
+                    for (int r = 0; r < 4; ++r) o4[r] = cwfa_act_ct<ACT1>(acc[mt][nt][r] + bias[r], al[r]);
                     const unsigned pb = (row < p.H && col < p.W) ? (unsigned)(((g >> 1) * HW + row * p.W + col) * 32 + (g & 1) * 16) : OOB;
-                    cwfa_buffer_store_b128(__builtin_bit_cast(cwfa_u32x4, o4), ry, pb, (cwave + mt * 16) * plane);   // (+ wait states: common.h)
+                    cwfa_buffer_store_b128(__builtin_bit_cast(u32x4, o4), ry, pb, (cwave + mt * 16) * plane);   // (+ wait states: common.h)
                     continue;
                 }
             }
@@ -562,7 +508,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
                     v += rv[nt][r];
                     v = cwfa_act(v, p.o.act2, al[r]);
                 } else {
-                    v = act_of<ACT1>(v, al[r]);
+                    v = cwfa_act_ct<ACT1>(v, al[r]);
                     if (want_stats) {
                         const float vm = po != OOB ? v : 0.f;
                         st1[r] += vm;
@@ -571,7 +517,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
                 }
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, po, soff, 0);
             }
-            FENCE();                 // keep the results from being staged in registers all at once
+            CWFA_FENCE();                 // keep the results from being staged in registers all at once
         }
         if constexpr (ACT1 != EPI_RUNTIME) {
             if (want_stats) {
@@ -621,7 +567,7 @@ __global__ __launch_bounds__(256) void split3x3_pack_kernel(const float* __restr
         float v = 0.f;
         if (co < Cout && ci < Cin && chunk < nchunks) v = w[((int64_t)co * Cin + ci) * ntap + tap];
         __bf16 a1, a2, a3;
-        split3<true>(v, a1, a2, a3);
+        cwfa_split3<true>(v, a1, a2, a3);
         pc[0][j] = __builtin_bit_cast(unsigned short, a1);
         pc[1][j] = __builtin_bit_cast(unsigned short, a2);
         pc[2][j] = __builtin_bit_cast(unsigned short, a3);

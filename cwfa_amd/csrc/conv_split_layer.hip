@@ -33,11 +33,6 @@
 // s+2 is issued at the start of step s and verified at its end (one barrier per step, 19 per tile).
 #include "conv_internal.h"
 
-#include <utility>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 extern int g_cwfa_split_products;       // conv2d.hip ("split_products" option: 6 or 1)
 extern int g_cwfa_split_xcd_map;        // conv2d.hip ("split3x3_xcd_map" option; also the tile walk of this kernel)
 
@@ -76,39 +71,11 @@ struct LParams {
                                       // NSL * WSL) and biases (b3 / b1 + problem * 64); nprob = 1: one bank for the whole batch
 };
 
-template <int K>
-struct ic {
-    static constexpr int value = K;
-};
-template <class F, int... S>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, S...>) {
-    (f(ic<S>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) {
-    sfor_impl(f, std::make_integer_sequence<int, N>{});
-}
-
 // ELU = median(v, exp(v) - 1, 0): for v > 0, exp(v) - 1 > v > 0; for v < 0, v <= exp(v) - 1 < 0 -- one v_med3_f32 instead of a
 // compare and a select (the 1x1 phase of the layer is bound by exactly these instructions: 192 ELUs per lane and tile)
 __device__ __forceinline__ float elu(float v) {
     return __builtin_amdgcn_fmed3f(v, __expf(v) - 1.0f, 0.f);
 }
-
-// v = a1 + a2 + a3 exactly (each difference is exact: the subtrahend is the minuend rounded to 8 significant bits)
-template <bool SIX>
-__device__ __forceinline__ void split3(float v, __bf16& a1, __bf16& a2, __bf16& a3) {
-    a1 = (__bf16)v;
-    if constexpr (SIX) {
-        const float r1 = v - (float)a1;
-        a2 = (__bf16)r1;
-        const float r2 = r1 - (float)a2;
-        a3 = (__bf16)r2;
-    }
-}
-
-#define MFMA(a, b, c) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
-#define FENCE() __builtin_amdgcn_sched_barrier(0)
 
 // (chunk, tap) unit u = 0..35 of the 3x3: byte offset of its B fragments relative to the lane base
 __host__ __device__ constexpr int unit_off(int u) {
@@ -142,7 +109,6 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
     const int plane = HW * 4;
     constexpr unsigned OOB = 0x80000000u;
     constexpr int NQ = SIX ? 3 : 1;
-    typedef __attribute__((address_space(3))) void* lds_ptr;
 
     // ---- staging entries e = tid + k*512 < NE of the [k half][18 rows][34 px] tile
     // (kept as ONE packed word + the LDS destination per entry: the kernel sits at the 256-register limit)
@@ -167,7 +133,7 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
         }
     };
     auto rsrc_of = [&](const float* base) {
-        return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, 64 * plane, 0x00020000);
+        return CWFA_RSRC(base, 64 * plane);
     };
     // XCD-aware walk: workgroup w sits on XCD w & 7 (round-robin dispatch), so the k-th tile of workgroup w -- logical index
     // w + k * gridDim.x -- is taken from XCD (w & 7)'s own contiguous eighth of the tile list: neighbouring tiles (shared halo
@@ -184,7 +150,7 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
     };
     auto load_entry = [&](f32x4 (&xv)[2], const float* base, unsigned fo, int chunk) {
         // (the staged tensor: 64 channels of x, or the u_ch channels of u -- channels past the end read 0.0)
-        const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (UIN ? p.u_ch : 64) * plane, 0x00020000);
+        const auto rs = CWFA_RSRC(base, (UIN ? p.u_ch : 64) * plane);
         if constexpr (INS) {                          // chunk = channel blocks 2 chunk, 2 chunk + 1: 16 planes further
             xv[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, fo, chunk * 16 * plane, 0));
             xv[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, fo, chunk * 16 * plane + 16, 0));   // (+16 in the SCALAR offset)
@@ -201,7 +167,7 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             __bf16 a1, a2 = (__bf16)0.f, a3 = (__bf16)0.f;
-            split3<SIX>(xv[j >> 2][j & 3], a1, a2, a3);
+            cwfa_split3<SIX>(xv[j >> 2][j & 3], a1, a2, a3);
             pc[0][j] = a1; pc[1][j] = a2; pc[2][j] = a3;
         }
         if (fin[k]) {
@@ -212,7 +178,7 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
     };
 
     // ---- weight slices: 12 x 1 KB; every wave issues two DMA instructions (waves 4..7: the second into the dump area)
-    const auto rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.wp), 0, p.nprob * NSLK * WSL, 0x00020000);
+    const auto rw = CWFA_RSRC(p.wp, p.nprob * NSLK * WSL);
     // `wb`: byte offset of the problem's packed image (scalar)
     auto dma_w = [&](int slice, int slot, int wb) {
         if constexpr (!SIX) {                        // plain bf16: only the leading piece plane (the first 4 KB) of a slice is read
@@ -250,13 +216,13 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
     };
     auto mfma6 = [&](f32x4& c, const bf16x8 (&a)[3], const bf16x8 (&b)[3]) {
         if constexpr (SIX) {
-            MFMA(a[2], b[0], c);
-            MFMA(a[1], b[1], c);
-            MFMA(a[0], b[2], c);
-            MFMA(a[1], b[0], c);
-            MFMA(a[0], b[1], c);
+            CWFA_MFMA(a[2], b[0], c);
+            CWFA_MFMA(a[1], b[1], c);
+            CWFA_MFMA(a[0], b[2], c);
+            CWFA_MFMA(a[1], b[0], c);
+            CWFA_MFMA(a[0], b[1], c);
         }
-        MFMA(a[0], b[0], c);
+        CWFA_MFMA(a[0], b[0], c);
     };
     auto bbase_of = [&](int offA, int offB) { return blane + (sel ? offB : offA); };
 
@@ -270,9 +236,9 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
     tile_coords(tile, tb, row0, col0);
     const float* xs_cur = UIN ? p.u + (int64_t)tb * p.u_bs : p.x + (int64_t)tb * p.x_bs;
     entry_offsets(true, row0, col0, fo_c);
-    sfor<3>([&](auto kc) { load_entry(xa[decltype(kc)::value], xs_cur, fo_c[decltype(kc)::value], 0); });
+    cwfa_static_for<3>([&](auto kc) { load_entry(xa[decltype(kc)::value], xs_cur, fo_c[decltype(kc)::value], 0); });
     if constexpr (!SHORT) {
-        sfor<3>([&](auto kc) { load_entry(xb[decltype(kc)::value], xs_cur, fo_c[decltype(kc)::value], 1); });
+        cwfa_static_for<3>([&](auto kc) { load_entry(xb[decltype(kc)::value], xs_cur, fo_c[decltype(kc)::value], 1); });
     } else {                                     // the odd buffer: zeros, once
 #pragma unroll
         for (int k = 0; k < 3; ++k)
@@ -283,7 +249,7 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
     }
     int wb_cur = problem_of(tb) * (NSLK * WSL);
     dma_w(0, 0, wb_cur);
-    sfor<3>([&](auto kc) { store_entry(kc, xa[decltype(kc)::value], 0); });
+    cwfa_static_for<3>([&](auto kc) { store_entry(kc, xa[decltype(kc)::value], 0); });
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     int cs = 0;                                  // ring slot of the current step's slice
@@ -313,7 +279,7 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
         }
 
         // ------------------------------------------------------------------------------------------ 18 conv steps
-        sfor<NSTEP>([&](auto sc) {
+        cwfa_static_for<NSTEP>([&](auto sc) {
             constexpr int S = decltype(sc)::value, P = S % 9, PER = S / 9;
             constexpr bool LASTP = PER == NPER - 1;            // the last period stages the NEXT tile's chunks 0 and 1
             const int s1 = next_slot(cs), s2 = next_slot(s1);
@@ -343,31 +309,31 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
             if constexpr (S == 1) read_a(0, ab, 0);             // slice 1 became visible with the barrier of step 0
             constexpr int NS = (S + 1) % NSTEP;                 // next step's B base (last step: unused, the 1x1 phase follows)
             const int bbn = bbase_of(unit_off(2 * NS), unit_off(2 * NS + 1));
-            FENCE();
+            CWFA_FENCE();
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
                 if (mt < 3) read_a((mt + 1) & 1, ab, mt + 1);
                 else if (S != 0 && S != NSTEP - 1) read_a(0, alane + s1 * WSL, 0);    // first fragments of the next step
-                FENCE();
+                CWFA_FENCE();
 #pragma unroll
                 for (int np = 0; np < 4; np += 2) {
                     mfma6(acc[mt][np], A[mt & 1], Bq[np]);
                     mfma6(acc[mt][np + 1], A[mt & 1], Bq[np + 1]);
-                    FENCE();
+                    CWFA_FENCE();
                     if (mt == 3 && S != NSTEP - 1) {
                         read_b(np, bbn);
                         read_b(np + 1, bbn);
-                        FENCE();
+                        CWFA_FENCE();
                     }
                 }
                 // after the first m-tile: this step's memory traffic, and the vector-heavy part of staging (split + LDS stores
                 // of one entry)
                 if (mt == 0) {
                     issue_memory();
-                    FENCE();
-                    if constexpr (!SHORT && P <= 2) store_entry(ic<P>{}, xb[P], 1);
-                    if constexpr (!SHORT && P >= 5 && P <= 7) store_entry(ic<P - 5>{}, xa[P - 5], 0);
-                    FENCE();
+                    CWFA_FENCE();
+                    if constexpr (!SHORT && P <= 2) store_entry(cwfa_ic<P>{}, xb[P], 1);
+                    if constexpr (!SHORT && P >= 5 && P <= 7) store_entry(cwfa_ic<P - 5>{}, xa[P - 5], 0);
+                    CWFA_FENCE();
                 }
             }
             // this step's slice DMA has landed; its 8 staging loads (issued after it) may stay in flight
@@ -385,15 +351,15 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
 
         // ------------------------------------------------------------------------------------------ 1x1 + epilogue
         if constexpr (SHORT) {      // the next tile's chunk into the even buffer: its last reader (step 4) is behind a barrier
-            sfor<3>([&](auto kc) { store_entry(kc, xa[decltype(kc)::value], 0); });
+            cwfa_static_for<3>([&](auto kc) { store_entry(kc, xa[decltype(kc)::value], 0); });
         }
         {
             const int sw0 = cs, sw1 = next_slot(cs), sn0 = next_slot(sw1);         // W1 slices, next tile's slice 0
             dma_w(0, sn0, wb_next);
             const auto rx = rsrc_of(XF ? p.y : p.x + (int64_t)tb * p.x_bs);        // (XF: unused)
-            const auto ru = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(XF ? p.u + (int64_t)tb * p.u_bs : p.y), 0, XF ? p.u_ch * plane : 0, 0x00020000);
-            const auto ry = __builtin_amdgcn_make_buffer_rsrc(p.y + (int64_t)tb * p.y_bs, 0, 64 * plane, 0x00020000);
-            const auto rh = __builtin_amdgcn_make_buffer_rsrc(TAPE ? p.hid + (int64_t)tb * p.hid_bs : p.y, 0, TAPE ? 64 * plane : 0, 0x00020000);
+            const auto ru = CWFA_RSRC(XF ? p.u + (int64_t)tb * p.u_bs : p.y, XF ? p.u_ch * plane : 0);
+            const auto ry = CWFA_RSRC(p.y + (int64_t)tb * p.y_bs, 64 * plane);
+            const auto rh = CWFA_RSRC(TAPE ? p.hid + (int64_t)tb * p.hid_bs : p.y, TAPE ? 64 * plane : 0);
             // offsets of this lane's (row, col) in the two layouts: NCHW: channel 4 g (+ 16 mt + r planes in the scalar offset);
             // blocked: 16-byte half g & 1 of the 32-byte entry of channel block g >> 1 (+ 2 mt blocks = 16 mt planes)
             unsigned oo[4], ob[4];
@@ -444,7 +410,7 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) o4[r] = elu(XF ? acc[mt][nt][r] : acc[mt][nt][r] + rv[mt][r]);
                         // (cwfa_buffer_store_b128: the store with the wait states its data registers need on gfx950, common.h)
-                        cwfa_buffer_store_b128(__builtin_bit_cast(cwfa_u32x4, o4), ry, ob[nt], mt * 16 * plane);
+                        cwfa_buffer_store_b128(__builtin_bit_cast(u32x4, o4), ry, ob[nt], mt * 16 * plane);
                     }
                     return;
                 }
@@ -489,14 +455,14 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
                         const float hv = elu(acc[2 * s + (j >> 2)][nt][j & 3]);
                         if constexpr (TAPE)
                             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, hv), rh, oo[nt], ((2 * s + (j >> 2)) * 16 + (j & 3)) * plane, 0);
-                        split3<SIX>(hv, h1, h2, h3);
+                        cwfa_split3<SIX>(hv, h1, h2, h3);
                         Hq[s][0][j] = h1; Hq[s][1][j] = h2; Hq[s][2][j] = h3;
                     }
                 if constexpr (XF) {
                     if (nt + 1 < 4) load_u(nt + 1, uv[(nt + 1) & 1]);
                 }
                 read_a1(0);
-                FENCE();
+                CWFA_FENCE();
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {       // (m-tile pair, k step): 12 MFMAs on two accumulator tiles
                     const int mp = (i >> 1) * 2, s = i & 1;
@@ -506,14 +472,14 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
                         acc[mp][nt] = bias4[16 + mp * 4 + g];
                         acc[mp + 1][nt] = bias4[16 + (mp + 1) * 4 + g];
                     }
-                    FENCE();
+                    CWFA_FENCE();
                     mfma6(acc[mp][nt], A1[i & (NA1 - 1)][0], Hq[s]);
                     mfma6(acc[mp + 1][nt], A1[i & (NA1 - 1)][1], Hq[s]);
-                    FENCE();
+                    CWFA_FENCE();
                     if (nt > 0) {
                         epilogue_piece(nt - 1, 2 * i, res);
                         epilogue_piece(nt - 1, 2 * i + 1, res);
-                        FENCE();
+                        CWFA_FENCE();
                     }
                 }
                 if constexpr (XF) {                 // third k step: + W0' . (u | 1) = the first map, never formed in memory
@@ -521,22 +487,22 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         __bf16 u1, u2 = (__bf16)0.f, u3 = (__bf16)0.f;
-                        split3<SIX>(uv[nt & 1][j], u1, u2, u3);
+                        cwfa_split3<SIX>(uv[nt & 1][j], u1, u2, u3);
                         Uq[0][j] = u1; Uq[1][j] = u2; Uq[2][j] = u3;
                     }
 #pragma unroll
                     for (int i = 4; i < 6; ++i) {
                         const int mp = (i - 4) * 2;
                         if (i + 1 < 6) read_a1(i + 1);
-                        FENCE();
+                        CWFA_FENCE();
                         mfma6(acc[mp][nt], A1[i & (NA1 - 1)][0], Uq);
                         mfma6(acc[mp + 1][nt], A1[i & (NA1 - 1)][1], Uq);
-                        FENCE();
+                        CWFA_FENCE();
                     }
                 } else {
                     load_res(nt, res);              // consumed by this n-tile's epilogue, one iteration later
                 }
-                FENCE();
+                CWFA_FENCE();
             }
 #pragma unroll
             for (int i = 0; i < 8; ++i) epilogue_piece(3, i, res);
@@ -587,7 +553,7 @@ __global__ __launch_bounds__(256) void split_layer_pack_kernel(const float* __re
             v = w0[co * 32 + 8 * g + j];
         }
         __bf16 a1, a2, a3;
-        split3<true>(v, a1, a2, a3);
+        cwfa_split3<true>(v, a1, a2, a3);
         pc[0][j] = __builtin_bit_cast(unsigned short, a1);
         pc[1][j] = __builtin_bit_cast(unsigned short, a2);
         pc[2][j] = __builtin_bit_cast(unsigned short, a3);

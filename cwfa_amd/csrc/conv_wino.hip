@@ -16,28 +16,8 @@
 // and stores them as one 8-byte word (256 B contiguous per half-wave).
 #include "conv_internal.h"
 #include <type_traits>
-#include <utility>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-#ifndef CWFA_WDEPTH
-#define CWFA_WDEPTH 2
-#endif
 
 namespace {
-
-template <int K>
-using sc_int = std::integral_constant<int, K>;
-template <class F, int... S>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, S...>) {
-    (f(sc_int<S>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 template <int CK_, int MT_, int WM_, int WN_>
 struct WCfg {
@@ -72,8 +52,6 @@ struct WParams {
     int64_t hidden_bs;
 };
 
-#define LSTAMP(k)
-
 struct WTile {
     int wm, wn, kh, l31, ct, b, row0, col0;
 };
@@ -107,8 +85,6 @@ __device__ __forceinline__ WTile make_wtile(const WParams& p) {
     t.col0 = tx * C::TCOLS;
     return t;
 }
-
-__device__ __forceinline__ int acc_row(int r, int kh) { return (r & 3) + 8 * (r >> 2) + 4 * kh; }
 
 // ------------------------------------------------------------------------------------------------ main loop
 template <class C, bool PRO>
@@ -148,15 +124,11 @@ __device__ __forceinline__ void wino_mainloop(const WParams& p, const WTile& t, 
     }
     const bool has_aff = PRO && p.o.in_scale != nullptr, has_add = PRO && p.o.in_add != nullptr;
     const int xbytes = (int)((int64_t)p.Cin * HW * 4);
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (int64_t)t.b * p.x_bs), 0, xbytes, 0x00020000);
-    const auto ra = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(has_add ? p.o.in_add + (int64_t)t.b * p.o.in_add_bs : p.x), 0, has_add ? xbytes : 0, 0x00020000);
-    const auto rsc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(has_aff ? p.o.in_scale + (int64_t)t.b * p.o.in_affine_bs : p.x), 0, has_aff ? p.Cin * 4 : 0, 0x00020000);
-    const auto rsh = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(has_aff ? p.o.in_shift + (int64_t)t.b * p.o.in_affine_bs : p.x), 0, has_aff ? p.Cin * 4 : 0, 0x00020000);
-    const auto rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wp + (int64_t)t.ct * p.nchunks * C::US), 0,
-                                                      p.nchunks * C::US * 4, 0x00020000);
+    const auto rx = CWFA_RSRC(p.x + (int64_t)t.b * p.x_bs, xbytes);
+    const auto ra = CWFA_RSRC(has_add ? p.o.in_add + (int64_t)t.b * p.o.in_add_bs : p.x, has_add ? xbytes : 0);
+    const auto rsc = CWFA_RSRC(has_aff ? p.o.in_scale + (int64_t)t.b * p.o.in_affine_bs : p.x, has_aff ? p.Cin * 4 : 0);
+    const auto rsh = CWFA_RSRC(has_aff ? p.o.in_shift + (int64_t)t.b * p.o.in_affine_bs : p.x, has_aff ? p.Cin * 4 : 0);
+    const auto rw = CWFA_RSRC(p.wp + (int64_t)t.ct * p.nchunks * C::US, p.nchunks * C::US * 4);
     const int chunk_bytes = (int)(C::CK * HW * 4);
     const unsigned uoff = tid * 4 * C::UV;
     auto ldf = [](decltype(rx) r, unsigned vo, int so) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0)); };
@@ -258,7 +230,7 @@ __device__ __forceinline__ void wino_mainloop(const WParams& p, const WTile& t, 
     // store of chunk c+1 is scheduled before it, and a wave's last reads of the current buffer are issued before it), the
     // first reads of chunk c+1 follow it immediately, and the remaining MFMAs of chunk c cover their latency -- with the
     // barrier at the very end both waves of a SIMD sat idle for one LDS round trip per chunk.
-    constexpr int NSTEP = 12 * (C::CK / 2), DEPTH = CWFA_WDEPTH, SLOT0 = 1, SLOTD = (NSTEP - DEPTH - 2) / NITEM;
+    constexpr int NSTEP = 12 * (C::CK / 2), DEPTH = 2, SLOT0 = 1, SLOTD = (NSTEP - DEPTH - 2) / NITEM;
     static_assert(NSTEP % (DEPTH + 1) == 0 && SLOT0 + (NITEM - 1) * SLOTD < NSTEP - DEPTH, "slot ring / staging before the barrier");
     float bq[DEPTH + 1], aq[DEPTH + 1][C::MT];
     auto ld = [&](int buf, int s, int slot) {
@@ -273,19 +245,14 @@ __device__ __forceinline__ void wino_mainloop(const WParams& p, const WTile& t, 
             aq[slot][0] = *ua;
         }
     };
-#define STAMP(k)
     // MORE / PF (is there a chunk c+1 to store, a chunk c+2 to load) are compile-time: the steady-state body carries no
     // branches, the last two chunks run their own copies
     auto mfmas = [&](int cur, int chunk, auto morec, auto pfc) {
         constexpr bool more = decltype(morec)::value, pf = decltype(pfc)::value;
         // compile-time step index: the staging item (and its register arrays) must resolve statically, whatever the unroller thinks
-        static_for<NSTEP>([&](auto sc) {
+        cwfa_static_for<NSTEP>([&](auto sc) {
             constexpr int s = decltype(sc)::value, xi = (s / (C::CK / 2)) % 4;
-            if constexpr (s % 6 == 0) STAMP(s / 6);
-            if constexpr (s + DEPTH == NSTEP) {
-                if constexpr (more) __syncthreads();
-                STAMP(8);
-            }
+            if constexpr (s + DEPTH == NSTEP && more) __syncthreads();
             if constexpr (s + DEPTH < NSTEP) {
                 ld(cur, s + DEPTH, (s + DEPTH) % (DEPTH + 1));
             } else if constexpr (more) {
@@ -296,14 +263,14 @@ __device__ __forceinline__ void wino_mainloop(const WParams& p, const WTile& t, 
                 acc[m][xi] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[s % (DEPTH + 1)][m], bq[s % (DEPTH + 1)], acc[m][xi], 0, 0, 0);
             if constexpr (s >= SLOT0 && (s - SLOT0) % SLOTD == 0 && (s - SLOT0) / SLOTD < NITEM) {
                 constexpr int k = (s - SLOT0) / SLOTD;
-                if constexpr (more) store_item(sc_int<k>{}, cur ^ 1);
-                if constexpr (pf) load_item(sc_int<k>{}, chunk + 2);
+                if constexpr (more) store_item(cwfa_ic<k>{}, cur ^ 1);
+                if constexpr (pf) load_item(cwfa_ic<k>{}, chunk + 2);
             }
             __builtin_amdgcn_sched_barrier(0);
         });
     };
-    static_for<NITEM>([&](auto kc) { load_item(kc, 0); });
-    static_for<NITEM>([&](auto kc) {
+    cwfa_static_for<NITEM>([&](auto kc) { load_item(kc, 0); });
+    cwfa_static_for<NITEM>([&](auto kc) {
         store_item(kc, 0);
         if (1 < p.nchunks) load_item(kc, 1);
     });
@@ -313,10 +280,7 @@ __device__ __forceinline__ void wino_mainloop(const WParams& p, const WTile& t, 
     typedef std::true_type T;
     typedef std::false_type F;
     int chunk = 0;
-    for (; chunk + 2 < p.nchunks; ++chunk) {
-        mfmas(chunk & 1, chunk, T{}, T{});
-        STAMP(9);
-    }
+    for (; chunk + 2 < p.nchunks; ++chunk) mfmas(chunk & 1, chunk, T{}, T{});
     if (chunk + 1 < p.nchunks) {
         mfmas(chunk & 1, chunk, T{}, F{});
         ++chunk;
@@ -365,7 +329,7 @@ __device__ __forceinline__ void wino_epilogue(const WParams& p, const WTile& t, 
                     }
                 }
             for (int r = 0; r < 16; ++r) {
-                const int co = t.ct * C::CT + (t.wm * C::MT + m) * 32 + acc_row(r, t.kh);
+                const int co = t.ct * C::CT + (t.wm * C::MT + m) * 32 + cwfa_acc_row(r, t.kh);
                 if (co >= p.Cout) continue;
                 const float bias = p.o.bias ? p.o.bias[co] : 0.f;
                 for (int px = 0; px < 2; ++px) {
@@ -386,7 +350,7 @@ __device__ __forceinline__ void wino_epilogue(const WParams& p, const WTile& t, 
         for (int m = 0; m < C::MT; ++m)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int co = t.ct * C::CT + (t.wm * C::MT + m) * 32 + acc_row(r, t.kh);
+                const int co = t.ct * C::CT + (t.wm * C::MT + m) * 32 + cwfa_acc_row(r, t.kh);
                 if (co >= p.Cout) continue;
                 const float bias = p.o.bias ? p.o.bias[co] : 0.f;
                 float e0 = (acc[m][0][r] + acc[m][1][r]) + acc[m][2][r];
@@ -421,11 +385,8 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void conv3x3_wino_kernel(WParams p)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const WTile t = make_wtile<C>(p);
     f32x16 acc[C::MT][4];
-    LSTAMP(0);
     wino_mainloop<C, PRO>(p, t, smem, smem + C::VS, acc);
-    LSTAMP(1);
     wino_epilogue<C, EPI>(p, t, acc, smem);
-    LSTAMP(2);
 }
 
 // ---- weight transform + repack: torch [Cout][Cin][3][3] -> [cout tile][chunk][ky][xi][ck][CT]
@@ -493,9 +454,7 @@ __global__ __launch_bounds__(W64::NTHREADS, 1) void wino_layer_kernel(WParams p)
     float* Us = smem + C::VS;
     const WTile t = make_wtile<C>(p);
     f32x16 acc[2][4];
-    LSTAMP(0);
     wino_mainloop<C, false>(p, t, smem, Us, acc);
-    LSTAMP(1);
 
     const int64_t HW = (int64_t)p.H * p.W;
     const int row = t.row0 + t.wn, col = t.col0 + 2 * t.l31;
@@ -514,7 +473,7 @@ __global__ __launch_bounds__(W64::NTHREADS, 1) void wino_layer_kernel(WParams p)
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) b3v[m][r] = ld1(p.o.bias, (unsigned)(m * 32 + acc_row(r, 0)) * 4u + (unsigned)t.kh * 16u);
+        for (int r = 0; r < 16; ++r) b3v[m][r] = ld1(p.o.bias, (unsigned)(m * 32 + cwfa_acc_row(r, 0)) * 4u + (unsigned)t.kh * 16u);
 
     // stage the 1x1 panel (4096 floats) where the transformed 3x3 weights were
     __syncthreads();
@@ -525,12 +484,11 @@ __global__ __launch_bounds__(W64::NTHREADS, 1) void wino_layer_kernel(WParams p)
     }
     __syncthreads();
     const float* wl = Us + (threadIdx.x & 63);
-    LSTAMP(2);
 
     auto load_res = [&](int mo, f32x2 (&res)[16]) {           // residual x + 1x1 bias of 16 output channels, both pixels
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const unsigned K = (unsigned)(mo * 32 + acc_row(r, 0));
+            const unsigned K = (unsigned)(mo * 32 + cwfa_acc_row(r, 0));
             const float b1 = ld1(p.b1x1, K * 4u + (unsigned)t.kh * 16u);
             res[r] = ld2(xb, K * HW4 + oo, vec, ok1) + b1;
         }
@@ -555,7 +513,7 @@ __global__ __launch_bounds__(W64::NTHREADS, 1) void wino_layer_kernel(WParams p)
                 if constexpr (TAPE) {
                     if (q == 1) {                           // both pixels of hidden channel m*32 + row(r) are final: keep them
                         const f32x2 hv = {acc[m][0][r], acc[m][1][r]};
-                        if (ok0) st2(hb, (unsigned)(m * 32 + acc_row(r, 0)) * HW4 + oo, hv, vech, ok0, ok1);
+                        if (ok0) st2(hb, (unsigned)(m * 32 + cwfa_acc_row(r, 0)) * HW4 + oo, hv, vech, ok0, ok1);
                     }
                 }
                 if (j == 0) {
@@ -566,7 +524,7 @@ __global__ __launch_bounds__(W64::NTHREADS, 1) void wino_layer_kernel(WParams p)
                 }
                 if (q == 3 && (j & 1)) {                    // output channels 0..31 are complete: one per two k-steps
                     const int rr = j >> 1;
-                    const unsigned K = (unsigned)acc_row(rr, 0);
+                    const unsigned K = (unsigned)cwfa_acc_row(rr, 0);
                     f32x2 o = {cwfa_elu(yq[0][rr] + rq0[rr][0]), cwfa_elu(yq[1][rr] + rq0[rr][1])};
                     if (ok0) st2(yb, K * HW4 + oo, o, vec, ok0, ok1);
                 }
@@ -575,11 +533,10 @@ __global__ __launch_bounds__(W64::NTHREADS, 1) void wino_layer_kernel(WParams p)
     }
 #pragma unroll
     for (int rr = 0; rr < 16; ++rr) {                       // tail: output channels 32..63
-        const unsigned K = (unsigned)(32 + acc_row(rr, 0));
+        const unsigned K = (unsigned)(32 + cwfa_acc_row(rr, 0));
         f32x2 o = {cwfa_elu(yq[2][rr] + rq1[rr][0]), cwfa_elu(yq[3][rr] + rq1[rr][1])};
         if (ok0) st2(yb, K * HW4 + oo, o, vec, ok0, ok1);
     }
-    LSTAMP(3);
 }
 
 struct WSel {

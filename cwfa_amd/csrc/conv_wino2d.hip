@@ -8,12 +8,13 @@
 //   16 MFMAs per (ci pair, 32 cout, 32 tiles = 2 rows x 64 pixels) where the direct form needs 36 and the 1-D F(2,3)
 //   kernel (conv_wino.hip) 24.
 //
-// STATUS: opt-in (cwfa_set_option("winograd_2d", 1)), parity-tested like the 1-D kernels.  Measured on MI355X it reaches
-// 205 / 240 / 246 TFLOP/s (algorithmic) on 256->256@512^2 / 512->512@256^2 / 1024->1024@128^2 against 203 / 213 / 216 for
-// the 1-D kernel, but is slower once a load-side prologue is compiled in; without any staging the loop runs at 93 % of
-// the 2.25 x 157 TF/s ceiling, and the ablation puts the gap on the input-transform item (64 vector instructions +
-// 8 ds_write_b128 per 64 MFMAs, un-hidden because vector and LDS-write work never overlap the fp32 MFMA here): a V value
-// feeds only CT/32 = 2 MFMAs, and CT cannot grow because the accumulators already fill the register file.
+// STATUS: used by default for the 3x3 layers with >= 512 output channels in fp32 mode (option "winograd_2d" = 512; 0 = never),
+// parity-tested like the 1-D kernels.  Measured on MI355X it reaches 205 / 240 / 246 TFLOP/s (algorithmic) on 256->256@512^2 /
+// 512->512@256^2 / 1024->1024@128^2 against 203 / 213 / 216 for the 1-D kernel, but is slower once a load-side prologue is
+// compiled in; without any staging the loop runs at 93 % of the 2.25 x 157 TF/s ceiling, and the ablation puts the gap on the
+// input-transform item (64 vector instructions + 8 ds_write_b128 per 64 MFMAs, un-hidden because vector and LDS-write work
+// never overlap the fp32 MFMA here): a V value feeds only CT/32 = 2 MFMAs, and CT cannot grow because the accumulators already
+// fill the register file.
 //
 // A wave holds 16 accumulator tiles = 256 registers, so the kernel runs ONE wave per SIMD (256 threads, 512-register
 // budget).  On gfx950 that costs nothing: the fp32 MFMA does not co-execute with vector instructions and a second wave
@@ -28,24 +29,8 @@
 #include "conv_internal.h"
 
 #include <type_traits>
-#include <utility>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
-
-template <int K>
-using sc_int = std::integral_constant<int, K>;
-template <class F, int... S>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, S...>) {
-    (f(sc_int<S>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 struct W2 {
     static constexpr int CK = 8, CT = 64, NTHREADS = 256;
@@ -67,8 +52,6 @@ struct W2Params {
     int64_t x_bs, y_bs;
     cwfa_conv_opts o;
 };
-
-__device__ __forceinline__ int acc_row(int r, int kh) { return (r & 3) + 8 * (r >> 2) + 4 * kh; }
 
 __device__ __forceinline__ void rowop(float x0, float x1, float x2, float x3, float (&o)[4]) {
     o[0] = x0 - x2;
@@ -132,15 +115,11 @@ __global__ __launch_bounds__(W2::NTHREADS) void conv3x3_wino2d_kernel(W2Params p
     }
     const bool has_aff = PRO && p.o.in_scale != nullptr, has_add = PRO && p.o.in_add != nullptr;
     const int xbytes = (int)((int64_t)p.Cin * HW * 4);
-    const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x + (int64_t)b * p.x_bs), 0, xbytes, 0x00020000);
-    const auto ra = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(has_add ? p.o.in_add + (int64_t)b * p.o.in_add_bs : p.x), 0, has_add ? xbytes : 0, 0x00020000);
-    const auto rsc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(has_aff ? p.o.in_scale + (int64_t)b * p.o.in_affine_bs : p.x), 0, has_aff ? p.Cin * 4 : 0, 0x00020000);
-    const auto rsh = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(has_aff ? p.o.in_shift + (int64_t)b * p.o.in_affine_bs : p.x), 0, has_aff ? p.Cin * 4 : 0, 0x00020000);
-    const auto rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wp + (int64_t)ct * p.nchunks * C::US), 0,
-                                                      p.nchunks * C::US * 4, 0x00020000);
+    const auto rx = CWFA_RSRC(p.x + (int64_t)b * p.x_bs, xbytes);
+    const auto ra = CWFA_RSRC(has_add ? p.o.in_add + (int64_t)b * p.o.in_add_bs : p.x, has_add ? xbytes : 0);
+    const auto rsc = CWFA_RSRC(has_aff ? p.o.in_scale + (int64_t)b * p.o.in_affine_bs : p.x, has_aff ? p.Cin * 4 : 0);
+    const auto rsh = CWFA_RSRC(has_aff ? p.o.in_shift + (int64_t)b * p.o.in_affine_bs : p.x, has_aff ? p.Cin * 4 : 0);
+    const auto rw = CWFA_RSRC(p.wp + (int64_t)ct * p.nchunks * C::US, p.nchunks * C::US * 4);
     const int chunk_bytes = (int)(C::CK * HW * 4);
     auto ldf = [](decltype(rx) r, unsigned vo, int so) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0)); };
     auto ldrow = [&](decltype(rx) r, int a, int so, float (&d)[6]) {
@@ -250,7 +229,7 @@ __global__ __launch_bounds__(W2::NTHREADS) void conv3x3_wino2d_kernel(W2Params p
         // second buffer's operand offsets past the 16-bit ds_read immediate (one v_add per read)
         int cur = set;
         asm volatile("" : "+s"(cur));
-        static_for<NSTEP>([&](auto sc) {
+        cwfa_static_for<NSTEP>([&](auto sc) {
             constexpr int s = decltype(sc)::value, cp = s & 7;
             if constexpr (s + DEPTH == NSTEP && more) __syncthreads();
             if constexpr (s + DEPTH < NSTEP) {
@@ -263,8 +242,8 @@ __global__ __launch_bounds__(W2::NTHREADS) void conv3x3_wino2d_kernel(W2Params p
             if constexpr (more && s >= SLOT0 && (s - SLOT0) % SLOTD == 0 && (s - SLOT0) / SLOTD < NITEM) {
                 constexpr int k = (s - SLOT0) / SLOTD;
                 if constexpr (k == 0) {
-                    store_v(sc_int<set ^ 1>{}, cur ^ 1);
-                    load_v(sc_int<set ^ 1>{}, chunk + 3);      // past the last chunk: out of range, reads zeros, never stored
+                    store_v(cwfa_ic<set ^ 1>{}, cur ^ 1);
+                    load_v(cwfa_ic<set ^ 1>{}, chunk + 3);      // past the last chunk: out of range, reads zeros, never stored
                 } else {
                     store_u(k - 1, cur ^ 1);
                     load_u(k - 1, chunk + 2);
@@ -274,15 +253,15 @@ __global__ __launch_bounds__(W2::NTHREADS) void conv3x3_wino2d_kernel(W2Params p
         });
     };
 
-    load_v(sc_int<0>{}, 0);
-    static_for<C::UPT>([&](auto kc) { load_u(decltype(kc)::value, 0); });
-    load_v(sc_int<1>{}, 1);
-    store_v(sc_int<0>{}, 0);
-    static_for<C::UPT>([&](auto kc) {
+    load_v(cwfa_ic<0>{}, 0);
+    cwfa_static_for<C::UPT>([&](auto kc) { load_u(decltype(kc)::value, 0); });
+    load_v(cwfa_ic<1>{}, 1);
+    store_v(cwfa_ic<0>{}, 0);
+    cwfa_static_for<C::UPT>([&](auto kc) {
         store_u(decltype(kc)::value, 0);
         load_u(decltype(kc)::value, 1);
     });
-    load_v(sc_int<0>{}, 2);
+    load_v(cwfa_ic<0>{}, 2);
     __syncthreads();
 #pragma unroll
     for (int s = 0; s < DEPTH; ++s) ld(0, s, s);
@@ -290,14 +269,14 @@ __global__ __launch_bounds__(W2::NTHREADS) void conv3x3_wino2d_kernel(W2Params p
     typedef std::false_type F;
     int chunk = 0;
     for (; chunk + 2 < p.nchunks; chunk += 2) {
-        chunk_body(sc_int<0>{}, chunk, T{});
-        chunk_body(sc_int<1>{}, chunk + 1, T{});
+        chunk_body(cwfa_ic<0>{}, chunk, T{});
+        chunk_body(cwfa_ic<1>{}, chunk + 1, T{});
     }
     if (chunk + 1 < p.nchunks) {            // two chunks left
-        chunk_body(sc_int<0>{}, chunk, T{});
-        chunk_body(sc_int<1>{}, chunk + 1, F{});
+        chunk_body(cwfa_ic<0>{}, chunk, T{});
+        chunk_body(cwfa_ic<1>{}, chunk + 1, F{});
     } else {                                // one chunk left
-        chunk_body(sc_int<0>{}, chunk, F{});
+        chunk_body(cwfa_ic<0>{}, chunk, F{});
     }
 
     // ---- epilogue: Y = A^T M A per accumulator row, bias / activation, 2x2 pixels per lane and channel
@@ -332,7 +311,7 @@ __global__ __launch_bounds__(W2::NTHREADS) void conv3x3_wino2d_kernel(W2Params p
             for (int k = 0; k < 4; ++k) mine[(r * 4 + k) * 64] = yv[k >> 1][k & 1];
         }
         for (int r = 0; r < 16; ++r) {
-            const int co = ct * C::CT + wm * 32 + acc_row(r, kh);
+            const int co = ct * C::CT + wm * 32 + cwfa_acc_row(r, kh);
             if (co >= p.Cout) continue;
             const float bias = p.o.bias ? p.o.bias[co] : 0.f;
             for (int k = 0; k < 4; ++k) {
@@ -349,7 +328,7 @@ __global__ __launch_bounds__(W2::NTHREADS) void conv3x3_wino2d_kernel(W2Params p
         if constexpr (EPI == W2EPI_PRELU) alpha = *p.o.prelu_alpha;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int co = ct * C::CT + wm * 32 + acc_row(r, kh);
+            const int co = ct * C::CT + wm * 32 + cwfa_acc_row(r, kh);
             if (co >= p.Cout) continue;
             const float bias = p.o.bias ? p.o.bias[co] : 0.f;
             float yv[2][2];

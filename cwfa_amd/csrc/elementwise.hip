@@ -338,20 +338,11 @@ extern "C" int cwfa_gather_f32(const float* x, const int64_t* perm, float* y, in
 }
 
 // ------------------------------------------------------------------------------------------------ affine apply
-__device__ __forceinline__ float soft_clamp(float a, int kind, float clamp) {
-    switch (kind) {
-        case CWFA_CLAMP_ATAN: return clamp * (0.636f * cwfa_atan(a));
-        case CWFA_CLAMP_TANH: return clamp * cwfa_tanh(a);
-        case CWFA_CLAMP_SIGMOID: return clamp * (2.f * (1.f / (1.f + expf(-a)) - 0.5f));
-        default: return clamp * a;
-    }
-}
-
 // read s (clamped) and t of a stage at linear in-sample offset `off`
 __device__ __forceinline__ void stage_st(const cwfa_affine_stage& st, int b, int64_t off, float& s, float& t) {
     s = 0.f;
     t = 0.f;
-    if (st.s_raw) s = soft_clamp(st.s_raw[b * st.s_bs + off] * st.pre_scale, st.clamp_kind, st.clamp);
+    if (st.s_raw) s = cwfa_soft_clamp(st.s_raw[b * st.s_bs + off] * st.pre_scale, st.clamp_kind, st.clamp);
     if (st.t) {
         const float tv = st.t[b * st.t_bs + off];
         t = st.t_neg_div_sqrt2 ? (-tv) / CWFA_SQRT2_F : tv * st.pre_scale;
@@ -739,72 +730,41 @@ __global__ __launch_bounds__(256) void chain_fwd_rows_kernel(const float* __rest
 // coefficients are always read at the thread's own columns: a column permutation moves the travelling VALUES between the
 // threads of a row through an 8 KB LDS exchange (one barrier each), so occupancy is not limited by LDS and a chain without
 // column permutations uses none.
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 // The coefficient rows, the low band and z are read ONCE by this kernel: non-temporal loads (no L2 allocation) move the inverse
 // chain from 4.75 to 5.0 TB/s and the forward chain from 4.6 to 5.0 - 5.3 TB/s at 48 channels x 512 x 512 (tools/chain_time.py);
-// non-temporal STORES add another 4 % to the inverse chain (5.25 TB/s) and cost the forward chain 2 %: CH_NT = 2 stores
-// non-temporally in the inverse direction only.
-#ifndef CH_NT
-#define CH_NT 2          // 0: plain accesses, 1: non-temporal loads, 2: + non-temporal stores of the inverse chain's output
-#endif
-#ifndef CH_SCALAR
-#define CH_SCALAR 0      // (tuning) 1: the block's row index through readfirstlane where a wave holds one row (scalar table loads)
-#endif
-__device__ __forceinline__ f4 ld_stream(const float* p) {
-#if CH_NT
-    return __builtin_nontemporal_load(reinterpret_cast<const f4*>(p));
-#else
-    return *reinterpret_cast<const f4*>(p);
-#endif
-}
+// non-temporal STORES add another 4 % to the inverse chain (5.25 TB/s) and cost the forward chain 2 %: stores are
+// non-temporal in the inverse direction only (NT).
+__device__ __forceinline__ f32x4 ld_stream(const float* p) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p)); }
 template <bool NT>
-__device__ __forceinline__ void st_stream(float* p, f4 v) {
-    if constexpr (NT && CH_NT > 1) __builtin_nontemporal_store(v, reinterpret_cast<f4*>(p));
-    else *reinterpret_cast<f4*>(p) = v;
+__device__ __forceinline__ void st_stream(float* p, f32x4 v) {
+    if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
+    else *reinterpret_cast<f32x4*>(p) = v;
 }
 
 // s (clamped) and t of four columns from the raw float4 rows of a stage
-__device__ __forceinline__ void stage_st4(const cwfa_affine_stage& st, const f4& sr, const f4& tr, f4& s, f4& t) {
+__device__ __forceinline__ void stage_st4(const cwfa_affine_stage& st, const f32x4& sr, const f32x4& tr, f32x4& s, f32x4& t) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        s[j] = st.s_raw ? soft_clamp(sr[j] * st.pre_scale, st.clamp_kind, st.clamp) : 0.f;
+        s[j] = st.s_raw ? cwfa_soft_clamp(sr[j] * st.pre_scale, st.clamp_kind, st.clamp) : 0.f;
         t[j] = st.t ? (st.t_neg_div_sqrt2 ? (-tr[j]) / CWFA_SQRT2_F : tr[j] * st.pre_scale) : 0.f;
     }
 }
 
-#ifndef CH_BLOCK
-#define CH_BLOCK 256     // (tuning) threads per block of chain_rows4_kernel: a block covers CH_BLOCK * 4 pixels = whole image rows
-#endif
-#ifndef CH_WAVES
-#define CH_WAVES 0       // (tuning) minimum waves per SIMD asked of the register allocator (0: none)
-#endif
+constexpr int CHAIN_THREADS = 256;     // threads per block of chain_rows4_kernel: a block covers CHAIN_THREADS * 4 pixels = whole image rows
 // NS: stages the register arrays are sized for (6 covers a CAT step: five conditional affines + the trailing permutation; sized for
 // CWFA_CHAIN_MAX = 8 the kernel held 87 registers = five waves per SIMD -- with <= 80 it holds six, i.e. 1536 resident blocks, which the
 // 1536 x 2^k blocks of the 6 / 12 / 24 / 48-channel levels at 512 x 512 fill in whole rounds)
 template <bool INV, int NS = CWFA_CHAIN_MAX>
-#if CH_WAVES
-__global__ __launch_bounds__(CH_BLOCK, CH_WAVES) void chain_rows4_kernel(
-#else
-__global__ __launch_bounds__(CH_BLOCK) void chain_rows4_kernel(
-#endif
-const float* __restrict__ a0, float* __restrict__ a1, float* __restrict__ a2,
-                                                          cwfa_chain ch, const int64_t* __restrict__ final_perm, int C, int H, int W,
-                                                          int64_t bs0, int64_t bs1, int64_t bs2, double* __restrict__ logdet,
-                                                          double* __restrict__ sumsq) {
+__global__ __launch_bounds__(CHAIN_THREADS) void chain_rows4_kernel(const float* __restrict__ a0, float* __restrict__ a1, float* __restrict__ a2,
+                                                                    cwfa_chain ch, const int64_t* __restrict__ final_perm, int C, int H, int W,
+                                                                    int64_t bs0, int64_t bs1, int64_t bs2, double* __restrict__ logdet,
+                                                                    double* __restrict__ sumsq) {
     // INV:  a0 = low [C], a1 = x out [2C], a2 = z in (may be null = zeros, const in effect)      (bs0, bs1, bs2 alike)
     // !INV: a0 = x in [2C], a1 = low out [C], a2 = z out [C]
     extern __shared__ float rows[];          // [2][row of the block][W]: exchange buffers of the travelling values (column gathers)
     __shared__ double red[16];
-    const int tpr = W >> 2, RB = CH_BLOCK / tpr;
-#if CH_SCALAR
-    // a wave holds ONE image row when a row takes a multiple of 64 threads: the row index (and every table entry read with it)
-    // is then wave-uniform and goes through the scalar unit
-    const int r = (tpr & 63) == 0 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x / tpr) : (int)threadIdx.x / tpr;
-    const int w4 = ((int)threadIdx.x - r * tpr) * 4;
-#else
+    const int tpr = W >> 2, RB = CHAIN_THREADS / tpr;
     const int r = threadIdx.x / tpr, w4 = (threadIdx.x - r * tpr) * 4;
-#endif
     const int b = blockIdx.z, c = blockIdx.y, hh = blockIdx.x * RB + r;
     const bool live = hh < H;
     const int h = live ? hh : H - 1;
@@ -825,8 +785,8 @@ const float* __restrict__ a0, float* __restrict__ a1, float* __restrict__ a2,
             }
     }
     // ---- every global load of this thread, back to back
-    f4 sr[NS], tr[NS];
-    const f4 zero = {0.f, 0.f, 0.f, 0.f};
+    f32x4 sr[NS], tr[NS];
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
         sr[k] = tr[k] = zero;
@@ -836,27 +796,27 @@ const float* __restrict__ a0, float* __restrict__ a1, float* __restrict__ a2,
             if (ch.stage[k].t) tr[k] = ld_stream(ch.stage[k].t + b * ch.stage[k].t_bs + off);
         }
     }
-    f4 v0 = zero, lo = zero, own0 = zero, own1 = zero;
+    f32x4 v0 = zero, lo = zero, own0 = zero, own1 = zero;
     const int64_t so = ((int64_t)src.h) * W + w4, oo = (int64_t)h * W + w4;
     if constexpr (INV) {
         if (a2) v0 = ld_stream(a2 + b * bs2 + (int64_t)src.c * HW + so);
         lo = ld_stream(a0 + b * bs0 + (int64_t)c * HW + oo);
     } else {
-        const f4 e0 = *reinterpret_cast<const f4*>(a0 + b * bs0 + (int64_t)(2 * src.c) * HW + so);      // (x is read twice: cached)
-        const f4 e1 = *reinterpret_cast<const f4*>(a0 + b * bs0 + (int64_t)(2 * src.c + 1) * HW + so);
-        own0 = *reinterpret_cast<const f4*>(a0 + b * bs0 + (int64_t)(2 * c) * HW + oo);
-        own1 = *reinterpret_cast<const f4*>(a0 + b * bs0 + (int64_t)(2 * c + 1) * HW + oo);
+        const f32x4 e0 = *reinterpret_cast<const f32x4*>(a0 + b * bs0 + (int64_t)(2 * src.c) * HW + so);      // (x is read twice: cached)
+        const f32x4 e1 = *reinterpret_cast<const f32x4*>(a0 + b * bs0 + (int64_t)(2 * src.c + 1) * HW + so);
+        own0 = *reinterpret_cast<const f32x4*>(a0 + b * bs0 + (int64_t)(2 * c) * HW + oo);
+        own1 = *reinterpret_cast<const f32x4*>(a0 + b * bs0 + (int64_t)(2 * c + 1) * HW + oo);
         v0 = (e0 - e1) * CWFA_INV_SQRT2_F;
     }
     // ---- coefficients at the thread's OWN four columns, then the chain.  A column permutation moves the travelling values
     // between the threads of a row (through one LDS row, double-buffered: one barrier per column permutation); channel and
     // row permutations only changed which rows were loaded above.
-    f4 ev[NS], tv[NS];
+    f32x4 ev[NS], tv[NS];
     float ssum = 0.f;
 #pragma unroll
     for (int k = 0; k < NS; ++k)
         if (k < n) {
-            f4 sv;
+            f32x4 sv;
             stage_st4(ch.stage[k], sr[k], tr[k], sv, tv[k]);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -864,7 +824,7 @@ const float* __restrict__ a0, float* __restrict__ a1, float* __restrict__ a2,
                 ev[k][j] = __expf(INV ? -sv[j] : sv[j]);          // v_exp_f32(s * log2 e): |s| <= clamp, relative error ~2e-7
             }
         }
-    f4 v = v0;
+    f32x4 v = v0;
     int nx = 0;
 #pragma unroll
     for (int k = 0; k < NS; ++k)
@@ -872,7 +832,7 @@ const float* __restrict__ a0, float* __restrict__ a1, float* __restrict__ a2,
             if (ch.stage[k].perm && ch.stage[k].perm_axis == 3) {           // uniform over the block
                 float* buf = rows + (size_t)((nx & 1) * RB + r) * W;
                 ++nx;
-                *reinterpret_cast<f4*>(buf + w4) = v;
+                *reinterpret_cast<f32x4*>(buf + w4) = v;
                 __syncthreads();
                 const int64_t* pk = ch.stage[k].perm + w4;
 #pragma unroll
@@ -886,8 +846,8 @@ const float* __restrict__ a0, float* __restrict__ a1, float* __restrict__ a2,
             st_stream<true>(a1 + b * bs1 + (int64_t)(2 * c) * HW + oo, (lo + v) * CWFA_INV_SQRT2_F);
             st_stream<true>(a1 + b * bs1 + (int64_t)(2 * c + 1) * HW + oo, (lo - v) * CWFA_INV_SQRT2_F);
         } else {
-            *reinterpret_cast<f4*>(a1 + b * bs1 + (int64_t)c * HW + oo) = (own0 + own1) * CWFA_INV_SQRT2_F;
-            *reinterpret_cast<f4*>(a2 + b * bs2 + (int64_t)c * HW + oo) = v;
+            *reinterpret_cast<f32x4*>(a1 + b * bs1 + (int64_t)c * HW + oo) = (own0 + own1) * CWFA_INV_SQRT2_F;
+            *reinterpret_cast<f32x4*>(a2 + b * bs2 + (int64_t)c * HW + oo) = v;
 #pragma unroll
             for (int j = 0; j < 4; ++j) sq += (double)v[j] * (double)v[j];
         }
@@ -1050,7 +1010,7 @@ static bool chain_rows_ok(const cwfa_chain* ch, int C, int H, int W, int B, size
 // 16-byte form usable?  W = 4 * (a divisor of 256), every row base and batch stride on a 16-byte boundary
 static bool chain_rows4_ok(const cwfa_chain* ch, int C, int H, int W, int B, size_t* lds, const void* p0, const void* p1,
                            const void* p2, int64_t bs0, int64_t bs1, int64_t bs2) {
-    if (W < 64 || (W & 3) || (W >> 2) > CH_BLOCK || CH_BLOCK % (W >> 2) != 0 || C > 65535 || B > 65535) return false;
+    if (W < 64 || (W & 3) || (W >> 2) > CHAIN_THREADS || CHAIN_THREADS % (W >> 2) != 0 || C > 65535 || B > 65535) return false;
     if (!cwfa_aligned16(p0) || !cwfa_aligned16(p1) || (p2 && !cwfa_aligned16(p2)) || (bs0 & 3) || (bs1 & 3) || (p2 && (bs2 & 3))) return false;
     for (int k = 0; k < ch->n_stages; ++k) {
         const cwfa_affine_stage& st = ch->stage[k];
@@ -1058,7 +1018,7 @@ static bool chain_rows4_ok(const cwfa_chain* ch, int C, int H, int W, int B, siz
     }
     bool col = false;
     for (int k = 0; k < ch->n_stages; ++k) col = col || (ch->stage[k].perm && ch->stage[k].perm_axis == 3);
-    *lds = col ? (size_t)2 * CH_BLOCK * 4 * sizeof(float) : 0;      // two exchange rows per block row, only for column gathers
+    *lds = col ? (size_t)2 * CHAIN_THREADS * 4 * sizeof(float) : 0;      // two exchange rows per block row, only for column gathers
     return *lds <= 64 * 1024;
 }
 
@@ -1084,12 +1044,12 @@ extern "C" int cwfa_chain_inv_f32(const float* z, const float* low, float* x, co
     if (B == 0 || n == 0) return CWFA_OK;
     size_t lds;
     if (chain_rows4_ok(ch, C, H, W, B, &lds, low, x, z, low_bs, x_bs, z_bs)) {
-        const int RB = CH_BLOCK * 4 / W;
+        const int RB = CHAIN_THREADS * 4 / W;
         if (ch->n_stages <= 6)
-            hipLaunchKernelGGL((chain_rows4_kernel<true, 6>), dim3((H + RB - 1) / RB, C, B), dim3(CH_BLOCK), lds, (hipStream_t)stream, low, x,
+            hipLaunchKernelGGL((chain_rows4_kernel<true, 6>), dim3((H + RB - 1) / RB, C, B), dim3(CHAIN_THREADS), lds, (hipStream_t)stream, low, x,
                                const_cast<float*>(z), *ch, (const int64_t*)nullptr, C, H, W, low_bs, x_bs, z_bs, logdet, (double*)nullptr);
         else
-            hipLaunchKernelGGL((chain_rows4_kernel<true, CWFA_CHAIN_MAX>), dim3((H + RB - 1) / RB, C, B), dim3(CH_BLOCK), lds, (hipStream_t)stream, low, x,
+            hipLaunchKernelGGL((chain_rows4_kernel<true, CWFA_CHAIN_MAX>), dim3((H + RB - 1) / RB, C, B), dim3(CHAIN_THREADS), lds, (hipStream_t)stream, low, x,
                                const_cast<float*>(z), *ch, (const int64_t*)nullptr, C, H, W, low_bs, x_bs, z_bs, logdet, (double*)nullptr);
         CWFA_LAUNCH_CHECK("cwfa_chain_inv_f32");
         return CWFA_OK;
@@ -1118,12 +1078,12 @@ extern "C" int cwfa_chain_fwd_f32(const float* x, float* low, float* z, const cw
     if (B == 0 || n == 0) return CWFA_OK;
     size_t lds;
     if (chain_rows4_ok(ch, C, H, W, B, &lds, x, low, z, x_bs, low_bs, z_bs)) {
-        const int RB = CH_BLOCK * 4 / W;
+        const int RB = CHAIN_THREADS * 4 / W;
         if (ch->n_stages <= 6)
-            hipLaunchKernelGGL((chain_rows4_kernel<false, 6>), dim3((H + RB - 1) / RB, C, B), dim3(CH_BLOCK), lds, (hipStream_t)stream, x, low, z,
+            hipLaunchKernelGGL((chain_rows4_kernel<false, 6>), dim3((H + RB - 1) / RB, C, B), dim3(CHAIN_THREADS), lds, (hipStream_t)stream, x, low, z,
                                *ch, final_perm, C, H, W, x_bs, low_bs, z_bs, logdet, sumsq);
         else
-            hipLaunchKernelGGL((chain_rows4_kernel<false, CWFA_CHAIN_MAX>), dim3((H + RB - 1) / RB, C, B), dim3(CH_BLOCK), lds, (hipStream_t)stream, x, low, z,
+            hipLaunchKernelGGL((chain_rows4_kernel<false, CWFA_CHAIN_MAX>), dim3((H + RB - 1) / RB, C, B), dim3(CHAIN_THREADS), lds, (hipStream_t)stream, x, low, z,
                                *ch, final_perm, C, H, W, x_bs, low_bs, z_bs, logdet, sumsq);
         CWFA_LAUNCH_CHECK("cwfa_chain_fwd_f32");
         return CWFA_OK;

@@ -5,7 +5,6 @@
 // ------------------------------------------------------------------------------------------------ BatchNorm statistics
 // grid (splits, C, B): each block sums a contiguous slice of one (sample, channel) plane and adds (sum, sumsq) in double.
 // Per thread the partial sums of <= 64 elements stay in fp32 pairs feeding doubles (the products are exact in double).
-typedef float cs_f4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void channel_stats_kernel(const float* __restrict__ x, double* __restrict__ stats, int64_t HW,
                                                             int64_t x_bs, int vec_ok) {
     __shared__ double red[16];
@@ -16,10 +15,10 @@ __global__ __launch_bounds__(256) void channel_stats_kernel(const float* __restr
     double s = 0.0, q = 0.0;
     if (vec_ok && (lo & 3) == 0) {
         const int64_t n4 = (hi - lo) >> 2;
-        const cs_f4* p4 = reinterpret_cast<const cs_f4*>(p + lo);
+        const f32x4* p4 = reinterpret_cast<const f32x4*>(p + lo);
         int64_t i = threadIdx.x;
         for (; i + 3 * (int64_t)blockDim.x < n4; i += 4 * (int64_t)blockDim.x) {        // four 16-byte loads in flight per thread
-            cs_f4 v[4];
+            f32x4 v[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) v[u] = p4[i + u * (int64_t)blockDim.x];
 #pragma unroll
@@ -29,7 +28,7 @@ __global__ __launch_bounds__(256) void channel_stats_kernel(const float* __restr
             }
         }
         for (; i < n4; i += blockDim.x) {
-            const cs_f4 v = p4[i];
+            const f32x4 v = p4[i];
             s += ((double)v[0] + (double)v[1]) + ((double)v[2] + (double)v[3]);
             q += ((double)v[0] * v[0] + (double)v[1] * v[1]) + ((double)v[2] * v[2] + (double)v[3] * v[3]);
         }
@@ -252,14 +251,14 @@ __global__ __launch_bounds__(256) void maxpool2x2_kernel(const float* __restrict
     const int oy = (int)(i / wq), q = (int)(i % wq);
     const float sc = scale ? scale[c] : 1.f, sh = shift ? shift[c] : 0.f;
     const int64_t o = (int64_t)bc * H * W + (int64_t)(2 * oy) * W + 4 * q;
-    cs_f4 r0 = *reinterpret_cast<const cs_f4*>(x + o), r1 = *reinterpret_cast<const cs_f4*>(x + o + W);
+    f32x4 r0 = *reinterpret_cast<const f32x4*>(x + o), r1 = *reinterpret_cast<const f32x4*>(x + o + W);
     if (scale) {
         r0 = r0 * sc + sh;
         r1 = r1 * sc + sh;
     }
     if (full) {
-        *reinterpret_cast<cs_f4*>(full + o) = r0;
-        *reinterpret_cast<cs_f4*>(full + o + W) = r1;
+        *reinterpret_cast<f32x4*>(full + o) = r0;
+        *reinterpret_cast<f32x4*>(full + o + W) = r1;
     }
     float m[2];
 #pragma unroll
