@@ -20,6 +20,7 @@ from torch import Tensor
 from ... import autograd as AG
 from ... import ops
 from ..modules.base import InvertibleModule
+from ...amp import amp_entry
 
 __all__ = ["SequenceINN", "ReversibleSequential", "GraphINN", "ReversibleGraphNet", "Node", "InputNode",
            "ConditionNode", "OutputNode", "topological_order"]
@@ -187,6 +188,7 @@ class GraphINN(InvertibleModule):
         return self.global_out_shapes
 
     # ------------------------------------------------------------------ execution
+    @amp_entry
     def forward(self, x_or_z: Union[Tensor, Iterable[Tensor]], c: Iterable[Tensor] = None, rev: bool = False,
                 jac: bool = True, intermediate_outputs: bool = False, x: None = None, sumsq: Tensor = None):
         """``sumsq`` (extension, optional float64[1] device tensor): the fused forward plan adds ||Z||^2 into it, which
@@ -627,6 +629,7 @@ class ReversibleGraphNet(GraphINN):
                              "switch to GraphINN.")
         super().__init__(node_list, verbose=verbose, force_tuple_output=force_tuple_output)
 
+    @amp_entry
     def forward(self, x_or_z, c=None, rev=False, jac=True, intermediate_outputs=False):
         warnings.warn("ReversibleGraphNet's forward() now returns a tuple (output, jacobian). It will be removed in the "
                       "next version of FrEIA.", DeprecationWarning)
@@ -659,6 +662,7 @@ class SequenceINN(InvertibleModule):
             raise ValueError("You can only call output_dims on a SequentialINN when setting force_tuple_output=True.")
         return input_dims
 
+    @amp_entry
     def forward(self, x_or_z, c=None, rev=False, jac=True):
         order = range(len(self.module_list))
         total = 0

@@ -17,6 +17,7 @@ import torch.nn as nn
 from ... import autograd as AG
 from ... import ops
 from .base import InvertibleModule, as_jac, new_logdet
+from ...amp import amp_entry
 
 __all__ = ["NICECouplingBlock", "RNVPCouplingBlock", "GLOWCouplingBlock", "GINCouplingBlock",
            "AffineCouplingOneSided", "ConditionalAffineTransform", "AllInOneBlock"]
@@ -99,6 +100,7 @@ class _TwoSided(_BaseCouplingBlock):
             y1, j1 = couple(x1, self._cond(y2, c), 2, l1)
         return (AG.concat([y1, y2]),), ((j1 + j2) if self._has_jac() else 0.)
 
+    @amp_entry
     def forward(self, x, c=[], rev=False, jac=True):
         x0 = x[0]
         if AG.tracking(x0, list(c), self):
@@ -192,6 +194,7 @@ class AffineCouplingOneSided(_BaseCouplingBlock):
         super().__init__(dims_in, dims_c, clamp, clamp_activation)
         self.subnet = subnet_constructor(self.split_len1 + self.condition_length, 2 * self.split_len2)
 
+    @amp_entry
     def forward(self, x, c=[], rev=False, jac=True):
         x0 = x[0]
         l1 = self.split_len1
@@ -232,6 +235,7 @@ class ConditionalAffineTransform(_BaseCouplingBlock):
         s_raw, t, tneg = self.coefficients(c)
         return self._stage(s_raw, t, t_neg_div_sqrt2=tneg, perm=perm, axis=axis)
 
+    @amp_entry
     def forward(self, x, c=[], rev=False, jac=True):
         if AG.tracking(x[0], list(c), self):
             s_raw, t, tneg = self.coefficients(c)
@@ -403,6 +407,7 @@ class AllInOneBlock(InvertibleModule):
         j = j + (-1) ** int(rev) * n_pix * torch.log(scale).sum()
         return (out,), j
 
+    @amp_entry
     def forward(self, x, c=[], rev=False, jac=True):
         if AG.tracking(x[0], list(c), self):
             return self._forward_tracked(x[0], c, rev)

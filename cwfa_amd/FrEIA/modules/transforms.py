@@ -15,6 +15,7 @@ import torch.nn as nn
 from ... import autograd as AG
 from ... import ops
 from .base import InvertibleModule
+from ...amp import amp_entry
 
 __all__ = ["PermuteRandom", "Fixed1x1Conv", "Split", "Concat", "HaarDownsampling", "HaarUpsampling", "ActNorm",
            "Split1D", "SplitChannel", "Concat1d", "ConcatChannel"]
@@ -45,6 +46,7 @@ class PermuteRandom(InvertibleModule):
     def table(self, rev):
         return self.perm_inv if rev else self.perm
 
+    @amp_entry
     def forward(self, x, rev=False, jac=True):
         if AG.tracking(x[0]):
             return [AG.gather(x[0], self.table(rev), 1, self.table(not rev))], 0.
@@ -75,6 +77,7 @@ class Fixed1x1Conv(InvertibleModule):
             pc = self._packed[rev] = ops.pack_conv_weight(w)
         return pc
 
+    @amp_entry
     def forward(self, x, rev=False, jac=True):
         n_pixels = x[0][0, 0].numel()
         j = self.logDetM * n_pixels
@@ -115,6 +118,7 @@ class Split(InvertibleModule):
                     section_sizes = list(section_sizes) + [l_dim - sum(section_sizes)]
             self.split_size_or_sections = section_sizes
 
+    @amp_entry
     def forward(self, x, rev=False, jac=True):
         if self.dim != 0:
             raise NotImplementedError("cwfa_amd Split: only the channel axis (dim=0) is on the HIP path")
@@ -146,6 +150,7 @@ class Concat(InvertibleModule):
         self.dim = dim
         self.split_size_or_sections = [dims_in[i][dim] for i in range(len(dims_in))]
 
+    @amp_entry
     def forward(self, x, rev=False, jac=True):
         if self.dim != 0:
             raise NotImplementedError("cwfa_amd Concat: only the channel axis (dim=0) is on the HIP path")
@@ -199,6 +204,7 @@ class HaarDownsampling(InvertibleModule):
         hw[3, 0, 1, 0] = hw[3, 0, 0, 1] = -1
         self.haar_weights = nn.Parameter(torch.cat([hw] * self.in_channels, 0), requires_grad=False)
 
+    @amp_entry
     def forward(self, x, c=None, jac=True, rev=False):
         inp = x[0]
         ndims = inp[0].numel()
@@ -226,6 +232,7 @@ class HaarUpsampling(HaarDownsampling):
         inv_shape = self.output_dims(dims_in)
         super().__init__(inv_shape, dims_c, order_by_wavelet, rebalance)
 
+    @amp_entry
     def forward(self, x, c=None, jac=True, rev=False):
         return super().forward(x, c=None, rev=not rev)
 
@@ -274,6 +281,7 @@ class ActNorm(InvertibleModule):
             self.bias.data = (-(mean * scale.exp())).to(torch.float32).view_as(self.bias)
         self.init_on_next_batch = False
 
+    @amp_entry
     def forward(self, x, rev=False, jac=True):
         if self.init_on_next_batch:
             self._initialize_with_data(x[0])

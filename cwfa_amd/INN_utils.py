@@ -12,6 +12,7 @@ import torch.nn as nn
 from . import autograd as AG
 from . import ops
 from .FrEIA import modules as Fm
+from .amp import amp_entry
 
 __all__ = ["HaarTransform1D", "PermuteDim"]
 
@@ -43,6 +44,7 @@ class PermuteDim(Fm.InvertibleModule):
     def table(self, rev):
         return self.perm_inv if rev else self.perm
 
+    @amp_entry
     def forward(self, x, rev=False, jac=True):
         if AG.tracking(x[0]):
             return [AG.gather(x[0], self.table(rev), self.axis, self.table(not rev))], 0.
@@ -66,6 +68,7 @@ class HaarTransform1D(Fm.InvertibleModule):
         self.jac_fwd = (np.log(16.) + 4 * np.log(self.fac_fwd)) / 4.
         self.jac_rev = (np.log(16.) + 4 * np.log(self.fac_rev)) / 4.
 
+    @amp_entry
     def forward(self, x_in, c=None, jac=True, rev=False):
         x = x_in[0]
         ndims = x[0].numel()

@@ -5,17 +5,25 @@ over hand-written HIP kernels in ``libcwfa_hip.so`` (C ABI: include/cwfa_hip.h).
 ops raise on non-HIP tensors and on a missing extension.
 
     import cwfa_amd; cwfa_amd.install()     # then the reference's main.py imports resolve to this package
+    cwfa_amd.install(precision="fp16")      # ... for its default --use_half_precision 1 (autocast)
 """
 import sys
 
 __version__ = "0.1.0"
 
 
-def install():
+def install(precision=None):
     """Register this package's modules under the reference's top-level import names (FrEIA, INN_utils, networks, unet)
     so that code written against the reference (``import FrEIA.framework as Ff``, ``from networks import *``) runs on
-    the HIP implementation unchanged.  Call before importing the reference's driver."""
+    the HIP implementation unchanged.  Call before importing the reference's driver.
+
+    ``precision``: None leaves the arithmetic as it is; a mode name ("fp32", "split_bf16", "bf16", "fp16") is passed to
+    ``ops.set_precision``.  "fp16" is the arithmetic of the reference's default ``--use_half_precision 1`` (CUDA autocast:
+    fp16 operands, fp32 accumulation); the installed modules compute the same inside and outside an autocast region."""
     from . import FrEIA, INN_utils, networks, unet
+    if precision is not None:
+        from . import ops
+        ops.set_precision(precision)
     sys.modules["FrEIA"] = FrEIA
     sys.modules["FrEIA.framework"] = FrEIA.framework
     sys.modules["FrEIA.modules"] = FrEIA.modules

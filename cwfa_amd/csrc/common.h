@@ -29,6 +29,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr;
 
@@ -188,8 +189,16 @@ __device__ __forceinline__ int cwfa_acc_row(int r, int kh) { return (r & 3) + 8 
 // The three-way bf16 split of the fp32-equivalent kernels: v = a1 + a2 + a3 EXACTLY (24 significand bits; each difference is
 // exact: the subtrahend is the minuend rounded to 8 significant bits).  SIX = false: the leading piece only (plain bf16
 // operands, `split_products` = 1); a2 and a3 are then not written.
-template <bool SIX>
+// F16 (`split_operand` = 1, single product only): the one piece is the fp16 value instead, round to nearest even like torch's
+// .half() (v_cvt_f16_f32, not the round-toward-zero packed form); beyond +-65504 it is +-inf.  Its bits ride in the __bf16:
+// the LDS images and fragments are 16-bit lanes either way, and the F16 MFMA reads them as fp16 (CWFA_MFMA_OP).
+template <bool SIX, bool F16 = false>
 __device__ __forceinline__ void cwfa_split3(float v, __bf16& a1, __bf16& a2, __bf16& a3) {
+    static_assert(!(SIX && F16), "fp16 operands: single product only");
+    if constexpr (F16) {
+        a1 = __builtin_bit_cast(__bf16, (_Float16)v);
+        return;
+    }
     a1 = (__bf16)v;
     if constexpr (SIX) {
         const float r1 = v - (float)a1;
@@ -201,4 +210,15 @@ __device__ __forceinline__ void cwfa_split3(float v, __bf16& a1, __bf16& a2, __b
 
 // c += a . b on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16), and a scheduling barrier no instruction is moved across
 #define CWFA_MFMA(a, b, c) c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
+// the same product with fp16 operands (v_mfma_f32_16x16x32_f16: the A / B fragment layouts of the two forms are the same)
+#define CWFA_MFMA_F16(a, b, c) \
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0)
+// CWFA_MFMA or CWFA_MFMA_F16 by the kernel's operand format
+#define CWFA_MFMA_OP(F16, a, b, c) \
+    do {                           \
+        if constexpr (F16)         \
+            CWFA_MFMA_F16(a, b, c); \
+        else                       \
+            CWFA_MFMA(a, b, c);    \
+    } while (0)
 #define CWFA_FENCE() __builtin_amdgcn_sched_barrier(0)

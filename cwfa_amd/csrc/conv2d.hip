@@ -664,6 +664,7 @@ int launch(const ConvParams& p, int epi, hipStream_t st) {
 
 }  // namespace
 int g_cwfa_split_products = 6;
+int g_cwfa_split_operand = 0;         // "split_operand": 0 bf16, 1 fp16 (with split_products = 1 only)
 int g_cwfa_split_xcd_map = 1;
 int g_cwfa_split_rows16 = 1;
 namespace {
@@ -698,6 +699,8 @@ int fill_params(ConvParams& p, const char* name, const float* x, const float* w_
 //   * weights are split at pack time into [cout tile][chunk of 16 ci][piece][k half][256 cout][8];
 //   * the GEMM kernel moves both with LDS-DMA (buffer_load ... lds, no staging registers, two chunks ahead, three LDS
 //     buffers), block = 256 cout x 8 rows x 32 px, 8 waves of 2 x 4 accumulator tiles, the epilogues of the fp32 path.
+//   * F16 (`split_operand` = 1, one product): plane 0 of the input and piece 0 of the weights hold fp16 values (round to nearest
+//     even), only they are moved, and the product runs on v_mfma_f32_32x32x16_f16 (same fragment layout as the bf16 form).
 typedef Cfg<1, 16, 2, 4, 4, 2> CS;     // 256 ch x 8 rows x 32 cols, 512 threads (geometry only: staging is its own)
 constexpr int CS_XB = 3 * 2 * 8 * 32 * 16, CS_WB = 3 * 2 * 256 * 16, CS_BUFB = CS_XB + CS_WB;    // bytes per LDS buffer
 
@@ -713,7 +716,11 @@ __device__ __forceinline__ void split3(float v, unsigned short (&o)[3]) {
     o[2] = __builtin_bit_cast(unsigned short, a3);
 }
 
-// grid (ceil(HW/256), CG2, B): thread = one pixel of one group of 8 channels
+// fp16 bits of v, round to nearest even (beyond +-65504: +-inf)
+__device__ __forceinline__ unsigned short f16_bits(float v) { return __builtin_bit_cast(unsigned short, (_Float16)v); }
+
+// grid (ceil(HW/256), CG2, B): thread = one pixel of one group of 8 channels.  F16: plane 0 only, in fp16
+template <bool F16 = false>
 __global__ __launch_bounds__(256) void split_input_kernel(const float* __restrict__ x, uint4* __restrict__ ws, int Cin, int CG2,
                                                           int64_t HW, int64_t x_bs, const float* __restrict__ sc,
                                                           const float* __restrict__ sh, int64_t aff_bs,
@@ -731,12 +738,16 @@ __global__ __launch_bounds__(256) void split_input_kernel(const float* __restric
             if (sc) v = v * sc[(int64_t)b * aff_bs + c] + sh[(int64_t)b * aff_bs + c];
             if (add) v += add[(int64_t)b * add_bs + (int64_t)c * HW + px];
         }
+        if constexpr (F16) {
+            pc[0][j] = f16_bits(v);
+            continue;
+        }
         unsigned short o[3];
         split3(v, o);
         pc[0][j] = o[0]; pc[1][j] = o[1]; pc[2][j] = o[2];
     }
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
+    for (int q = 0; q < (F16 ? 1 : 3); ++q) {
         uint4 u;
         u.x = pc[q][0] | ((unsigned)pc[q][1] << 16);
         u.y = pc[q][2] | ((unsigned)pc[q][3] << 16);
@@ -746,7 +757,8 @@ __global__ __launch_bounds__(256) void split_input_kernel(const float* __restric
     }
 }
 
-// one thread per (cout tile, chunk, tap, k half, cout) 8-channel fragment: writes its three pieces
+// one thread per (cout tile, chunk, tap, k half, cout) 8-channel fragment: writes its three pieces (F16: the fp16 value, two zeros)
+template <bool F16 = false>
 __global__ __launch_bounds__(256) void split_pack_kernel(const float* __restrict__ w, uint4* __restrict__ out, int Cout, int Cin,
                                                          int nchunks, int taps, int transposed, int64_t total) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       // over [ctile][chunk][tap][h][co 256]
@@ -762,6 +774,11 @@ __global__ __launch_bounds__(256) void split_pack_kernel(const float* __restrict
         float v = 0.f;
         if (co < Cout && ci < Cin)
             v = transposed ? w[((int64_t)ci * (Cout / 4) + (co >> 2)) * 4 + (co & 3)] : w[((int64_t)co * Cin + ci) * taps + tap];
+        if constexpr (F16) {
+            pc[0][j] = f16_bits(v);
+            pc[1][j] = pc[2][j] = 0;
+            continue;
+        }
         unsigned short o[3];
         split3(v, o);
         pc[0][j] = o[0]; pc[1][j] = o[1]; pc[2][j] = o[2];
@@ -784,7 +801,7 @@ struct SplitParams {
     int64_t ws_bs;          // bytes per sample
 };
 
-template <int EPI>
+template <int EPI, bool F16 = false>
 __global__ __launch_bounds__(512, 1) void conv1x1_split_kernel(SplitParams sp) {
     typedef CS C;
     const ConvParams& p = sp.c;
@@ -808,13 +825,14 @@ __global__ __launch_bounds__(512, 1) void conv1x1_split_kernel(SplitParams sp) {
     const auto rx = CWFA_RSRC(reinterpret_cast<const char*>(sp.ws) + (int64_t)t.b * sp.ws_bs, (int)sp.ws_bs);
     const auto rw = CWFA_RSRC(reinterpret_cast<const char*>(p.wp) + (int64_t)t.ct * p.nchunks * CS_WB, p.nchunks * CS_WB);
     const int xchunk = (int)(2 * HW * 16);
+    constexpr int NPC = F16 ? 1 : 3;             // pieces moved (entry i = piece i)
     auto dma = [&](int chunk, int buf) {          // chunks past the end: out of range, zeros, never read
         char* base = lds + buf * CS_BUFB + wave * 1024;
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
+        for (int i = 0; i < NPC; ++i)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr)(base + i * 8192), 16, xoff[i], chunk * xchunk, 0, 0);
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
+        for (int i = 0; i < NPC; ++i)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(base + CS_XB + i * 8192), 16, (unsigned)(tid + i * 512) * 16u,
                                                      chunk * CS_WB, 0, 0);
     };
@@ -832,7 +850,8 @@ __global__ __launch_bounds__(512, 1) void conv1x1_split_kernel(SplitParams sp) {
 
     dma(0, 0);
     dma(1, 1);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+    if constexpr (F16) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     int buf = 0;
     for (int chunk = 0; chunk < p.nchunks; ++chunk) {
@@ -858,6 +877,11 @@ __global__ __launch_bounds__(512, 1) void conv1x1_split_kernel(SplitParams sp) {
             for (int m = 0; m < 2; ++m) {
                 // smallest terms first: (3,1) (2,2) (1,3) (2,1) (1,2) (1,1)
                 f32x16 c = acc[m][n];
+                if constexpr (F16) {
+                    acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, A[m][0]), __builtin_bit_cast(f16x8, Bq[n & 1][0]),
+                                                                       c, 0, 0, 0);
+                    continue;
+                }
                 if (six) {
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[m][2], Bq[n & 1][0], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[m][1], Bq[n & 1][1], c, 0, 0, 0);
@@ -869,8 +893,9 @@ __global__ __launch_bounds__(512, 1) void conv1x1_split_kernel(SplitParams sp) {
                 acc[m][n] = c;
             }
         }
-        // the DMA of chunk + 1 (issued one chunk ago) must have landed everywhere; the six just issued may stay in flight
-        asm volatile("s_waitcnt vmcnt(6)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+        // the DMA of chunk + 1 (issued one chunk ago) must have landed everywhere; the six (F16: two) just issued may stay in flight
+        if constexpr (F16) asm volatile("s_waitcnt vmcnt(2)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(6)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         buf = buf + 1 == 3 ? 0 : buf + 1;
     }
@@ -879,7 +904,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_split_kernel(SplitParams sp) {
     epilogue<C, EPI>(p, t, acc);
 }
 
-template <int EPI>
+template <int EPI, bool F16 = false>
 int launch_split(SplitParams sp, hipStream_t stream) {
     ConvParams& p = sp.c;
     p.tiles_x = (p.W + CS::TC - 1) / CS::TC;
@@ -888,7 +913,7 @@ int launch_split(SplitParams sp, hipStream_t stream) {
     CWFA_REQUIRE((int64_t)p.tiles_x * p.tiles_y < (1ll << 31) && ctiles <= 65535 && p.B <= 65535, CWFA_E_SHAPE,
                  "cwfa_conv_split_f32: grid too large");
     constexpr int LDS = 3 * CS_BUFB;
-    auto kern = &conv1x1_split_kernel<EPI>;
+    auto kern = &conv1x1_split_kernel<EPI, F16>;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
@@ -902,6 +927,9 @@ int launch_split(SplitParams sp, hipStream_t stream) {
     CWFA_LAUNCH_CHECK("cwfa_conv_split_f32");
     return CWFA_OK;
 }
+
+// fp16 operands in the single-product kernels
+bool split_f16() { return g_cwfa_split_products == 1 && g_cwfa_split_operand != 0; }
 
 }  // namespace
 
@@ -921,8 +949,12 @@ extern "C" int cwfa_split_input_f32(const float* x, void* ws, int B, int Cin, in
     if (B == 0 || HW == 0) return CWFA_OK;
     const int CG2 = 2 * ((Cin + 15) / 16);
     CWFA_REQUIRE((int64_t)3 * CG2 * HW * 16 < (1ll << 31), CWFA_E_SHAPE, "cwfa_split_input_f32: one sample's planes must stay below 2 GiB");
-    hipLaunchKernelGGL(split_input_kernel, dim3((unsigned)((HW + 255) / 256), CG2, B), dim3(256), 0, (hipStream_t)stream, x,
-                       reinterpret_cast<uint4*>(ws), Cin, CG2, HW, x_bs, in_scale, in_shift, in_affine_bs, in_add, in_add_bs);
+    if (split_f16())
+        hipLaunchKernelGGL(split_input_kernel<true>, dim3((unsigned)((HW + 255) / 256), CG2, B), dim3(256), 0, (hipStream_t)stream, x,
+                           reinterpret_cast<uint4*>(ws), Cin, CG2, HW, x_bs, in_scale, in_shift, in_affine_bs, in_add, in_add_bs);
+    else
+        hipLaunchKernelGGL(split_input_kernel<>, dim3((unsigned)((HW + 255) / 256), CG2, B), dim3(256), 0, (hipStream_t)stream, x,
+                           reinterpret_cast<uint4*>(ws), Cin, CG2, HW, x_bs, in_scale, in_shift, in_affine_bs, in_add, in_add_bs);
     CWFA_LAUNCH_CHECK("cwfa_split_input_f32");
     return CWFA_OK;
 }
@@ -939,8 +971,12 @@ extern "C" int cwfa_conv_split_pack_f32(const float* w, void* packed, int Cout, 
     CWFA_REQUIRE(cwfa_aligned16(packed), CWFA_E_ALIGN, "cwfa_conv_split_pack_f32: packed image must be 16-byte aligned");
     const int nchunks = (Cin + 15) / 16, taps = ks * ks;
     const int64_t total = (int64_t)((Cout + 255) / 256) * nchunks * taps * 512;
-    hipLaunchKernelGGL(split_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
-                       reinterpret_cast<uint4*>(packed), Cout, Cin, nchunks, taps, transposed, total);
+    if (split_f16())
+        hipLaunchKernelGGL(split_pack_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
+                           reinterpret_cast<uint4*>(packed), Cout, Cin, nchunks, taps, transposed, total);
+    else
+        hipLaunchKernelGGL(split_pack_kernel<>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
+                           reinterpret_cast<uint4*>(packed), Cout, Cin, nchunks, taps, transposed, total);
     CWFA_LAUNCH_CHECK("cwfa_conv_split_pack_f32");
     return CWFA_OK;
 }
@@ -967,6 +1003,13 @@ extern "C" int cwfa_conv_split_f32(const void* ws, const void* w_packed, float* 
                  "cwfa_conv_split_f32: one sample's planes / one cout tile's weights must stay below 2 GiB");
     const int epi = classify_epilogue(p.o);
     hipStream_t st = (hipStream_t)stream;
+    if (split_f16()) {
+        switch (epi) {
+            case EPI_NONE: return launch_split<EPI_NONE, true>(sp, st);
+            case EPI_UP: return launch_split<EPI_UP, true>(sp, st);
+            default: return launch_split<EPI_GENERIC, true>(sp, st);
+        }
+    }
     switch (epi) {
         case EPI_NONE: return launch_split<EPI_NONE>(sp, st);
         case EPI_UP: return launch_split<EPI_UP>(sp, st);
@@ -1003,9 +1046,18 @@ extern "C" int cwfa_set_option(const char* name, int value) {
         g_cwfa_split_rows16 = value;
         return CWFA_OK;
     }
-    if (strcmp(name, "split_products") == 0) {      // 6: fp32-accurate split; 1: plain bf16 operands (BASELINE configs[4])
+    if (strcmp(name, "split_products") == 0) {      // 6: fp32-accurate split; 1: plain bf16 / fp16 operands (BASELINE configs[4])
         CWFA_REQUIRE(value == 1 || value == 6, CWFA_E_INVAL, "cwfa_set_option: split_products must be 1 or 6");
+        CWFA_REQUIRE(value == 1 || g_cwfa_split_operand == 0, CWFA_E_INVAL,
+                     "cwfa_set_option: split_products = 6 needs split_operand = 0 (the three-piece split is a bf16 format)");
         g_cwfa_split_products = value;
+        return CWFA_OK;
+    }
+    if (strcmp(name, "split_operand") == 0) {       // 0: bf16 operands; 1: fp16 operands (single product only)
+        CWFA_REQUIRE(value == 0 || value == 1, CWFA_E_INVAL, "cwfa_set_option: split_operand must be 0 (bf16) or 1 (fp16)");
+        CWFA_REQUIRE(value == 0 || g_cwfa_split_products == 1, CWFA_E_INVAL,
+                     "cwfa_set_option: split_operand = 1 (fp16) needs split_products = 1 (fp16 operands take one product)");
+        g_cwfa_split_operand = value;
         return CWFA_OK;
     }
     cwfa_set_error("cwfa_set_option: unknown option '%s'", name);

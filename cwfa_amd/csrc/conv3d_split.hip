@@ -1,7 +1,8 @@
 // Fused condition-net 3-D stage  Conv3d(1->K, 3^3) -> PReLU -> Conv3d(K->1, 3^3)  (networks.py:221-225,239) with
 // fp32-equivalent arithmetic on the bf16 matrix cores: every fp32 operand is split EXACTLY into three bf16 pieces and the
 // six partial products with i + j <= 4 are accumulated in fp32 by v_mfma_f32_16x16x32_bf16 (conv_split3x3.hip has the
-// argument; `split_products` = 1: plain bf16 operands, BASELINE.json configs[4]).  K <= 32.
+// argument; `split_products` = 1: plain bf16 operands, BASELINE.json configs[4]; with `split_operand` = 1 as well: plain fp16
+// operands on v_mfma_f32_16x16x32_f16, template flag F16).  K <= 32.
 //
 // Both convolutions are GEMMs over N = 16 hidden voxels of one image row (lanes n = lane & 15; g = lane >> 4):
 //   conv1   hid[k][n] = b1[k] + sum_tap w1[k][tap] x[voxel n + tap]      M = k (2 m-tiles), K = 27 taps (of 32 slots)
@@ -22,6 +23,7 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 extern int g_cwfa_split_products;       // conv2d.hip ("split_products" option: 6 or 1)
+extern int g_cwfa_split_operand;        // conv2d.hip ("split_operand" option: 0 bf16, 1 fp16)
 
 namespace {
 
@@ -48,6 +50,7 @@ struct P3 {
 
 // (returns the product instead of assigning it like CWFA_MFMA: mfma6 below chains it through a value)
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
+#define MFMA_F16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0)
 
 // (v0, v1) -> the packed pairs of their three bf16 pieces (round-to-nearest split: v = p0 + p1 + p2 exactly).  The packed
 // conversion result passes through an EMPTY asm statement: seeing through `pk << 16` the compiler would otherwise convert the
@@ -60,8 +63,18 @@ __device__ __forceinline__ unsigned cvt_pk_bf16(float a, float b) {
     asm("" : "+v"(r));
     return r;
 }
-template <bool SIX>
+// (v0, v1) -> their fp16 values (round to nearest even: v_cvt_f16_f32, not the round-toward-zero packed form), packed
+__device__ __forceinline__ unsigned cvt_pk_f16(float a, float b) {
+    const unsigned lo = __builtin_bit_cast(unsigned short, (_Float16)a), hi = __builtin_bit_cast(unsigned short, (_Float16)b);
+    return lo | (hi << 16);
+}
+template <bool SIX, bool F16 = false>
 __device__ __forceinline__ void split_pair(float v0, float v1, unsigned (&pk)[3]) {
+    static_assert(!(SIX && F16), "fp16 operands: single product only");
+    if constexpr (F16) {
+        pk[0] = cvt_pk_f16(v0, v1);
+        return;
+    }
     pk[0] = cvt_pk_bf16(v0, v1);
     if constexpr (SIX) {
         const float r0 = v0 - __builtin_bit_cast(float, pk[0] << 16), r1 = v1 - __builtin_bit_cast(float, pk[0] & 0xffff0000u);
@@ -71,13 +84,13 @@ __device__ __forceinline__ void split_pair(float v0, float v1, unsigned (&pk)[3]
     }
 }
 
-template <bool SIX>
+template <bool SIX, bool F16 = false>
 __device__ __forceinline__ void pack8(const float (&v)[8], bf16x8 (&out)[SIX ? 3 : 1]) {
     u32x4 w[3];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         unsigned pk[3];
-        split_pair<SIX>(v[2 * i], v[2 * i + 1], pk);
+        split_pair<SIX, F16>(v[2 * i], v[2 * i + 1], pk);
 #pragma unroll
         for (int q = 0; q < (SIX ? 3 : 1); ++q) w[q][i] = pk[q];
     }
@@ -86,8 +99,9 @@ __device__ __forceinline__ void pack8(const float (&v)[8], bf16x8 (&out)[SIX ? 3
 }
 
 // six products, those of b's first piece first: they can start as soon as that piece is converted
-template <bool SIX>
+template <bool SIX, bool F16 = false>
 __device__ __forceinline__ f32x4 mfma6(f32x4 c, const bf16x8 (&a)[SIX ? 3 : 1], const bf16x8 (&b)[SIX ? 3 : 1]) {
+    if constexpr (F16) return MFMA_F16(a[0], b[0], c);
     if constexpr (SIX) {
         c = MFMA(a[2], b[0], c);
         c = MFMA(a[1], b[0], c);
@@ -103,7 +117,7 @@ __device__ __forceinline__ f32x4 mfma6(f32x4 c, const bf16x8 (&a)[SIX ? 3 : 1], 
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-template <bool SIX>
+template <bool SIX, bool F16 = false>
 __global__ __launch_bounds__(512, 1) void conv3d_split_kernel(P3 p) {
     typedef G3 C;
     constexpr int NQ = SIX ? 3 : 1;
@@ -133,7 +147,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_kernel(P3 p) {
             const float wv = p.w1[min(k, K - 1) * 27 + min(tap, 26)];
             v[j] = (k < K && tap < 27) ? wv : 0.f;
         }
-        pack8<SIX>(v, A1[t]);
+        pack8<SIX, F16>(v, A1[t]);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int kk = 16 * t + 4 * g + r;
@@ -151,7 +165,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_kernel(P3 p) {
             const float wv = p.w2[min(k, K - 1) * 27 + min(9 * dh + 3 * dw + dd, 26)];
             v[j] = (k < K && dh < 3 && dw < 3) ? wv : 0.f;
         }
-        pack8<SIX>(v, A2[dd]);
+        pack8<SIX, F16>(v, A2[dd]);
     }
 
     // ---- x staging: entry e = tid + 512 i of the 18 x 34 slab tile
@@ -180,7 +194,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_kernel(P3 p) {
 #pragma unroll
         for (int i = 0; i < C::NEK; ++i) {
             unsigned pk[3] = {0u, 0u, 0u};
-            split_pair<SIX>(xr[i], 0.f, pk);
+            split_pair<SIX, F16>(xr[i], 0.f, pk);
             if (xin[i]) *reinterpret_cast<u32x2*>(lds + slot * C::SLABB + xlo[i]) = u32x2{(pk[0] & 0xffffu) | (pk[1] << 16), pk[2] & 0xffffu};
         }
     };
@@ -308,7 +322,7 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_kernel(P3 p) {
                 rd_b1(e[1], a, 1);
                 mk_b1(e[0], B1);
 #pragma unroll
-                for (int t = 0; t < 2; ++t) hd[0][t] = mfma6<SIX>(bias1[t], A1[t], B1);
+                for (int t = 0; t < 2; ++t) hd[0][t] = mfma6<SIX, F16>(bias1[t], A1[t], B1);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int col = 0; col < NCOL; ++col) {
@@ -316,17 +330,17 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_kernel(P3 p) {
                     float hv[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) hv[j] = __builtin_amdgcn_fmed3f(hd[col & 1][j >> 2][j & 3], alpha * hd[col & 1][j >> 2][j & 3], prelu_m);
-                    pack8<SIX>(hv, B2[col & 1]);
+                    pack8<SIX, F16>(hv, B2[col & 1]);
                     if (col + 1 < NCOL) {
                         mk_b1(e[(col + 1) & 1], B1);
                         if (col + 2 < NCOL) rd_b1(e[col & 1], a, col + 2);
 #pragma unroll
-                        for (int t = 0; t < 2; ++t) hd[(col + 1) & 1][t] = mfma6<SIX>(bias1[t], A1[t], B1);
+                        for (int t = 0; t < 2; ++t) hd[(col + 1) & 1][t] = mfma6<SIX, F16>(bias1[t], A1[t], B1);
                     }
                     if (col > 0) {
-                        ring[S0][col - 1] = mfma6<SIX>(zero4, A2[0], B2[(col - 1) & 1]);
-                        ring[S1][col - 1] = mfma6<SIX>(ring[S1][col - 1], A2[1], B2[(col - 1) & 1]);
-                        ring[S2][col - 1] = mfma6<SIX>(ring[S2][col - 1], A2[2], B2[(col - 1) & 1]);
+                        ring[S0][col - 1] = mfma6<SIX, F16>(zero4, A2[0], B2[(col - 1) & 1]);
+                        ring[S1][col - 1] = mfma6<SIX, F16>(ring[S1][col - 1], A2[1], B2[(col - 1) & 1]);
+                        ring[S2][col - 1] = mfma6<SIX, F16>(ring[S2][col - 1], A2[2], B2[(col - 1) & 1]);
                     }
 #pragma unroll
                     for (int i = 0; i < (SIX ? 30 : 5); ++i) {
@@ -335,9 +349,9 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_kernel(P3 p) {
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                ring[S0][NCOL - 1] = mfma6<SIX>(zero4, A2[0], B2[(NCOL - 1) & 1]);
-                ring[S1][NCOL - 1] = mfma6<SIX>(ring[S1][NCOL - 1], A2[1], B2[(NCOL - 1) & 1]);
-                ring[S2][NCOL - 1] = mfma6<SIX>(ring[S2][NCOL - 1], A2[2], B2[(NCOL - 1) & 1]);
+                ring[S0][NCOL - 1] = mfma6<SIX, F16>(zero4, A2[0], B2[(NCOL - 1) & 1]);
+                ring[S1][NCOL - 1] = mfma6<SIX, F16>(ring[S1][NCOL - 1], A2[1], B2[(NCOL - 1) & 1]);
+                ring[S2][NCOL - 1] = mfma6<SIX, F16>(ring[S2][NCOL - 1], A2[2], B2[(NCOL - 1) & 1]);
             } else {
                 if (late) side_work();
 #pragma unroll
@@ -361,17 +375,17 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_kernel(P3 p) {
                     mk_b1(e, B1);
                     f32x4 hd[2];
 #pragma unroll
-                    for (int t = 0; t < 2; ++t) hd[t] = mfma6<SIX>(bias1[t], A1[t], B1);
+                    for (int t = 0; t < 2; ++t) hd[t] = mfma6<SIX, F16>(bias1[t], A1[t], B1);
                     float hv[8];
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         const float v = __builtin_amdgcn_fmed3f(hd[j >> 2][j & 3], alpha * hd[j >> 2][j & 3], prelu_m);
                         hv[j] = in_w[nt] ? v : 0.f;
                     }
-                    pack8<SIX>(hv, B2);
-                    if (do0) ring[S0][col] = mfma6<SIX>(zero4, A2[0], B2);
-                    if (do1) ring[S1][col] = mfma6<SIX>(ring[S1][col], A2[1], B2);
-                    if (do2) ring[S2][col] = mfma6<SIX>(ring[S2][col], A2[2], B2);
+                    pack8<SIX, F16>(hv, B2);
+                    if (do0) ring[S0][col] = mfma6<SIX, F16>(zero4, A2[0], B2);
+                    if (do1) ring[S1][col] = mfma6<SIX, F16>(ring[S1][col], A2[1], B2);
+                    if (do2) ring[S2][col] = mfma6<SIX, F16>(ring[S2][col], A2[2], B2);
                 }
             }
         }
@@ -406,9 +420,9 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_kernel(P3 p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the x slab loaded past the end
 }
 
-template <bool SIX>
+template <bool SIX, bool F16 = false>
 int launch3(const P3& p, int B, int tiles, int chunks, hipStream_t st) {
-    auto kern = &conv3d_split_kernel<SIX>;
+    auto kern = &conv3d_split_kernel<SIX, F16>;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G3::LDS);
@@ -452,7 +466,9 @@ extern "C" int cwfa_conv3d_1k1_split_f32(const float* x, const float* w1, const 
     CWFA_REQUIRE(chunks <= 65535, CWFA_E_SHAPE, "cwfa_conv3d_1k1_split_f32: grid too large");
     P3 p{x, w1, b1, alpha, w2, b2, y, D, H, W, K, tw, DC};
     hipStream_t st = (hipStream_t)stream;
-    const int rc = g_cwfa_split_products != 1 ? launch3<true>(p, B, (int)tiles, chunks, st) : launch3<false>(p, B, (int)tiles, chunks, st);
+    const int rc = g_cwfa_split_products != 1 ? launch3<true>(p, B, (int)tiles, chunks, st)
+                   : g_cwfa_split_operand     ? launch3<false, true>(p, B, (int)tiles, chunks, st)
+                                              : launch3<false>(p, B, (int)tiles, chunks, st);
     if (rc != CWFA_OK) return rc;
     CWFA_LAUNCH_CHECK("cwfa_conv3d_1k1_split_f32");
     return CWFA_OK;

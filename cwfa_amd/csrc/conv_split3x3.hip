@@ -4,7 +4,8 @@
 //
 // Every fp32 operand is split EXACTLY into three bf16 pieces (24 significand bits) and the six partial products with
 // i + j <= 4 are accumulated in fp32 by v_mfma_f32_16x16x32_bf16 (dropped terms <= 2^-24 relative); `split_products` = 1:
-// plain bf16 operands (BASELINE.json configs[4]).  The input is the fp32 tensor itself: the load-side prologue of the UNet
+// plain bf16 operands (BASELINE.json configs[4]); with `split_operand` = 1 as well: plain fp16 operands on
+// v_mfma_f32_16x16x32_f16 (template flag F16; same fragments, LDS images and schedule).  The input is the fp32 tensor itself: the load-side prologue of the UNet
 // (BatchNorm affine x dropout mask of the producer, + skip tensor) is applied and the value split on the way into LDS.
 //
 // Block = 512 threads = 8 waves, two per SIMD, tile = CT = 64*MPW output channels x 8 rows x 32 pixels.  Wave (wm, wn) owns
@@ -25,6 +26,7 @@
 extern int g_cwfa_split_products;       // conv2d.hip ("split_products" option: 6 or 1)
 extern int g_cwfa_split_xcd_map;        // conv2d.hip ("split3x3_xcd_map" option)
 extern int g_cwfa_split_rows16;         // conv2d.hip ("split3x3_rows16" option: 16-row tiles for the 64-channel tiling)
+extern int g_cwfa_split_operand;        // conv2d.hip ("split_operand" option: 0 bf16, 1 fp16)
 
 namespace {
 
@@ -82,7 +84,8 @@ enum { EPI_RUNTIME = -1, EPI_COUPLE = -2 };
 // WM = channel groups per block (4: the form described above; 2 / 1: the narrow tilings for banks with <= 32 / <= 16 outputs -- the
 // condition nets' 2-D convolutions and the output convolutions of the coarse steps' sub-networks, networks.py:212-219,633-638 --
 // on the 16-row tile: the eight waves are WM channel groups x 8 / WM row groups of 16 WM / 8 rows each)
-template <int MPW, bool SIX, bool ADD, int ACT1, int KS = 3, int RPW = 4, int WM = 4>
+// F16: fp16 operands (single product only)
+template <int MPW, bool SIX, bool ADD, int ACT1, int KS = 3, int RPW = 4, int WM = 4, bool F16 = false>
 __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
     typedef XG<KS, RPW> G;
     constexpr int XC = G::XC, EPK = G::EPK, KHB = G::KHB, XPB = G::XPB, XB = G::XB, NTAP = G::NTAP, PAD = G::PAD;
@@ -201,7 +204,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
             if (has_aff) v = fok[k] ? v * scv[j] + shv[j] : 0.f;       // padding stays zero
             if constexpr (ADD) v += av[j];
             __bf16 a1, a2 = (__bf16)0.f, a3 = (__bf16)0.f;
-            cwfa_split3<SIX>(v, a1, a2, a3);
+            cwfa_split3<SIX, F16>(v, a1, a2, a3);
             pc[0][j] = a1; pc[1][j] = a2; pc[2][j] = a3;
         }
         char* dst = lds + buf * XB + ekh[k] * KHB + eidx[k] * 16;
@@ -261,7 +264,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
             CWFA_MFMA(a[1], bb[0], c);
             CWFA_MFMA(a[0], bb[1], c);
         }
-        CWFA_MFMA(a[0], bb[0], c);
+        CWFA_MFMA_OP(F16, a[0], bb[0], c);
     };
 
     // ---------------------------------------------------------------------------------------------- prologue
@@ -553,7 +556,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
 
 // packed image: [cout tile][step][piece 3][k group 4][CT][8] of bf16; group g of step s = unit u = 2s + (g >> 1) =
 // (chunk u / 9, tap u % 9), k half g & 1: element j = w[co][chunk*16 + (g&1)*8 + j][tap] (0 beyond Cout / Cin / the last unit)
-template <int CT>
+// F16: piece 0 holds the fp16 weights, pieces 1 and 2 are zero (the same image size and layout)
+template <int CT, bool F16 = false>
 __global__ __launch_bounds__(256) void split3x3_pack_kernel(const float* __restrict__ w, uint4* __restrict__ out, int Cout, int Cin,
                                                             int nchunks, int nsteps, int64_t total, int ntap) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       // over [ctile][step][g 4][co CT]
@@ -567,7 +571,12 @@ __global__ __launch_bounds__(256) void split3x3_pack_kernel(const float* __restr
         float v = 0.f;
         if (co < Cout && ci < Cin && chunk < nchunks) v = w[((int64_t)co * Cin + ci) * ntap + tap];
         __bf16 a1, a2, a3;
-        cwfa_split3<true>(v, a1, a2, a3);
+        if constexpr (F16) {
+            cwfa_split3<false, true>(v, a1, a2, a3);
+            a2 = a3 = __builtin_bit_cast(__bf16, (unsigned short)0);
+        } else {
+            cwfa_split3<true>(v, a1, a2, a3);
+        }
         pc[0][j] = __builtin_bit_cast(unsigned short, a1);
         pc[1][j] = __builtin_bit_cast(unsigned short, a2);
         pc[2][j] = __builtin_bit_cast(unsigned short, a3);
@@ -593,11 +602,11 @@ inline int wm_of(int Cout) { return Cout > 96 ? 4 : Cout > 64 ? 2 : Cout > 48 ? 
 inline int ct_of(int Cout) { return 16 * mpw_of(Cout) * wm_of(Cout); }
 inline int nsteps_of(int Cin, int ntap = 9) { return ntap * (((Cin + 15) / 16 + 1) / 2); }   // whole periods of two 16-channel chunks
 
-template <int MPW, bool SIX, bool ADD, int ACT1, int KS = 3, int RPW = 4, int WM = 4>
+template <int MPW, bool SIX, bool ADD, int ACT1, int KS = 3, int RPW = 4, int WM = 4, bool F16 = false>
 int launch(const SParams& p, hipStream_t stream) {
     typedef Geo<MPW, KS, RPW, WM> G;
     constexpr int TRW = XG<KS, RPW>::TRW;
-    auto kern = &conv3x3_split_kernel<MPW, SIX, ADD, ACT1, KS, RPW, WM>;
+    auto kern = &conv3x3_split_kernel<MPW, SIX, ADD, ACT1, KS, RPW, WM, F16>;
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
@@ -621,16 +630,26 @@ int launch(const SParams& p, hipStream_t stream) {
     return CWFA_OK;
 }
 
-template <int MPW, bool SIX>
-int launch_epi(const SParams& p, hipStream_t st) {
+// operand format of a launch: 0 = three-piece split, six products; 1 = plain bf16; 2 = plain fp16 (split_op())
+inline int split_op() { return g_cwfa_split_products != 1 ? 0 : g_cwfa_split_operand ? 2 : 1; }
+
+template <int MPW, bool ADD, int ACT1, int KS = 3, int RPW = 4, int WM = 4>
+int launch_op(int op, const SParams& p, hipStream_t st) {
+    if (op == 0) return launch<MPW, true, ADD, ACT1, KS, RPW, WM>(p, st);
+    if (op == 1) return launch<MPW, false, ADD, ACT1, KS, RPW, WM>(p, st);
+    return launch<MPW, false, ADD, ACT1, KS, RPW, WM, true>(p, st);
+}
+
+template <int MPW>
+int launch_epi(int op, const SParams& p, hipStream_t st) {
     const bool plain = !p.o.residual && p.o.act2 == CWFA_ACT_NONE;
     if (p.o.in_add) {
-        if (plain && p.o.act == CWFA_ACT_PRELU) return launch<MPW, SIX, true, CWFA_ACT_PRELU>(p, st);
-        return launch<MPW, SIX, true, EPI_RUNTIME>(p, st);
+        if (plain && p.o.act == CWFA_ACT_PRELU) return launch_op<MPW, true, CWFA_ACT_PRELU>(op, p, st);
+        return launch_op<MPW, true, EPI_RUNTIME>(op, p, st);
     }
-    if (plain && p.o.act == CWFA_ACT_PRELU) return launch<MPW, SIX, false, CWFA_ACT_PRELU>(p, st);
-    if (plain && p.o.act == CWFA_ACT_NONE) return launch<MPW, SIX, false, CWFA_ACT_NONE>(p, st);
-    return launch<MPW, SIX, false, EPI_RUNTIME>(p, st);
+    if (plain && p.o.act == CWFA_ACT_PRELU) return launch_op<MPW, false, CWFA_ACT_PRELU>(op, p, st);
+    if (plain && p.o.act == CWFA_ACT_NONE) return launch_op<MPW, false, CWFA_ACT_NONE>(op, p, st);
+    return launch_op<MPW, false, EPI_RUNTIME>(op, p, st);
 }
 
 }  // namespace
@@ -686,13 +705,13 @@ extern "C" int cwfa_conv3x3_split_couple_f32(const float* x, const void* w_packe
     CWFA_REQUIRE((int64_t)p.tiles_x * ((H + TR - 1) / TR) < (1ll << 31) && B <= 65535, CWFA_E_SHAPE,
                  "cwfa_conv3x3_split_couple_f32: grid too large");
     hipStream_t st = (hipStream_t)stream;
-    const bool six = g_cwfa_split_products != 1;
+    const int op = split_op();
     if (p.Cout == 64) {
         if (g_cwfa_split_rows16 && H > 8)       // 16-row tiles (no load-side prologue here by construction)
-            return six ? launch<1, true, false, EPI_COUPLE, 3, 8>(p, st) : launch<1, false, false, EPI_COUPLE, 3, 8>(p, st);
-        return six ? launch<1, true, false, EPI_COUPLE>(p, st) : launch<1, false, false, EPI_COUPLE>(p, st);
+            return launch_op<1, false, EPI_COUPLE, 3, 8>(op, p, st);
+        return launch_op<1, false, EPI_COUPLE>(op, p, st);
     }
-    return six ? launch<2, true, false, EPI_COUPLE>(p, st) : launch<2, false, false, EPI_COUPLE>(p, st);
+    return launch_op<2, false, EPI_COUPLE>(op, p, st);
 }
 
 extern "C" int64_t cwfa_conv3x3_split_packed_bytes(int Cout, int Cin) {
@@ -709,7 +728,15 @@ extern "C" int cwfa_conv3x3_split_pack_f32(const float* w, void* packed, int Cou
     const int64_t total = (int64_t)((Cout + ct - 1) / ct) * nsteps * 4 * ct;
     const dim3 grid((unsigned)((total + 255) / 256));
     uint4* out = reinterpret_cast<uint4*>(packed);
-    if (ct == 32) hipLaunchKernelGGL(split3x3_pack_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
+    if (split_op() == 2) {
+        if (ct == 32) hipLaunchKernelGGL((split3x3_pack_kernel<32, true>), grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
+        else if (ct == 48) hipLaunchKernelGGL((split3x3_pack_kernel<48, true>), grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
+        else if (ct == 96) hipLaunchKernelGGL((split3x3_pack_kernel<96, true>), grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
+        else if (ct == 16) hipLaunchKernelGGL((split3x3_pack_kernel<16, true>), grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
+        else if (mpw == 4) hipLaunchKernelGGL((split3x3_pack_kernel<256, true>), grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
+        else if (mpw == 2) hipLaunchKernelGGL((split3x3_pack_kernel<128, true>), grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
+        else hipLaunchKernelGGL((split3x3_pack_kernel<64, true>), grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
+    } else if (ct == 32) hipLaunchKernelGGL(split3x3_pack_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
     else if (ct == 48) hipLaunchKernelGGL(split3x3_pack_kernel<48>, grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
     else if (ct == 96) hipLaunchKernelGGL(split3x3_pack_kernel<96>, grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
     else if (ct == 16) hipLaunchKernelGGL(split3x3_pack_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
@@ -756,7 +783,7 @@ extern "C" int cwfa_conv3x3_split_f32(const float* x, const void* w_packed, floa
                  "cwfa_conv3x3_split_f32: one sample's input / output / one cout tile's weights must stay below 2 GiB");
     CWFA_REQUIRE((int64_t)p.tiles_x * ((H + TR - 1) / TR) < (1ll << 31) && B <= 65535, CWFA_E_SHAPE, "cwfa_conv3x3_split_f32: grid too large");
     hipStream_t st = (hipStream_t)stream;
-    const bool six = g_cwfa_split_products != 1;
+    const int op = split_op();
     const int wm = wm_of(Cout);
     if (wm != 4) {       // narrow tilings (<= 48 or 65 .. 96 outputs): 16-row tile, no load-side prologue, NCHW / blocked input, bias / PReLU / generic epilogue
         CWFA_REQUIRE(!p.o.in_scale && !p.o.in_add && !p.o.out_blocked8, CWFA_E_INVAL,
@@ -765,9 +792,9 @@ extern "C" int cwfa_conv3x3_split_f32(const float* x, const void* w_packed, floa
         const int epi = plain && p.o.act == CWFA_ACT_NONE ? 0 : plain && p.o.act == CWFA_ACT_PRELU ? 1 : 2;
 #define CWFA_NARROW(M, W_)                                                                                                                   \
     do {                                                                                                                                     \
-        if (epi == 0) return six ? launch<M, true, false, CWFA_ACT_NONE, 3, 8, W_>(p, st) : launch<M, false, false, CWFA_ACT_NONE, 3, 8, W_>(p, st);   \
-        if (epi == 1) return six ? launch<M, true, false, CWFA_ACT_PRELU, 3, 8, W_>(p, st) : launch<M, false, false, CWFA_ACT_PRELU, 3, 8, W_>(p, st); \
-        return six ? launch<M, true, false, EPI_RUNTIME, 3, 8, W_>(p, st) : launch<M, false, false, EPI_RUNTIME, 3, 8, W_>(p, st);                     \
+        if (epi == 0) return launch_op<M, false, CWFA_ACT_NONE, 3, 8, W_>(op, p, st);                                                    \
+        if (epi == 1) return launch_op<M, false, CWFA_ACT_PRELU, 3, 8, W_>(op, p, st);                                                   \
+        return launch_op<M, false, EPI_RUNTIME, 3, 8, W_>(op, p, st);                                                                    \
     } while (0)
         if (mpw == 3 && wm == 2) CWFA_NARROW(3, 2);
         if (mpw == 3) CWFA_NARROW(3, 1);
@@ -775,18 +802,18 @@ extern "C" int cwfa_conv3x3_split_f32(const float* x, const void* w_packed, floa
         CWFA_NARROW(1, 1);
 #undef CWFA_NARROW
     }
-    if (mpw == 4) return six ? launch_epi<4, true>(p, st) : launch_epi<4, false>(p, st);
-    if (mpw == 2) return six ? launch_epi<2, true>(p, st) : launch_epi<2, false>(p, st);
+    if (mpw == 4) return launch_epi<4>(op, p, st);
+    if (mpw == 2) return launch_epi<2>(op, p, st);
     // 64-channel tiling: 16-row tiles for the plain bias-only form (the output convolutions of the sub-networks)
     if (g_cwfa_split_rows16 && H > 8 && !p.o.in_scale && !p.o.in_add && !p.o.residual && p.o.act == CWFA_ACT_NONE && p.o.act2 == CWFA_ACT_NONE)
-        return six ? launch<2, true, false, CWFA_ACT_NONE, 3, 8, 2>(p, st) : launch<2, false, false, CWFA_ACT_NONE, 3, 8, 2>(p, st);
+        return launch_op<2, false, CWFA_ACT_NONE, 3, 8, 2>(op, p, st);
     // (two m-tiles per wave x two channel groups instead of one x four: the same 64 channels per block and the same packed image, but a
     //  B fragment feeds two m-tiles -- 30 instead of 51 ds_read_b128 per 96 MFMAs)
     // ... and for any other epilogue without a load-side prologue (activation / residual / second activation: the data-gradient and
     // unfused forward convolutions of the sub-networks in training, 64 -> 64): 160 -> ~100 us at 512 x 512
     if (g_cwfa_split_rows16 && H > 8 && !p.o.in_scale && !p.o.in_add)
-        return six ? launch<2, true, false, EPI_RUNTIME, 3, 8, 2>(p, st) : launch<2, false, false, EPI_RUNTIME, 3, 8, 2>(p, st);
-    return six ? launch_epi<1, true>(p, st) : launch_epi<1, false>(p, st);
+        return launch_op<2, false, EPI_RUNTIME, 3, 8, 2>(op, p, st);
+    return launch_epi<1>(op, p, st);
 }
 
 // ------------------------------------------------------------------------------------------------ 7x7 (ConvNeXt, networks.py:488)
@@ -801,8 +828,12 @@ extern "C" int cwfa_conv7x7_split_pack_f32(const float* w, void* packed, int Cou
     CWFA_REQUIRE(cwfa_aligned16(packed), CWFA_E_ALIGN, "cwfa_conv7x7_split_pack_f32: packed image must be 16-byte aligned");
     const int nchunks = (Cin + 15) / 16, nsteps = nsteps_of(Cin, 49);
     const int64_t total = (int64_t)nsteps * 4 * 64;
-    hipLaunchKernelGGL(split3x3_pack_kernel<64>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
-                       reinterpret_cast<uint4*>(packed), Cout, Cin, nchunks, nsteps, total, 49);
+    if (split_op() == 2)
+        hipLaunchKernelGGL((split3x3_pack_kernel<64, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
+                           reinterpret_cast<uint4*>(packed), Cout, Cin, nchunks, nsteps, total, 49);
+    else
+        hipLaunchKernelGGL(split3x3_pack_kernel<64>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
+                           reinterpret_cast<uint4*>(packed), Cout, Cin, nchunks, nsteps, total, 49);
     CWFA_LAUNCH_CHECK("cwfa_conv7x7_split_pack_f32");
     return CWFA_OK;
 }
@@ -829,5 +860,5 @@ extern "C" int cwfa_conv7x7_split_f32(const float* x, const void* w_packed, floa
     CWFA_REQUIRE((int64_t)p.tiles_x * ((H + TR - 1) / TR) < (1ll << 31) && B <= 65535, CWFA_E_SHAPE, "cwfa_conv7x7_split_f32: grid too large");
     hipStream_t st = (hipStream_t)stream;
     // (2 m-tiles per wave x 2 channel groups: a B fragment feeds two m-tiles -- 18 instead of 27 ds_read_b128 per 48 MFMAs)
-    return g_cwfa_split_products != 1 ? launch<2, true, false, CWFA_ACT_NONE, 7, 4, 2>(p, st) : launch<2, false, false, CWFA_ACT_NONE, 7, 4, 2>(p, st);
+    return launch_op<2, false, CWFA_ACT_NONE, 7, 4, 2>(split_op(), p, st);
 }

@@ -4,7 +4,8 @@
 //
 // Every fp32 operand is split EXACTLY into three bf16 pieces (v = v1 + v2 + v3: 3 x 8 = 24 significand bits) and the six
 // partial products with i + j <= 4 are accumulated in fp32 by v_mfma_f32_16x16x32_bf16 (dropped terms <= 2^-24 relative).
-// With `products == 1` only the leading piece is used: plain bf16 operands (BASELINE.json configs[4]).
+// With `products == 1` only the leading piece is used: plain bf16 operands (BASELINE.json configs[4]); with `split_operand` = 1
+// as well, plain fp16 operands on v_mfma_f32_16x16x32_f16 (template flag F16: same fragments, LDS images and schedule).
 // (16x16x32, not 32x32x16: under this load the chip is clock-limited by power and holds a 1.2x higher rate on the
 //  small shape -- tools/probe/mfma_shape.hip: 2200 vs 1800 TF/s bf16 with every operand re-read from LDS.)
 //
@@ -35,6 +36,7 @@
 
 extern int g_cwfa_split_products;       // conv2d.hip ("split_products" option: 6 or 1)
 extern int g_cwfa_split_xcd_map;        // conv2d.hip ("split3x3_xcd_map" option; also the tile walk of this kernel)
+extern int g_cwfa_split_operand;        // conv2d.hip ("split_operand" option: 0 bf16, 1 fp16)
 
 namespace {
 
@@ -95,7 +97,7 @@ __host__ __device__ constexpr int unit_off(int u) {
 // zeros and the four steps that pair only its taps add nothing: five conv steps per tile.  The odd LDS buffer is zeroed once (its tap 0
 // rides in step 4 beside tap 8 against zero weights); the next tile's chunk is requested during steps 0 .. 2 and written into the even
 // buffer behind step 4's barrier, at the head of the 1x1 phase (whose closing barrier publishes it).
-template <bool SIX, bool INB, bool OUTB, int NPER = 2, bool TAPE = false, bool XF = false, bool SHORT = false>
+template <bool SIX, bool INB, bool OUTB, int NPER = 2, bool TAPE = false, bool XF = false, bool SHORT = false, bool F16 = false>
 __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
     static_assert(!TAPE || (!INB && !OUTB && NPER == 2), "tape form: NCHW maps, full layer");
     static_assert(!XF || (NPER == 1 && !INB && !TAPE), "fused first map: the composed first-layer form");
@@ -167,7 +169,7 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             __bf16 a1, a2 = (__bf16)0.f, a3 = (__bf16)0.f;
-            cwfa_split3<SIX>(xv[j >> 2][j & 3], a1, a2, a3);
+            cwfa_split3<SIX, F16>(xv[j >> 2][j & 3], a1, a2, a3);
             pc[0][j] = a1; pc[1][j] = a2; pc[2][j] = a3;
         }
         if (fin[k]) {
@@ -222,7 +224,7 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
             CWFA_MFMA(a[1], b[0], c);
             CWFA_MFMA(a[0], b[1], c);
         }
-        CWFA_MFMA(a[0], b[0], c);
+        CWFA_MFMA_OP(F16, a[0], b[0], c);
     };
     auto bbase_of = [&](int offA, int offB) { return blane + (sel ? offB : offA); };
 
@@ -455,7 +457,7 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
                         const float hv = elu(acc[2 * s + (j >> 2)][nt][j & 3]);
                         if constexpr (TAPE)
                             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, hv), rh, oo[nt], ((2 * s + (j >> 2)) * 16 + (j & 3)) * plane, 0);
-                        cwfa_split3<SIX>(hv, h1, h2, h3);
+                        cwfa_split3<SIX, F16>(hv, h1, h2, h3);
                         Hq[s][0][j] = h1; Hq[s][1][j] = h2; Hq[s][2][j] = h3;
                     }
                 if constexpr (XF) {
@@ -487,7 +489,7 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         __bf16 u1, u2 = (__bf16)0.f, u3 = (__bf16)0.f;
-                        cwfa_split3<SIX>(uv[nt & 1][j], u1, u2, u3);
+                        cwfa_split3<SIX, F16>(uv[nt & 1][j], u1, u2, u3);
                         Uq[0][j] = u1; Uq[1][j] = u2; Uq[2][j] = u3;
                     }
 #pragma unroll
@@ -526,7 +528,7 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // slice DMAs issued past the end
 }
 
-// packed image: 20 slices [piece 3][k group 4][64 cout][8] of bf16.
+// packed image: 20 slices [piece 3][k group 4][64 cout][8] of bf16 (F16: piece 0 = the fp16 weights, pieces 1, 2 zero).
 //   slices 0..17 (conv step s): group g = unit u = 2s + (g >> 1) = (chunk u / 9, tap u % 9), k half g & 1:
 //                 element j = w3[co][chunk*16 + (g&1)*8 + j][tap]
 //   slices 18, 19 (k step s of the 1x1): element j of group g = w1[co][16*(2s + (j>>2)) + 4g + (j&3)] -- the hidden
@@ -534,6 +536,7 @@ __global__ __launch_bounds__(512, 1) void split_layer_kernel(LParams p) {
 // (n3 = 18 slices over cin3 = 64 input channels, or the first-layer form: n3 = 9 over cin3 = 32)
 //   first-layer form, optional slice n3 + 2 (w0 != NULL): element j of group g = w0[co][8g + j], the [64][32] matrix [W0 | b0 | 0] of the
 //                 1x1 in front of the layer (third k step of the 1x1 phase: the fused first map)
+template <bool F16 = false>
 __global__ __launch_bounds__(256) void split_layer_pack_kernel(const float* __restrict__ w3, const float* __restrict__ w1,
                                                                uint4* __restrict__ out, int n3, int cin3, const float* __restrict__ w0 = nullptr) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;            // over [slice n3 + 2 (+ 1)][g 4][co 64]
@@ -553,7 +556,12 @@ __global__ __launch_bounds__(256) void split_layer_pack_kernel(const float* __re
             v = w0[co * 32 + 8 * g + j];
         }
         __bf16 a1, a2, a3;
-        cwfa_split3<true>(v, a1, a2, a3);
+        if constexpr (F16) {
+            cwfa_split3<false, true>(v, a1, a2, a3);
+            a2 = a3 = __builtin_bit_cast(__bf16, (unsigned short)0);
+        } else {
+            cwfa_split3<true>(v, a1, a2, a3);
+        }
         pc[0][j] = __builtin_bit_cast(unsigned short, a1);
         pc[1][j] = __builtin_bit_cast(unsigned short, a2);
         pc[2][j] = __builtin_bit_cast(unsigned short, a3);
@@ -571,6 +579,16 @@ __global__ __launch_bounds__(256) void split_layer_pack_kernel(const float* __re
 
 int g_num_cus = 0;
 
+// the pack kernel of the active operand format (the image is read by the launches made under the same options)
+void layer_pack(const float* w3, const float* w1, void* packed, int n3, int cin3, const float* w0, void* stream) {
+    const dim3 grid((unsigned)(((n3 + 2 + (w0 ? 1 : 0)) * 256 + 255) / 256));
+    uint4* out = reinterpret_cast<uint4*>(packed);
+    if (g_cwfa_split_products == 1 && g_cwfa_split_operand != 0)
+        hipLaunchKernelGGL(split_layer_pack_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, w3, w1, out, n3, cin3, w0);
+    else
+        hipLaunchKernelGGL(split_layer_pack_kernel<>, grid, dim3(256), 0, (hipStream_t)stream, w3, w1, out, n3, cin3, w0);
+}
+
 }  // namespace
 
 extern "C" int64_t cwfa_subnet_layer_split_packed_bytes(void) { return (int64_t)NSL * WSL; }
@@ -578,8 +596,7 @@ extern "C" int64_t cwfa_subnet_layer_split_packed_bytes(void) { return (int64_t)
 extern "C" int cwfa_subnet_layer_split_pack_f32(const float* w3, const float* w1, void* packed, void* stream) {
     CWFA_REQUIRE(w3 && w1 && packed, CWFA_E_INVAL, "cwfa_subnet_layer_split_pack_f32: null pointer");
     CWFA_REQUIRE(cwfa_aligned16(packed), CWFA_E_ALIGN, "cwfa_subnet_layer_split_pack_f32: packed image must be 16-byte aligned");
-    hipLaunchKernelGGL(split_layer_pack_kernel, dim3((NSL * 256 + 255) / 256), dim3(256), 0, (hipStream_t)stream, w3, w1,
-                       reinterpret_cast<uint4*>(packed), 18, 64);
+    layer_pack(w3, w1, packed, 18, 64, nullptr, stream);
     CWFA_LAUNCH_CHECK("cwfa_subnet_layer_split_pack_f32");
     return CWFA_OK;
 }
@@ -590,8 +607,9 @@ extern "C" int cwfa_subnet_layer_first_pack_f32(const float* w3c, const float* w
     CWFA_REQUIRE(w3c && w1 && packed, CWFA_E_INVAL, "cwfa_subnet_layer_first_pack_f32: null pointer");
     CWFA_REQUIRE(cwfa_aligned16(packed), CWFA_E_ALIGN, "cwfa_subnet_layer_first_pack_f32: packed image must be 16-byte aligned");
     CWFA_REQUIRE(!short_form || w0c, CWFA_E_INVAL, "cwfa_subnet_layer_first_pack_f32: the short form is a form of the fused first map (w0c)");
-    hipLaunchKernelGGL(split_layer_pack_kernel, dim3((12 * 256 + 255) / 256), dim3(256), 0, (hipStream_t)stream, w3c, w1,
-                       reinterpret_cast<uint4*>(packed), short_form ? 5 : 9, 32, w0c);
+    // (fp16 operands: the composed weights w3c / w0c -- products of the 1x1 and 3x3 weights, see ops.py -- are what is rounded to
+    //  fp16; autocast in the reference rounds the two factors separately)
+    layer_pack(w3c, w1, packed, short_form ? 5 : 9, 32, w0c, stream);
     CWFA_LAUNCH_CHECK("cwfa_subnet_layer_first_pack_f32");
     return CWFA_OK;
 }
@@ -662,25 +680,34 @@ static int layer_launch(const float* x, const void* packed, const float* b3, con
         }
         g_num_cus = n;
     }
-    const bool six = g_cwfa_split_products != 1;
+    const int six = g_cwfa_split_products != 1 ? 1 : g_cwfa_split_operand ? 2 : 0;     // operand format: 1 split, 0 plain bf16, 2 plain fp16
     typedef void (*kern_t)(LParams);
-    static const kern_t kerns[2][2][4] = {
+    static const kern_t kerns[2][3][4] = {
         {{&split_layer_kernel<false, false, false>, &split_layer_kernel<false, true, false>, &split_layer_kernel<false, false, true>,
           &split_layer_kernel<false, true, true>},
          {&split_layer_kernel<true, false, false>, &split_layer_kernel<true, true, false>, &split_layer_kernel<true, false, true>,
-          &split_layer_kernel<true, true, true>}},
+          &split_layer_kernel<true, true, true>},
+         {&split_layer_kernel<false, false, false, 2, false, false, false, true>, &split_layer_kernel<false, true, false, 2, false, false, false, true>,
+          &split_layer_kernel<false, false, true, 2, false, false, false, true>, &split_layer_kernel<false, true, true, 2, false, false, false, true>}},
         {{&split_layer_kernel<false, false, false, 1>, &split_layer_kernel<false, true, false, 1>, &split_layer_kernel<false, false, true, 1>,
           &split_layer_kernel<false, true, true, 1>},
          {&split_layer_kernel<true, false, false, 1>, &split_layer_kernel<true, true, false, 1>, &split_layer_kernel<true, false, true, 1>,
-          &split_layer_kernel<true, true, true, 1>}}};
-    static const kern_t tape_kerns[2] = {&split_layer_kernel<false, false, false, 2, true>, &split_layer_kernel<true, false, false, 2, true>};
-    static const kern_t xf_kerns[2][2] = {{&split_layer_kernel<false, false, false, 1, false, true>, &split_layer_kernel<false, false, true, 1, false, true>},
-                                          {&split_layer_kernel<true, false, false, 1, false, true>, &split_layer_kernel<true, false, true, 1, false, true>}};
-    static const kern_t xs_kerns[2][2] = {{&split_layer_kernel<false, false, false, 1, false, true, true>, &split_layer_kernel<false, false, true, 1, false, true, true>},
-                                          {&split_layer_kernel<true, false, false, 1, false, true, true>, &split_layer_kernel<true, false, true, 1, false, true, true>}};
+          &split_layer_kernel<true, true, true, 1>},
+         {&split_layer_kernel<false, false, false, 1, false, false, false, true>, &split_layer_kernel<false, true, false, 1, false, false, false, true>,
+          &split_layer_kernel<false, false, true, 1, false, false, false, true>, &split_layer_kernel<false, true, true, 1, false, false, false, true>}}};
+    static const kern_t tape_kerns[3] = {&split_layer_kernel<false, false, false, 2, true>, &split_layer_kernel<true, false, false, 2, true>,
+                                         &split_layer_kernel<false, false, false, 2, true, false, false, true>};
+    static const kern_t xf_kerns[3][2] = {{&split_layer_kernel<false, false, false, 1, false, true>, &split_layer_kernel<false, false, true, 1, false, true>},
+                                          {&split_layer_kernel<true, false, false, 1, false, true>, &split_layer_kernel<true, false, true, 1, false, true>},
+                                          {&split_layer_kernel<false, false, false, 1, false, true, false, true>,
+                                           &split_layer_kernel<false, false, true, 1, false, true, false, true>}};
+    static const kern_t xs_kerns[3][2] = {{&split_layer_kernel<false, false, false, 1, false, true, true>, &split_layer_kernel<false, false, true, 1, false, true, true>},
+                                          {&split_layer_kernel<true, false, false, 1, false, true, true>, &split_layer_kernel<true, false, true, 1, false, true, true>},
+                                          {&split_layer_kernel<false, false, false, 1, false, true, true, true>,
+                                           &split_layer_kernel<false, false, true, 1, false, true, true, true>}};
     const int first = shortf ? 4 : fused_x ? 3 : u != nullptr ? 1 : hid != nullptr ? 2 : 0;
     kern_t kern = first == 4 ? xs_kerns[six][layout >> 1] : first == 3 ? xf_kerns[six][layout >> 1] : first == 2 ? tape_kerns[six] : kerns[first][six][layout];
-    static bool attr_set_all[5][2][4] = {};
+    static bool attr_set_all[5][3][4] = {};
     bool& attr_done = attr_set_all[first][six][layout];
     if (!attr_done) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);

@@ -26,6 +26,7 @@ from .FrEIA import framework as Ff
 from .FrEIA import modules as Fm
 from .INN_utils import HaarTransform1D, PermuteDim
 from .unet import UNet, _Packed
+from .amp import amp_entry
 
 __all__ = ["conditional_wavelet_flow", "wavelet_flow_subnetwork", "wavelet_flow_subnetwork2D",
            "wavelet_flow_subnetwork2D_first", "cond_network", "ResidualBlock", "GlobalAttention", "drop_path", "ConvNeXt",
@@ -303,6 +304,7 @@ class wavelet_flow_subnetwork(nn.Module):
                 return a[:, :n_s], a[:, n_s:], False
         return self._stack(om, self.block1, self.block7[1]), mean, True
 
+    @amp_entry
     def forward(self, input):
         if self.normal:
             return self._stack(input, self.block12, self.block72[1])
@@ -408,6 +410,7 @@ class ResidualBlock(nn.Module):
         self.out_channels = out_channels
         self._packed = _Packed()
 
+    @amp_entry
     def forward(self, x):
         if not isinstance(self.relu, nn.PReLU) or self.relu.weight.numel() != 1:
             raise NotImplementedError("ResidualBlock activation must be a single-parameter PReLU")
@@ -501,6 +504,7 @@ class cond_network(nn.Module):
         self.global_attention = None
         self.subnetworks = nn.Sequential(ResidualBlock(c_in, c_out, chans_3D=cond_chans))
 
+    @amp_entry
     def forward(self, lf_img):
         return [self.subnetworks[0](lf_img)]
 
@@ -524,6 +528,7 @@ class GlobalAttention(nn.Module):
         """att(mean), or fused ``x + m*2*(att-0.5)`` (networks.py:552-554)."""
         return ops.attention_combine(mean, self.m[0].weight, self.m[0].bias, self.m[2].weight, self.m[2].bias, m, x)
 
+    @amp_entry
     def forward(self, input):
         return self.combine(input)
 
@@ -550,6 +555,7 @@ class ConvNeXt(nn.Module):
                                nn.Conv2d(c_out, c_out, 1, 1), nn.GELU())
         self._packed = _Packed()
 
+    @amp_entry
     def forward(self, input):
         P = self._packed.get
         u = ops.conv2d(input, P(self.input), bias=self.input.bias)
@@ -582,6 +588,7 @@ class LRNN(nn.Module):
         self.deconv[0].apply(subnet_initialization_positive)
         self._packed = _Packed()
 
+    @amp_entry
     def forward(self, x_in, mean_vol=None):
         if AG.tracking(x_in, mean_vol, self):
             # training (CWFA.py:880-886,936-950,1002-1006): the whole network as one autograd node (training.lrnn_forward_train /
@@ -602,6 +609,7 @@ class Encoder(nn.Module):
         super().__init__()
         self.net = LRNN(c_in, c_out, use_bias)
 
+    @amp_entry
     def forward(self, im_in, mean_vol=None):
         return [self.net(im_in)] if mean_vol is None else [self.net(im_in, mean_vol)]
 

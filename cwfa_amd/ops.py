@@ -395,8 +395,8 @@ def pack_conv_weight(w, transposed=False, direct=False):
         packed = torch.empty(L.cwfa_conv_split_packed_bytes(cout, cin, ks), dtype=torch.uint8, device=w.device)
         check(L.cwfa_conv_split_pack_f32(_p(w), _p(packed), cout, cin, ks, int(transposed), _stream()), "conv_split_pack")
         return PackedConv(packed, cout, cin, ks, transposed, w._version, w.data_ptr(), split=True)
-    # (bf16 mode: one product per multiply-add -- there the 32-channel tiling beats the fp32 Winograd kernel for 17 .. 32 outputs too)
-    narrow_max = 32 if _plain_bf16 else SPLIT_3X3_NARROW_MAX
+    # (bf16 / fp16 mode: one product per multiply-add -- there the 32-channel tiling beats the fp32 Winograd kernel for 17 .. 32 outputs too)
+    narrow_max = 32 if single_product() else SPLIT_3X3_NARROW_MAX
     if not direct and _split_bf16 >= 2 and ks == 3 and cout >= SPLIT_3X3_MIN_COUT and (cout > 32 or (cout <= narrow_max and cin >= 29)):
         packed = torch.empty(L.cwfa_conv3x3_split_packed_bytes(cout, cin), dtype=torch.uint8, device=w.device)
         check(L.cwfa_conv3x3_split_pack_f32(_p(w), _p(packed), cout, cin, _stream()), "conv3x3_split_pack")
@@ -1259,8 +1259,14 @@ def extract_views(image, coords_yx, subimage_shape, mean=0.0, std=1.0):
 
 
 _split_bf16 = 0
-_plain_bf16 = False      # set_precision("bf16"): the split kernels with ONE product (BASELINE.json configs[4])
+_precision = "fp32"      # the mode of the last set_precision()
 _pack_epoch = 0
+
+
+def single_product():
+    """True in the "bf16" and "fp16" modes: the split kernels with ONE product of plain 16-bit operands (BASELINE.json configs[4]);
+    the two modes route every convolution alike and differ only in the operand format."""
+    return _precision in ("bf16", "fp16")
 
 
 def pack_epoch():
@@ -1294,17 +1300,25 @@ def set_option(name, value):
     check(_lib.lib().cwfa_set_option(name.encode(), int(value)), "set_option")
 
 
+PRECISIONS = ("fp32", "split_bf16", "bf16", "fp16")
+
+
 def set_precision(mode):
     """"fp32" (library default: plain fp32 MFMA / Winograd kernels) | "split_bf16" (the benchmark's arithmetic, fp32-equivalent:
     three bf16 pieces per operand, six products, fp32 accumulation) | "bf16" (BASELINE.json configs[4]: the same kernels with ONE
-    product, i.e. plain bf16 operands and fp32 accumulation).  The split / bf16 kernels take: 1x1 and transposed convolutions with
-    >= 128 outputs, 3x3 convolutions with >= SPLIT_3X3_MIN_COUT outputs, the 64-channel fused layers; wavelets, couplings,
-    permutations, the Conv3d of the condition nets and the remaining small convolutions stay fp32."""
-    if mode not in ("fp32", "split_bf16", "bf16"):
+    product, i.e. plain bf16 operands and fp32 accumulation) | "fp16" (the same as "bf16" with fp16 operands, rounded to nearest
+    even as torch's .half(): the arithmetic of the reference's CUDA autocast).  The split / bf16 / fp16 kernels
+    take: 1x1 and transposed convolutions with >= 128 outputs, 3x3 convolutions with >= SPLIT_3X3_MIN_COUT outputs, the 64-channel
+    fused layers, the Conv3d of the condition nets; wavelets, couplings, permutations and the remaining small convolutions stay fp32.
+    Weight gradients (training) take the split arithmetic in "split_bf16" and plain bf16 operands in "bf16" and "fp16"."""
+    if mode not in PRECISIONS:
         raise ValueError(f"set_precision: unknown mode {mode!r}")
-    global _plain_bf16
-    _plain_bf16 = mode == "bf16"
-    set_option("split_products", 1 if mode == "bf16" else 6)
+    global _precision
+    _precision = mode
+    set_option("split_operand", 0)                              # (first: (6 products, fp16) is not a valid pair)
+    set_option("split_products", 1 if single_product() else 6)
+    if mode == "fp16":
+        set_option("split_operand", 1)
     set_option("split_bf16", 0 if mode == "fp32" else 2)
     set_option("wgrad_split", 0 if mode == "fp32" else 1)        # training: 3x3 weight gradients in the same arithmetic (csrc/conv_bwd.hip)
 

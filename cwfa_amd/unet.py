@@ -18,6 +18,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .amp import amp_entry
 
 __all__ = ["UNet", "UNetConvBlock", "UNetUpBlock"]
 
@@ -203,6 +204,7 @@ class UNetConvBlock(nn.Module):
                 aff = None
         return x, aff
 
+    @amp_entry
     def forward(self, x):
         y, aff = self.run(x)
         if aff is None:
@@ -239,6 +241,7 @@ class UNetUpBlock(nn.Module):
         add = self.center_crop(bridge, up.shape[2:]) if self.skip_conn else None
         return self.conv_block.run(up, in_add=add, out_mask=out_mask)
 
+    @amp_entry
     def forward(self, x, bridge):
         y, aff = self.run(x, bridge)
         return y if aff is None else ops.channel_affine(y, aff[0], aff[1])
@@ -266,6 +269,7 @@ class UNet(nn.Module):
         self.last = nn.Sequential(nn.Conv2d(prev, n_classes, kernel_size=1, bias=use_bias), activation())
         self._packed = _Packed()
 
+    @amp_entry
     def forward(self, x, store_activations=False, in_affine=None):
         if store_activations:
             raise NotImplementedError("store_activations is a debugging aid of the reference, not on the hot path")

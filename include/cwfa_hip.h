@@ -54,14 +54,21 @@ const char* cwfa_last_error(void);
  *                         (+1..13 % on plain convolutions, slower with a load-side prologue); 0: the 1-D F(2,3) kernel
  *                         as for the narrower layers.
  *   "split_products"    : 6 (default): the split-bf16 kernels form every fp32 product from six bf16 products
- *                         (fp32-equivalent); 1: plain bf16 operands (BASELINE.json configs[4]).
+ *                         (fp32-equivalent); 1: plain 16-bit operands (BASELINE.json configs[4]), one product each.
+ *   "split_operand"     : 0 (default): bf16 operands; 1: fp16 operands (round to nearest even, beyond +-65504 +-inf) on the
+ *                         f16 matrix-core forms, for the single-product kernels: the split 1x1 / transposed GEMM and its
+ *                         input split, the split 3x3 / 7x7 and coupling-epilogue convolutions, the fused sub-network layers,
+ *                         the split Conv3d, and their pack functions (a packed image is valid for the option values it was
+ *                         packed under).  The valid pairs (split_products, split_operand) are (6, 0), (1, 0) and (1, 1): a call
+ *                         that would make (6, 1) returns CWFA_E_INVAL, so set split_products = 1 before split_operand = 1, and
+ *                         split_operand = 0 before split_products = 6.  The 3x3 weight gradient ("wgrad_split") is not affected.
  *   "wgrad_rows"        : 0: the 3x3 weight gradient always takes its first (register-staged) form.
  *   "wgrad_split"       : 1: the 3x3 weight gradient (16-byte aligned rows) runs on the bf16 matrix cores in the split
  *                         arithmetic of "split_products" (training in split / bf16 precision); 0 (default): fp32 MFMA.
  *   "split3x3_xcd_map"  : 0: (ablation) blocks of the split 3x3 kernel in plain (spatial tile, cout tile) order instead of
  *                         the XCD-aware one.
  *   "split3x3_rows16"   : 0: (ablation) the 64-channel tiling of the split 3x3 kernel always on 8-row tiles.
- * returns 0, or CWFA_E_INVAL for an unknown name. */
+ * returns 0, or CWFA_E_INVAL for an unknown name or an invalid value. */
 int cwfa_set_option(const char* name, int value);
 
 /* ------------------------------------------------------------------------------------------------
