@@ -619,16 +619,8 @@ int launch_epi(ConvParams p, hipStream_t stream) {
     if (rc) return rc;
     // the generic epilogue stages accumulators through 4 KB of LDS per wave
     constexpr int LDS = EPI == EPI_GENERIC && C::LDS_BYTES < C::NTHREADS * 64 ? C::NTHREADS * 64 : C::LDS_BYTES;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv2d_mfma_kernel<C, EPI, PRO>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            cwfa_set_error("cwfa_conv2d_f32: hipFuncSetAttribute(%d bytes LDS): %s", LDS, hipGetErrorString(e));
-            return CWFA_E_HIP;
-        }
-        attr_set = true;
-    }
+    rc = cwfa_max_lds<&conv2d_mfma_kernel<C, EPI, PRO>>(LDS, "cwfa_conv2d_f32");
+    if (rc) return rc;
     hipLaunchKernelGGL((conv2d_mfma_kernel<C, EPI, PRO>), grid, dim3(C::NTHREADS), LDS, stream, p);
     CWFA_LAUNCH_CHECK("cwfa_conv2d_f32");
     return CWFA_OK;
@@ -663,8 +655,6 @@ int launch(const ConvParams& p, int epi, hipStream_t st) {
 }
 
 }  // namespace
-int g_cwfa_split_products = 6;
-int g_cwfa_split_operand = 0;         // "split_operand": 0 bf16, 1 fp16 (with split_products = 1 only)
 int g_cwfa_split_xcd_map = 1;
 int g_cwfa_split_rows16 = 1;
 namespace {
@@ -679,7 +669,7 @@ int fill_params(ConvParams& p, const char* name, const float* x, const float* w_
     p.x = x; p.wp = w_packed; p.y = y;
     p.B = B; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout;
     p.x_bs = x_bs; p.y_bs = y_bs;
-    p.products = g_cwfa_split_products;
+    p.products = g_cwfa_operand == CwfaOperand::split3 ? 6 : 1;
     if (opts) p.o = *opts;
     CWFA_REQUIRE(!(p.o.in_scale && !p.o.in_shift), CWFA_E_INVAL, "%s: in_scale without in_shift", name);
     CWFA_REQUIRE(p.o.act >= 0 && p.o.act <= CWFA_ACT_RELU && p.o.act2 >= 0 && p.o.act2 <= CWFA_ACT_RELU, CWFA_E_INVAL,
@@ -904,7 +894,7 @@ __global__ __launch_bounds__(512, 1) void conv1x1_split_kernel(SplitParams sp) {
     epilogue<C, EPI>(p, t, acc);
 }
 
-template <int EPI, bool F16 = false>
+template <int EPI>
 int launch_split(SplitParams sp, hipStream_t stream) {
     ConvParams& p = sp.c;
     p.tiles_x = (p.W + CS::TC - 1) / CS::TC;
@@ -913,23 +903,15 @@ int launch_split(SplitParams sp, hipStream_t stream) {
     CWFA_REQUIRE((int64_t)p.tiles_x * p.tiles_y < (1ll << 31) && ctiles <= 65535 && p.B <= 65535, CWFA_E_SHAPE,
                  "cwfa_conv_split_f32: grid too large");
     constexpr int LDS = 3 * CS_BUFB;
-    auto kern = &conv1x1_split_kernel<EPI, F16>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            cwfa_set_error("cwfa_conv_split_f32: hipFuncSetAttribute(%d bytes LDS): %s", LDS, hipGetErrorString(e));
-            return CWFA_E_HIP;
-        }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_x * p.tiles_y), ctiles, p.B), dim3(512), LDS, stream, sp);
-    CWFA_LAUNCH_CHECK("cwfa_conv_split_f32");
-    return CWFA_OK;
+    return cwfa_with_operand([&](auto, auto f16) -> int {      // (split or plain bf16: the kernel reads p.products)
+        constexpr auto kern = &conv1x1_split_kernel<EPI, f16>;
+        const int rc = cwfa_max_lds<kern>(LDS, "cwfa_conv_split_f32");
+        if (rc) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_x * p.tiles_y), ctiles, p.B), dim3(512), LDS, stream, sp);
+        CWFA_LAUNCH_CHECK("cwfa_conv_split_f32");
+        return CWFA_OK;
+    });
 }
-
-// fp16 operands in the single-product kernels
-bool split_f16() { return g_cwfa_split_products == 1 && g_cwfa_split_operand != 0; }
 
 }  // namespace
 
@@ -949,14 +931,12 @@ extern "C" int cwfa_split_input_f32(const float* x, void* ws, int B, int Cin, in
     if (B == 0 || HW == 0) return CWFA_OK;
     const int CG2 = 2 * ((Cin + 15) / 16);
     CWFA_REQUIRE((int64_t)3 * CG2 * HW * 16 < (1ll << 31), CWFA_E_SHAPE, "cwfa_split_input_f32: one sample's planes must stay below 2 GiB");
-    if (split_f16())
-        hipLaunchKernelGGL(split_input_kernel<true>, dim3((unsigned)((HW + 255) / 256), CG2, B), dim3(256), 0, (hipStream_t)stream, x,
+    return cwfa_with_operand([&](auto, auto f16) -> int {
+        hipLaunchKernelGGL(split_input_kernel<f16>, dim3((unsigned)((HW + 255) / 256), CG2, B), dim3(256), 0, (hipStream_t)stream, x,
                            reinterpret_cast<uint4*>(ws), Cin, CG2, HW, x_bs, in_scale, in_shift, in_affine_bs, in_add, in_add_bs);
-    else
-        hipLaunchKernelGGL(split_input_kernel<>, dim3((unsigned)((HW + 255) / 256), CG2, B), dim3(256), 0, (hipStream_t)stream, x,
-                           reinterpret_cast<uint4*>(ws), Cin, CG2, HW, x_bs, in_scale, in_shift, in_affine_bs, in_add, in_add_bs);
-    CWFA_LAUNCH_CHECK("cwfa_split_input_f32");
-    return CWFA_OK;
+        CWFA_LAUNCH_CHECK("cwfa_split_input_f32");
+        return CWFA_OK;
+    });
 }
 
 extern "C" int64_t cwfa_conv_split_packed_bytes(int Cout, int Cin, int ks) {
@@ -971,14 +951,12 @@ extern "C" int cwfa_conv_split_pack_f32(const float* w, void* packed, int Cout, 
     CWFA_REQUIRE(cwfa_aligned16(packed), CWFA_E_ALIGN, "cwfa_conv_split_pack_f32: packed image must be 16-byte aligned");
     const int nchunks = (Cin + 15) / 16, taps = ks * ks;
     const int64_t total = (int64_t)((Cout + 255) / 256) * nchunks * taps * 512;
-    if (split_f16())
-        hipLaunchKernelGGL(split_pack_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
+    return cwfa_with_operand([&](auto, auto f16) -> int {
+        hipLaunchKernelGGL(split_pack_kernel<f16>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
                            reinterpret_cast<uint4*>(packed), Cout, Cin, nchunks, taps, transposed, total);
-    else
-        hipLaunchKernelGGL(split_pack_kernel<>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
-                           reinterpret_cast<uint4*>(packed), Cout, Cin, nchunks, taps, transposed, total);
-    CWFA_LAUNCH_CHECK("cwfa_conv_split_pack_f32");
-    return CWFA_OK;
+        CWFA_LAUNCH_CHECK("cwfa_conv_split_pack_f32");
+        return CWFA_OK;
+    });
 }
 
 extern "C" int cwfa_conv_split_f32(const void* ws, const void* w_packed, float* y, int B, int Cin, int H, int W, int Cout, int ks,
@@ -1003,13 +981,6 @@ extern "C" int cwfa_conv_split_f32(const void* ws, const void* w_packed, float* 
                  "cwfa_conv_split_f32: one sample's planes / one cout tile's weights must stay below 2 GiB");
     const int epi = classify_epilogue(p.o);
     hipStream_t st = (hipStream_t)stream;
-    if (split_f16()) {
-        switch (epi) {
-            case EPI_NONE: return launch_split<EPI_NONE, true>(sp, st);
-            case EPI_UP: return launch_split<EPI_UP, true>(sp, st);
-            default: return launch_split<EPI_GENERIC, true>(sp, st);
-        }
-    }
     switch (epi) {
         case EPI_NONE: return launch_split<EPI_NONE>(sp, st);
         case EPI_UP: return launch_split<EPI_UP>(sp, st);
@@ -1019,6 +990,7 @@ extern "C" int cwfa_conv_split_f32(const void* ws, const void* w_packed, float* 
 
 int g_cwfa_wino_min_cout = 1;
 int g_cwfa_wino_2d = 512;     // 2-D F(2x2,3x3) for >= 512 output channels (the UNet's plain convolutions), see conv_internal.h
+CwfaOperand g_cwfa_operand = CwfaOperand::split3;
 
 extern "C" int cwfa_set_option(const char* name, int value) {
     CWFA_REQUIRE(name, CWFA_E_INVAL, "cwfa_set_option: null name");
@@ -1048,16 +1020,18 @@ extern "C" int cwfa_set_option(const char* name, int value) {
     }
     if (strcmp(name, "split_products") == 0) {      // 6: fp32-accurate split; 1: plain bf16 / fp16 operands (BASELINE configs[4])
         CWFA_REQUIRE(value == 1 || value == 6, CWFA_E_INVAL, "cwfa_set_option: split_products must be 1 or 6");
-        CWFA_REQUIRE(value == 1 || g_cwfa_split_operand == 0, CWFA_E_INVAL,
+        CWFA_REQUIRE(value == 1 || g_cwfa_operand != CwfaOperand::fp16, CWFA_E_INVAL,
                      "cwfa_set_option: split_products = 6 needs split_operand = 0 (the three-piece split is a bf16 format)");
-        g_cwfa_split_products = value;
+        if (value == 6) g_cwfa_operand = CwfaOperand::split3;
+        else if (g_cwfa_operand == CwfaOperand::split3) g_cwfa_operand = CwfaOperand::bf16;
         return CWFA_OK;
     }
     if (strcmp(name, "split_operand") == 0) {       // 0: bf16 operands; 1: fp16 operands (single product only)
         CWFA_REQUIRE(value == 0 || value == 1, CWFA_E_INVAL, "cwfa_set_option: split_operand must be 0 (bf16) or 1 (fp16)");
-        CWFA_REQUIRE(value == 0 || g_cwfa_split_products == 1, CWFA_E_INVAL,
+        CWFA_REQUIRE(value == 0 || g_cwfa_operand != CwfaOperand::split3, CWFA_E_INVAL,
                      "cwfa_set_option: split_operand = 1 (fp16) needs split_products = 1 (fp16 operands take one product)");
-        g_cwfa_split_operand = value;
+        if (value == 1) g_cwfa_operand = CwfaOperand::fp16;
+        else if (g_cwfa_operand == CwfaOperand::fp16) g_cwfa_operand = CwfaOperand::bf16;
         return CWFA_OK;
     }
     cwfa_set_error("cwfa_set_option: unknown option '%s'", name);

@@ -17,13 +17,10 @@
 // Block = 512 threads = 8 waves (two per SIMD); tile = 14 x 30 output voxels x DC depth slabs; hidden tile 16 rows x 32
 // columns, wave w owns hidden rows 2w, 2w + 1 (4 n-tile columns, 48 ring registers).  x slabs stream through a 4-slot LDS
 // ring: slab d' + 2 is written while hidden slab d' is computed, slab d' + 3 is in flight in registers.  One barrier per slab.
-#include "common.h"
+#include "conv_internal.h"
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-extern int g_cwfa_split_products;       // conv2d.hip ("split_products" option: 6 or 1)
-extern int g_cwfa_split_operand;        // conv2d.hip ("split_operand" option: 0 bf16, 1 fp16)
 
 namespace {
 
@@ -420,20 +417,15 @@ __global__ __launch_bounds__(512, 1) void conv3d_split_kernel(P3 p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the x slab loaded past the end
 }
 
-template <bool SIX, bool F16 = false>
 int launch3(const P3& p, int B, int tiles, int chunks, hipStream_t st) {
-    auto kern = &conv3d_split_kernel<SIX, F16>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G3::LDS);
-        if (e != hipSuccess) {
-            cwfa_set_error("cwfa_conv3d_1k1_split_f32: hipFuncSetAttribute(%d bytes LDS): %s", G3::LDS, hipGetErrorString(e));
-            return CWFA_E_HIP;
-        }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)chunks, (unsigned)B), dim3(512), G3::LDS, st, p);
-    return 0;
+    return cwfa_with_operand([&](auto six, auto f16) -> int {
+        constexpr auto kern = &conv3d_split_kernel<six, f16>;
+        const int rc = cwfa_max_lds<kern>(G3::LDS, "cwfa_conv3d_1k1_split_f32");
+        if (rc) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)chunks, (unsigned)B), dim3(512), G3::LDS, st, p);
+        CWFA_LAUNCH_CHECK("cwfa_conv3d_1k1_split_f32");
+        return CWFA_OK;
+    });
 }
 
 }  // namespace
@@ -465,11 +457,5 @@ extern "C" int cwfa_conv3d_1k1_split_f32(const float* x, const float* w1, const 
     const int chunks = (D + DC - 1) / DC;
     CWFA_REQUIRE(chunks <= 65535, CWFA_E_SHAPE, "cwfa_conv3d_1k1_split_f32: grid too large");
     P3 p{x, w1, b1, alpha, w2, b2, y, D, H, W, K, tw, DC};
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = g_cwfa_split_products != 1 ? launch3<true>(p, B, (int)tiles, chunks, st)
-                   : g_cwfa_split_operand     ? launch3<false, true>(p, B, (int)tiles, chunks, st)
-                                              : launch3<false>(p, B, (int)tiles, chunks, st);
-    if (rc != CWFA_OK) return rc;
-    CWFA_LAUNCH_CHECK("cwfa_conv3d_1k1_split_f32");
-    return CWFA_OK;
+    return launch3(p, B, (int)tiles, chunks, (hipStream_t)stream);
 }

@@ -12,7 +12,7 @@
 // Strips are double-buffered: the next strip's global loads are issued before the 32 k-steps of the current one and
 // stored to the other buffer after them.  Every pixel worker writes its partial filter bank; a second kernel sums the
 // partials in a fixed order, so the result is deterministic (no float atomics).
-#include "common.h"
+#include "conv_internal.h"
 
 namespace {
 
@@ -617,9 +617,8 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_split_kernel(WgParams p) {
 }
 
 }  // namespace
-int g_cwfa_wgrad_rows = 1;
+int g_cwfa_wgrad_rows = 1;   // 3x3: the LDS-DMA / row-paired form when the image rows are 16-byte aligned (option "wgrad_rows")
 int g_cwfa_wgrad_split = 0;  // 3x3: the split-bf16 form on the bf16 matrix cores (option "wgrad_split"; ops.set_precision sets it)
-extern int g_cwfa_split_products;   // 3x3: the LDS-DMA / row-paired form when the image rows are 16-byte aligned (option "wgrad_rows")
 namespace {
 
 int wgrad_workers(int B, int H, int W, int Cout, int Cin, int ks) {
@@ -630,6 +629,15 @@ int wgrad_workers(int B, int H, int W, int Cout, int Cin, int ks) {
     int64_t w = ((ks == 1 ? 512 : 256) + tiles - 1) / tiles;
     if (w > strips) w = strips;
     return (int)(w < 1 ? 1 : w);
+}
+
+template <bool SIX, int KS>
+int wgrad_split(const WgParams& p, dim3 grid, hipStream_t st) {
+    const int rc = cwfa_max_lds<&conv_wgrad_split_kernel<SIX, KS>>(ws::LDS_BYTES, "cwfa_conv2d_wgrad_f32");
+    if (rc) return rc;
+    hipLaunchKernelGGL((conv_wgrad_split_kernel<SIX, KS>), grid, dim3(512), ws::LDS_BYTES, st, p);
+    CWFA_LAUNCH_CHECK("cwfa_conv2d_wgrad_f32");
+    return CWFA_OK;
 }
 
 }  // namespace
@@ -685,13 +693,8 @@ extern "C" int cwfa_conv2d_wgrad_f32(const float* x, const float* dy, float* dw,
     if (ks == 7) {
         const int64_t nrow = (int64_t)Cout * Cin * 7;
         float* row = p.part + (int64_t)workers * (nrow + Cout);
-        static bool attr7 = false;
-        if (!attr7) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<1, 7>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, WgCfg<1, 7>::LDS_BYTES);
-            CWFA_REQUIRE(e == hipSuccess, CWFA_E_HIP, "cwfa_conv2d_wgrad_f32: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr7 = true;
-        }
+        const int rc = cwfa_max_lds<&conv_wgrad_kernel<1, 7>>(WgCfg<1, 7>::LDS_BYTES, "cwfa_conv2d_wgrad_f32");
+        if (rc) return rc;
         dim3 grid7(workers, (Cout + 63) / 64, (Cin + 63) / 64);
         for (int ky = 0; ky < 7; ++ky) {
             p.row_off = ky - 3;
@@ -712,7 +715,6 @@ extern "C" int cwfa_conv2d_wgrad_f32(const float* x, const float* dy, float* dw,
     }
     p.bpart = db ? p.part + (int64_t)workers * n : nullptr;
     dim3 grid(workers, (Cout + 63) / 64, (Cin + 63) / 64);
-    static bool attr1 = false, attr3 = false;
     // (1x1: only banks of one 64 x 64 tile -- the sub-networks' -- where a block stages each operand once: 60 -> 52 us at 512 x 512; with
     //  several tiles every block re-splits its operands for 12 MFMAs per step and the fp32 form is faster, 444 vs 628 us at 256 -> 256)
     if ((ks == 3 || (ks == 1 && Cout <= 64 && Cin <= 64)) && g_cwfa_wgrad_split && W % 4 == 0 && x_bs % 4 == 0 && dy_bs % 4 == 0 && cwfa_aligned16(x) && cwfa_aligned16(dy) &&
@@ -721,21 +723,14 @@ extern "C" int cwfa_conv2d_wgrad_f32(const float* x, const float* dy, float* dw,
         p.sx = (W + 31) / 32;
         p.sy = (H + ws::SEG - 1) / ws::SEG;
         p.nstrips = B * p.sy * p.sx;
-        const bool six = g_cwfa_split_products != 1;
-        auto kern = ks == 3 ? (six ? &conv_wgrad_split_kernel<true, 3> : &conv_wgrad_split_kernel<false, 3>)
-                            : (six ? &conv_wgrad_split_kernel<true, 1> : &conv_wgrad_split_kernel<false, 1>);
-        static bool attr_s4[4] = {false, false, false, false};
-        bool& attr_ok = attr_s4[(ks == 1 ? 2 : 0) + (six ? 1 : 0)];
-        if (!attr_ok) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, ws::LDS_BYTES);
-            CWFA_REQUIRE(e == hipSuccess, CWFA_E_HIP, "cwfa_conv2d_wgrad_f32: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr_ok = true;
-        }
         // (one block per CU: 144 KB of LDS; the fp32 1x1 form asks for two per CU)
         const int tiles = (int)(grid.y * grid.z);
         dim3 sgrid(min(min(workers, max(1, (256 + tiles - 1) / tiles)), p.nstrips), grid.y, grid.z);
-        hipLaunchKernelGGL(kern, sgrid, dim3(512), ws::LDS_BYTES, st, p);
-        CWFA_LAUNCH_CHECK("cwfa_conv2d_wgrad_f32");
+        // the split arithmetic in split3 mode; plain bf16 operands in bf16 and fp16 mode (ops.set_precision)
+        const bool six = g_cwfa_operand == CwfaOperand::split3;
+        const int rc = ks == 3 ? (six ? wgrad_split<true, 3>(p, sgrid, st) : wgrad_split<false, 3>(p, sgrid, st))
+                               : (six ? wgrad_split<true, 1>(p, sgrid, st) : wgrad_split<false, 1>(p, sgrid, st));
+        if (rc) return rc;
         {
             const int nbw = (int)((n + 63) / 64), nbb = db ? (Cout + 63) / 64 : 0;
             hipLaunchKernelGGL(wgrad_reduce2_kernel, dim3((unsigned)(nbw + nbb)), dim3(256), 0, st, p.part, dw, n, p.bpart, db, (int64_t)Cout, nbw,
@@ -747,29 +742,16 @@ extern "C" int cwfa_conv2d_wgrad_f32(const float* x, const float* dy, float* dw,
     const bool rows_form = ks == 3 && g_cwfa_wgrad_rows && W % 4 == 0 && x_bs % 4 == 0 && dy_bs % 4 == 0 && cwfa_aligned16(x) &&
                            cwfa_aligned16(dy) && (int64_t)H * W % 4 == 0;
     if (rows_form) {
-        static bool attr_r = false;
-        if (!attr_r) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_rows_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, wr::LDS_BYTES);
-            CWFA_REQUIRE(e == hipSuccess, CWFA_E_HIP, "cwfa_conv2d_wgrad_f32: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr_r = true;
-        }
+        const int rc = cwfa_max_lds<&conv_wgrad_rows_kernel>(wr::LDS_BYTES, "cwfa_conv2d_wgrad_f32");
+        if (rc) return rc;
         hipLaunchKernelGGL(conv_wgrad_rows_kernel, grid, dim3(256), wr::LDS_BYTES, st, p);
     } else if (ks == 3) {
-        if (!attr3) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<3, 3>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, WgCfg<3, 3>::LDS_BYTES);
-            CWFA_REQUIRE(e == hipSuccess, CWFA_E_HIP, "cwfa_conv2d_wgrad_f32: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr3 = true;
-        }
+        const int rc = cwfa_max_lds<&conv_wgrad_kernel<3, 3>>(WgCfg<3, 3>::LDS_BYTES, "cwfa_conv2d_wgrad_f32");
+        if (rc) return rc;
         hipLaunchKernelGGL((conv_wgrad_kernel<3, 3>), grid, dim3(256), (WgCfg<3, 3>::LDS_BYTES), st, p);
     } else {
-        if (!attr1) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_kernel<1, 1>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, WgCfg<1, 1>::LDS_BYTES);
-            CWFA_REQUIRE(e == hipSuccess, CWFA_E_HIP, "cwfa_conv2d_wgrad_f32: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr1 = true;
-        }
+        const int rc = cwfa_max_lds<&conv_wgrad_kernel<1, 1>>(WgCfg<1, 1>::LDS_BYTES, "cwfa_conv2d_wgrad_f32");
+        if (rc) return rc;
         hipLaunchKernelGGL((conv_wgrad_kernel<1, 1>), grid, dim3(256), (WgCfg<1, 1>::LDS_BYTES), st, p);
     }
     CWFA_LAUNCH_CHECK("cwfa_conv2d_wgrad_f32");

@@ -1,6 +1,38 @@
-// Internal (non-ABI) interface between conv2d.hip (dispatch + direct kernels) and conv_wino.hip (Winograd kernels).
+// Internal (non-ABI) interface between conv2d.hip (dispatch, direct kernels and the options) and the other convolution sources.
 #pragma once
 #include "common.h"
+#include <type_traits>
+
+// Operand format of the split kernels (options "split_products" / "split_operand", cwfa_set_option): the exact three-piece
+// bf16 split with six products, or one product on plain bf16 / plain fp16 operands.
+enum class CwfaOperand : int { split3, bf16, fp16 };
+extern CwfaOperand g_cwfa_operand;
+
+// f(SIX, F16) with the active format as the kernels' compile-time flags (std::bool_constant): split3 = (true, false),
+// bf16 = (false, false), fp16 = (false, true); no other pair is instantiated.
+template <class F>
+int cwfa_with_operand(F&& f) {
+    switch (g_cwfa_operand) {
+        case CwfaOperand::split3: return f(std::true_type{}, std::false_type{});
+        case CwfaOperand::bf16: return f(std::false_type{}, std::false_type{});
+        case CwfaOperand::fp16: break;
+    }
+    return f(std::false_type{}, std::true_type{});
+}
+
+// raises KERN's dynamic-LDS limit to `bytes` before its first launch (one attribute call per kernel)
+template <auto KERN>
+int cwfa_max_lds(int bytes, const char* entry) {
+    static bool done = false;
+    if (done) return CWFA_OK;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) {
+        cwfa_set_error("%s: cannot raise the dynamic LDS limit to %d bytes: %s", entry, bytes, hipGetErrorString(e));
+        return CWFA_E_HIP;
+    }
+    done = true;
+    return CWFA_OK;
+}
 
 // 3x3 convolutions with at least g_cwfa_wino_min_cout output channels run the Winograd kernels (1.5x / 2.25x fewer MFMAs).
 // The packed weight image differs (G-transformed), so pack and launch must agree on these predicates.

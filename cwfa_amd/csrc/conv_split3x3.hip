@@ -23,10 +23,8 @@
 //   step before, verified at its end; one barrier per step.
 #include "conv_internal.h"
 
-extern int g_cwfa_split_products;       // conv2d.hip ("split_products" option: 6 or 1)
 extern int g_cwfa_split_xcd_map;        // conv2d.hip ("split3x3_xcd_map" option)
 extern int g_cwfa_split_rows16;         // conv2d.hip ("split3x3_rows16" option: 16-row tiles for the 64-channel tiling)
-extern int g_cwfa_split_operand;        // conv2d.hip ("split_operand" option: 0 bf16, 1 fp16)
 
 namespace {
 
@@ -602,20 +600,10 @@ inline int wm_of(int Cout) { return Cout > 96 ? 4 : Cout > 64 ? 2 : Cout > 48 ? 
 inline int ct_of(int Cout) { return 16 * mpw_of(Cout) * wm_of(Cout); }
 inline int nsteps_of(int Cin, int ntap = 9) { return ntap * (((Cin + 15) / 16 + 1) / 2); }   // whole periods of two 16-channel chunks
 
-template <int MPW, bool SIX, bool ADD, int ACT1, int KS = 3, int RPW = 4, int WM = 4, bool F16 = false>
+template <int MPW, bool ADD, int ACT1, int KS = 3, int RPW = 4, int WM = 4>
 int launch(const SParams& p, hipStream_t stream) {
     typedef Geo<MPW, KS, RPW, WM> G;
     constexpr int TRW = XG<KS, RPW>::TRW;
-    auto kern = &conv3x3_split_kernel<MPW, SIX, ADD, ACT1, KS, RPW, WM, F16>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS);
-        if (e != hipSuccess) {
-            cwfa_set_error("cwfa_conv3x3_split_f32: hipFuncSetAttribute(%d bytes LDS): %s", G::LDS, hipGetErrorString(e));
-            return CWFA_E_HIP;
-        }
-        attr_set = true;
-    }
     const int tiles_y = (p.H + TRW - 1) / TRW, ctiles = (p.Cout + G::CT - 1) / G::CT;
     SParams q = p;
     q.ntiles = p.tiles_x * tiles_y;
@@ -625,31 +613,46 @@ int launch(const SParams& p, hipStream_t stream) {
         cwfa_set_error("cwfa_conv3x3_split_f32: grid too large");
         return CWFA_E_SHAPE;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(q.ntiles * ctiles), 1, p.B), dim3(512), G::LDS, stream, q);
-    CWFA_LAUNCH_CHECK("cwfa_conv3x3_split_f32");
-    return CWFA_OK;
-}
-
-// operand format of a launch: 0 = three-piece split, six products; 1 = plain bf16; 2 = plain fp16 (split_op())
-inline int split_op() { return g_cwfa_split_products != 1 ? 0 : g_cwfa_split_operand ? 2 : 1; }
-
-template <int MPW, bool ADD, int ACT1, int KS = 3, int RPW = 4, int WM = 4>
-int launch_op(int op, const SParams& p, hipStream_t st) {
-    if (op == 0) return launch<MPW, true, ADD, ACT1, KS, RPW, WM>(p, st);
-    if (op == 1) return launch<MPW, false, ADD, ACT1, KS, RPW, WM>(p, st);
-    return launch<MPW, false, ADD, ACT1, KS, RPW, WM, true>(p, st);
+    return cwfa_with_operand([&](auto six, auto f16) -> int {
+        constexpr auto kern = &conv3x3_split_kernel<MPW, six, ADD, ACT1, KS, RPW, WM, f16>;
+        const int rc = cwfa_max_lds<kern>(G::LDS, "cwfa_conv3x3_split_f32");
+        if (rc) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(q.ntiles * ctiles), 1, p.B), dim3(512), G::LDS, stream, q);
+        CWFA_LAUNCH_CHECK("cwfa_conv3x3_split_f32");
+        return CWFA_OK;
+    });
 }
 
 template <int MPW>
-int launch_epi(int op, const SParams& p, hipStream_t st) {
+int launch_epi(const SParams& p, hipStream_t st) {
     const bool plain = !p.o.residual && p.o.act2 == CWFA_ACT_NONE;
     if (p.o.in_add) {
-        if (plain && p.o.act == CWFA_ACT_PRELU) return launch_op<MPW, true, CWFA_ACT_PRELU>(op, p, st);
-        return launch_op<MPW, true, EPI_RUNTIME>(op, p, st);
+        if (plain && p.o.act == CWFA_ACT_PRELU) return launch<MPW, true, CWFA_ACT_PRELU>(p, st);
+        return launch<MPW, true, EPI_RUNTIME>(p, st);
     }
-    if (plain && p.o.act == CWFA_ACT_PRELU) return launch_op<MPW, false, CWFA_ACT_PRELU>(op, p, st);
-    if (plain && p.o.act == CWFA_ACT_NONE) return launch_op<MPW, false, CWFA_ACT_NONE>(op, p, st);
-    return launch_op<MPW, false, EPI_RUNTIME>(op, p, st);
+    if (plain && p.o.act == CWFA_ACT_PRELU) return launch<MPW, false, CWFA_ACT_PRELU>(p, st);
+    if (plain && p.o.act == CWFA_ACT_NONE) return launch<MPW, false, CWFA_ACT_NONE>(p, st);
+    return launch<MPW, false, EPI_RUNTIME>(p, st);
+}
+
+// the weight image of a bank for ct output channels per block (ct_of; the 7x7: 64) in the active operand format
+void pack_bank(const float* w, void* packed, int Cout, int Cin, int ct, int ntap, hipStream_t st) {
+    const int nchunks = (Cin + 15) / 16, nsteps = nsteps_of(Cin, ntap);
+    const int64_t total = (int64_t)((Cout + ct - 1) / ct) * nsteps * 4 * ct;
+    cwfa_with_operand([&](auto, auto f16) -> int {
+        auto go = [&](auto CT) {
+            hipLaunchKernelGGL((split3x3_pack_kernel<decltype(CT)::value, f16>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, w,
+                               reinterpret_cast<uint4*>(packed), Cout, Cin, nchunks, nsteps, total, ntap);
+        };
+        if (ct == 16) go(cwfa_ic<16>{});
+        else if (ct == 32) go(cwfa_ic<32>{});
+        else if (ct == 48) go(cwfa_ic<48>{});
+        else if (ct == 96) go(cwfa_ic<96>{});
+        else if (ct == 128) go(cwfa_ic<128>{});
+        else if (ct == 256) go(cwfa_ic<256>{});
+        else go(cwfa_ic<64>{});
+        return CWFA_OK;
+    });
 }
 
 }  // namespace
@@ -705,13 +708,12 @@ extern "C" int cwfa_conv3x3_split_couple_f32(const float* x, const void* w_packe
     CWFA_REQUIRE((int64_t)p.tiles_x * ((H + TR - 1) / TR) < (1ll << 31) && B <= 65535, CWFA_E_SHAPE,
                  "cwfa_conv3x3_split_couple_f32: grid too large");
     hipStream_t st = (hipStream_t)stream;
-    const int op = split_op();
     if (p.Cout == 64) {
         if (g_cwfa_split_rows16 && H > 8)       // 16-row tiles (no load-side prologue here by construction)
-            return launch_op<1, false, EPI_COUPLE, 3, 8>(op, p, st);
-        return launch_op<1, false, EPI_COUPLE>(op, p, st);
+            return launch<1, false, EPI_COUPLE, 3, 8>(p, st);
+        return launch<1, false, EPI_COUPLE>(p, st);
     }
-    return launch_op<2, false, EPI_COUPLE>(op, p, st);
+    return launch<2, false, EPI_COUPLE>(p, st);
 }
 
 extern "C" int64_t cwfa_conv3x3_split_packed_bytes(int Cout, int Cin) {
@@ -724,25 +726,7 @@ extern "C" int cwfa_conv3x3_split_pack_f32(const float* w, void* packed, int Cou
     CWFA_REQUIRE(w && packed, CWFA_E_INVAL, "cwfa_conv3x3_split_pack_f32: null pointer");
     CWFA_REQUIRE(Cout > 0 && Cin > 0, CWFA_E_SHAPE, "cwfa_conv3x3_split_pack_f32: bad shape");
     CWFA_REQUIRE(cwfa_aligned16(packed), CWFA_E_ALIGN, "cwfa_conv3x3_split_pack_f32: packed image must be 16-byte aligned");
-    const int mpw = mpw_of(Cout), ct = ct_of(Cout), nchunks = (Cin + 15) / 16, nsteps = nsteps_of(Cin);
-    const int64_t total = (int64_t)((Cout + ct - 1) / ct) * nsteps * 4 * ct;
-    const dim3 grid((unsigned)((total + 255) / 256));
-    uint4* out = reinterpret_cast<uint4*>(packed);
-    if (split_op() == 2) {
-        if (ct == 32) hipLaunchKernelGGL((split3x3_pack_kernel<32, true>), grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
-        else if (ct == 48) hipLaunchKernelGGL((split3x3_pack_kernel<48, true>), grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
-        else if (ct == 96) hipLaunchKernelGGL((split3x3_pack_kernel<96, true>), grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
-        else if (ct == 16) hipLaunchKernelGGL((split3x3_pack_kernel<16, true>), grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
-        else if (mpw == 4) hipLaunchKernelGGL((split3x3_pack_kernel<256, true>), grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
-        else if (mpw == 2) hipLaunchKernelGGL((split3x3_pack_kernel<128, true>), grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
-        else hipLaunchKernelGGL((split3x3_pack_kernel<64, true>), grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
-    } else if (ct == 32) hipLaunchKernelGGL(split3x3_pack_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
-    else if (ct == 48) hipLaunchKernelGGL(split3x3_pack_kernel<48>, grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
-    else if (ct == 96) hipLaunchKernelGGL(split3x3_pack_kernel<96>, grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
-    else if (ct == 16) hipLaunchKernelGGL(split3x3_pack_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
-    else if (mpw == 4) hipLaunchKernelGGL(split3x3_pack_kernel<256>, grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
-    else if (mpw == 2) hipLaunchKernelGGL(split3x3_pack_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
-    else hipLaunchKernelGGL(split3x3_pack_kernel<64>, grid, dim3(256), 0, (hipStream_t)stream, w, out, Cout, Cin, nchunks, nsteps, total, 9);
+    pack_bank(w, packed, Cout, Cin, ct_of(Cout), 9, (hipStream_t)stream);
     CWFA_LAUNCH_CHECK("cwfa_conv3x3_split_pack_f32");
     return CWFA_OK;
 }
@@ -783,7 +767,6 @@ extern "C" int cwfa_conv3x3_split_f32(const float* x, const void* w_packed, floa
                  "cwfa_conv3x3_split_f32: one sample's input / output / one cout tile's weights must stay below 2 GiB");
     CWFA_REQUIRE((int64_t)p.tiles_x * ((H + TR - 1) / TR) < (1ll << 31) && B <= 65535, CWFA_E_SHAPE, "cwfa_conv3x3_split_f32: grid too large");
     hipStream_t st = (hipStream_t)stream;
-    const int op = split_op();
     const int wm = wm_of(Cout);
     if (wm != 4) {       // narrow tilings (<= 48 or 65 .. 96 outputs): 16-row tile, no load-side prologue, NCHW / blocked input, bias / PReLU / generic epilogue
         CWFA_REQUIRE(!p.o.in_scale && !p.o.in_add && !p.o.out_blocked8, CWFA_E_INVAL,
@@ -792,9 +775,9 @@ extern "C" int cwfa_conv3x3_split_f32(const float* x, const void* w_packed, floa
         const int epi = plain && p.o.act == CWFA_ACT_NONE ? 0 : plain && p.o.act == CWFA_ACT_PRELU ? 1 : 2;
 #define CWFA_NARROW(M, W_)                                                                                                                   \
     do {                                                                                                                                     \
-        if (epi == 0) return launch_op<M, false, CWFA_ACT_NONE, 3, 8, W_>(op, p, st);                                                    \
-        if (epi == 1) return launch_op<M, false, CWFA_ACT_PRELU, 3, 8, W_>(op, p, st);                                                   \
-        return launch_op<M, false, EPI_RUNTIME, 3, 8, W_>(op, p, st);                                                                    \
+        if (epi == 0) return launch<M, false, CWFA_ACT_NONE, 3, 8, W_>(p, st);                                                               \
+        if (epi == 1) return launch<M, false, CWFA_ACT_PRELU, 3, 8, W_>(p, st);                                                              \
+        return launch<M, false, EPI_RUNTIME, 3, 8, W_>(p, st);                                                                               \
     } while (0)
         if (mpw == 3 && wm == 2) CWFA_NARROW(3, 2);
         if (mpw == 3) CWFA_NARROW(3, 1);
@@ -802,18 +785,18 @@ extern "C" int cwfa_conv3x3_split_f32(const float* x, const void* w_packed, floa
         CWFA_NARROW(1, 1);
 #undef CWFA_NARROW
     }
-    if (mpw == 4) return launch_epi<4>(op, p, st);
-    if (mpw == 2) return launch_epi<2>(op, p, st);
+    if (mpw == 4) return launch_epi<4>(p, st);
+    if (mpw == 2) return launch_epi<2>(p, st);
     // 64-channel tiling: 16-row tiles for the plain bias-only form (the output convolutions of the sub-networks)
     if (g_cwfa_split_rows16 && H > 8 && !p.o.in_scale && !p.o.in_add && !p.o.residual && p.o.act == CWFA_ACT_NONE && p.o.act2 == CWFA_ACT_NONE)
-        return launch_op<2, false, CWFA_ACT_NONE, 3, 8, 2>(op, p, st);
+        return launch<2, false, CWFA_ACT_NONE, 3, 8, 2>(p, st);
     // (two m-tiles per wave x two channel groups instead of one x four: the same 64 channels per block and the same packed image, but a
     //  B fragment feeds two m-tiles -- 30 instead of 51 ds_read_b128 per 96 MFMAs)
     // ... and for any other epilogue without a load-side prologue (activation / residual / second activation: the data-gradient and
     // unfused forward convolutions of the sub-networks in training, 64 -> 64): 160 -> ~100 us at 512 x 512
     if (g_cwfa_split_rows16 && H > 8 && !p.o.in_scale && !p.o.in_add)
-        return launch_op<2, false, EPI_RUNTIME, 3, 8, 2>(op, p, st);
-    return launch_epi<1>(op, p, st);
+        return launch<2, false, EPI_RUNTIME, 3, 8, 2>(p, st);
+    return launch_epi<1>(p, st);
 }
 
 // ------------------------------------------------------------------------------------------------ 7x7 (ConvNeXt, networks.py:488)
@@ -826,14 +809,7 @@ extern "C" int cwfa_conv7x7_split_pack_f32(const float* w, void* packed, int Cou
     CWFA_REQUIRE(w && packed, CWFA_E_INVAL, "cwfa_conv7x7_split_pack_f32: null pointer");
     CWFA_REQUIRE(Cout > 0 && Cout <= 64 && Cin > 0, CWFA_E_SHAPE, "cwfa_conv7x7_split_pack_f32: 1 <= Cout <= 64");
     CWFA_REQUIRE(cwfa_aligned16(packed), CWFA_E_ALIGN, "cwfa_conv7x7_split_pack_f32: packed image must be 16-byte aligned");
-    const int nchunks = (Cin + 15) / 16, nsteps = nsteps_of(Cin, 49);
-    const int64_t total = (int64_t)nsteps * 4 * 64;
-    if (split_op() == 2)
-        hipLaunchKernelGGL((split3x3_pack_kernel<64, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
-                           reinterpret_cast<uint4*>(packed), Cout, Cin, nchunks, nsteps, total, 49);
-    else
-        hipLaunchKernelGGL(split3x3_pack_kernel<64>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w,
-                           reinterpret_cast<uint4*>(packed), Cout, Cin, nchunks, nsteps, total, 49);
+    pack_bank(w, packed, Cout, Cin, 64, 49, (hipStream_t)stream);
     CWFA_LAUNCH_CHECK("cwfa_conv7x7_split_pack_f32");
     return CWFA_OK;
 }
@@ -860,5 +836,5 @@ extern "C" int cwfa_conv7x7_split_f32(const float* x, const void* w_packed, floa
     CWFA_REQUIRE((int64_t)p.tiles_x * ((H + TR - 1) / TR) < (1ll << 31) && B <= 65535, CWFA_E_SHAPE, "cwfa_conv7x7_split_f32: grid too large");
     hipStream_t st = (hipStream_t)stream;
     // (2 m-tiles per wave x 2 channel groups: a B fragment feeds two m-tiles -- 18 instead of 27 ds_read_b128 per 48 MFMAs)
-    return launch_op<2, false, CWFA_ACT_NONE, 7, 4, 2>(split_op(), p, st);
+    return launch<2, false, CWFA_ACT_NONE, 7, 4, 2>(p, st);
 }

@@ -34,9 +34,7 @@
 // s+2 is issued at the start of step s and verified at its end (one barrier per step, 19 per tile).
 #include "conv_internal.h"
 
-extern int g_cwfa_split_products;       // conv2d.hip ("split_products" option: 6 or 1)
 extern int g_cwfa_split_xcd_map;        // conv2d.hip ("split3x3_xcd_map" option; also the tile walk of this kernel)
-extern int g_cwfa_split_operand;        // conv2d.hip ("split_operand" option: 0 bf16, 1 fp16)
 
 namespace {
 
@@ -583,10 +581,29 @@ int g_num_cus = 0;
 void layer_pack(const float* w3, const float* w1, void* packed, int n3, int cin3, const float* w0, void* stream) {
     const dim3 grid((unsigned)(((n3 + 2 + (w0 ? 1 : 0)) * 256 + 255) / 256));
     uint4* out = reinterpret_cast<uint4*>(packed);
-    if (g_cwfa_split_products == 1 && g_cwfa_split_operand != 0)
-        hipLaunchKernelGGL(split_layer_pack_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, w3, w1, out, n3, cin3, w0);
-    else
-        hipLaunchKernelGGL(split_layer_pack_kernel<>, grid, dim3(256), 0, (hipStream_t)stream, w3, w1, out, n3, cin3, w0);
+    cwfa_with_operand([&](auto, auto f16) -> int {
+        hipLaunchKernelGGL(split_layer_pack_kernel<f16>, grid, dim3(256), 0, (hipStream_t)stream, w3, w1, out, n3, cin3, w0);
+        return CWFA_OK;
+    });
+}
+
+// one launch of a form of the layer (NPER, TAPE, XF, SHORT) on the layout of p: the tape form is built for NCHW maps only,
+// the fused first map (XF) has no x and so no input layout
+template <bool SIX, bool F16, int NPER, bool TAPE = false, bool XF = false, bool SHORT = false>
+int layer_form(const LParams& p, int grid, hipStream_t st) {
+    auto go = [&](auto inb, auto outb) -> int {
+        constexpr auto kern = &split_layer_kernel<SIX, inb, outb, NPER, TAPE, XF, SHORT, F16>;
+        const int rc = cwfa_max_lds<kern>(LDS_BYTES, "cwfa_subnet_layer_split_f32");
+        if (rc) return rc;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS_BYTES, st, p);
+        CWFA_LAUNCH_CHECK("cwfa_subnet_layer_split_f32");
+        return CWFA_OK;
+    };
+    if constexpr (!TAPE && !XF)
+        if (p.in_blocked) return p.out_blocked ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
+    if constexpr (!TAPE)
+        if (p.out_blocked) return go(std::false_type{}, std::true_type{});
+    return go(std::false_type{}, std::false_type{});
 }
 
 }  // namespace
@@ -680,45 +697,13 @@ static int layer_launch(const float* x, const void* packed, const float* b3, con
         }
         g_num_cus = n;
     }
-    const int six = g_cwfa_split_products != 1 ? 1 : g_cwfa_split_operand ? 2 : 0;     // operand format: 1 split, 0 plain bf16, 2 plain fp16
-    typedef void (*kern_t)(LParams);
-    static const kern_t kerns[2][3][4] = {
-        {{&split_layer_kernel<false, false, false>, &split_layer_kernel<false, true, false>, &split_layer_kernel<false, false, true>,
-          &split_layer_kernel<false, true, true>},
-         {&split_layer_kernel<true, false, false>, &split_layer_kernel<true, true, false>, &split_layer_kernel<true, false, true>,
-          &split_layer_kernel<true, true, true>},
-         {&split_layer_kernel<false, false, false, 2, false, false, false, true>, &split_layer_kernel<false, true, false, 2, false, false, false, true>,
-          &split_layer_kernel<false, false, true, 2, false, false, false, true>, &split_layer_kernel<false, true, true, 2, false, false, false, true>}},
-        {{&split_layer_kernel<false, false, false, 1>, &split_layer_kernel<false, true, false, 1>, &split_layer_kernel<false, false, true, 1>,
-          &split_layer_kernel<false, true, true, 1>},
-         {&split_layer_kernel<true, false, false, 1>, &split_layer_kernel<true, true, false, 1>, &split_layer_kernel<true, false, true, 1>,
-          &split_layer_kernel<true, true, true, 1>},
-         {&split_layer_kernel<false, false, false, 1, false, false, false, true>, &split_layer_kernel<false, true, false, 1, false, false, false, true>,
-          &split_layer_kernel<false, false, true, 1, false, false, false, true>, &split_layer_kernel<false, true, true, 1, false, false, false, true>}}};
-    static const kern_t tape_kerns[3] = {&split_layer_kernel<false, false, false, 2, true>, &split_layer_kernel<true, false, false, 2, true>,
-                                         &split_layer_kernel<false, false, false, 2, true, false, false, true>};
-    static const kern_t xf_kerns[3][2] = {{&split_layer_kernel<false, false, false, 1, false, true>, &split_layer_kernel<false, false, true, 1, false, true>},
-                                          {&split_layer_kernel<true, false, false, 1, false, true>, &split_layer_kernel<true, false, true, 1, false, true>},
-                                          {&split_layer_kernel<false, false, false, 1, false, true, false, true>,
-                                           &split_layer_kernel<false, false, true, 1, false, true, false, true>}};
-    static const kern_t xs_kerns[3][2] = {{&split_layer_kernel<false, false, false, 1, false, true, true>, &split_layer_kernel<false, false, true, 1, false, true, true>},
-                                          {&split_layer_kernel<true, false, false, 1, false, true, true>, &split_layer_kernel<true, false, true, 1, false, true, true>},
-                                          {&split_layer_kernel<false, false, false, 1, false, true, true, true>,
-                                           &split_layer_kernel<false, false, true, 1, false, true, true, true>}};
-    const int first = shortf ? 4 : fused_x ? 3 : u != nullptr ? 1 : hid != nullptr ? 2 : 0;
-    kern_t kern = first == 4 ? xs_kerns[six][layout >> 1] : first == 3 ? xf_kerns[six][layout >> 1] : first == 2 ? tape_kerns[six] : kerns[first][six][layout];
-    static bool attr_set_all[5][3][4] = {};
-    bool& attr_done = attr_set_all[first][six][layout];
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        if (e != hipSuccess) {
-            cwfa_set_error("cwfa_subnet_layer_split_f32: hipFuncSetAttribute(%d bytes LDS): %s", LDS_BYTES, hipGetErrorString(e));
-            return CWFA_E_HIP;
-        }
-        attr_done = true;
-    }
     const int grid = (int)(ntiles < g_num_cus ? ntiles : g_num_cus);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, p);
-    CWFA_LAUNCH_CHECK("cwfa_subnet_layer_split_f32");
-    return CWFA_OK;
+    const hipStream_t st = (hipStream_t)stream;
+    return cwfa_with_operand([&](auto six, auto f16) -> int {
+        if (shortf) return layer_form<six, f16, 1, false, true, true>(p, grid, st);
+        if (fused_x) return layer_form<six, f16, 1, false, true>(p, grid, st);
+        if (u) return layer_form<six, f16, 1>(p, grid, st);
+        if (hid) return layer_form<six, f16, 2, true>(p, grid, st);
+        return layer_form<six, f16, 2>(p, grid, st);
+    });
 }

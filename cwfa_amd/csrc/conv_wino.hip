@@ -555,16 +555,8 @@ int wlaunch(WParams p, hipStream_t stream) {
     CWFA_REQUIRE((int64_t)(p.Cin + C::CK) * p.H * p.W * 4 < (1ll << 31), CWFA_E_SHAPE,
                  "cwfa_conv2d_f32: one sample's input must stay below 2 GiB (32-bit buffer offsets)");
     constexpr int LDS = EPI == WEPI_GENERIC && C::LDS_BYTES < C::NTHREADS * 128 ? C::NTHREADS * 128 : C::LDS_BYTES;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_kernel<C, EPI, PRO>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) {
-            cwfa_set_error("cwfa_conv2d_f32 (winograd): hipFuncSetAttribute(%d bytes LDS): %s", LDS, hipGetErrorString(e));
-            return CWFA_E_HIP;
-        }
-        attr_set = true;
-    }
+    const int rc = cwfa_max_lds<&conv3x3_wino_kernel<C, EPI, PRO>>(LDS, "cwfa_conv2d_f32 (winograd)");
+    if (rc) return rc;
     dim3 grid((unsigned)(p.tiles_x * p.tiles_y * ctiles), 1, p.B);
     hipLaunchKernelGGL((conv3x3_wino_kernel<C, EPI, PRO>), grid, dim3(C::NTHREADS), LDS, stream, p);
     CWFA_LAUNCH_CHECK("cwfa_conv2d_f32 (winograd)");
@@ -660,19 +652,9 @@ int cwfa_wino_layer(const float* x, const float* w3_packed, const float* b3, con
     CWFA_REQUIRE((int64_t)p.tiles_x * p.tiles_y < (1ll << 31) && B <= 65535, CWFA_E_SHAPE, "cwfa_subnet_layer_f32: grid too large");
     CWFA_REQUIRE((int64_t)(64 + C::CK) * H * W * 4 < (1ll << 31), CWFA_E_SHAPE,
                  "cwfa_subnet_layer_f32: one sample's input must stay below 2 GiB (32-bit buffer offsets)");
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_layer_kernel<false>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&wino_layer_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    C::LDS_BYTES);
-        if (e != hipSuccess) {
-            cwfa_set_error("cwfa_subnet_layer_f32: hipFuncSetAttribute(%d bytes LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-            return CWFA_E_HIP;
-        }
-        attr_set = true;
-    }
+    int rc = cwfa_max_lds<&wino_layer_kernel<false>>(C::LDS_BYTES, "cwfa_subnet_layer_f32");
+    if (rc == CWFA_OK) rc = cwfa_max_lds<&wino_layer_kernel<true>>(C::LDS_BYTES, "cwfa_subnet_layer_f32");
+    if (rc) return rc;
     dim3 grid((unsigned)(p.tiles_x * p.tiles_y), 1, B);
     if (hidden)
         hipLaunchKernelGGL(wino_layer_kernel<true>, grid, dim3(C::NTHREADS), C::LDS_BYTES, stream, p);

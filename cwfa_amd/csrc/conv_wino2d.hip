@@ -393,16 +393,8 @@ int launch2d(W2Params p, hipStream_t stream) {
                  "cwfa_conv2d_f32: grid too large");
     CWFA_REQUIRE((int64_t)(p.Cin + 4 * C::CK) * p.H * p.W * 4 < (1ll << 31), CWFA_E_SHAPE,
                  "cwfa_conv2d_f32: one sample's input must stay below 2 GiB (32-bit buffer offsets)");
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino2d_kernel<EPI, PRO, ALIGNED>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
-        if (e != hipSuccess) {
-            cwfa_set_error("cwfa_conv2d_f32: hipFuncSetAttribute(%d bytes LDS): %s", C::LDS_BYTES, hipGetErrorString(e));
-            return CWFA_E_HIP;
-        }
-        attr_set = true;
-    }
+    const int rc = cwfa_max_lds<&conv3x3_wino2d_kernel<EPI, PRO, ALIGNED>>(C::LDS_BYTES, "cwfa_conv2d_f32");
+    if (rc) return rc;
     dim3 grid((unsigned)(p.tiles_x * p.tiles_y * ctiles), 1, p.B);
     hipLaunchKernelGGL((conv3x3_wino2d_kernel<EPI, PRO, ALIGNED>), grid, dim3(C::NTHREADS), C::LDS_BYTES, stream, p);
     CWFA_LAUNCH_CHECK("cwfa_conv2d_f32 (winograd 2-D)");
