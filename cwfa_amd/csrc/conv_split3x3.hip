@@ -613,6 +613,12 @@ int launch(const SParams& p, hipStream_t stream) {
         cwfa_set_error("cwfa_conv3x3_split_f32: grid too large");
         return CWFA_E_SHAPE;
     }
+    // the run-time and coupling epilogues write neither statistics nor a channel-blocked output: a dispatch that lands here
+    // with either requested would drop them silently
+    if ((ACT1 == EPI_RUNTIME || ACT1 == EPI_COUPLE) && (p.o.out_stats || p.o.out_blocked8)) {
+        cwfa_set_error("cwfa_conv3x3_split_f32: out_stats / out_blocked8 reached a run-time epilogue");
+        return CWFA_E_INVAL;
+    }
     return cwfa_with_operand([&](auto six, auto f16) -> int {
         constexpr auto kern = &conv3x3_split_kernel<MPW, six, ADD, ACT1, KS, RPW, WM, f16>;
         const int rc = cwfa_max_lds<kern>(G::LDS, "cwfa_conv3x3_split_f32");
@@ -751,6 +757,9 @@ extern "C" int cwfa_conv3x3_split_f32(const float* x, const void* w_packed, floa
     CWFA_REQUIRE(!p.o.out_stats || (!p.o.out_blocked8 && !p.o.residual && p.o.act2 == CWFA_ACT_NONE &&
                                     (p.o.act == CWFA_ACT_NONE || p.o.act == CWFA_ACT_PRELU)),
                  CWFA_E_INVAL, "cwfa_conv3x3_split_f32: out_stats needs an NCHW output and a bias / PReLU epilogue");
+    // (a skip add with a bias-only epilogue runs on the run-time epilogue, which writes neither: launch_epi)
+    CWFA_REQUIRE(!((p.o.out_stats || p.o.out_blocked8) && p.o.in_add && p.o.act == CWFA_ACT_NONE), CWFA_E_INVAL,
+                 "cwfa_conv3x3_split_f32: out_stats / out_blocked8 with in_add need a PReLU epilogue");
     CWFA_REQUIRE(p.o.act >= 0 && p.o.act <= CWFA_ACT_RELU && p.o.act2 >= 0 && p.o.act2 <= CWFA_ACT_RELU, CWFA_E_INVAL,
                  "cwfa_conv3x3_split_f32: bad activation");
     CWFA_REQUIRE(!((p.o.act == CWFA_ACT_PRELU || p.o.act2 == CWFA_ACT_PRELU) && !p.o.prelu_alpha), CWFA_E_INVAL,
@@ -793,8 +802,9 @@ extern "C" int cwfa_conv3x3_split_f32(const float* x, const void* w_packed, floa
     // (two m-tiles per wave x two channel groups instead of one x four: the same 64 channels per block and the same packed image, but a
     //  B fragment feeds two m-tiles -- 30 instead of 51 ds_read_b128 per 96 MFMAs)
     // ... and for any other epilogue without a load-side prologue (activation / residual / second activation: the data-gradient and
-    // unfused forward convolutions of the sub-networks in training, 64 -> 64): 160 -> ~100 us at 512 x 512
-    if (g_cwfa_split_rows16 && H > 8 && !p.o.in_scale && !p.o.in_add)
+    // unfused forward convolutions of the sub-networks in training, 64 -> 64): 160 -> ~100 us at 512 x 512; not when statistics or a
+    // blocked output are asked for (only the compile-time epilogues write them: a plain PReLU then takes launch_epi<1>)
+    if (g_cwfa_split_rows16 && H > 8 && !p.o.in_scale && !p.o.in_add && !p.o.out_stats && !p.o.out_blocked8)
         return launch<2, false, EPI_RUNTIME, 3, 8, 2>(p, st);
     return launch_epi<1>(p, st);
 }

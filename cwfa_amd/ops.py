@@ -430,10 +430,12 @@ def pack_conv_weight_cat(w, c1):
     return pc
 
 
-def conv_writes_stats(pc, act=None, residual=None, act2=None, out_blocked=False):
+def conv_writes_stats(pc, act=None, residual=None, act2=None, out_blocked=False, in_add=False):
     """True when conv2d(..., out_stats=) is available for this bank / epilogue: the split-bf16 3x3 kernel with an NCHW output and
-    a bias / PReLU epilogue takes the per-channel (sum, sum of squares) of its output from the accumulators."""
-    return bool(pc.split and pc.ks == 3 and act in (None, "prelu") and residual is None and act2 is None and not out_blocked)
+    a bias / PReLU epilogue takes the per-channel (sum, sum of squares) of its output from the accumulators.  ``in_add``: the
+    call adds a tensor on load; with a bias-only epilogue that runs on the kernel's run-time epilogue, which has no statistics."""
+    return bool(pc.split and pc.ks == 3 and act in (None, "prelu") and residual is None and act2 is None and not out_blocked
+                and not (in_add and act is None))
 
 
 def conv2d(x, pc, bias=None, act=None, prelu_alpha=None, residual=None, act2=None, in_scale=None, in_shift=None,
@@ -503,14 +505,14 @@ def conv2d(x, pc, bias=None, act=None, prelu_alpha=None, residual=None, act2=Non
         o.in_blocked8 = 1
     if out_blocked:                         # y leaves channel-blocked: the split-bf16 3x3 kernel (bias / PReLU epilogue), or plain 1x1
         ok3 = (pc.split and pc.ks == 3 and pc.cout % 8 == 0 and residual is None and act2 is None and act in (None, "prelu")
-               and not split3x3_narrow(pc.cout))
+               and not split3x3_narrow(pc.cout) and not (in_add is not None and act is None))
         ok1 = not pc.split and pc.ks == 1 and pc.cout >= 33 and pc.cout % 8 == 0 and not up
         if not (ok3 or ok1):                # banks with 33..64 outputs on the fp32 MFMA kernel
             raise ValueError("conv2d: channel-blocked output is written by the split-bf16 3x3 kernel (bias / PReLU) and by the "
                              "direct 1x1 kernel with 40..64 output channels only")
         o.out_blocked8 = 1
     if out_stats is not None:
-        if not conv_writes_stats(pc, act, residual, act2, out_blocked):
+        if not conv_writes_stats(pc, act, residual, act2, out_blocked, in_add is not None):
             raise ValueError("conv2d: out_stats needs the split-bf16 3x3 kernel with an NCHW output and a bias / PReLU epilogue")
         if out_stats.dtype != torch.float64 or out_stats.numel() != 2 * pc.cout or not out_stats.is_cuda:
             raise ValueError("conv2d: out_stats must be a float64 [2*Cout] tensor on the HIP device")

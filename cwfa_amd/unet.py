@@ -190,7 +190,7 @@ class UNetConvBlock(nn.Module):
             # kernel can do that (split-bf16 3x3, NCHW output)
             st = None
             if (STATS_IN_EPILOGUE and bn is not None and _bn_batch_stats(bn)
-                    and ops.conv_writes_stats(packs[li], kind)):
+                    and ops.conv_writes_stats(packs[li], kind, in_add=add is not None)):
                 st = _bn_stats_buffer(bn, x.device)
             x = ops.conv2d(x, packs[li], bias=conv.bias, act=kind, prelu_alpha=alpha, in_scale=sc,
                            in_shift=sh, in_add=add, out_stats=st)

@@ -215,7 +215,7 @@ typedef struct {
     int out_blocked8;         /* y is written channel-blocked [B][Cout/8][H][W][8]: cwfa_conv2d_f32 for 1x1 banks
                                  with 33..64 outputs, bias only (the first convolution of a coupling sub-network
                                  feeding cwfa_subnet_layer_split_f32 with layout bit 0); cwfa_conv3x3_split_f32
-                                 with a bias / PReLU epilogue (consumer: in_blocked8)                         */
+                                 with a bias / PReLU epilogue, with in_add PReLU only (consumer: in_blocked8) */
     const float* in_cat;      /* cwfa_conv2d_f32, 1x1 banks with <= 64 outputs, no other in_*: the input is the channel
                                  concatenation cat(x, in_cat) WITHOUT materialising it (the input of a coupling
                                  sub-network, cat(half, *conditions): coupling_layers.py:74-87, all_in_one_block.py:
@@ -223,9 +223,9 @@ typedef struct {
                                  channels(in_cat) with zero columns in [in_cat_c1, in_cat_from), in_cat_from % 16 == 0 */
     int64_t in_cat_bs;
     int in_cat_from, in_cat_c1;
-    double* out_stats;        /* cwfa_conv3x3_split_f32 only (NCHW output, bias / PReLU epilogue): nullable [2*Cout]; the
-                                 launch ADDS (sum y, sum y^2) of its output over (B,H,W) per channel -- the train-mode
-                                 BatchNorm statistics of the layer that follows the convolution (unet.py:99-107), taken
+    double* out_stats;        /* cwfa_conv3x3_split_f32 only (NCHW output, bias / PReLU epilogue; with in_add PReLU only):
+                                 nullable [2*Cout]; the launch ADDS (sum y, sum y^2) of its output over (B,H,W) per
+                                 channel -- the train-mode BatchNorm statistics of the layer that follows the convolution (unet.py:99-107), taken
                                  from the accumulators instead of a second pass over y (cwfa_channel_stats_f32)       */
     int prelu_per_channel;    /* cwfa_conv3x3_split_f32 only: prelu_alpha points to Cout slopes, one per output channel
                                  (slope 1.0 = no activation on that channel): several filter banks that read the same

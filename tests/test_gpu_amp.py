@@ -9,9 +9,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from split_ref import F16_TOL, _pro32, b16, check16, h, maxrel, pack_split3x3
+
 
 pytestmark = pytest.mark.gpu
-F16_TOL = 2e-5
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -28,37 +29,6 @@ def _restore_precision():
     from cwfa_amd import ops
     yield
     ops.set_precision("fp32")
-
-
-def h(t):
-    return t.half().double()
-
-
-def b16(t):
-    return t.bfloat16().double()
-
-
-def maxrel(got, want):
-    got, want = got.detach().double().cpu(), want.detach().double().cpu()
-    return float((got - want).abs().max() / want.abs().max())
-
-
-def check16(got, ref_h, ref_b, what, tol=F16_TOL):
-    """fp16 reference within tol; the bf16 reference at least 10x further away"""
-    e_h, e_b = maxrel(got, ref_h), maxrel(got, ref_b)
-    assert e_h <= tol, (what, "vs fp16-rounded reference", e_h)
-    assert e_b >= 10 * e_h, (what, "the bf16-rounded reference is not clearly further away", e_h, e_b)
-    return e_h, e_b
-
-
-def _pro32(x, sc=None, sh=None, add=None):
-    """the kernels' load-side prologue in fp32: (x * sc + sh) + add"""
-    v = x
-    if sc is not None:
-        v = v * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1)
-    if add is not None:
-        v = v + add
-    return v
 
 
 # ------------------------------------------------------------------------------------------------ kernel units
@@ -106,16 +76,6 @@ def test_fp16_conv_transpose():
     check16(y, ct(h), ct(b16), "transposed")
 
 
-def _pack3x3(ops, w, Cout, Cin):
-    if Cin >= 29 or Cout > 32:
-        return ops.pack_conv_weight(w)
-    L_ = ops._lib.lib()                  # (the selection rule wants >= 29 inputs for the narrow tilings: pack directly)
-    packed = torch.empty(L_.cwfa_conv3x3_split_packed_bytes(Cout, Cin), dtype=torch.uint8, device="cuda")
-    wc = w.contiguous()
-    ops.check(L_.cwfa_conv3x3_split_pack_f32(ops._p(wc), ops._p(packed), Cout, Cin, ops._stream()), "pack")
-    return ops.PackedConv(packed, Cout, Cin, 3, False, wc._version, wc.data_ptr(), split=True)
-
-
 @pytest.mark.parametrize("cfg", [(1, 70, 7, 63, 200), (1, 256, 8, 64, 256), (2, 20, 12, 37, 320), (1, 6, 19, 40, 256),
                                  (1, 48, 9, 33, 130), (2, 33, 17, 50, 520), (1, 64, 16, 32, 96), (1, 64, 5, 20, 12),
                                  (1, 64, 33, 50, 24), (2, 29, 20, 40, 6), (1, 24, 16, 32, 32), (1, 64, 40, 64, 17), (1, 29, 9, 12, 16),
@@ -138,7 +98,7 @@ def test_fp16_3x3(cfg):
     keep_min = ops.SPLIT_3X3_MIN_COUT
     ops.SPLIT_3X3_MIN_COUT = 1
     try:
-        pc = _pack3x3(ops, w.cuda(), Cout, Cin)
+        pc = pack_split3x3(ops, w.cuda())
         assert pc.split
         got = {"plain": ops.conv2d(x.cuda(), pc, bias=b.cuda()),
                "prelu": ops.conv2d(x.cuda(), pc, bias=b.cuda(), act="prelu", prelu_alpha=alpha.cuda()),

@@ -1449,7 +1449,7 @@ def test_conv1x1_two_source_input_equals_the_concatenation(cfg):
 
 
 @pytest.mark.parametrize("cfg", [(1, 64, 256, 64, 64, "prelu"), (2, 24, 100, 19, 45, "prelu"), (2, 40, 40, 33, 31, None), (1, 16, 300, 8, 32, "prelu"),
-                                 (1, 64, 64, 40, 64, None)])
+                                 (1, 64, 64, 40, 64, None), (1, 64, 64, 40, 64, "prelu"), (2, 33, 56, 8, 31, "prelu")])
 def test_conv_epilogue_statistics_equal_a_pass_over_the_output(cfg):
     """cwfa_conv_opts.out_stats (unet.py:99-107: conv -> PReLU -> train-mode BatchNorm): the (sum, sum of squares) the split-bf16
     3x3 kernel takes from its accumulators against ops.channel_stats of the tensor it wrote -- every tiling (64 / 128 / 256
