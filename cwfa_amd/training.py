@@ -81,9 +81,16 @@ def _packT(conv):
 
 
 def _conv_param_grads(conv, x, dy):
-    """Accumulate dL/dW, dL/db of ``y = conv(x)`` into conv.weight.grad / conv.bias.grad."""
+    """Accumulate dL/dW, dL/db of ``y = conv(x)`` into conv.weight.grad / conv.bias.grad.  Frozen parameters
+    (requires_grad=False) get no .grad: an optimiser steps every parameter whose .grad is not None."""
     ks = conv.kernel_size[0]
     w, b = conv.weight, conv.bias
+    if b is not None and not b.requires_grad:
+        b = None
+    if not w.requires_grad:
+        if b is not None:                                                    # frozen weight: the bias gradient is sum(dy)
+            _acc(b, ops.channel_stats(dy).view(-1, 2)[:, 0])
+        return
     if b is not None and (w.grad is None) != (b.grad is None):            # mixed state: give the missing one zeros
         for t in (w, b):
             if t.grad is None:
@@ -292,6 +299,8 @@ def _masked_w2(w2, mask_b):
 
 
 def _acc(param, g):
+    if not param.requires_grad:             # frozen: no .grad (see _conv_param_grads)
+        return
     g = g.to(param.dtype).reshape(param.shape)
     if param.grad is None:
         param.grad = g.clone()
@@ -519,10 +528,15 @@ def _convnext_backward(tape, g_out, want_input_grad):
     g_p = ops.gelu_bwd(g_out, p)
     _conv_param_grads(cn.m[2], vln, g_p)
     g_vln = ops.conv2d(g_p, _packT(cn.m[2]))
+    dw_db = []
     for t in (ln.weight, ln.bias):
+        if not t.requires_grad:             # frozen: the kernel still adds into a buffer, a scratch one
+            dw_db.append(torch.zeros_like(t))
+            continue
         if t.grad is None:
             t.grad = torch.zeros_like(t)
-    g_v = ops.layernorm_bwd(g_vln, v, ln.weight, mean, invstd, ln.weight.grad, ln.bias.grad)
+        dw_db.append(t.grad)
+    g_v = ops.layernorm_bwd(g_vln, v, ln.weight, mean, invstd, *dw_db)
     _conv_param_grads(cn.m[0], u, g_v)
     g_u = ops.conv2d(g_v, _packT(cn.m[0]))
     g_res = g_out if gate is None else ops.scale_channels(g_out, gate.expand(g_out.shape[0], g_out.shape[1]).contiguous())
