@@ -2,19 +2,24 @@
 (``evaluate_INN_forward`` :134-196), the per-volume inverse loop (:865-924) and the training-time NLL (:966-978),
 plus the batch-sharded multi-GPU NLL (new; the reference is single-device).
 
+The evaluation block behind every reconstructed volume (CWFA.py:1032-1117) is at the end of this file: step metrics
+(``compute_INN_step_performance`` :98-132, fused as ``evaluate_step``) and the neuron traces (``corr_coeff_3D`` :240-379).
+
 Out of scope: experiment management of ``run_CWFA`` -- checkpoint discovery, optimisers,
-TensorBoard, metrics, figures, TIFF export.
+TensorBoard, figures, TIFF export.
 """
 import math
 
 import torch
 
 from . import ops
+from .amp import amp_function
 
 __all__ = ["sample_z_truncated", "check_empty_depths", "evaluate_INN_forward", "inverse_pass", "nll_step",
            "nll_terms", "allreduce_nll", "build_networks", "step_log_likelihoods", "allgather_scores", "detect_ood",
            "forward_nll_pass", "mean_volume_cache", "save_mean_volume_cache", "load_mean_volume_cache",
-           "denormalise_prediction", "denormalise_ground_truth"]
+           "denormalise_prediction", "denormalise_ground_truth", "compute_INN_step_performance", "evaluate_step", "roi_boxes",
+           "corr_coeff_3D"]
 
 
 def _no_grad_trunc_normal_(tensor, mean=0., std=1., a=-1., b=1.):
@@ -333,3 +338,177 @@ def denormalise_ground_truth(gt_volume, std_vols, mean_vols):
     shift = torch.as_tensor(mean_vols, dtype=torch.float32).reshape(()).to(x.device)
     v = ops.channel_affine(x, scale.expand(C_).contiguous(), shift.expand(C_).contiguous())[0]
     return v - v.min()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Evaluation pass (CWFA.py:1032-1117): step metrics, projections, neuron traces.  Inputs are assumed finite.
+# ---------------------------------------------------------------------------------------------------------------------
+def _metric_scalars(sums, numel):
+    """(PSNR in dB, masked MAE * 100) from the [B,4] float64 sums of ``ops.volume_metrics`` over the whole batch; PSNR with the
+    ``mse == 0`` branches of utils.py:389-392."""
+    sse, sg, sam, _ = sums.sum(0).tolist()
+    if sse == 0:
+        p = 0.0 if sg == 0 else 100.0
+    else:
+        p = 20.0 * math.log10(1.0 / math.sqrt(sse / numel))
+    return p, sam / numel * 100.0
+
+
+def _mask_threshold(max_abs_pred, ths):
+    """``p.abs().max() * ths`` as the reference forms it (fp32 scalar times Python number, CWFA.py:126); ths == 0: no mask."""
+    if ths == 0:
+        return float("-inf")
+    return float(torch.as_tensor(max_abs_pred, dtype=torch.float32).reshape(()).cpu() * ths)
+
+
+def _raw_volume(x, step, mean, std, offset=None):
+    """(x / 2**step) * std - mean as a tensor, bit for bit (one per-channel affine launch: the power of two commutes with the
+    rounding of the product, the kernel multiplies, then adds)."""
+    C_ = x.shape[1]
+    scale = (torch.as_tensor(std, dtype=torch.float32).reshape(()).cpu() * (2.0 ** -int(step))).to(x.device)
+    shift = (-torch.as_tensor(mean, dtype=torch.float32).reshape(()).cpu()).to(x.device)
+    return ops.channel_affine(x, scale.expand(C_).contiguous(), shift.expand(C_).contiguous())
+
+
+def _minus(x, value):
+    """x - value (fp32 scalar) through the per-channel affine kernel: x * 1 + (-value) is exact in its first step."""
+    C_ = x.shape[1]
+    one = torch.ones(C_, dtype=torch.float32, device=x.device)
+    return ops.channel_affine(x, one, torch.full((C_,), -float(value), dtype=torch.float32, device=x.device))
+
+
+@amp_function
+def compute_INN_step_performance(gt_volume_in, pred_volume_in, step, mean, std, normaliaze_before_metrics=False, ths=0.05):
+    """PSNR and masked MAE ("MAPE") of one pyramid step; CWFA.py:98-132, same signature.  Returns
+    ``(psnr, masked_mae * 100, gt_volume_raw, pred_volume_raw)``: the raw volumes are materialised because the signature returns
+    them (``evaluate_step`` is the form that does not).  The sums are float64 device sums of one pass over both raw volumes.
+
+    Not mirrored: the reference's bare ``except`` that returns the 5-tuple ``0, 0, 1, gt, pred``.  ``ths == 0``: the reference
+    leaves ``masked_psnr`` unassigned and raises UnboundLocalError; here the mask is empty and the value is the plain MAE * 100."""
+    gt_raw = _raw_volume(ops._dev(gt_volume_in, "gt_volume_in"), step, mean, std)
+    pred_raw = _raw_volume(ops._dev(pred_volume_in, "pred_volume_in"), step, mean, std)
+    ext = ops.volume_extrema(pred_raw, gt_raw).cpu()
+    max_abs_pred = ext[:, 3].max()
+    if normaliaze_before_metrics:
+        gt_raw, pred_raw = _minus(gt_raw, ext[:, 4].min()), _minus(pred_raw, ext[:, 0].min())
+        max_abs_pred = ops.volume_extrema(pred_raw).cpu()[:, 3].max()
+    sums = ops.volume_metrics(pred_raw, gt_raw, _mask_threshold(max_abs_pred, ths))
+    p, m = _metric_scalars(sums, gt_raw.numel())
+    return p, m, gt_raw, pred_raw
+
+
+@amp_function
+def evaluate_step(gt, pred, step, mean, std, ths=0.05, projections=True, on_device=False):
+    """What the body of the reference's evaluation loop (CWFA.py:1065-1085) amounts to for one pyramid step, without writing a raw
+    volume: one extrema pass and one metrics pass over (pred, gt) with the de-normalisation applied on load, and one pass that
+    forms the maximum projections of |pred|, |gt| and |pred - gt| together.  Returns ``(psnr, masked_mae * 100, img_pred, img_gt,
+    img_diff)``: the scalars of ``compute_INN_step_performance`` and the composites ``volume_2_projections`` gives for the raw
+    prediction, the raw ground truth and their absolute difference (CPU float32 [B,1,H',W'] like there; ``on_device=True`` keeps
+    them on the GPU; ``projections=False``: None)."""
+    from . import utils as U
+    ops._dev(gt, "gt"), ops._dev(pred, "pred")
+    aff = ops.eval_affine(step, mean, std)
+    ext = ops.volume_extrema(pred, gt, aff).cpu()
+    sums = ops.volume_metrics(pred, gt, _mask_threshold(ext[:, 3].max(), ths), aff)
+    imgs = [None, None, None]
+    if projections:
+        U.check_layout(pred.shape, [1, 1, 2])
+        zp, xp, yp, _ = ops.mip3(pred, gt, triple=True, affine=aff)
+        imgs = [U.compose_projections(zp[q], xp[q], yp[q], [1, 1, 2], 2, False) for q in range(3)]
+        if not on_device:
+            imgs = [im.cpu() for im in imgs]
+    p, m = _metric_scalars(sums, gt.numel())
+    return (p, m, *imgs)
+
+
+def roi_boxes(coords, shape, r12, r3, start_plane_offset=-25 // 2):
+    """The index ranges of the reference's ROIs (CWFA.py:282-285) for a stack of ``shape`` [T,D,H,W]: int32 [N,6] rows
+    (z0, z1, y0, y1, x0, x1), half-open, with z shifted by ``D // 2 + start_plane_offset`` (the coordinates come from the central
+    25 planes of a stack).  An empty range is written as (0, 0).  Each range is clipped by the axis it indexes (the reference
+    clips x by shape[2] and y by shape[3] but indexes the other way round: the same for H == W)."""
+    import numpy as np
+    _, D, H, W = shape
+    out = np.zeros((len(coords), 6), dtype=np.int32)
+    for ix, (x_coord, y_coord, z_coord) in enumerate(coords):
+        z_coord = z_coord + D // 2 + start_plane_offset
+        for k, (c, r, n) in enumerate(((z_coord, r3, D), (y_coord, r12, H), (x_coord, r12, W))):
+            lo, hi = max(0, int(c) - r), min(n, int(c) + r)
+            if hi > lo:
+                out[ix, 2 * k], out[ix, 2 * k + 1] = lo, hi
+    return out
+
+
+def correlate_traces(coords, boxes, traces_gt, traces_pred, median_gt, depth_shift, n_time_steps, minmax_ths=50, filter_width=10):
+    """The host part of ``corr_coeff_3D`` (CWFA.py:259-337) on the [N,T] ROI traces of the two max-normalised stacks and the
+    median of the positive ground-truth voxels: ``norm_data``, the ``minmax < img_ths`` gate, the threshold-halving loop (the
+    lists keep growing over its sweeps, as there), ``np.corrcoef``, the data frame.
+    Not mirrored: the reference's bare ``try / except`` around an ROI (coefficient 0, the previous ROI's signals reused in the
+    frame, a ``roi_outside`` print).  Nothing in it raises here: an empty box gives NaN traces in the reference too, which is
+    what this returns."""
+    import numpy as np
+    from .utils import norm_data
+    cols = ['patch_n', 'coord_x', 'coord_y', 'coord_z', 'corr_coeff', 'is_gt'] + [f't{t}' for t in range(n_time_steps)]
+    all_corr_coeffs, rows, index = [], [], []
+    required_coords = int(len(coords) * 0.2)
+    n_divisions = 0
+    while len(all_corr_coeffs) <= required_coords and n_divisions < 5:
+        img_ths = np.float32(median_gt) * np.float32(minmax_ths)
+        for ix, (x_coord, y_coord, z_coord) in enumerate(coords):
+            z_coord = z_coord + depth_shift
+            width = min(filter_width, int(boxes[ix, 1] - boxes[ix, 0]))          # min(filter_width, gt_data.shape[-1]): the z extent
+            GT_signal, minmax = norm_data(traces_gt[ix], width)
+            if minmax < img_ths:
+                continue
+            pred_signal, _ = norm_data(traces_pred[ix], width)
+            if GT_signal.max() == 0 or pred_signal.max() == 0:
+                corr_coeff = 0
+            else:
+                corr_coeff = np.corrcoef(GT_signal, pred_signal)[0][1]
+            all_corr_coeffs.append(corr_coeff)
+            for is_gt, sig in ((1, GT_signal), (0, pred_signal)):
+                row = {'patch_n': ix, 'coord_x': x_coord, 'coord_y': y_coord, 'coord_z': z_coord, 'corr_coeff': corr_coeff, 'is_gt': is_gt}
+                row.update({f't{t}': sig[t] for t in range(len(sig))})
+                rows.append(row)
+                index.append(ix)
+        if len(all_corr_coeffs) <= required_coords:
+            minmax_ths /= 2
+            n_divisions += 1
+    return all_corr_coeffs, _trace_frame(rows, index, cols)
+
+
+def _trace_frame(rows, index, cols):
+    import pandas as pd
+    return pd.DataFrame(rows, index=index, columns=cols).astype(float)
+
+
+@amp_function
+def corr_coeff_3D(stack_gt, pred_3D, coords, r12, r3, n_time_steps=None, start_plane_offset=-25 // 2, output_path=None, n_show=20,
+                  minmax_ths=50, filter_width=10):
+    """Correlation coefficients between the ROI traces of a ground-truth and a predicted time series of volumes; CWFA.py:240-379,
+    same signature, device tensors [T,D,H,W].  Returns ``(all_corr_coeffs, neural_activity_dataframe)``.
+
+    On the GPU: the maximum of each stack, the median of the positive ground-truth voxels (exact radix selection) and the
+    float64 mean of every ROI at every time step (one launch per stack and 128 ROIs).  On the host: ``correlate_traces``.
+    Two departures, invisible in the results: the reference divides both stacks in place by their maxima -- here the inputs stay
+    untouched and the traces and the median are scaled instead (division by a positive number is monotone, so the median of the
+    scaled values is the scaled median, bit for bit); and the ROI ranges are clipped by the axis they index (see ``roi_boxes``).
+    ``output_path is not None`` (the reference's figure) raises NotImplementedError.  The selection counts in 64 bits: a
+    stack may hold up to 2^45 voxels per time step."""
+    import numpy as np
+    if output_path is not None:
+        raise NotImplementedError("corr_coeff_3D: plotting (output_path) is the reference's business")
+    ops._dev(stack_gt, "stack_gt"), ops._dev(pred_3D, "pred_3D")
+    if stack_gt.dim() != 4 or tuple(stack_gt.shape) != tuple(pred_3D.shape):
+        raise ValueError("corr_coeff_3D: two [T,D,H,W] stacks of one shape")
+    if n_time_steps is None:
+        n_time_steps = stack_gt.shape[0]
+    coords = [tuple(c) for c in coords]
+    boxes = roi_boxes(coords, stack_gt.shape, r12, r3, start_plane_offset)
+    max_gt = ops.volume_extrema(stack_gt)[:, 1]
+    max_pred = ops.volume_extrema(pred_3D)[:, 1]
+    median, _ = ops.select_positive(stack_gt, -1)
+    tr_gt, tr_pred = ops.roi_means(stack_gt, boxes), ops.roi_means(pred_3D, boxes)
+    m_gt, m_pred = np.float32(max_gt.cpu().numpy().max()), np.float32(max_pred.cpu().numpy().max())
+    median_scaled = np.float32(median.cpu().numpy()[0]) / m_gt                         # fp32 division: the median of stack / max
+    return correlate_traces(coords, boxes, tr_gt.cpu().numpy() / np.float64(m_gt), tr_pred.cpu().numpy() / np.float64(m_pred),
+                            median_scaled, stack_gt.shape[1] // 2 + start_plane_offset, n_time_steps, minmax_ths, filter_width)

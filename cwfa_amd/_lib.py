@@ -44,6 +44,18 @@ class Couple(C.Structure):
                 ("clamp", C.c_float), ("pre_scale", C.c_float), ("rev", C.c_int), ("logdet", c_f64p), ("in_blocked8", C.c_int)]
 
 
+class EvalAffine(C.Structure):
+    _fields_ = [("enabled", C.c_int), ("scale", C.c_float), ("std", C.c_float), ("mean", C.c_float)]
+
+
+class EvalPost(C.Structure):
+    _fields_ = [("normalize", C.c_int), ("threshold", C.c_int), ("norm_sub", C.c_float), ("norm_div", C.c_float),
+                ("vol_min", C.c_float), ("lower", C.c_float), ("upper", C.c_float), ("clamp_value", C.c_float)]
+
+
+EXTREMA_STRIDE = 12                # CWFA_EXTREMA_STRIDE
+SELECT_WORKSPACE_BYTES = 8448      # CWFA_SELECT_WORKSPACE_BYTES
+
 # name -> (restype, argtypes); must list EVERY function declared in include/cwfa_hip.h (tests/test_boundary.py checks)
 i, i64, f, d, p = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_void_p
 SIGNATURES = {
@@ -119,6 +131,13 @@ SIGNATURES = {
     "cwfa_subnet_layer_first_pack_f32": (i, [p, p, p, i, p, p]),
     "cwfa_subnet_layer_first_f32": (i, [p, p, p, p, p, p, i, i, i, i, i64, i64, i64, i, p]),
     "cwfa_extract_views_f32": (i, [p, p, p, i, i, i, i, i, i, f, f, i64, p]),
+    "cwfa_eval_splits": (i64, [i, i64]),
+    "cwfa_volume_extrema_f32": (i, [p, p, p, p, i, i64, i64, i64, C.POINTER(EvalAffine), p]),
+    "cwfa_volume_metrics_f32": (i, [p, p, p, p, i, i64, i64, i64, C.POINTER(EvalAffine), f, f, f, p]),
+    "cwfa_mip3_f32": (i, [p, p, p, p, p, p, i, i, i, i, i64, i64, i, C.POINTER(EvalAffine), C.POINTER(EvalPost), p]),
+    "cwfa_projection_compose_f32": (i, [p, p, p, p, p, i, i, i, i, i, i, i, p]),
+    "cwfa_roi_means_f32": (i, [p, p, p, i, i, i, i, i, i64, p]),
+    "cwfa_select_positive_f32": (i, [p, i, i64, i64, i64, p, p, p, p]),
 }
 del i, i64, f, d, p
 

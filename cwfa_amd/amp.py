@@ -9,7 +9,7 @@ import functools
 
 import torch
 
-__all__ = ["amp_entry"]
+__all__ = ["amp_entry", "amp_function"]
 
 
 def _up(v):
@@ -28,4 +28,15 @@ def amp_entry(forward):
             return forward(self, *args, **kwargs)
         with torch.autocast("cuda", enabled=False):
             return forward(self, *_up(args), **{k: _up(v) for k, v in kwargs.items()})
+    return wrapped
+
+
+def amp_function(fn):
+    """``amp_entry`` for a plain function (the evaluation mirrors of ``utils`` and ``CWFA``)."""
+    @functools.wraps(fn)
+    def wrapped(*args, **kwargs):
+        if not torch.is_autocast_enabled("cuda"):
+            return fn(*args, **kwargs)
+        with torch.autocast("cuda", enabled=False):
+            return fn(*_up(args), **{k: _up(v) for k, v in kwargs.items()})
     return wrapped

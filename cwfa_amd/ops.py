@@ -1352,3 +1352,114 @@ def concat_channels(parts):
                                         t.shape[1], H * W, bs, Ct * H * W, _stream()), "concat_channels")
         c0 += t.shape[1]
     return out
+
+
+# ------------------------------------------------------------------------------------------------ evaluation pass
+def eval_affine(step, mean, std):
+    """The de-normalisation the evaluation kernels apply on load: v -> (v * 2^-step) * std - mean (CWFA.py:112-117).  mean and std
+    may be numbers or one-element tensors; they are rounded to fp32 like the reference's scalar operands."""
+    a = _lib.EvalAffine()
+    a.enabled, a.scale = 1, 2.0 ** -int(step)
+    a.std = float(torch.as_tensor(std, dtype=torch.float32).reshape(()).cpu())
+    a.mean = float(torch.as_tensor(mean, dtype=torch.float32).reshape(()).cpu())
+    return a
+
+
+def _aff(a):
+    return None if a is None else C.byref(a)
+
+
+def _pair(a, b, what):
+    a, a_bs = planes(a, what)
+    b_bs = 0
+    if b is not None:
+        b, b_bs = planes(b, what)
+        if tuple(a.shape) != tuple(b.shape):
+            raise ValueError(f"{what}: the two tensors differ in shape: {tuple(a.shape)} vs {tuple(b.shape)}")
+    return a, a_bs, b, b_bs
+
+
+def volume_extrema(a, b=None, affine=None):
+    """Per sample of [B,D,H,W]: float32 [B, 12] = (min, max, min|.|, max|.|) of a, the same of b, (min, max) of |a - b|, 0, 0.
+    Exact.  Inputs are assumed finite."""
+    L = _lib.lib()
+    a, a_bs, b, b_bs = _pair(a, b, "volume_extrema")
+    B = a.shape[0]
+    out = torch.zeros(B, _lib.EXTREMA_STRIDE, dtype=torch.float32, device=a.device)
+    ws = torch.empty(max(1, B * L.cwfa_eval_splits(B, a[0].numel()) * 10), dtype=torch.float32, device=a.device)
+    check(L.cwfa_volume_extrema_f32(_p(a), _p(b), _p(out), _p(ws), B, a[0].numel(), a_bs, b_bs, _aff(affine), _stream()), "volume_extrema")
+    return out
+
+
+def volume_metrics(pred, gt, thr=float("-inf"), affine=None, pred_offset=0.0, gt_offset=0.0):
+    """Per sample: float64 [B, 4] = (sum (g-p)^2, sum g, sum |g - p~|, #{p < thr}), p~ = p with every p < thr set to 0.
+    One pass, float64 sums added in a fixed order.  Inputs are assumed finite."""
+    L = _lib.lib()
+    pred, p_bs, gt, g_bs = _pair(pred, gt, "volume_metrics")
+    B = pred.shape[0]
+    out = torch.zeros(B, 4, dtype=torch.float64, device=pred.device)
+    ws = torch.empty(max(1, B * L.cwfa_eval_splits(B, pred[0].numel()) * 4), dtype=torch.float64, device=pred.device)
+    check(L.cwfa_volume_metrics_f32(_p(pred), _p(gt), _p(out), _p(ws), B, pred[0].numel(), p_bs, g_bs, _aff(affine),
+                                    float(pred_offset), float(gt_offset), float(thr), _stream()), "volume_metrics")
+    return out
+
+
+def mip3(a, b=None, triple=False, affine=None, post=None):
+    """The three maximum projections of |a| (or |a - b|) of [B,D,H,W] in one read: (over depth [B,H,W], over H [B,W,D],
+    over W [B,H,D], min [B]).  ``triple``: those of |a|, |b| and |a - b| in the same read, every output with a leading [3].
+    Bit-exact and bitwise reproducible.  Inputs are assumed finite."""
+    L = _lib.lib()
+    a, a_bs, b, b_bs = _pair(a, b, "mip3")
+    B, D, H, W = a.shape
+    lead = (3, B) if triple else (B,)
+    dev = a.device
+    zp = torch.empty(*lead, H, W, dtype=torch.float32, device=dev)
+    xp = torch.empty(*lead, W, D, dtype=torch.float32, device=dev)
+    yp = torch.empty(*lead, H, D, dtype=torch.float32, device=dev)
+    gmin = torch.empty(*lead, dtype=torch.float32, device=dev)
+    check(L.cwfa_mip3_f32(_p(a), _p(b), _p(zp), _p(xp), _p(yp), _p(gmin), B, D, H, W, a_bs, b_bs, int(bool(triple)), _aff(affine),
+                          None if post is None else C.byref(post), _stream()), "mip3")
+    return zp, xp, yp, gmin
+
+
+def projection_compose(zp, xp, yp, fill, depth_scale=2, border=2, scale_bars=False):
+    """The composite image of utils.py:305-325 from the projections of ``mip3``: [B, H + D*depth_scale + border, W + ...].
+    ``fill``: one-element device tensor (the reference's ``z_projection.min()``)."""
+    L = _lib.lib()
+    zp, xp, yp, fill = (_dev(t).contiguous() for t in (zp, xp, yp, fill))
+    B, H, W = zp.shape
+    D = xp.shape[2]
+    if tuple(xp.shape) != (B, W, D) or tuple(yp.shape) != (B, H, D) or fill.numel() != 1:
+        raise ValueError("projection_compose: projections of different volumes")
+    side = D * int(depth_scale) + int(border)
+    out = torch.empty(B, H + side, W + side, dtype=torch.float32, device=zp.device)
+    check(L.cwfa_projection_compose_f32(_p(zp), _p(xp), _p(yp), _p(fill), _p(out), B, D, H, W, int(depth_scale), int(border),
+                                        int(bool(scale_bars)), _stream()), "projection_compose")
+    return out
+
+
+def roi_means(stack, boxes):
+    """float64 [N, T]: the mean of stack[t, z0:z1, y0:y1, x0:x1] for every box (z0,z1,y0,y1,x0,x1) of the integer [N,6] host table
+    (inside the volume; an empty box gives NaN).  stack: [T,D,H,W]."""
+    import numpy as np
+    L = _lib.lib()
+    stack, t_bs = planes(stack, "roi_means")
+    T, D, H, W = stack.shape
+    bx = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 6))
+    out = torch.empty(len(bx), T, dtype=torch.float64, device=stack.device)
+    check(L.cwfa_roi_means_f32(_p(stack), C.c_void_p(bx.ctypes.data), _p(out), T, D, H, W, len(bx), t_bs, _stream()), "roi_means")
+    return out
+
+
+def select_positive(x, k=-1):
+    """(value float32[1], count int64[1]) on the device: the k-th smallest (k = 0 ..) of the strictly positive elements of x
+    ([B,D,H,W]); k = -1: their lower median (torch's ``median``).  Exact (radix selection, 64-bit counters: up to 2^45 elements per
+    sample); NaN if k >= count.  Inputs are assumed finite."""
+    L = _lib.lib()
+    x, x_bs = planes(x, "select_positive")
+    value = torch.empty(1, dtype=torch.float32, device=x.device)
+    count = torch.empty(1, dtype=torch.int64, device=x.device)
+    ws = torch.empty(_lib.SELECT_WORKSPACE_BYTES, dtype=torch.uint8, device=x.device)
+    check(L.cwfa_select_positive_f32(_p(x), x.shape[0], x[0].numel(), x_bs, int(k), _p(value), _p(count), _p(ws), _stream()),
+          "select_positive")
+    return value, count

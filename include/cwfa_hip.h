@@ -67,6 +67,8 @@ const char* cwfa_last_error(void);
  *                         arithmetic of "split_products" (training in split / bf16 precision); 0 (default): fp32 MFMA.
  *   "split3x3_xcd_map"  : 0: (ablation) blocks of the split 3x3 kernel in plain (spatial tile, cout tile) order instead of
  *                         the XCD-aware one.
+ *   "mip3_ablate"       : measurement only (results are then WRONG): mask, bit 0 / 1 / 2 drops the over-depth / over-H / over-W
+ *                         reduction of cwfa_mip3_f32 (which of the three bounds the kernel); default 0.
  *   "split3x3_rows16"   : 0: (ablation) the 64-channel tiling of the split 3x3 kernel always on 8-row tiles.
  * returns 0, or CWFA_E_INVAL for an unknown name or an invalid value. */
 int cwfa_set_option(const char* name, int value);
@@ -507,6 +509,61 @@ int cwfa_layernorm_bwd_f32(const float* g, const float* v, const float* w, const
                            float* gv, float* dw, float* db, int B, int64_t n, void* stream);
 int cwfa_attention_bwd_f32(const float* mean, const float* w1, const float* b1, const float* w2, const float* b2, const float* m,
                            const float* g, float* gm, double* pgrad, int B, int C, int64_t HW, void* stream);
+
+/* The evaluation pass behind every reconstructed volume (CWFA.py:1032-1117): compute_INN_step_performance (CWFA.py:98-132) with
+ * psnr (utils.py:380-394), volume_2_projections (utils.py:281-327) and the reductions of corr_coeff_3D (CWFA.py:240-379).
+ * Streaming kernels over fp32 [B, D, H, W] tensors, n = D*H*W elements per sample, contiguous per sample, `*_bs` the batch
+ * stride in elements.  Inputs are assumed finite (no NaN propagation).  They clear their own outputs and workspaces on `stream`.
+ *
+ * cwfa_eval_affine (host struct, NULL = none): every element is read as (v * scale) * std - mean, scale = 2^-step -- the
+ * reference's `x / 2**step`, `x*std - mean` (CWFA.py:112-117) bit for bit, so the raw volumes need not be materialised.
+ *
+ *   volume_extrema: out[B][CWFA_EXTREMA_STRIDE] = {min a, max a, min|a|, max|a|, the same four of b, min|a-b|, max|a-b|, 0, 0}
+ *                   (b nullable: slots 4..9 are 0).  Exact.  workspace: B * cwfa_eval_splits(B, n) * 10 floats.
+ *   volume_metrics: out[B][4] (double) = {sum (g-p)^2, sum g, sum |g - p~|, #{p < thr}} with p~ = (p < thr ? 0 : p), p and g
+ *                   read through the affine and then less pred_offset / gt_offset (`normaliaze_before_metrics`).  thr = -inf:
+ *                   no mask.  workspace: B * cwfa_eval_splits(B, n) * 4 doubles; the sums are added in a fixed order
+ *                   (bitwise reproducible).
+ *   mip3:           the maximum projections of v = |a| (b NULL) or |a-b|: zproj [B,H,W] over depth, xproj [B,W,D] over H,
+ *                   yproj [B,H,D] over W, gmin[B] = min v -- one read.  triple != 0: the three sets for |a|, |b|, |a-b| in the
+ *                   same read, each output [3][B]...  cwfa_eval_post (one-image form only, NULL = none): the maps of
+ *                   utils.py:295-303 applied to v before projecting: normalize: v = (v - norm_sub) / norm_div; threshold:
+ *                   (v - vol_min) < lower -> 0, then (v - vol_min) > upper -> clamp_value.  Exact, bitwise reproducible.
+ *   projection_compose: utils.py:305-325 for scaling_factors [1, 1, depth_scale]: out [B, H + D*depth_scale + border,
+ *                   W + D*depth_scale + border] filled with *fill (device scalar: z_projection.min()), nearest replication
+ *                   along depth, optional scale-bar lines.  H == W (the reference's size=[.., vol_size[-3]] fits no other).
+ *   roi_means:      out[N][T] (double) = mean of x[t, z0:z1, y0:y1, x0:x1] for the N boxes {z0,z1,y0,y1,x0,x1} (HOST int32
+ *                   [N][6], inside the volume; an empty box gives NaN).  x: [T, D, H, W] with time stride t_stride.
+ *   select_positive: *value = the k-th smallest (k = 0 ..) of the strictly positive elements, k = -1: their lower median
+ *                   (k = (count - 1) / 2, torch's convention); *count = the number of positive elements; k >= count gives NaN.
+ *                   Radix selection on the bit patterns, 64-bit counters: exact.  workspace: CWFA_SELECT_WORKSPACE_BYTES device bytes. */
+#define CWFA_EXTREMA_STRIDE 12
+#define CWFA_EVAL_MAX_SPLITS 2048
+#define CWFA_SELECT_WORKSPACE_BYTES 8448
+typedef struct {
+    int enabled;
+    float scale, std, mean;
+} cwfa_eval_affine;
+typedef struct {
+    int normalize, threshold;
+    float norm_sub, norm_div, vol_min, lower, upper, clamp_value;
+} cwfa_eval_post;
+/* blocks per sample of the extrema / metrics kernels for B samples of n elements (<= CWFA_EVAL_MAX_SPLITS, about 2048 / B): sizes
+ * their workspaces; 0 for an empty problem, CWFA_E_INVAL for a negative size */
+int64_t cwfa_eval_splits(int B, int64_t n);
+int cwfa_volume_extrema_f32(const float* a, const float* b, float* out, float* workspace, int B, int64_t n, int64_t a_bs,
+                            int64_t b_bs, const cwfa_eval_affine* affine, void* stream);
+int cwfa_volume_metrics_f32(const float* pred, const float* gt, double* out, double* workspace, int B, int64_t n, int64_t pred_bs,
+                            int64_t gt_bs, const cwfa_eval_affine* affine, float pred_offset, float gt_offset, float thr,
+                            void* stream);
+int cwfa_mip3_f32(const float* a, const float* b, float* zproj, float* xproj, float* yproj, float* gmin, int B, int D, int H, int W,
+                  int64_t a_bs, int64_t b_bs, int triple, const cwfa_eval_affine* affine, const cwfa_eval_post* post, void* stream);
+int cwfa_projection_compose_f32(const float* zproj, const float* xproj, const float* yproj, const float* fill, float* out, int B,
+                                int D, int H, int W, int depth_scale, int border, int scale_bars, void* stream);
+int cwfa_roi_means_f32(const float* x, const int32_t* boxes, double* out, int T, int D, int H, int W, int N, int64_t t_stride,
+                       void* stream);
+int cwfa_select_positive_f32(const float* x, int B, int64_t n, int64_t x_bs, int64_t k, float* value, int64_t* count,
+                             void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
