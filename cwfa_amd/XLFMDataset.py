@@ -1,9 +1,13 @@
-"""The one piece of the reference's XLFMDataset.py that sits directly in front of the hot path:
-cropping the 29 lenslet views out of the sensor frame.  Not registered by cwfa_amd.install() (the reference's own module
-holds the dataset classes); a maintainer patches the static method, see INTEGRATION.md."""
-from . import ops
+"""The pieces of the reference's XLFMDataset.py around the hot path: cropping the 29 lenslet views out of the sensor frame
+(SURVEY.md section 8f, row 2), the clean-up and centre crop of the raw frames (XLFMDataset.py:15-40,101-104,160-162) and the
+statistics / normalisation of ``ConcatDataset`` (:251-395) on device tensors.  File reading stays the
+reference's.  Not registered by cwfa_amd.install(); a maintainer patches the calls, see INTEGRATION.md."""
+import torch
 
-__all__ = ["XLFMDatasetFull", "extract_views"]
+from . import ops
+from .amp import amp_function
+
+__all__ = ["XLFMDatasetFull", "ConcatDataset", "extract_views", "pad_img_to_min", "center_crop", "prepare_frames"]
 
 
 def extract_views(image, lenslet_coords, subimage_shape, debug=False):
@@ -14,10 +18,197 @@ def extract_views(image, lenslet_coords, subimage_shape, debug=False):
     return ops.extract_views(image, lenslet_coords, subimage_shape)
 
 
+def pad_amounts(h, w):
+    """(rows, columns) ``pad_img_to_min`` takes off EACH side of an h x w image: it pads by the floor-halved negative difference to
+    the shorter side, so it crops, and by one more than half where the difference is odd (the result is then one short)."""
+    m = min(h, w)
+    return -((m - h) // 2), -((m - w) // 2)
+
+
+def pad_img_to_min(image):
+    """XLFMDataset.py:15-25 as a view of the last two axes."""
+    h, w = image.shape[-2:]
+    ph, pw = pad_amounts(h, w)
+    return image[..., ph:h - ph, pw:w - pw]
+
+
+def center_crop(layer, target_size, pad=0):
+    """XLFMDataset.py:27-40 for a [B,C,H,W] tensor, as a view."""
+    dy, dx = (layer.shape[2] - target_size[0]) // 2 - pad, (layer.shape[3] - target_size[1]) // 2 - pad
+    return layer[:, :, dy:dy + target_size[0], dx:dx + target_size[1]]
+
+
+def frame_offsets(h, w, img_shape):
+    """The index map of ``pad_img_to_min`` followed by ``center_crop``: output (r, c) is source (r + oy, c + ox).  Raises where the
+    crop does not fit the padded image (the reference's slice comes out short and its store into ``stacked_views`` fails)."""
+    ph, pw = pad_amounts(h, w)
+    h1, w1 = h - 2 * ph, w - 2 * pw
+    dy, dx = (h1 - int(img_shape[0])) // 2, (w1 - int(img_shape[1])) // 2
+    if dy < 0 or dx < 0 or dy + img_shape[0] > h1 or dx + img_shape[1] > w1:
+        raise ValueError(f"prepare_frames: a {img_shape[0]} x {img_shape[1]} crop does not fit the {h1} x {w1} image left of {h} x {w}")
+    return ph + dy, pw + dx
+
+
+@amp_function
+def prepare_frames(raw, img_shape):
+    """``stacked_views`` [N, img_shape[0], img_shape[1]] from raw fp32 frames [N,h,w] on the device, XLFMDataset.py:101-104,160-162 in
+    one kernel: NaN -> 0, clip to [0, 50000], the round trip through fp16, ``pad_img_to_min`` and ``center_crop``."""
+    return ops.prep_frames(raw, img_shape, frame_offsets(raw.shape[-2], raw.shape[-1], img_shape))
+
+
+def _scalar(v):
+    """A float64 statistic as the 0-dim float32 CPU tensor the reference returns (rounded once)."""
+    return torch.tensor(v, dtype=torch.float64).to(torch.float32)
+
+
+def _channels(ds):
+    """The image tensors behind the two statistics channels of a dataset: (views, views) for [N,H,W], the strided copies of
+    [..., 0] and [..., 1] for the sparse [N,H,W,2] layout."""
+    sv = ds.stacked_views
+    if sv.dim() == 4:
+        return sv[..., 0].contiguous(), sv[..., 1].contiguous()
+    return sv, sv
+
+
+def _max(t):
+    return ops.volume_extrema(t.reshape(1, 1, 1, -1) if t.is_contiguous() else t.contiguous().reshape(1, 1, 1, -1))[0, 1].cpu()
+
+
 class XLFMDatasetFull:
+    """The tensor side of the reference's dataset class: ``stacked_views`` (fp32 [N,H,W]) and ``vols`` on the HIP device."""
     extract_views = staticmethod(extract_views)
+
+    def __init__(self, stacked_views=None, vols=None, ds_id=""):
+        self.stacked_views, self.vols, self.dataset_id = stacked_views, vols, ds_id
+        self.load_vols = vols is not None
+        self.gt_cache = []
+
+    @classmethod
+    def from_tensors(cls, raw_frames, vols, img_shape, ds_id=""):
+        """From raw fp32 frames [N,h,w] and fp16 volumes [N,D,H0,W0] as read from the files."""
+        return cls(prepare_frames(raw_frames, img_shape), vols, ds_id)
+
+    def __len__(self):
+        return int(self.stacked_views.shape[0])
+
+    def __getitem__(self, index):
+        views_out = self.stacked_views[[index], ...]
+        if not self.load_vols:
+            return views_out
+        return views_out, self.vols[index, ...], index, self.gt_cache
+
+    def get_n_depths(self):
+        return self.vols.shape[1]
+
+    def get_max(self):
+        m = _max(self.stacked_views.float())
+        return m, m, _max(self.vols.float())
+
+    def get_statistics(self):
+        mi, si, _ = ops.mean_std([self.stacked_views.float()])
+        mv, sv, _ = ops.mean_std([self.vols.float()])
+        return _scalar(mi), _scalar(si), _scalar(mv), _scalar(sv)
+
+    def standarize(self, stats):
+        mean_imgs, std_imgs, mean_imgs_s, std_imgs_s, mean_vols, std_vols = stats
+        self.stacked_views = self.standarize_sample(self.stacked_views, mean_imgs, std_imgs)
+        self.vols = self.standarize_sample(self.vols, mean_vols, std_vols)
+
+    @staticmethod
+    def standarize_sample(sample, mean, std):
+        """(sample - mean) / std in fp32, in place where ``sample`` is contiguous."""
+        return ops.prep_apply(sample if sample.is_contiguous() else sample.contiguous(), "sub_div", mean, std)
 
     @staticmethod
     def extract_views_normalized(image, lenslet_coords, subimage_shape, mean_imgs, std_imgs):
         """extract_views followed by ``(views - mean_imgs) / std_imgs`` (CWFA.py:796-797), fused."""
         return ops.extract_views(image, lenslet_coords, subimage_shape, float(mean_imgs), float(std_imgs))
+
+
+class ConcatDataset:
+    """XLFMDataset.py:251-395 over datasets whose ``stacked_views`` and ``vols`` are fp32 tensors on the HIP device.  The statistics
+    are float64 device sums accumulated over the datasets (nothing is concatenated) and come back as 0-dim float32 CPU tensors,
+    rounded once.  ``add_random_shot_noise_to_dataset`` is left out: it calls a dataset method the reference does not define."""
+
+    def __init__(self, *datasets):
+        self.datasets = datasets
+        self.max_values = None
+
+    def _locate(self, i):
+        for n, d in enumerate(self.datasets):
+            if i < len(d) or n == len(self.datasets) - 1:
+                return n, i
+            i -= len(d)
+
+    def __getitem__(self, input):
+        n, i = self._locate(input)
+        return tuple(self.datasets[n][i])
+
+    def __len__(self):
+        return sum(len(d) for d in self.datasets)
+
+    @amp_function
+    def mean_std(self, dim=0):
+        """``(mean(dim), std(dim))`` from ONE pass over the volumes: the kernel produces both, and ``mean`` / ``std`` each take
+        their half of it, so a caller that wants both asks here.  Several datasets are concatenated for the pass (the kernel
+        reads one stack); a single dataset is read in place."""
+        if dim != 0:
+            raise NotImplementedError("ConcatDataset.mean / std: over the samples (dim=0) only")
+        vols = [d.vols.float() for d in self.datasets]
+        m, s = ops.stack_mean_std(vols[0] if len(vols) == 1 else torch.cat(vols, dim=0))
+        return m.unsqueeze(0), s.unsqueeze(0)
+
+    def mean(self, dim=0):
+        """The per-voxel mean over all samples, [1,D,H,W] like the reference's permuted result."""
+        return self.mean_std(dim)[0]
+
+    def std(self, dim=0):
+        return self.mean_std(dim)[1]
+
+    @amp_function
+    def get_statistics(self):
+        """mean_imgs, std_imgs, mean_imgs_s, std_imgs_s, mean_vols, std_vols (unbiased std over every element of every dataset)."""
+        chans = [_channels(d) for d in self.datasets]
+        mi, si, _ = ops.mean_std([c[0] for c in chans])
+        if self.datasets[0].stacked_views.dim() == 4:
+            ms, ss, _ = ops.mean_std([c[1] for c in chans])
+        else:
+            ms, ss = mi, si
+        mv, sv, _ = ops.mean_std([d.vols.float() for d in self.datasets])
+        return _scalar(mi), _scalar(si), _scalar(ms), _scalar(ss), _scalar(mv), _scalar(sv)
+
+    @amp_function
+    def get_max(self):
+        if self.max_values is None:
+            chans = [_channels(d) for d in self.datasets]
+            self.max_values = [torch.stack([_max(c[0]) for c in chans]).max()]
+            # the dense layout has one image channel: its maximum serves both entries, one extrema pass per dataset
+            sparse = self.datasets[0].stacked_views.dim() == 4
+            self.max_values.append(torch.stack([_max(c[1]) for c in chans]).max() if sparse else self.max_values[0].clone())
+            self.max_values.append(torch.stack([_max(d.vols.float()) for d in self.datasets]).max())
+        return self.max_values
+
+    @amp_function
+    def normalize_datasets(self):
+        """Every dataset scaled to the common maxima: x / max(x) * max_values in fp32, in place.  In the sparse layout channel 0 takes
+        ``max_values[1]`` and channel 1 ``max_values[0]``, as in the reference."""
+        if self.max_values is None:
+            self.max_values = self.get_max()
+        for d in self.datasets:
+            if d.stacked_views.dim() == 4:
+                for k in (0, 1):
+                    c = d.stacked_views[..., k].contiguous()
+                    d.stacked_views[..., k] = ops.prep_apply(c, "div_mul", _max(c), self.max_values[1 - k])
+            else:
+                v = d.stacked_views.float()
+                d.stacked_views = ops.prep_apply(v if v.is_contiguous() else v.contiguous(), "div_mul", _max(v), self.max_values[0])
+            v = d.vols.float()
+            v = v if v.is_contiguous() else v.contiguous()
+            d.vols = ops.prep_apply(v, "div_mul", _max(v), self.max_values[2])
+
+    @amp_function
+    def standarize_datasets(self, stats=None):
+        if stats is None:
+            stats = self.get_statistics()
+        for d in self.datasets:
+            d.standarize(stats)

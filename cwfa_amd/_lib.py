@@ -55,6 +55,10 @@ class EvalPost(C.Structure):
 
 EXTREMA_STRIDE = 12                # CWFA_EXTREMA_STRIDE
 SELECT_WORKSPACE_BYTES = 8448      # CWFA_SELECT_WORKSPACE_BYTES
+PREP_MAX_BINS = 10239              # CWFA_PREP_MAX_BINS
+PREP_MOMENTS_WORKSPACE = 4096      # CWFA_PREP_MOMENTS_WORKSPACE (doubles)
+PREP_VOL = {"none": 0, "two": 1, "le": 2, "maxnorm": 3, "max_only": 4}          # CWFA_PREP_VOL_*
+PREP_APPLY = {"clamp_zero": 0, "sub_div": 1, "div_mul": 2}                      # CWFA_PREP_*
 
 # name -> (restype, argtypes); must list EVERY function declared in include/cwfa_hip.h (tests/test_boundary.py checks)
 i, i64, f, d, p = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_void_p
@@ -138,6 +142,12 @@ SIGNATURES = {
     "cwfa_projection_compose_f32": (i, [p, p, p, p, p, i, i, i, i, i, i, i, p]),
     "cwfa_roi_means_f32": (i, [p, p, p, i, i, i, i, i, i64, p]),
     "cwfa_select_positive_f32": (i, [p, i, i64, i64, i64, p, p, p, p]),
+    "cwfa_prep_volumes_f16": (i, [p, p, p, i, i, i, i, i, i, i, i, i, f, f, i, p]),
+    "cwfa_prep_frames_f32": (i, [p, p, i, i, i, i, i, i, i, p]),
+    "cwfa_histogram_f32": (i, [p, i64, f, f, p, i, p, i, p]),
+    "cwfa_prep_apply_f32": (i, [p, i64, i, f, f, i, p]),
+    "cwfa_moments_f64": (i, [p, i64, d, p, p, i, p]),
+    "cwfa_stack_mean_std_f32": (i, [p, p, p, i, i64, i64, p]),
 }
 del i, i64, f, d, p
 

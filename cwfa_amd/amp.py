@@ -9,7 +9,7 @@ import functools
 
 import torch
 
-__all__ = ["amp_entry", "amp_function"]
+__all__ = ["amp_entry", "amp_function", "amp_region"]
 
 
 def _up(v):
@@ -39,4 +39,16 @@ def amp_function(fn):
             return fn(*args, **kwargs)
         with torch.autocast("cuda", enabled=False):
             return fn(*_up(args), **{k: _up(v) for k, v in kwargs.items()})
+    return wrapped
+
+
+def amp_region(fn):
+    """``amp_function`` without the upcast, for the data preparation mirrors: their fp16 volumes are data in the reference's own
+    storage format (XLFMDatasetFull keeps them in fp16), not autocast products, and the kernels read them as fp16."""
+    @functools.wraps(fn)
+    def wrapped(*args, **kwargs):
+        if not torch.is_autocast_enabled("cuda"):
+            return fn(*args, **kwargs)
+        with torch.autocast("cuda", enabled=False):
+            return fn(*args, **kwargs)
     return wrapped

@@ -1463,3 +1463,151 @@ def select_positive(x, k=-1):
     check(L.cwfa_select_positive_f32(_p(x), x.shape[0], x[0].numel(), x_bs, int(k), _p(value), _p(count), _p(ws), _stream()),
           "select_positive")
     return value, count
+
+
+# ------------------------------------------------------------------------------------------------ data preparation
+def _f32(v):
+    """A number or one-element tensor as the Python float of its fp32 rounding (how torch's scalar operands enter fp32 kernels)."""
+    return float(torch.as_tensor(v, dtype=torch.float32).reshape(()).cpu())
+
+
+def _flat(x, name):
+    _dev(x, name)
+    return x if x.is_contiguous() else x.contiguous()
+
+
+def prep_volumes(x, size, offsets, mode="none", t0=0.0, t1=0.0, out_dtype=torch.float32):
+    """The crop x[:, :, oh:oh+H, ow:ow+W] of an fp16 [N,D,H0,W0] tensor with the threshold step of ``load_process_volume`` fused in
+    (cwfa_prep_volumes_f16; ``mode`` one of none / two / le / maxnorm).  Returns (out, max): max is the one-element device tensor
+    of the cropped region's maximum for ``maxnorm``, else None.  ``mode="max_only"`` returns (None, max)."""
+    L = _lib.lib()
+    if not torch.is_tensor(x) or not x.is_cuda:
+        raise RuntimeError("prep_volumes: cwfa_amd runs on MI355X only -- expected a HIP tensor (no CPU fallback exists)")
+    if x.dtype != torch.float16 or x.dim() != 4:
+        raise TypeError(f"prep_volumes: expected a float16 [N,D,H0,W0] tensor, got {x.dtype} {tuple(x.shape)}")
+    if out_dtype not in (torch.float32, torch.float16):
+        raise TypeError("prep_volumes: out_dtype must be float32 or float16")
+    x = x if x.is_contiguous() else x.contiguous()
+    N, D, H0, W0 = x.shape
+    (H, W), (oh, ow) = size, offsets
+    need_max = mode in ("maxnorm", "max_only")
+    mb = torch.empty(2, dtype=torch.float32, device=x.device) if need_max else None
+    out = None if mode == "max_only" else torch.empty(N, D, H, W, dtype=out_dtype, device=x.device)
+    check(L.cwfa_prep_volumes_f16(_p(x), _p(out), _p(mb), N, D, H0, W0, int(H), int(W), int(oh), int(ow), _lib.PREP_VOL[mode], float(t0),
+                                  float(t1), int(out_dtype == torch.float16), _stream()), "prep_volumes")
+    return out, (mb[1:2] if need_max else None)
+
+
+def prep_frames(raw, size, offsets):
+    """Raw fp32 frames [N,h,w] -> [N,S0,S1]: NaN -> 0, clip to [0, 50000], fp16 round trip, out[n,r,c] = raw[n, r+oy, c+ox] (0 outside)."""
+    L = _lib.lib()
+    raw = _flat(raw, "raw")
+    if raw.dim() != 3:
+        raise ValueError(f"prep_frames: expected [N,h,w], got {tuple(raw.shape)}")
+    N, h, w = raw.shape
+    out = torch.empty(N, int(size[0]), int(size[1]), dtype=torch.float32, device=raw.device)
+    check(L.cwfa_prep_frames_f32(_p(raw), _p(out), N, h, w, int(size[0]), int(size[1]), int(offsets[0]), int(offsets[1]), _stream()), "prep_frames")
+    return out
+
+
+def histogram_range(lo, hi):
+    """The outer edges torch.histogram takes for data spanning [lo, hi] (fp32): an empty range is widened by 0.5 on both sides."""
+    lo, hi = torch.as_tensor(lo, dtype=torch.float32).reshape(()).cpu(), torch.as_tensor(hi, dtype=torch.float32).reshape(()).cpu()
+    if not (torch.isfinite(lo) and torch.isfinite(hi)):
+        raise ValueError(f"histogram: the extrema [{float(lo)}, {float(hi)}] are not finite")
+    if lo == hi:
+        lo, hi = lo - 0.5, hi + 0.5
+    return lo, hi
+
+
+def histogram(x, bins=10000, range=None, counts=None):
+    """(counts int64 [bins] on the device, edges float32 [bins+1] on the CPU) of an fp32 tensor of any shape: torch.histogram's counts
+    on the CPU, exactly.  ``range`` = (lo, hi) defaults to the tensor's extrema (one extrema pass); ``counts``: add into these
+    (a dataset fed in chunks passes the whole dataset's ``range`` and the running ``counts``)."""
+    L = _lib.lib()
+    x = _flat(x, "x")
+    bins = int(bins)
+    if bins < 1 or bins > _lib.PREP_MAX_BINS:
+        raise ValueError(f"histogram: bins = {bins} is not in 1 .. {_lib.PREP_MAX_BINS}")
+    if range is None:
+        if x.numel() == 0:
+            raise ValueError("histogram: an empty tensor has no extrema; pass range=(lo, hi)")
+        ext = volume_extrema(x.reshape(1, 1, 1, -1))[0, :2].cpu()
+        range = (ext[0], ext[1])
+    lo, hi = histogram_range(*range)
+    if not lo < hi:
+        raise ValueError(f"histogram: max {float(hi)} is below min {float(lo)}")
+    edges = torch.linspace(lo, hi, bins + 1, dtype=torch.float32)           # host, 10001 floats: bit-equal to torch.histogram's
+    if counts is None:
+        acc, counts = 0, torch.empty(bins, dtype=torch.int64, device=x.device)
+    else:
+        acc = 1
+        if counts.dtype != torch.int64 or not counts.is_cuda or counts.numel() != bins or not counts.is_contiguous():
+            raise ValueError("histogram: counts must be a contiguous int64 [bins] device tensor")
+    check(L.cwfa_histogram_f32(_p(x), x.numel(), float(lo), float(hi), _p(edges.to(x.device)), bins, _p(counts), acc, _stream()), "histogram")
+    return counts, edges
+
+
+def prep_apply(x, mode, a=0.0, b=0.0, upper=True, lower=True):
+    """In place on a contiguous fp32 tensor: "clamp_zero": x > a -> a (``upper``), then x < b -> 0 (``lower``); "sub_div": (x - a) / b;
+    "div_mul": x / a * b.  a and b are rounded to fp32 first.  Returns x."""
+    L = _lib.lib()
+    _dev(x, "x")
+    if not x.is_contiguous():
+        raise ValueError("prep_apply: works in place on a contiguous tensor")
+    check(L.cwfa_prep_apply_f32(_p(x), x.numel(), _lib.PREP_APPLY[mode], _f32(a), _f32(b), int(bool(upper)) | 2 * int(bool(lower)), _stream()),
+          "prep_apply")
+    return x
+
+
+def moments(x, shift=0.0, out=None):
+    """float64 [3] on the device: (sum (x - shift), sum (x - shift)^2, count).  ``out``: add to these three (chunked datasets)."""
+    L = _lib.lib()
+    x = _flat(x, "x")
+    shift = float(shift)
+    if shift != shift or shift in (float("inf"), float("-inf")):
+        raise ValueError(f"moments: the shift {shift} is not finite")
+    acc = 1
+    if out is None:
+        acc, out = 0, torch.empty(3, dtype=torch.float64, device=x.device)
+    elif out.dtype != torch.float64 or not out.is_cuda or out.numel() != 3 or not out.is_contiguous():
+        raise ValueError("moments: out must be a contiguous float64 [3] device tensor")
+    ws = torch.empty(_lib.PREP_MOMENTS_WORKSPACE, dtype=torch.float64, device=x.device)
+    check(L.cwfa_moments_f64(_p(x), x.numel(), shift, _p(out), _p(ws), acc, _stream()), "moments")
+    return out
+
+
+def mean_std(tensors):
+    """(mean, unbiased std, count) as Python floats (float64) over ALL elements of the given fp32 device tensors, without
+    concatenating them: one ``moments`` pass per tensor for the mean, one centred on that mean for the spread (a large mean with a
+    small spread survives)."""
+    tensors = list(tensors)
+    first = None
+    for t in tensors:
+        first = moments(t, 0.0, first)
+    s1, _, n = first.tolist()
+    if n == 0:
+        return float("nan"), float("nan"), 0
+    c = s1 / n
+    if c != c or c in (float("inf"), float("-inf")):
+        raise ValueError("moments: the data are not finite")
+    second = None
+    for t in tensors:
+        second = moments(t, c, second)
+    d1, d2, n = second.tolist()
+    var = (d2 - d1 * d1 / n) / (n - 1) if n > 1 else float("nan")
+    return c + d1 / n, max(var, 0.0) ** 0.5 if var == var else var, int(n)
+
+
+def stack_mean_std(x):
+    """(mean, std) float32 [D,H,W] over the N samples of [N,D,H,W]: float64 sums centred on the first sample, unbiased std
+    (N = 1: NaN, as torch)."""
+    L = _lib.lib()
+    x = _flat(x, "x")
+    if x.dim() < 1 or x.shape[0] < 1:
+        raise ValueError("stack_mean_std: needs at least one sample")
+    N, m = x.shape[0], x[0].numel()
+    mean = torch.empty(x.shape[1:], dtype=torch.float32, device=x.device)
+    std = torch.empty_like(mean)
+    check(L.cwfa_stack_mean_std_f32(_p(x), _p(mean), _p(std), N, m, m, _stream()), "stack_mean_std")
+    return mean, std

@@ -565,6 +565,41 @@ int cwfa_roi_means_f32(const float* x, const int32_t* boxes, double* out, int T,
 int cwfa_select_positive_f32(const float* x, int B, int64_t n, int64_t x_bs, int64_t k, float* value, int64_t* count,
                              void* workspace, void* stream);
 
+/* The data preparation pass in front of every run: load_XLFM_data (utils.py:187-220) with load_process_volume (:128-184),
+ * crop_volume_center (:105-126) and fast_quantile (:84-102), the frame clean-up of XLFMDatasetFull (XLFMDataset.py:101-104,
+ * 160-162) and the statistics of ConcatDataset (XLFMDataset.py:293-395).  Streaming kernels; every fp32 operation is rounded
+ * separately, in the reference's order.  Inputs are assumed free of NaN except where stated.
+ *
+ *   prep_volumes:  x fp16 [N,D,H0,W0] -> out [N,D,H,W] (fp32, or fp16 with out_f16), the crop x[:, :, off_h:off_h+H, off_w:off_w+W]
+ *                  with the threshold step of load_process_volume on the fp16 values (compare in fp32, store fp16, widen):
+ *                  VOL_NONE; VOL_TWO: v < t0 -> 0, then v >= t1 -> t1 (t1 an fp16 value); VOL_LE: v <= t0 -> 0; VOL_MAXNORM:
+ *                  q = fp16(v / max) (fp32 quotient, round to nearest even), q < t0 -> 0, max taken over the cropped region by a
+ *                  pass of its own; VOL_MAX_ONLY: that pass alone (out may be NULL).  maxbuf: 2 device floats (needed by the last
+ *                  two modes), maxbuf[1] receives the maximum.
+ *   prep_frames:   x fp32 [N,h,w] -> out fp32 [N,S0,S1]: out[n,r,c] = clean(x[n, r+off_y, c+off_x]), 0 outside the source;
+ *                  clean: NaN -> 0, clip to [0, 50000], round trip through fp16 (round to nearest even).
+ *   histogram:     counts[bins] (int64) of x by torch.histogram's CPU bin rule for the range [lo, hi] and the device table of
+ *                  bins + 1 fp32 edges (torch.linspace(lo, hi, bins + 1)); elements outside [lo, hi] are not counted.
+ *                  accumulate != 0 adds to the existing counts (chunked input).  Exact.  bins <= CWFA_PREP_MAX_BINS, lo < hi.
+ *   prep_apply:    in place: PREP_CLAMP_ZERO: x > a -> a (flags bit 0), then x < b -> 0 (flags bit 1); PREP_SUB_DIV: (x - a) / b;
+ *                  PREP_DIV_MUL: x / a * b.
+ *   moments:       out[3] (double) = {sum (x - c), sum (x - c)^2, n}; accumulate != 0 adds to the existing three.  Float64 sums
+ *                  added in a fixed order (bitwise reproducible).  workspace: CWFA_PREP_MOMENTS_WORKSPACE device doubles.
+ *   stack_mean_std: mean[m], std[m] (fp32) over the N samples of x [N, m] (sample stride x_ss elements): float64 sums centred
+ *                  on the first sample, unbiased std (N = 1: NaN). */
+#define CWFA_PREP_MAX_BINS 10239 /* counts + edges of one block: 81916 bytes of LDS, two blocks per CU */
+#define CWFA_PREP_MOMENTS_WORKSPACE 4096
+enum { CWFA_PREP_VOL_NONE = 0, CWFA_PREP_VOL_TWO = 1, CWFA_PREP_VOL_LE = 2, CWFA_PREP_VOL_MAXNORM = 3, CWFA_PREP_VOL_MAX_ONLY = 4 };
+enum { CWFA_PREP_CLAMP_ZERO = 0, CWFA_PREP_SUB_DIV = 1, CWFA_PREP_DIV_MUL = 2 };
+int cwfa_prep_volumes_f16(const void* x, void* out, float* maxbuf, int N, int D, int H0, int W0, int H, int W, int off_h, int off_w,
+                          int mode, float t0, float t1, int out_f16, void* stream);
+int cwfa_prep_frames_f32(const float* x, float* out, int N, int h, int w, int S0, int S1, int off_y, int off_x, void* stream);
+int cwfa_histogram_f32(const float* x, int64_t n, float lo, float hi, const float* edges, int bins, int64_t* counts, int accumulate,
+                       void* stream);
+int cwfa_prep_apply_f32(float* x, int64_t n, int mode, float a, float b, int flags, void* stream);
+int cwfa_moments_f64(const float* x, int64_t n, double c, double* out, double* workspace, int accumulate, void* stream);
+int cwfa_stack_mean_std_f32(const float* x, float* mean, float* std, int N, int64_t m, int64_t x_ss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
