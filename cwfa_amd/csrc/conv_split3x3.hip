@@ -10,7 +10,9 @@
 //
 // Block = 512 threads = 8 waves, two per SIMD, tile = CT = 64*MPW output channels x 8 rows x 32 pixels.  Wave (wm, wn) owns
 // 16*MPW channels x 4 rows: MPW m-tiles x 8 n-tiles of 16x16 accumulators (MPW = 4: 128 registers); a B fragment (16 bytes
-// per lane from LDS) feeds 6*MPW MFMAs and an A fragment 48.  (One wave per SIMD with the whole 256-pixel tile -- 256
+// per lane from LDS) feeds 6*MPW MFMAs and an A fragment 48: a k-step is ONE pass over the n-tiles with the A fragments of all MPW
+// m-tiles held, so every fragment is read from LDS once per step (MPW = 4: 12 + 24 ds_read_b128 per 192 MFMAs, B fragments
+// requested two n-tiles ahead of the MFMAs that consume them).  (One wave per SIMD with the whole 256-pixel tile -- 256
 // accumulator registers -- was tried first: every issue cost of the single stream, LDS-DMA above all (12 instructions of
 // ~60 cycles per step), is then exposed: 225 TF/s against 260 for the two-wave form's predecessor.)
 //   K = 32 per MFMA = TWO (16-channel chunk, tap) units of the 9 * ceil(Cin / 16) a 3x3 has; lane group g = lane >> 4
@@ -239,15 +241,22 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
     for (int mt = 0; mt < MPW; ++mt)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    constexpr int MH = MPW < 2 ? MPW : MPW == 3 ? 3 : 2;   // m-tiles whose A fragments are held at a time (register budget)
-    bf16x8 A[MH][3], Bq[2][3];
-    float xa[NEK][8], xb[NEK][8], aa[NEK][8], ab[NEK][8];    // staged entries of the next even / odd chunk (+ skip tensor)
+    // ONE pass over the n-tiles per step: the A fragments of all MPW m-tiles are held (MPW = 4: 48 registers), so every B fragment is
+    // read once per step and feeds 6 MPW MFMAs.  NB sets of B fragments = NB - 1 n-tiles of look-ahead (256-channel tiling: two);
+    // the A fragments of m-tiles >= MA are requested behind the step's first MFMAs, not in front of them.
+    constexpr int NB = MPW == 4 ? 3 : 2, MA = MPW == 4 ? 2 : MPW;
+    static_assert(NB - 1 < NT, "B look-ahead");
+    bf16x8 A[MPW][3], Bq[NB][3];
+    // staged entries of the chunk after next (+ skip tensor): ONE register set per entry serves the even and the odd chunk in turn
+    // (its even-chunk value is stored at SA + k, before the odd-chunk load at LB + k, and that one at SB + k of the next period,
+    // before the even-chunk load at LA + k: see the staging schedule in the loop)
+    float xs[NEK][8], sk[NEK][8];
 
-    auto read_a = [&](int abase, int m0) {
+    auto read_a = [&](int abase, int m0, int m1) {
 #pragma unroll
-        for (int mt = 0; mt < MH; ++mt)
+        for (int mt = m0; mt < m1; ++mt)
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) A[mt][q] = *reinterpret_cast<const bf16x8*>(lds + abase + (q * 4 * CT + (m0 + mt) * 16) * 16);
+            for (int q = 0; q < NQ; ++q) A[mt][q] = *reinterpret_cast<const bf16x8*>(lds + abase + (q * 4 * CT + mt * 16) * 16);
     };
     auto read_b = [&](int set, int bbase, int nt) {
 #pragma unroll
@@ -266,10 +275,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
     };
 
     // ---------------------------------------------------------------------------------------------- prologue
-    cwfa_static_for<NEK>([&](auto kc) { load_entry(kc, xa[decltype(kc)::value], aa[decltype(kc)::value], 0); });
-    cwfa_static_for<NEK>([&](auto kc) { load_entry(kc, xb[decltype(kc)::value], ab[decltype(kc)::value], 1); });
-    dma_w(0, 0);
-    cwfa_static_for<NEK>([&](auto kc) { store_entry(kc, xa[decltype(kc)::value], aa[decltype(kc)::value], 0, 0); });
+    {
+        float x0[NEK][8], s0[NEK][8];                     // chunk 0: stored right here; chunk 1 goes straight into the set (stored at SB + k)
+        cwfa_static_for<NEK>([&](auto kc) { load_entry(kc, x0[decltype(kc)::value], s0[decltype(kc)::value], 0); });
+        cwfa_static_for<NEK>([&](auto kc) { load_entry(kc, xs[decltype(kc)::value], sk[decltype(kc)::value], 1); });
+        dma_w(0, 0);
+        cwfa_static_for<NEK>([&](auto kc) { store_entry(kc, x0[decltype(kc)::value], s0[decltype(kc)::value], 0, 0); });
+    }
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
 
@@ -289,65 +301,64 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
         // a few steps earlier); the odd chunk after next is loaded at LB + k
         constexpr int SB = 0, SA = KS == 3 ? 5 : 26, LA = KS == 3 ? 2 : 22, LB = KS == 3 ? 6 : 44;       // (+ k < NEK: all below NTAP)
         static_assert(LB + NEK - 1 < NTAP && LA + NEK - 1 < SA, "staging schedule");
+        static_assert(SB < LA && SA <= LB, "staging schedule: one register set per entry (a step's stores come before its loads)");
         // -- order matters: in this rolled loop the compiler cannot count the vector-memory operations between a staging load
         // and its use, so it waits for ALL of them (vmcnt(0)) before the split below: that must come BEFORE this step issues
         // its own DMA and loads, when everything older has long landed (after them it cost 2 - 9 thousand cycles per step).
         // the vector-heavy part of staging: split + LDS stores of one entry of the chunk after next
         // (written out per entry: behind a generic lambda the staged-entry arrays stopped being promoted to registers)
-        if (P == SB) store_entry(cwfa_ic<0>{}, xb[0], ab[0], co, 1);
-        if (P == SB + 1) store_entry(cwfa_ic<1>{}, xb[1], ab[1], co, 1);
-        if constexpr (NEK > 2) {
-            if (P == SB + 2) store_entry(cwfa_ic<NEK - 1>{}, xb[NEK - 1], ab[NEK - 1], co, 1);
-        }
-        if (P == SA) store_entry(cwfa_ic<0>{}, xa[0], aa[0], ce + 2, 0);
-        if (P == SA + 1) store_entry(cwfa_ic<1>{}, xa[1], aa[1], ce + 2, 0);
-        if constexpr (NEK > 2) {
-            if (P == SA + 2) store_entry(cwfa_ic<NEK - 1>{}, xa[NEK - 1], aa[NEK - 1], ce + 2, 0);
+        {
+            const bool odd0 = P == SB, odd1 = P == SB + 1;          // the entry in the set: of the odd chunk (-> buffer 1) or the even one
+            if (odd0 || P == SA) store_entry(cwfa_ic<0>{}, xs[0], sk[0], odd0 ? co : ce + 2, odd0);
+            if (odd1 || P == SA + 1) store_entry(cwfa_ic<1>{}, xs[1], sk[1], odd1 ? co : ce + 2, odd1);
+            if constexpr (NEK > 2) {
+                const bool odd2 = P == SB + 2;
+                if (odd2 || P == SA + 2) store_entry(cwfa_ic<NEK - 1>{}, xs[NEK - 1], sk[NEK - 1], odd2 ? co : ce + 2, odd2);
+            }
         }
         CWFA_FENCE();
-        // first A fragments (the step's first B fragments were requested before the barrier of the step before)
+        // first A fragments (the step's first B fragments were requested before the barrier of the step before).  Nothing else is
+        // requested in front of the first MFMA: behind the conditional staging stores the compiler drains the LDS counter there
+        // (lgkmcnt(0)), so every read issued up here would be waited for
         const int abase = alane + sl * WSL;
         const int bbase = blane + (sel ? offB : offA);
-        read_a(abase, 0);
+        read_a(abase, 0, MA);
         CWFA_FENCE();
 #pragma unroll
-        for (int m0 = 0; m0 < MPW; m0 += MH) {
-            if (m0 > 0) {
-                read_a(abase, m0);
-                read_b(0, bbase, 0);
+        for (int nt = 0; nt < NT; ++nt) {
+            // NB - 1 n-tiles ahead, into the set the n-tile before this one has just been multiplied from (256-channel tiling, n-tile 0:
+            // behind its first MFMAs, see there); from here on the compiler's waits are counted: only the fragment about to be used
+            if ((MA == MPW || nt > 0) && nt + NB - 1 < NT) read_b((nt + NB - 1) % NB, bbase, nt + NB - 1);
+            CWFA_FENCE();
+#pragma unroll
+            for (int mt = 0; mt < MPW; ++mt) {
+                mfma6(acc[mt][nt], A[mt], Bq[nt % NB]);
+                CWFA_FENCE();                 // keep the six products of a tile back to back (accumulator forwarding)
+                if (MA < MPW && nt == 0 && mt == 0) {
+                    // behind the step's first MFMAs, in the order of their use: the remaining A fragments (the MFMAs of m-tile 1
+                    // cover them), then the B fragments of the look-ahead
+                    read_a(abase, MA, MPW);
+#pragma unroll
+                    for (int n2 = 1; n2 < NB && n2 < NT; ++n2) read_b(n2, bbase, n2);
+                    CWFA_FENCE();
+                }
+            }
+            // this step's staging loads and the next weight slice are issued from INSIDE the MFMA stream (after the first
+            // n-tiles): issued in a burst right behind the barrier, all eight waves stood in their issue cost (~100 cycles per
+            // DMA instruction) at once with the matrix pipe idle; here the SIMD partner's MFMAs run meanwhile.  Loads BEFORE
+            // the DMA: they overwrite loop-carried registers, so the compiler waits for every older vector-memory
+            // operation first -- which must not include a DMA issued a moment ago.
+            if (nt == 0) {
+                if (P == LA || P == LB) load_entry(cwfa_ic<0>{}, xs[0], sk[0], P == LA ? ce + 2 : co + 2);
+                if (P == LA + 1 || P == LB + 1) load_entry(cwfa_ic<1>{}, xs[1], sk[1], P == LA + 1 ? ce + 2 : co + 2);
+                if constexpr (NEK > 2) {
+                    if (P == LA + 2 || P == LB + 2) load_entry(cwfa_ic<NEK - 1>{}, xs[NEK - 1], sk[NEK - 1], P == LA + 2 ? ce + 2 : co + 2);
+                }
                 CWFA_FENCE();
             }
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                if (nt + 1 < NT) read_b((nt + 1) & 1, bbase, nt + 1);
+            if (nt == 1) {
+                dma_w(step + 1, sl ^ 1);
                 CWFA_FENCE();
-#pragma unroll
-                for (int mt = 0; mt < MH; ++mt) {
-                    mfma6(acc[m0 + mt][nt], A[mt], Bq[nt & 1]);
-                    CWFA_FENCE();                 // keep the six products of a tile back to back (accumulator forwarding)
-                }
-                // this step's staging loads and the next weight slice are issued from INSIDE the MFMA stream (after the first
-                // n-tiles): issued in a burst right behind the barrier, all eight waves stood in their issue cost (~100 cycles per
-                // DMA instruction) at once with the matrix pipe idle; here the SIMD partner's MFMAs run meanwhile.  Loads BEFORE
-                // the DMA: they overwrite loop-carried registers, so the compiler waits for every older vector-memory
-                // operation first -- which must not include a DMA issued a moment ago.
-                if (m0 == 0 && nt == 0) {
-                    if (P == LA) load_entry(cwfa_ic<0>{}, xa[0], aa[0], ce + 2);
-                    if (P == LA + 1) load_entry(cwfa_ic<1>{}, xa[1], aa[1], ce + 2);
-                    if constexpr (NEK > 2) {
-                        if (P == LA + 2) load_entry(cwfa_ic<NEK - 1>{}, xa[NEK - 1], aa[NEK - 1], ce + 2);
-                    }
-                    if (P == LB) load_entry(cwfa_ic<0>{}, xb[0], ab[0], co + 2);
-                    if (P == LB + 1) load_entry(cwfa_ic<1>{}, xb[1], ab[1], co + 2);
-                    if constexpr (NEK > 2) {
-                        if (P == LB + 2) load_entry(cwfa_ic<NEK - 1>{}, xb[NEK - 1], ab[NEK - 1], co + 2);
-                    }
-                    CWFA_FENCE();
-                }
-                if (m0 == 0 && nt == 1) {
-                    dma_w(step + 1, sl ^ 1);
-                    CWFA_FENCE();
-                }
             }
         }
         // first B fragments of the next step: the input tiles it reads were completed at least two barriers ago
