@@ -6,20 +6,25 @@ ops raise on non-HIP tensors and on a missing extension.
 
     import cwfa_amd; cwfa_amd.install()     # then the reference's main.py imports resolve to this package
     cwfa_amd.install(precision="fp16")      # ... for its default --use_half_precision 1 (autocast)
+    cwfa_amd.install(lion=True)             # ... and `from lion_pytorch import Lion` resolves to cwfa_amd.optim.Lion
 """
 import sys
 
 __version__ = "0.1.0"
 
 
-def install(precision=None):
+def install(precision=None, lion=False):
     """Register this package's modules under the reference's top-level import names (FrEIA, INN_utils, networks, unet)
     so that code written against the reference (``import FrEIA.framework as Ff``, ``from networks import *``) runs on
     the HIP implementation unchanged.  Call before importing the reference's driver.
 
     ``precision``: None leaves the arithmetic as it is; a mode name ("fp32", "split_bf16", "bf16", "fp16") is passed to
     ``ops.set_precision``.  "fp16" is the arithmetic of the reference's default ``--use_half_precision 1`` (CUDA autocast:
-    fp16 operands, fp32 accumulation); the installed modules compute the same inside and outside an autocast region."""
+    fp16 operands, fp32 accumulation); the installed modules compute the same inside and outside an autocast region.
+
+    ``lion``: True also registers a module ``lion_pytorch`` whose ``Lion`` is ``cwfa_amd.optim.Lion`` (the fused HIP step), so that
+    the reference's ``from lion_pytorch import Lion`` and its ``opt_to_use=Lion`` default (CWFA.py:24,381) resolve to it.  With the
+    default False nothing is registered under that name."""
     from . import FrEIA, INN_utils, networks, unet
     if precision is not None:
         from . import ops
@@ -30,4 +35,11 @@ def install(precision=None):
     sys.modules["INN_utils"] = INN_utils
     sys.modules["networks"] = networks
     sys.modules["unet"] = unet
+    if lion:
+        import types
+        from . import optim
+        mod = types.ModuleType("lion_pytorch", "cwfa_amd.optim.Lion under the name the reference imports it by")
+        mod.Lion = optim.Lion
+        mod.__all__ = ["Lion"]
+        sys.modules["lion_pytorch"] = mod
     return FrEIA, INN_utils, networks, unet

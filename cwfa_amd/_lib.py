@@ -53,6 +53,18 @@ class EvalPost(C.Structure):
                 ("vol_min", C.c_float), ("lower", C.c_float), ("upper", C.c_float), ("clamp_value", C.c_float)]
 
 
+LION_MAX_TENSORS = 96              # CWFA_LION_MAX_TENSORS
+LION_BLOCK_ELEMS = 4096            # CWFA_LION_BLOCK_ELEMS
+
+
+class LionTensor(C.Structure):
+    _fields_ = [("p", c_f32p), ("g", c_f32p), ("m", c_f32p), ("numel", C.c_int64)]
+
+
+class LionTable(C.Structure):
+    _fields_ = [("n", C.c_int), ("t", LionTensor * LION_MAX_TENSORS)]
+
+
 EXTREMA_STRIDE = 12                # CWFA_EXTREMA_STRIDE
 SELECT_WORKSPACE_BYTES = 8448      # CWFA_SELECT_WORKSPACE_BYTES
 PREP_MAX_BINS = 10239              # CWFA_PREP_MAX_BINS
@@ -148,6 +160,7 @@ SIGNATURES = {
     "cwfa_prep_apply_f32": (i, [p, i64, i, f, f, i, p]),
     "cwfa_moments_f64": (i, [p, i64, d, p, p, i, p]),
     "cwfa_stack_mean_std_f32": (i, [p, p, p, i, i64, i64, p]),
+    "cwfa_lion_step_f32": (i, [C.POINTER(LionTable), f, f, f, f, p, p, p]),
 }
 del i, i64, f, d, p
 

@@ -10,7 +10,7 @@ from ._lib import AffineStage, Chain, ConvOpts, check
 
 __all__ = ["haar1d", "haar2d", "gather", "affine", "channel_affine", "chain_inv", "chain_fwd", "pack_conv_weight",
            "conv2d", "conv2d_wgrad", "elu_bwd", "set_precision", "gelu_add", "gelu_bwd", "layernorm_bwd", "attention_bwd", "plane_affine", "bn_bwd_stats", "bn_act_bwd", "maxpool2_bwd", "chain_bwd", "chain_inv_bwd", "prelu_bwd", "conv3d_1k1_backward", "pack_1x1_panel", "pack_split_layer_weight", "subnet_layer", "conv3d_1k1", "channel_stats", "bn_fold", "bn_running_update", "maxpool", "sample_stats", "layernorm_apply",
-           "attention_combine", "scale_channels", "axpby", "stage"]
+           "attention_combine", "scale_channels", "axpby", "stage", "lion_step"]
 
 
 def _stream():
@@ -1611,3 +1611,50 @@ def stack_mean_std(x):
     std = torch.empty_like(mean)
     check(L.cwfa_stack_mean_std_f32(_p(x), _p(mean), _p(std), N, m, m, _stream()), "stack_mean_std")
     return mean, std
+
+
+# ------------------------------------------------------------------------------------------------ optimiser
+def _scalar_arg(t, name, device):
+    """A GradScaler scalar (``grad_scale`` / ``found_inf``) as a one-element fp32 tensor on ``device``, without a host round trip."""
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.numel() != 1 or t.dtype != torch.float32:
+        raise TypeError(f"lion_step: {name} must be a one-element float32 tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"lion_step: {name} must live on the HIP device (it is read by the kernel; no CPU fallback exists)")
+    return t if t.device == device else t.to(device, non_blocking=True)
+
+
+def lion_step(params, grads, moments, lr, betas, weight_decay, grad_scale=None, found_inf=None):
+    """The Lion update of DESIGN.md section 14 on lists of fp32 device tensors, in place on ``params`` and ``moments``
+    (cwfa_lion_step_f32): one launch per ``_lib.LION_MAX_TENSORS`` tensors, the tables passed as kernel arguments.  ``grad_scale`` /
+    ``found_inf``: optional one-element fp32 DEVICE tensors (a GradScaler's); the gradients are divided by the first and nothing is
+    written when the second is non-zero -- both are read by the kernel, nothing here waits for the device."""
+    import struct
+    L = _lib.lib()
+    params, grads, moments = list(params), list(grads), list(moments)
+    if not (len(params) == len(grads) == len(moments)):
+        raise ValueError("lion_step: params, grads and moments differ in length")
+    if not params:
+        return
+    flat = []
+    for k, (p, g, m) in enumerate(zip(params, grads, moments)):
+        _dev(p, f"params[{k}]"), _dev(g, f"grads[{k}]"), _dev(m, f"moments[{k}]")
+        if not (p.is_contiguous() and g.is_contiguous() and m.is_contiguous()):
+            raise ValueError(f"lion_step: params[{k}], its gradient and its moment must be contiguous (the update is in place)")
+        if not (p.numel() == g.numel() == m.numel()):
+            raise ValueError(f"lion_step: params[{k}], its gradient and its moment differ in size")
+        if not (p.device == g.device == m.device == params[0].device):
+            raise ValueError("lion_step: all tensors of one call must live on one device")
+        flat += (p.data_ptr(), g.data_ptr(), m.data_ptr(), p.numel())
+    dev = params[0].device
+    gs, fi = _scalar_arg(grad_scale, "grad_scale", dev), _scalar_arg(found_inf, "found_inf", dev)
+    b1, b2 = betas
+    size, M = C.sizeof(_lib.LionTable), _lib.LION_MAX_TENSORS
+    with torch.cuda.device(dev):
+        stream = _stream()
+        for i in range(0, len(params), M):
+            chunk = flat[4 * i:4 * (i + M)]
+            tab = _lib.LionTable.from_buffer_copy(struct.pack(f"=i4x{len(chunk)}q", len(chunk) // 4, *chunk).ljust(size, b"\0"))
+            check(L.cwfa_lion_step_f32(C.byref(tab), float(lr), float(b1), float(b2), float(weight_decay), _p(gs), _p(fi), stream),
+                  "lion_step")

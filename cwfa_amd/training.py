@@ -29,7 +29,7 @@ from . import ops
 
 __all__ = ["subnet_forward_train", "subnet_backward", "nll_backward", "step_backward", "cond_forward_train", "cond_backward", "unet_forward_train", "unet_backward",
            "lrnn_forward_train", "lrnn_backward", "lrnn_step_backward", "train_iteration", "allreduce_gradients",
-           "sgd_step"]
+           "sgd_step", "make_optimizers"]
 
 
 class _Tape:
@@ -303,7 +303,9 @@ def _acc(param, g):
         return
     g = g.to(param.dtype).reshape(param.shape)
     if param.grad is None:
-        param.grad = g.clone()
+        # contiguous like the parameter, as autograd lays gradients out (a permuted view would keep its strides through a plain clone;
+        # the fused optimiser step works on contiguous tensors)
+        param.grad = g.clone(memory_format=torch.contiguous_format)
     else:
         param.grad.add_(g)
 
@@ -771,3 +773,27 @@ def sgd_step(params, lr):
         for p in params:
             if p.grad is not None:
                 p.add_(p.grad, alpha=-lr)
+
+
+def make_optimizers(conv_inn, cond_nets, lr, lr_first_step, lr_cond, weight_decay, steps=None):
+    """The optimisers of the reference's training set-up (CWFA.py:587-610) as the per-step list ``train_iteration(optimizers=...)``
+    takes, built on ``cwfa_amd.optim.Lion`` (the reference's ``opt_to_use``): for a flow step n the pair
+    (Lion over ``conv_inn[n]`` with ``lr`` and ``weight_decay``, Lion over ``cond_nets[n]`` with ``lr_cond`` and no weight decay --
+    ``optimizer`` / ``optimizer_cond``), for the last step one Lion over the LRNN ``cond_nets[-1]`` with ``lr_first_step`` and
+    ``weight_decay``.  ``steps``: the pyramid steps to optimise (indices into the returned list, 0 = finest; the reference's
+    ``fine_tune_optimize_steps`` less one), None = all; the other entries are None.  ``cond_nets`` without an LRNN (as many entries
+    as ``conv_inn``) gives the flow steps only."""
+    from .optim import Lion
+    n_flow, has_lrnn = len(conv_inn), len(cond_nets) > len(conv_inn)
+    total = n_flow + int(has_lrnn)
+    chosen = set(range(total)) if steps is None else {int(s) for s in steps}
+    if not chosen <= set(range(total)):
+        raise ValueError(f"make_optimizers: steps {sorted(chosen)} are not all in 0 .. {total - 1}")
+    out = [None] * total
+    for n in sorted(chosen):
+        if n < n_flow:
+            flow = Lion([{"params": conv_inn[n].parameters(), "lr": lr, "weight_decay": weight_decay}], lr=lr)
+            out[n] = (flow, Lion(cond_nets[n].parameters(), lr=lr_cond))
+        else:
+            out[n] = Lion([{"params": cond_nets[-1].parameters(), "lr": lr_first_step, "weight_decay": weight_decay}], lr=lr_first_step)
+    return out

@@ -600,6 +600,36 @@ int cwfa_prep_apply_f32(float* x, int64_t n, int mode, float a, float b, int fla
 int cwfa_moments_f64(const float* x, int64_t n, double c, double* out, double* workspace, int accumulate, void* stream);
 int cwfa_stack_mean_std_f32(const float* x, float* mean, float* std, int N, int64_t m, int64_t x_ss, void* stream);
 
+/* The parameter update: `scaler.step(optimizer)` / `optimizer.step()` of CWFA.py:1011-1027 with the reference's optimiser, Lion
+ * (CWFA.py:24,381,608-610; Chen et al. 2023, decoupled weight decay), INCLUDING what torch's GradScaler does around it: the
+ * unscale pass over every gradient and the skip of the step when a gradient holds inf / NaN (CWFA.py:613,1011-1027).
+ * One launch updates every tensor of the table.  Per element, with g' = g / *grad_scale (g' = g for grad_scale == NULL):
+ *     p <- p * (1 - lr * wd);   u = sign(beta1 * m + (1 - beta1) * g')  (sign(0) = 0);   p <- p - lr * u;
+ *     m <- beta2 * m + (1 - beta2) * g'
+ * every fp32 operation rounded separately, 1 - beta and 1 - lr * wd formed in fp32 on the host.
+ *   tab:        HOST struct: n <= CWFA_LION_MAX_TENSORS entries (p, g, m, numel) of fp32 device tensors, contiguous, 4-byte aligned,
+ *               numel < 2^31; entries with numel == 0 are skipped (their pointers may be NULL).  The table is copied into the
+ *               kernel's arguments: nothing is allocated or uploaded, the caller issues one call per chunk of tensors.
+ *   grad_scale: nullable DEVICE scalar, read by the kernel.
+ *   found_inf:  nullable DEVICE scalar, read by the kernel: if *found_inf != 0 the launch writes nothing.
+ * The launch writes p and m only.  Tensors whose p, g and m are all 16-byte aligned move on 16-byte loads and stores, the others
+ * and every ragged end element by element.  A block works on CWFA_LION_BLOCK_ELEMS consecutive elements of one tensor.
+ * n == 0 or no elements at all: returns 0 without a launch. */
+#define CWFA_LION_MAX_TENSORS 96
+#define CWFA_LION_BLOCK_ELEMS 4096
+typedef struct {
+    float* p;        /* parameter, updated in place              */
+    const float* g;  /* gradient (scaled by *grad_scale), read   */
+    float* m;        /* momentum (`exp_avg`), updated in place   */
+    int64_t numel;
+} cwfa_lion_tensor;
+typedef struct {
+    int n;
+    cwfa_lion_tensor t[CWFA_LION_MAX_TENSORS];
+} cwfa_lion_table;
+int cwfa_lion_step_f32(const cwfa_lion_table* tab, float lr, float beta1, float beta2, float weight_decay, const float* grad_scale,
+                       const float* found_inf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
