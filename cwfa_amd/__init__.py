@@ -7,13 +7,14 @@ ops raise on non-HIP tensors and on a missing extension.
     import cwfa_amd; cwfa_amd.install()     # then the reference's main.py imports resolve to this package
     cwfa_amd.install(precision="fp16")      # ... for its default --use_half_precision 1 (autocast)
     cwfa_amd.install(lion=True)             # ... and `from lion_pytorch import Lion` resolves to cwfa_amd.optim.Lion
+    cwfa_amd.install(losses=True)           # ... and `import losses as Losses` resolves to cwfa_amd.losses (the fused wL2 loss)
 """
 import sys
 
 __version__ = "0.1.0"
 
 
-def install(precision=None, lion=False):
+def install(precision=None, lion=False, losses=False):
     """Register this package's modules under the reference's top-level import names (FrEIA, INN_utils, networks, unet)
     so that code written against the reference (``import FrEIA.framework as Ff``, ``from networks import *``) runs on
     the HIP implementation unchanged.  Call before importing the reference's driver.
@@ -24,7 +25,11 @@ def install(precision=None, lion=False):
 
     ``lion``: True also registers a module ``lion_pytorch`` whose ``Lion`` is ``cwfa_amd.optim.Lion`` (the fused HIP step), so that
     the reference's ``from lion_pytorch import Lion`` and its ``opt_to_use=Lion`` default (CWFA.py:24,381) resolve to it.  With the
-    default False nothing is registered under that name."""
+    default False nothing is registered under that name.
+
+    ``losses``: True also registers ``cwfa_amd.losses`` under the name ``losses``, so that the reference's ``import losses as Losses``
+    (CWFA.py:27) and its ``Losses.weighted_mse_loss(curr_gt, upsampled_vol)`` calls (the `wL2` loss) run the fused HIP pass.  That
+    module holds only what CWFA.py uses from losses.py.  With the default False nothing is registered under that name."""
     from . import FrEIA, INN_utils, networks, unet
     if precision is not None:
         from . import ops
@@ -42,4 +47,7 @@ def install(precision=None, lion=False):
         mod.Lion = optim.Lion
         mod.__all__ = ["Lion"]
         sys.modules["lion_pytorch"] = mod
+    if losses:
+        from . import losses as losses_mod
+        sys.modules["losses"] = losses_mod
     return FrEIA, INN_utils, networks, unet

@@ -161,6 +161,8 @@ SIGNATURES = {
     "cwfa_moments_f64": (i, [p, i64, d, p, p, i, p]),
     "cwfa_stack_mean_std_f32": (i, [p, p, p, i, i64, i64, p]),
     "cwfa_lion_step_f32": (i, [C.POINTER(LionTable), f, f, f, f, p, p, p]),
+    "cwfa_wmse_workspace_bytes": (i64, [i64]),
+    "cwfa_wmse_loss_f32": (i, [p, p, p, f, f, p, p, p, i64, p]),
 }
 del i, i64, f, d, p
 

@@ -10,7 +10,7 @@ from ._lib import AffineStage, Chain, ConvOpts, check
 
 __all__ = ["haar1d", "haar2d", "gather", "affine", "channel_affine", "chain_inv", "chain_fwd", "pack_conv_weight",
            "conv2d", "conv2d_wgrad", "elu_bwd", "set_precision", "gelu_add", "gelu_bwd", "layernorm_bwd", "attention_bwd", "plane_affine", "bn_bwd_stats", "bn_act_bwd", "maxpool2_bwd", "chain_bwd", "chain_inv_bwd", "prelu_bwd", "conv3d_1k1_backward", "pack_1x1_panel", "pack_split_layer_weight", "subnet_layer", "conv3d_1k1", "channel_stats", "bn_fold", "bn_running_update", "maxpool", "sample_stats", "layernorm_apply",
-           "attention_combine", "scale_channels", "axpby", "stage", "lion_step"]
+           "attention_combine", "scale_channels", "axpby", "stage", "lion_step", "global_extrema", "wmse_loss"]
 
 
 def _stream():
@@ -1658,3 +1658,47 @@ def lion_step(params, grads, moments, lr, betas, weight_decay, grad_scale=None, 
             tab = _lib.LionTable.from_buffer_copy(struct.pack(f"=i4x{len(chunk)}q", len(chunk) // 4, *chunk).ljust(size, b"\0"))
             check(L.cwfa_lion_step_f32(C.byref(tab), float(lr), float(b1), float(b2), float(weight_decay), _p(gs), _p(fi), stream),
                   "lion_step")
+
+
+# ------------------------------------------------------------------------------------------------ training loss
+def global_extrema(a, b=None):
+    """float32 [EXTREMA_STRIDE] row of ``volume_extrema`` over ALL elements of the contiguous tensor ``a`` (and ``b``) as one sample:
+    slots 0, 1 (4, 5) are the global minimum and maximum of a (b).  Exact; an empty tensor gives zeros."""
+    L = _lib.lib()
+    n = a.numel()
+    out = torch.zeros(_lib.EXTREMA_STRIDE, dtype=torch.float32, device=a.device)
+    if n:
+        ws = torch.empty(L.cwfa_eval_splits(1, n) * 10, dtype=torch.float32, device=a.device)
+        check(L.cwfa_volume_extrema_f32(_p(a), _p(b), _p(out), _p(ws), 1, n, n, n, None, _stream()), "global_extrema")
+    return out
+
+
+def wmse_loss(output, target, ths_perc=0.05, gscale=1.0, want_grad=True, extrema=None):
+    """The sums of the weighted-MSE loss `wL2` (cwfa_wmse_loss_f32) over two contiguous fp32 device tensors of
+    one shape: returns (out, grad) with out float64[2] = (sum (o - t)^2 inside both masks, number of elements inside both masks) and
+    grad = d(gscale * out[0]) / d output, exactly zero outside the masks (None unless ``want_grad``; the target's gradient is its
+    negative).  The masks are (v - min v) > (max v - min v) * ths_perc in fp32.  ``extrema``: the ``global_extrema(output, target)``
+    row if the caller has it already (or has reduced it over its ranks: training.allreduce_extrema); None: computed here.  Two
+    launches (three kernels), nothing waits for the device."""
+    L = _lib.lib()
+    _dev(output, "output"), _dev(target, "target")
+    if tuple(output.shape) != tuple(target.shape):
+        raise ValueError(f"wmse_loss: output and target differ in shape: {tuple(output.shape)} vs {tuple(target.shape)}")
+    if output.device != target.device:
+        raise ValueError("wmse_loss: output and target live on different devices")
+    if not (output.is_contiguous() and target.is_contiguous()):
+        raise ValueError("wmse_loss: output and target must be contiguous")
+    n = output.numel()
+    with torch.cuda.device(output.device):
+        if extrema is None:
+            extrema = global_extrema(output, target)
+        else:
+            _dev(extrema, "extrema")
+            if extrema.numel() < _lib.EXTREMA_STRIDE or not extrema.is_contiguous() or extrema.device != output.device:
+                raise ValueError(f"wmse_loss: extrema must be a contiguous row of {_lib.EXTREMA_STRIDE} floats on the tensors' device")
+        out = torch.empty(2, dtype=torch.float64, device=output.device)
+        grad = torch.empty_like(output) if want_grad else None
+        ws = torch.empty(max(1, L.cwfa_wmse_workspace_bytes(n) // 8), dtype=torch.float64, device=output.device)
+        check(L.cwfa_wmse_loss_f32(_p(output), _p(target), _p(extrema), float(ths_perc), float(gscale), _p(grad), _p(out), _p(ws), n,
+                                   _stream()), "wmse_loss")
+    return out, grad

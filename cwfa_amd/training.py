@@ -19,7 +19,8 @@ and issues one all-reduce per bucket (RCCL over xGMI on MI355X; gloo in the CPU 
 
 Scope: gradients of a flow step's own parameters (the reference's ``optimizer``), of its condition net
 (``optimizer_cond`` for the flow steps: ``cond_forward_train`` / ``cond_backward``) and of the LRNN, the last step's
-network (``lrnn_step_backward``: UNet + mean-volume branch, L1/L2 loss).
+network (``lrnn_step_backward``: UNet + mean-volume branch), with the reconstruction losses L1, L2 and wL2 (the weighted MSE of
+``cwfa_amd.losses``).  `LL` is not built: in fp32 the reference's expression is log(0) at the minimum.
 """
 from typing import Sequence
 
@@ -28,8 +29,11 @@ import torch
 from . import ops
 
 __all__ = ["subnet_forward_train", "subnet_backward", "nll_backward", "step_backward", "cond_forward_train", "cond_backward", "unet_forward_train", "unet_backward",
-           "lrnn_forward_train", "lrnn_backward", "lrnn_step_backward", "train_iteration", "allreduce_gradients",
+           "lrnn_forward_train", "lrnn_backward", "lrnn_step_backward", "train_iteration", "allreduce_gradients", "allreduce_extrema",
            "sgd_step", "make_optimizers"]
+
+
+_LOSSES = ("L1", "L2", "wL2")      # the reconstruction losses built here (main.py:42-43); `LL` is not: see the module docstring
 
 
 class _Tape:
@@ -143,14 +147,15 @@ def step_backward(graph, gt, c, low=None, z=None, cond_weight=0.40984, loss_func
     The reference evaluates every sub-network twice (inverse and forward pass) and lets autograd add the two gradient
     contributions; both passes see the same conditions, so here the sub-networks run ONCE (with a tape), the two chain
     backward kernels add their coefficient gradients in place, and one sub-network backward follows.
-    ``cond_weight = 0`` or ``low is None``: the NLL alone.  ``loss_func``: "L1" | "L2" (main.py:43).
+    ``cond_weight = 0`` or ``low is None``: the NLL alone.  ``loss_func``: "L1" | "L2" | "wL2" (main.py:43; wL2 =
+    ``losses.weighted_mse_loss(gt, xhat)``, its masks from the extrema of the GLOBAL batch).
     Returns a dict: full_loss, nll, recon (mean), Z, xhat, cond_grads."""
     from .CWFA import allreduce_nll
     plan = getattr(graph, "_plan", None)
     if plan is None or hasattr(plan, "rest") or any(k == "act" for k, _ in plan.chain):    # no plan / mixed plan / ActNorm stages
         raise NotImplementedError("step_backward: only conditional-affine (CAT) steps lowered to a chain plan are built")
-    if loss_func not in ("L1", "L2"):
-        raise NotImplementedError(f"step_backward: loss_func {loss_func!r} (L1 and L2 are built)")
+    if loss_func not in _LOSSES:
+        raise NotImplementedError(f"step_backward: loss_func {loss_func!r} (L1, L2 and wL2 are built)")
     recon = low is not None and cond_weight != 0.0
     w_c = float(cond_weight) if recon else 0.0
     x = gt
@@ -221,7 +226,16 @@ def step_backward(graph, gt, c, low=None, z=None, cond_weight=0.40984, loss_func
             grads.append((g_a, g_mean))
             holders.append((tape, g_a, g_mean, parts))
     recon_mean = None
-    if recon:
+    if recon and loss_func == "wL2":
+        # Losses.weighted_mse_loss(curr_gt, upsampled_vol): the map is d sum / d gt, the reconstruction's gradient its negative --
+        # handed to the inverse chain's backward as an upstream gradient (loss_kind 0) with the sign in its scale
+        xc = x.contiguous()
+        ext = allreduce_extrema(ops.global_extrema(xc, xhat), group)
+        rsum, gmap = ops.wmse_loss(xc, xhat, gscale=1.0, extrema=ext)
+        ops.chain_inv_bwd(xhat, gmap, stages, grads, gscale=-w_c / numel_total, loss_kind=0)
+        rsum = allreduce_nll(rsum, group)
+        recon_mean = rsum[0] / numel_total
+    elif recon:
         kind = 2 if loss_func == "L2" else 1
         rsum = ops.chain_inv_bwd(xhat, x, stages, grads, gscale=w_c * kind / numel_total, loss_kind=kind)
         rsum = allreduce_nll(rsum, group)
@@ -582,16 +596,23 @@ def lrnn_backward(tape, g_out):
 
 def lrnn_step_backward(encoder, views, mean_vol, gt, loss_func="L2", group=None):
     """Training step of the LAST pyramid step (`is_last_step`, CWFA.py:880-886,936-950): upsampled_vol = LRNN(views, mean_vol),
-    loss = F.mse_loss / F.l1_loss(curr_gt, upsampled_vol) (main.py:42: L2), backward into every LRNN parameter.
+    loss = F.mse_loss / F.l1_loss / Losses.weighted_mse_loss(curr_gt, upsampled_vol) (main.py:42: L2), backward into every LRNN parameter.
     ``encoder`` is the ``Encoder`` (or its ``.net``).  The loss is the mean over the GLOBAL batch when torch.distributed is
     initialised (gradients are local contributions: ``allreduce_gradients`` sums them).  Returns (loss, upsampled_vol)."""
     from .CWFA import allreduce_nll
     lrnn = getattr(encoder, "net", encoder)
-    if loss_func not in ("L1", "L2"):
-        raise NotImplementedError(f"lrnn_step_backward: loss_func {loss_func!r} (L1 and L2 are built)")
+    if loss_func not in _LOSSES:
+        raise NotImplementedError(f"lrnn_step_backward: loss_func {loss_func!r} (L1, L2 and wL2 are built)")
     out, tape = lrnn_forward_train(lrnn, views, mean_vol)
     cnt = allreduce_nll(torch.tensor([float(out.numel())], dtype=torch.float64, device=out.device), group)
     numel = float(cnt[0])
+    if loss_func == "wL2":                                # the extrema pass and the loss pass; the map is d loss / d out
+        gt = gt.contiguous()
+        ext = allreduce_extrema(ops.global_extrema(out, gt), group)
+        lsum, g = ops.wmse_loss(out, gt, gscale=1.0 / numel, extrema=ext)
+        loss = allreduce_nll(lsum, group)[0] / numel
+        lrnn_backward(tape, g)
+        return loss, out
     diff = ops.axpby(out, 1.0, gt, -1.0)
     if loss_func == "L2":
         g = ops.axpby(diff, 2.0 / numel)
@@ -723,6 +744,20 @@ def train_iteration(conv_inn, cond_nets, gt_volume, cond_input, mean_vols_cache,
         update(n, [g, cn])
         up = out["xhat"]                                     # `upsampled_vol.detach()`: nothing here records a graph
     return {"losses": losses, "nll": nlls, "recon": recons, "volume": up}
+
+
+def allreduce_extrema(ext, group=None):
+    """Make the ``ops.global_extrema`` row of this rank's batch shard the row of the GLOBAL batch: the minima (slots 0, 4) by MIN and
+    the maxima (slots 1, 5) by MAX over the ranks, as one four-element all-reduce (MAX over the negated minima: exact).  The other
+    slots are left as they are.  Returns ``ext``; a no-op without an initialised process group or with one rank."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1):
+        return ext
+    row = ext.view(-1)
+    v = torch.stack([-row[0], row[1], -row[4], row[5]])
+    dist.all_reduce(v, op=dist.ReduceOp.MAX, group=group)
+    row[0], row[1], row[4], row[5] = -v[0], v[1], -v[2], v[3]
+    return ext
 
 
 def allreduce_gradients(params: Sequence[torch.nn.Parameter], group=None, bucket_bytes: int = 64 << 20):

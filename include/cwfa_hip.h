@@ -630,6 +630,25 @@ typedef struct {
 int cwfa_lion_step_f32(const cwfa_lion_table* tab, float lr, float beta1, float beta2, float weight_decay, const float* grad_scale,
                        const float* found_inf, void* stream);
 
+/* The weighted-MSE training loss `wL2` (losses.py:477-500; CWFA.py:936-959): the squared error over the elements that are brighter
+ * than ths_perc of the range in BOTH tensors,
+ *     m_o = (o - min o) > (max o - min o) * ths_perc,   m_t likewise for t      (every operation rounded to fp32, as the reference)
+ *     out[0] = sum (o - t)^2 m_o m_t   (float64: exact differences, partial sums added in a fixed order -- bitwise reproducible)
+ *     out[1] = #{m_o and m_t}          (exact)
+ *     grad[i] = (2 gscale) (o_i - t_i) inside both masks, +0.0f outside: d(gscale * out[0]) / d output; the target's is its negative.
+ * One streaming pass over n contiguous elements (any n): output and target read once, grad written once; 16-byte accesses where
+ * output, target and grad are 16-byte aligned, element by element otherwise and at the ragged end.
+ *   extrema:   DEVICE row of cwfa_volume_extrema_f32(a = output, b = target, B = 1 over all n elements): slots 0, 1, 4, 5 = min o,
+ *              max o, min t, max t are read by the kernel -- nothing goes through the host (a caller on several ranks reduces those
+ *              four between the two launches).
+ *   grad:      nullable: no map is written.
+ *   out:       2 device doubles, written (not accumulated).
+ *   workspace: cwfa_wmse_workspace_bytes(n) device bytes, 8-byte aligned; no clearing needed.
+ * Nothing is allocated, nothing synchronises.  n == 0: out is zeroed, no launch.  Inputs are assumed finite. */
+int64_t cwfa_wmse_workspace_bytes(int64_t n);
+int cwfa_wmse_loss_f32(const float* output, const float* target, const float* extrema, float ths_perc, float gscale, float* grad,
+                       double* out, void* workspace, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
