@@ -563,6 +563,217 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------ 7x7 over <= 8 input channels
+// The few-channel form of the 7x7 (the ConvNeXt 1x1 + 7x7 of the LRNN's mean-volume branch composed into ONE 7x7 over the block's
+// few inputs and a ones channel, ops.pack_convnext_composed): with <= 8 input channels a 16-byte B fragment is ALL the channels of a
+// pixel, so a K = 32 step is FOUR (8-channel, tap) units -- lane group g reads the fragment of tap 4 s + g -- and the 49 taps take
+// 13 steps instead of the 49 a 16-channel chunk costs on the kernel above.  The same block (512 threads, 64 channels x 8 rows x 32
+// pixels, 2 m-tiles x 2 channel groups, 4 n-tiles per wave), fragments, XCD block map and bias-only NCHW epilogue.
+//   input tile: one k half only, [piece 3][14 rows][38 px] x 16 B = 25 536 bytes, staged ONCE per block (two entries per thread;
+//   channels >= Cin and pixels outside the image come back as 0.0 from the range check); nothing is refilled in the step loop.
+//   taps 49 .. 51 (the padding of the last step) have zero weights; their B address is that of tap 48: staged, finite data.
+//   weights: one slice [piece][k group 4][64][8] per step (group g of step s = tap 4 s + g) through the two-slot LDS-DMA ring of
+//   the kernel above: slice s + 1 is requested behind the first n-tile of step s and has landed at the step's one barrier.
+//   With 13 steps a tile's fill (the staging round trip) and drain (64 KB of stores) weigh as much as its loop, and nothing inside a
+//   block overlaps them: the block needs 50 112 bytes of LDS and <= 128 registers, so TWO blocks share a CU and one block's steps run
+//   under the other's fill and drain (and under its barriers).
+namespace few {
+constexpr int XR = TR + 6, XC = TC + 6, EPK = XR * XC;      // 14 x 38 = 532 entries
+constexpr int XPB = EPK * 16;                               // one piece plane: 8512 bytes (= 64 modulo 256)
+constexpr int NSTEP = 13, CT = 64, MPW = 2, WM = 2, WN = 4, RW = 2, NT = 4;
+constexpr int WSL = 3 * 4 * CT * 16;                        // one weight slice: 12 288 bytes
+constexpr int OFF_W = 3 * XPB, LDS = OFF_W + 2 * WSL;       // 50 112 bytes
+static_assert(2 * 512 >= EPK && 2 * LDS <= 160 * 1024, "few-channel 7x7: staging map / two blocks per CU");
+}  // namespace few
+
+template <bool SIX, bool F16>
+__global__ __launch_bounds__(512, 2) void conv7x7_few_split_kernel(SParams p) {
+    using namespace few;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave % WM, wn = wave / WM;
+    const int plane = p.H * p.W * 4;
+    constexpr unsigned OOB = 0x80000000u;
+    constexpr int NQ = SIX ? 3 : 1;
+    const int b = blockIdx.z;
+    int sp;                                              // (one cout tile: Cout <= 64) the XCD map of the kernel above
+    if (p.xcd_map && (p.ntiles & 7) == 0) sp = (blockIdx.x & 7) * (p.ntiles >> 3) + (blockIdx.x >> 3);
+    else sp = blockIdx.x;
+    const int row0 = (sp / p.tiles_x) * TR, col0 = (sp % p.tiles_x) * TC;
+
+    // ---- weight slices by LDS-DMA, 1 KB pieces dealt over the waves (plain 16-bit operands: the leading piece plane only)
+    constexpr int NPC = (SIX ? WSL : WSL / 3) / 1024;
+    const auto rw = CWFA_RSRC(p.wp, NSTEP * WSL);
+    auto dma_w = [&](int slice, int slot) {
+        cwfa_static_for<(NPC + 7) / 8>([&](auto ic_) {
+            constexpr int i = decltype(ic_)::value;
+            const int piece = i * 8 + wave;
+            if (piece < NPC) {                           // wave-uniform
+                char* dst = lds + OFF_W + slot * WSL + piece * 1024;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)dst, 16, (unsigned)(lane * 16), slice * WSL + piece * 1024, 0, 0);
+            }
+        });
+    };
+
+    // ---- the input tile, once: entries tid and tid + 512 of the 532; the eight channels of a pixel -> three 16-byte pieces
+    {
+        const auto rx = CWFA_RSRC(p.x + (int64_t)b * p.x_bs, p.Cin * plane);       // channels >= Cin: out of range, 0.0
+        float xv[2][8];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int e = tid + 512 * k, r = e / XC, c = e % XC;
+            const int gr = row0 + r - 3, gc = col0 + c - 3;
+            const bool ok = e < EPK && gr >= 0 && gr < p.H && gc >= 0 && gc < p.W;
+            const unsigned fo = ok ? (unsigned)((gr * p.W + gc) * 4) : OOB;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) xv[k][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, fo, j * plane, 0));
+        }
+        dma_w(0, 0);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int e = tid + 512 * k;
+            bf16x8 pc[3];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                __bf16 a1, a2 = (__bf16)0.f, a3 = (__bf16)0.f;
+                cwfa_split3<SIX, F16>(xv[k][j], a1, a2, a3);
+                pc[0][j] = a1; pc[1][j] = a2; pc[2][j] = a3;
+            }
+            if (e < EPK) {
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) *reinterpret_cast<bf16x8*>(lds + q * XPB + e * 16) = pc[q];
+            }
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+
+    const int alane = OFF_W + (g * CT + wm * MPW * 16 + c16) * 16;       // + slot*WSL + (q*4*CT + mt*16)*16
+    const int blane = (wn * RW * XC + c16) * 16;                         // + tap offset + q*XPB + ((nt>>1)*XC + 16*(nt&1))*16
+    // B-fragment base of step s for this lane group: tap 4 s + g, the padding taps of the last step on tap 48's (staged) data
+    auto bbase_of = [&](int s) {
+        const int t = 4 * s + g < 48 ? 4 * s + g : 48;
+        return blane + ((t / 7) * XC + t % 7) * 16;
+    };
+
+    f32x4 acc[MPW][NT];
+#pragma unroll
+    for (int mt = 0; mt < MPW; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    bf16x8 A[MPW][3], Bq[2][3];
+    auto read_b = [&](int set, int bbase, int nt) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+            Bq[set][q] = *reinterpret_cast<const bf16x8*>(lds + bbase + q * XPB + ((nt >> 1) * XC + 16 * (nt & 1)) * 16);
+    };
+    auto mfma6 = [&](f32x4& c, const bf16x8 (&a)[3], const bf16x8 (&bb)[3]) {
+        if constexpr (SIX) {
+            CWFA_MFMA(a[2], bb[0], c);
+            CWFA_MFMA(a[1], bb[1], c);
+            CWFA_MFMA(a[0], bb[2], c);
+            CWFA_MFMA(a[1], bb[0], c);
+            CWFA_MFMA(a[0], bb[1], c);
+        }
+        CWFA_MFMA_OP(F16, a[0], bb[0], c);
+    };
+
+    int bbase = bbase_of(0);
+    read_b(0, bbase, 0);
+    int sl = 0;
+#pragma unroll 1
+    for (int step = 0; step < NSTEP; ++step) {           // rolled: the accumulators are loop-carried (see the kernel above)
+        const int abase = alane + sl * WSL;
+#pragma unroll
+        for (int mt = 0; mt < MPW; ++mt)
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) A[mt][q] = *reinterpret_cast<const bf16x8*>(lds + abase + (q * 4 * CT + mt * 16) * 16);
+        CWFA_FENCE();
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            if (nt + 1 < NT) read_b((nt + 1) & 1, bbase, nt + 1);
+            CWFA_FENCE();
+#pragma unroll
+            for (int mt = 0; mt < MPW; ++mt) {
+                mfma6(acc[mt][nt], A[mt], Bq[nt & 1]);
+                CWFA_FENCE();
+            }
+            // the next slice, from inside the MFMA stream; its slot was last read in the step before this one's barrier
+            if (nt == 0 && step + 1 < NSTEP) {
+                dma_w(step + 1, sl ^ 1);
+                CWFA_FENCE();
+            }
+        }
+        bbase = bbase_of(step + 1 < NSTEP ? step + 1 : step);     // (last step: a staged address, read and dropped)
+        read_b(0, bbase, 0);
+        CWFA_FENCE();
+        // the next slice has landed; every LDS read of this step but the B fragments just requested is done
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (SIX) asm volatile("s_waitcnt lgkmcnt(3)" ::: "memory");
+        else asm volatile("s_waitcnt lgkmcnt(1)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        sl ^= 1;
+    }
+
+    // ---- epilogue (bias only, NCHW): accumulator register r of tile (mt, nt) = channel (wm*MPW + mt)*16 + 4g + r, pixel
+    // (row0 + 2 wn + nt/2, col0 + 16 (nt&1) + c16); the descriptor ends at channel Cout, pixels outside the image are out of range
+    const auto ry = CWFA_RSRC(p.y + (int64_t)b * p.y_bs, p.Cout * plane);
+    const auto rb = CWFA_RSRC(p.o.bias ? p.o.bias : p.y, p.o.bias ? p.Cout * 4 : 0);
+    const int cwave = wm * MPW * 16;
+    const unsigned glane = (unsigned)(4 * g) * (unsigned)plane;
+#pragma unroll
+    for (int mt = 0; mt < MPW; ++mt) {
+        float bias[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            bias[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rb, (unsigned)(16 * g), (cwave + mt * 16 + r) * 4, 0));
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int row = row0 + wn * RW + (nt >> 1), col = col0 + 16 * (nt & 1) + c16;
+            const unsigned po = (row < p.H && col < p.W) ? (unsigned)((row * p.W + col) * 4) + glane : OOB;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, acc[mt][nt][r] + bias[r]), ry, po, (cwave + mt * 16 + r) * plane, 0);
+            CWFA_FENCE();
+        }
+    }
+}
+
+// its packed image: [step 13][piece 3][k group 4][64][8] of bf16, group g of step s = tap 4 s + g: element j = w[co][j][tap]
+// (0 beyond Cout / Cin / tap 48); F16 as below
+template <bool F16>
+__global__ __launch_bounds__(256) void split7x7_few_pack_kernel(const float* __restrict__ w, uint4* __restrict__ out, int Cout, int Cin) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;                    // over [step][g 4][co 64]
+    if (i >= few::NSTEP * 4 * 64) return;
+    const int co = i % 64, g = (i / 64) % 4, s = i / 256, tap = 4 * s + g;
+    unsigned short pc[3][8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float v = 0.f;
+        if (co < Cout && j < Cin && tap < 49) v = w[((int64_t)co * Cin + j) * 49 + tap];
+        __bf16 a1, a2, a3;
+        if constexpr (F16) {
+            cwfa_split3<false, true>(v, a1, a2, a3);
+            a2 = a3 = __builtin_bit_cast(__bf16, (unsigned short)0);
+        } else {
+            cwfa_split3<true>(v, a1, a2, a3);
+        }
+        pc[0][j] = __builtin_bit_cast(unsigned short, a1);
+        pc[1][j] = __builtin_bit_cast(unsigned short, a2);
+        pc[2][j] = __builtin_bit_cast(unsigned short, a3);
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        uint4 v4;
+        v4.x = pc[q][0] | ((unsigned)pc[q][1] << 16);
+        v4.y = pc[q][2] | ((unsigned)pc[q][3] << 16);
+        v4.z = pc[q][4] | ((unsigned)pc[q][5] << 16);
+        v4.w = pc[q][6] | ((unsigned)pc[q][7] << 16);
+        out[((s * 3 + q) * 4 + g) * 64 + co] = v4;
+    }
+}
+
 // packed image: [cout tile][step][piece 3][k group 4][CT][8] of bf16; group g of step s = unit u = 2s + (g >> 1) =
 // (chunk u / 9, tap u % 9), k half g & 1: element j = w[co][chunk*16 + (g&1)*8 + j][tap] (0 beyond Cout / Cin / the last unit)
 // F16: piece 0 holds the fp16 weights, pieces 1 and 2 are zero (the same image size and layout)
@@ -823,6 +1034,7 @@ extern "C" int cwfa_conv3x3_split_f32(const float* x, const void* w_packed, floa
 // ------------------------------------------------------------------------------------------------ 7x7 (ConvNeXt, networks.py:488)
 extern "C" int64_t cwfa_conv7x7_split_packed_bytes(int Cout, int Cin) {
     if (Cout <= 0 || Cout > 64 || Cin <= 0) return -1;
+    if (Cin <= 8) return (int64_t)few::NSTEP * few::WSL;          // the few-channel form: 13 slices of four (8-channel, tap) units
     return (int64_t)nsteps_of(Cin, 49) * 3 * 4 * 64 * 16;
 }
 
@@ -830,7 +1042,15 @@ extern "C" int cwfa_conv7x7_split_pack_f32(const float* w, void* packed, int Cou
     CWFA_REQUIRE(w && packed, CWFA_E_INVAL, "cwfa_conv7x7_split_pack_f32: null pointer");
     CWFA_REQUIRE(Cout > 0 && Cout <= 64 && Cin > 0, CWFA_E_SHAPE, "cwfa_conv7x7_split_pack_f32: 1 <= Cout <= 64");
     CWFA_REQUIRE(cwfa_aligned16(packed), CWFA_E_ALIGN, "cwfa_conv7x7_split_pack_f32: packed image must be 16-byte aligned");
-    pack_bank(w, packed, Cout, Cin, 64, 49, (hipStream_t)stream);
+    if (Cin <= 8) {
+        cwfa_with_operand([&](auto, auto f16) -> int {
+            hipLaunchKernelGGL((split7x7_few_pack_kernel<f16>), dim3((few::NSTEP * 4 * 64 + 255) / 256), dim3(256), 0, (hipStream_t)stream, w,
+                               reinterpret_cast<uint4*>(packed), Cout, Cin);
+            return CWFA_OK;
+        });
+    } else {
+        pack_bank(w, packed, Cout, Cin, 64, 49, (hipStream_t)stream);
+    }
     CWFA_LAUNCH_CHECK("cwfa_conv7x7_split_pack_f32");
     return CWFA_OK;
 }
@@ -850,12 +1070,27 @@ extern "C" int cwfa_conv7x7_split_f32(const float* x, const void* w_packed, floa
                  CWFA_E_INVAL, "cwfa_conv7x7_split_f32: bias-only epilogue, no load-side prologue, NCHW maps");
     p.nchunks = (Cin + 15) / 16;
     p.nsteps = nsteps_of(Cin, 49);
-    p.nrun = p.nsteps;
+    // a single 16-channel chunk (9 .. 16 inputs): the odd chunk of the one period is all zeros (zero-filled in steps 0 .. 2, zero weights) and
+    // the steps that pair ONLY its taps add nothing -- taps (0,1) .. (46,47), then tap 48 with the odd buffer's tap 0: 25 steps of the 49
+    p.nrun = p.nchunks == 1 ? 25 : p.nsteps;
     p.tiles_x = (W + TC - 1) / TC;
     CWFA_REQUIRE((int64_t)(Cin + 64) * H * W * 4 < (1ll << 31) && (int64_t)(Cout + 64) * H * W * 4 < (1ll << 31), CWFA_E_SHAPE,
                  "cwfa_conv7x7_split_f32: one sample's input / output must stay below 2 GiB");
     CWFA_REQUIRE((int64_t)p.tiles_x * ((H + TR - 1) / TR) < (1ll << 31) && B <= 65535, CWFA_E_SHAPE, "cwfa_conv7x7_split_f32: grid too large");
     hipStream_t st = (hipStream_t)stream;
+    if (Cin <= 8) {                        // the few-channel form: 13 steps of four (8-channel, tap) units
+        p.ntiles = p.tiles_x * ((H + TR - 1) / TR);
+        p.ctiles = 1;
+        p.xcd_map = g_cwfa_split_xcd_map;
+        return cwfa_with_operand([&](auto six, auto f16) -> int {
+            constexpr auto kern = &conv7x7_few_split_kernel<six, f16>;
+            const int rc = cwfa_max_lds<kern>(few::LDS, "cwfa_conv7x7_split_f32");
+            if (rc) return rc;
+            hipLaunchKernelGGL(kern, dim3((unsigned)p.ntiles, 1, B), dim3(512), few::LDS, st, p);
+            CWFA_LAUNCH_CHECK("cwfa_conv7x7_split_f32");
+            return CWFA_OK;
+        });
+    }
     // (2 m-tiles per wave x 2 channel groups: a B fragment feeds two m-tiles -- 18 instead of 27 ds_read_b128 per 48 MFMAs)
     return launch<2, false, CWFA_ACT_NONE, 7, 4, 2>(p, st);
 }

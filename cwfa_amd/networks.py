@@ -554,12 +554,25 @@ class ConvNeXt(nn.Module):
         self.m = nn.Sequential(nn.Conv2d(c_out, c_out, 7, 1, 3), nn.LayerNorm([c_out, size, size]),
                                nn.Conv2d(c_out, c_out, 1, 1), nn.GELU())
         self._packed = _Packed()
+        self._composed_bank = None
+
+    def _composed(self):
+        srcs = [self.input.weight, self.input.bias, self.m[0].weight]
+        key = tuple((t._version, t.data_ptr()) for t in srcs) + (ops.pack_epoch(),)
+        hit = self._composed_bank
+        if hit is None or hit[0] != key:
+            hit = self._composed_bank = (key, ops.pack_convnext_composed(*srcs))
+        return hit[1]
 
     @amp_entry
     def forward(self, input):
         P = self._packed.get
-        u = ops.conv2d(input, P(self.input), bias=self.input.bias)
-        v = ops.conv2d(u, P(self.m[0]), bias=self.m[0].bias)
+        u = ops.conv2d(input, P(self.input), bias=self.input.bias)     # (the residual; memory-bound either way)
+        if ops.convnext_composed(self.input.in_channels, self.m[0].out_channels, self.input.bias is not None and self.m[0].bias is not None):
+            # the 7x7 over the block's few inputs and a ones channel instead of over the c_out-channel map u (K = 49 x 8 or 16, not 49 x c_out)
+            v = ops.conv2d(ops.with_ones(input), self._composed(), bias=self.m[0].bias)
+        else:
+            v = ops.conv2d(u, P(self.m[0]), bias=self.m[0].bias)
         ln = self.m[1]
         if tuple(v.shape[1:]) != tuple(ln.normalized_shape):
             raise RuntimeError(f"Given normalized_shape={list(ln.normalized_shape)}, expected input with shape "

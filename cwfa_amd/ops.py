@@ -712,6 +712,36 @@ def pack_first_layer_weight(w0, b0, w3, w1, short=None):
     return pc
 
 
+CONVNEXT_COMPOSED = True      # (tuning / ablation) False: the 7x7 of a ConvNeXt block reads the 64-channel map of the 1x1 in front (K = 49 x 64)
+
+
+def convnext_composed(c_in, c_out, biases=True):
+    """True when a ConvNeXt block's 1x1 (c_in -> c_out) and 7x7 run as ONE composed few-channel 7x7 (pack_convnext_composed) in the
+    active precision mode: split / bf16 / fp16, at most 16 inputs with the ones channel, at most 64 outputs, both biases present."""
+    return bool(CONVNEXT_COMPOSED and SPLIT_7X7 and _split_bf16 >= 2 and c_in + 1 <= 16 and c_out <= 64 and biases)
+
+
+def pack_convnext_composed(w0, b0, w7):
+    """The composed bank of a ConvNeXt block's 7x7: conv7x7(conv1x1(x, w0) + b0, w7) = conv7x7(x | 1, wc) with wc[o][i][tap] =
+    sum_m w7[o][m][tap] [w0 | b0][m][i] (formed in float64, rounded once; exact with zero padding: the padded ones channel carries no
+    bias), zero-padded to 8 or 16 input channels for the few-channel forms of the split 7x7 kernel.  w0 [c,cin,1,1] with cin <= 15,
+    b0 [c], w7 [cout <= 64,c,7,7].  The bank is launched on with_ones(x): ``cin`` + 1 channels."""
+    L = _lib.lib()
+    w0, b0, w7 = _dev(w0, "w0").detach(), _dev(b0, "b0").detach(), _dev(w7, "w7").detach()
+    c, cin = w0.shape[0], w0.shape[1]
+    cout = w7.shape[0]
+    if tuple(w0.shape) != (c, cin, 1, 1) or cin + 1 > 16 or tuple(w7.shape) != (cout, c, 7, 7) or cout > 64 or tuple(b0.shape) != (c,):
+        raise ValueError("pack_convnext_composed: a 1x1 bank with <= 15 inputs and a bias in front of a 7x7 bank with <= 64 outputs only")
+    w0p = torch.cat([w0.reshape(c, cin).double(), b0.double().reshape(c, 1)], 1)
+    wc = torch.einsum("omt,mi->oit", w7.double().reshape(cout, c, 49), w0p)
+    cpad = 8 if cin + 1 <= 8 else 16
+    w7c = torch.zeros((cout, cpad, 7, 7), dtype=torch.float32, device=w0.device)
+    w7c[:, :cin + 1] = wc.reshape(cout, cin + 1, 7, 7).to(torch.float32)
+    packed = torch.empty(L.cwfa_conv7x7_split_packed_bytes(cout, cpad), dtype=torch.uint8, device=w0.device)
+    check(L.cwfa_conv7x7_split_pack_f32(_p(w7c), _p(packed), cout, cpad, _stream()), "conv7x7_split_pack (composed bank)")
+    return PackedConv(packed, cout, cin + 1, 7, False, w7._version, w7.data_ptr(), split=True)
+
+
 def subnet_layer_first(u1, x, pc, b3, b1, layout=0):
     """y = ELU(conv1x1(ELU(conv3x3'(u1) + b3)) + b1 + x): the first layer of a sub-network with its 3x3 composed with the 1x1 in
     front (pack_first_layer_weight).  ``u1``: the sub-network's input plus a constant-one channel [B, cin + 1 <= 32, H, W];

@@ -334,7 +334,13 @@ int cwfa_conv3x3_split_f32(const float* x, const void* w_packed, float* y, int B
 int cwfa_conv_split_f32(const void* ws, const void* w_packed, float* y, int B, int Cin, int H, int W, int Cout, int ks, int64_t y_bs,
                            const cwfa_conv_opts* opts, void* stream);
 /* 7x7 (stride 1, zero padding 3; nn.Conv2d(C, C, 7, 1, 3) of the ConvNeXt block, networks.py:488) in the same arithmetic on the same
- * kernel: 3-pixel halo, 49 taps, a 49-step period over two 16-channel chunks.  Cout <= 64; epilogue: bias only; no in_* prologue. */
+ * kernel: 3-pixel halo, 49 taps, a 49-step period over two 16-channel chunks.  Cout <= 64; epilogue: bias only; no in_* prologue.
+ * Few input channels (the ConvNeXt 1x1 + 7x7 composed into one 7x7 over the block's inputs and a ones channel) take shorter forms;
+ * the three entry points agree on them by Cin alone:
+ *   Cin <= 8:        a kernel of its own whose K = 32 step is four (8-channel, tap) units: 13 steps, image of 13 slices
+ *                    [step][piece 3][k group 4][64][8] (group g of step s = tap 4 s + g); the input tile is staged once per block;
+ *   9 <= Cin <= 16:  the kernel and image of Cin >= 17 (49 slices), of which only the 25 steps that touch the one chunk are run.
+ * A bank packed for Cin' inputs may be launched with any Cin that selects the same form (channels >= Cin read as 0.0). */
 int64_t cwfa_conv7x7_split_packed_bytes(int Cout, int Cin);
 int cwfa_conv7x7_split_pack_f32(const float* w, void* packed, int Cout, int Cin, void* stream);
 int cwfa_conv7x7_split_f32(const float* x, const void* w_packed, float* y, int B, int Cin, int H, int W, int Cout,
