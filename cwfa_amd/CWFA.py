@@ -19,7 +19,7 @@ __all__ = ["sample_z_truncated", "check_empty_depths", "evaluate_INN_forward", "
            "nll_terms", "allreduce_nll", "build_networks", "step_log_likelihoods", "allgather_scores", "detect_ood",
            "forward_nll_pass", "mean_volume_cache", "save_mean_volume_cache", "load_mean_volume_cache",
            "denormalise_prediction", "denormalise_ground_truth", "compute_INN_step_performance", "evaluate_step", "roi_boxes",
-           "corr_coeff_3D"]
+           "corr_coeff_3D", "truncated_normal_variance", "posterior_moments", "posterior_samples"]
 
 
 def _no_grad_trunc_normal_(tensor, mean=0., std=1., a=-1., b=1.):
@@ -203,6 +203,137 @@ def _inverse_steps(conv_inn, cond_nets, cond_input, mean_vols_cache, up, vols, t
             up = acc
         vols.append(up)
     return vols if keep_all else up
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The posterior of a CAT pyramid.  In a ConditionalAffineTransform step every s,t depends on the
+# conditions (the views and the mean-volume cache) only, so given the views the whole pyramid is an AFFINE map of the
+# latents: its mean is the temperature-0 reconstruction, its per-voxel variance has a closed form in the s rows, and N
+# samples need every network once.
+# ---------------------------------------------------------------------------------------------------------------------
+def truncated_normal_variance(temperature):
+    """Variance of the latent ``sample_z_truncated`` draws: a STANDARD normal truncated to [-T, T] (T is the truncation
+    bound, not a standard deviation; CWFA.py:47-64).  z_var(T) = 1 - 2 T phi(T) / (2 Phi(T) - 1); z_var(0) = 0,
+    z_var(1) = 0.2911..., z_var(inf) = 1.  float64 on the host.  The closed form cancels for small T (z_var -> T^2/3); below
+    T = 0.5 the quotient is evaluated as a ratio of two series in T^2, which keeps the relative error near 1e-15."""
+    T = float(temperature)
+    if not T >= 0.0:
+        raise ValueError(f"temperature {temperature!r}: the truncation bound must be >= 0")
+    if T == 0.0:
+        return 0.0
+    if math.isinf(T):
+        return 1.0
+    if T < 0.5:
+        # with u = T^2/2:  2 Phi(T) - 1 = 2 T phi(T) * sum_n T^(2n) / (2n+1)!!  =: 2 T phi(T) * (1 + A), so that
+        # z_var = A / (1 + A):  no cancellation, every term positive
+        A, term, n = 0.0, 1.0, 0
+        while True:
+            n += 1
+            term *= T * T / (2 * n + 1)
+            A += term
+            if term <= 1e-18 * A:
+                break
+        return A / (1.0 + A)
+    phi = math.exp(-0.5 * T * T) / math.sqrt(2.0 * math.pi)
+    return 1.0 - 2.0 * T * phi / math.erf(T / math.sqrt(2.0))
+
+
+def _affine_plans(conv_inn, what):
+    """The CAT plans of a pyramid, or NotImplementedError where a step is not an affine map of its latent."""
+    from .FrEIA.framework import _CatStepPlan
+    plans = []
+    for n, g in enumerate(conv_inn):
+        plan = getattr(g, "_plan", None)
+        if plan is None:
+            raise NotImplementedError(f"{what}: step {n} has no fused CAT plan (its graph is not the conditional wavelet-flow step)")
+        if type(plan) is not _CatStepPlan:
+            raise NotImplementedError(f"{what}: step {n} has data-dependent coupling blocks (GLOW / RNVP / GIN / AllInOne): its output "
+                                      "is not affine in z, so there is no closed-form posterior and no shared coefficients")
+        if plan.needs_walk():
+            raise NotImplementedError(f"{what}: step {n} holds an ActNorm that still has to initialise itself from its first batch")
+        plans.append(plan)
+    return plans
+
+
+def _coarsest(conv_inn, cond_nets, cond_input, mean_vols_cache, low):
+    S1 = len(conv_inn)
+    return cond_nets[S1](cond_input, mean_vols_cache[S1 - 1])[-1] if low is None else low
+
+
+@amp_function
+@torch.no_grad()          # inference only: the plans' stage lists are built without a tape
+def posterior_moments(conv_inn, cond_nets, cond_input, mean_vols_cache, low=None, temperature=1.0, std_scale=1.0,
+                      keep_all=False):
+    """(mean, std) per voxel of the volumes ``inverse_pass`` would reconstruct with latents drawn at ``temperature`` (every
+    step all-CAT; NotImplementedError otherwise).  The loop of ``inverse_pass``: per step the sub-networks run once, one
+    ``ops.chain_inv`` with z = None gives the mean -- the launches of ``inverse_pass(..., temperature=0)``, so bit-identical
+    to it: the truncated normal is symmetric -- and one ``ops.chain_inv_var`` carries the variance down:
+    var_x[2c] = var_x[2c+1] = (var_low[c] + z_var * exp(-2 * sum of s along the voxel's path)) / 2, with var_low = 0 behind
+    the (deterministic) LRNN or a given ``low``.  The shifts never enter; ``low`` and the detail band are independent because
+    the latents of different steps are drawn independently.
+
+    ``std_scale`` multiplies the finest level's std in its own launch.  For the de-normalised volume of CWFA.py:1041
+    (``denormalise_prediction``: volume * std_vols * 2**len(batch)) pass ``std_scale = std_vols * 2**len(batch)``.
+    With ``keep_all`` both results are lists, coarse -> fine; the stds of the levels below the finest are unscaled (and the
+    coarsest level's std is zero)."""
+    plans = _affine_plans(conv_inn, "posterior_moments")
+    if not float(std_scale) > 0.0:
+        raise ValueError(f"std_scale {std_scale!r} must be > 0")
+    z_var = truncated_normal_variance(temperature)
+    S1 = len(conv_inn)
+    up = _coarsest(conv_inn, cond_nets, cond_input, mean_vols_cache, low)
+    var = None                                       # None = 0: the coarsest volume is deterministic
+    means, stds = [up], [torch.zeros_like(up)] if keep_all else None
+    from .networks import omega_first_scope
+    with omega_first_scope(list(cond_nets[:S1]), cond_input):
+        for n in range(S1 - 1, -1, -1):
+            c = [cond_nets[n](cond_input)[-1], mean_vols_cache[n]]
+            stages, tabs = plans[n].inverse_stages(c, tuple(up.shape[1:]), up.device)
+            shape = tuple(up.shape)
+            up = ops.chain_inv(None, up, stages, tables=tabs)
+            last = n == 0                            # the finest level: the launch returns std_scale * sqrt(variance)
+            var = ops.chain_inv_var(var, stages, z_var, shape=shape, std_scale=float(std_scale) if last else 0.0, tables=tabs)
+            if keep_all:
+                stds.append(var if last else var.sqrt())
+            means.append(up)
+    return (means, stds) if keep_all else (up, var)
+
+
+@amp_function
+@torch.no_grad()
+def posterior_samples(conv_inn, cond_nets, cond_input, mean_vols_cache, n_samples, low=None, temperature=1.0,
+                      return_z=False):
+    """``n_samples`` genuine posterior samples [n_samples, B, D, H, W] of the reconstruction (every step all-CAT;
+    NotImplementedError otherwise).  Every condition net and every sub-network runs ONCE per step; per sample only the
+    latent draw (``sample_z_truncated``) and one ``ops.chain_inv`` follow.  Each sample carries its own coarser volume down
+    the pyramid and nothing is averaged between the steps -- unlike ``inverse_pass(n_samples=...)``, which repeats the
+    conditions, runs every network per sample and averages after every step (CWFA.py:913-914).  ``temperature = 0`` yields
+    ``n_samples`` copies of the mean.  With ``return_z`` also the latents: a list over the steps in execution order (coarse
+    -> fine) of [n_samples, B, C_n, H, W] tensors (None per step at temperature 0)."""
+    plans = _affine_plans(conv_inn, "posterior_samples")
+    n_samples = int(n_samples)
+    if n_samples < 1:
+        raise ValueError("posterior_samples: n_samples must be >= 1")
+    if not float(temperature) >= 0.0:
+        raise ValueError(f"temperature {temperature!r}: the truncation bound must be >= 0")
+    S1 = len(conv_inn)
+    ups = [_coarsest(conv_inn, cond_nets, cond_input, mean_vols_cache, low)] * n_samples
+    latents = []
+    from .networks import omega_first_scope
+    with omega_first_scope(list(cond_nets[:S1]), cond_input):
+        for n in range(S1 - 1, -1, -1):
+            c = [cond_nets[n](cond_input)[-1], mean_vols_cache[n]]
+            stages, tabs = plans[n].inverse_stages(c, tuple(ups[0].shape[1:]), ups[0].device)
+            if temperature == 0:
+                zs = None                             # z == 0: the chain never reads it; every sample is the mean
+                out = ops.chain_inv(None, ups[0], stages, tables=tabs)
+                ups = [out] * n_samples
+            else:
+                zs = torch.stack([sample_z_truncated(ups[0], device=ups[0].device, temperature=temperature) for _ in range(n_samples)])
+                ups = [ops.chain_inv(zs[i], ups[i], stages, tables=tabs) for i in range(n_samples)]
+            latents.append(zs)
+    out = torch.stack(ups)
+    return (out, latents) if return_z else out
 
 
 def nll_step(graph, x, c, group=None):

@@ -438,26 +438,45 @@ class _CatStepPlan:
         xhat, ld = AG.chain_inv(z, low, rstages, rtabs, fstages, final_perm, coef_of(fstages))
         return (xhat if not g.force_tuple_output else (xhat,)), ld
 
-    def run(self, x_or_z, c, rev, sumsq=None, jac=True):
-        """``jac=False`` skips the log-det reduction (the reconstruction loop discards it, CWFA.py:912) and returns
-        ``None`` in its place."""
-        g = self.graph
-        cond_of = dict(zip(g.condition_nodes, c))
+    def _evaluated_stages(self, c, rev):
+        """``_stages`` with every block's sub-network evaluated on the conditions ``c`` (inference: no tape)."""
+        cond_of = dict(zip(self.graph.condition_nodes, c))
         from ...networks import merged_first_maps
         jobs = [(n.module.subnet, [cond_of[cn] for cn in n.conditions]) for k, n in self.chain if k == "cat"]
         # the blocks' sub-networks share their condition: its ones channel is built once, their first 1x1 maps in one launch
         with ops.ones_channel_scope(), ops.first_map_scope(merged_first_maps(jobs)):
-            stages, pending = self._stages(cond_of, rev)
+            return self._stages(cond_of, rev)
+
+    def inverse_stages(self, c, shape=None, device=None):
+        """(stages, tables) of the inverse direction for the conditions ``c``: every sub-network runs once, and the result serves
+        any number of launches over the same conditions (``ops.chain_inv`` with different latents, ``ops.chain_inv_var``) --
+        the step is an affine map of z whose coefficients depend on the conditions only.  ``shape`` = (C, H, W) of the low band
+        and ``device`` default to the graph's own output shape and the conditions' device.  A plain CAT plan only: the mixed
+        plan's blocks read the data."""
+        if type(self) is not _CatStepPlan:
+            raise NotImplementedError(f"inverse_stages: {type(self).__name__} has data-dependent blocks; the step is not affine in z")
+        if shape is None:
+            shape = tuple(int(v) for v in self.graph.global_out_shapes[self.low_out_idx])
+        if device is None:
+            device = c[0].device
+        stages, pending = self._evaluated_stages(c, True)
+        if pending is not None:
+            stages.append(ops.stage(None, None, perm=pending[0], axis=pending[1]))
+        return stages, self._composed(True, self._perms_of(stages), None, tuple(shape), device)
+
+    def run(self, x_or_z, c, rev, sumsq=None, jac=True):
+        """``jac=False`` skips the log-det reduction (the reconstruction loop discards it, CWFA.py:912) and returns
+        ``None`` in its place."""
+        g = self.graph
         first = next(t for t in x_or_z if t is not None)
         acc = torch.zeros(first.shape[0], dtype=torch.float64, device=first.device) if jac else None
         if rev:
             z, low = x_or_z[self.flow_out_idx], x_or_z[self.low_out_idx]
-            if pending is not None:
-                stages.append(ops.stage(None, None, perm=pending[0], axis=pending[1]))
-            tabs = self._composed(True, self._perms_of(stages), None, tuple(low.shape[1:]), low.device)
+            stages, tabs = self.inverse_stages(c, tuple(low.shape[1:]), low.device)
             out = ops.chain_inv(z, low, stages, logdet=acc, tables=tabs)
             res = out if not g.force_tuple_output else (out,)
             return res, (acc.to(torch.float32) if jac else None)
+        stages, pending = self._evaluated_stages(c, False)
         final_perm = None
         if pending is not None:
             if pending[1] == 1:

@@ -3,6 +3,7 @@
 // reference ((a+b)*f, exp(s)*x+t, (x-t)*exp(-s)) round exactly like the reference's separate torch ops.
 #include "common.h"
 
+#include <cmath>
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -864,6 +865,117 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_rows4_kernel(const float*
     }
 }
 
+// ---- per-voxel variance of the inverse chain's output (cwfa_chain_inv_var_f32).  Every s,t of a CAT step depends on the conditions
+// only, so x is an affine map of z whose matrix has ONE entry per row: x[2c], x[2c+1] = (low[c] +- v[c]) / sqrt 2 with
+// v[p] = z[start(p)] * exp(-sum_k s_k[path_k(p)]) + (terms in t).  For independent z of variance z_var the variance of v[p] is
+// z_var * exp(a[p]) with the travelling sum  a <- gather_k(a) - 2 s_k  (a = 0 at the start): the walk of the inverse chain with the
+// s rows alone.  The host entry hands the kernels a chain whose t pointers are NULL, so stage_st / stage_st4 never read a shift.
+__device__ __forceinline__ float chain_var_out(float var_low, float a, float z_var, float std_scale) {
+    const float vv = z_var == 0.f ? 0.f : z_var * expf(a);        // one exp per voxel: the precise one (|a| reaches 2 * stages * clamp)
+    const float var = (var_low + vv) * 0.5f;
+    return std_scale > 0.f ? std_scale * sqrtf(var) : var;
+}
+
+// general form: one thread owns one final position and walks the gathers (any shape, any alignment)
+__global__ __launch_bounds__(256) void chain_inv_var_kernel(const float* __restrict__ var_low, float* __restrict__ out, cwfa_chain ch,
+                                                            float z_var, float std_scale, int C, int H, int W, int64_t vl_bs,
+                                                            int64_t out_bs) {
+    const int64_t HW = (int64_t)H * W, n = (int64_t)C * HW;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    if (i >= n) return;
+    Pos p{(int)(i / HW), (int)((i / W) % H), (int)(i % W)};
+    int64_t off[CWFA_CHAIN_MAX];
+#pragma unroll
+    for (int k = CWFA_CHAIN_MAX - 1; k >= 0; --k) {
+        if (k < ch.n_stages) {
+            off[k] = lin(p, H, W);
+            p = gather_pos(p, ch.stage[k].perm, ch.stage[k].perm_axis);
+        }
+    }
+    float a = 0.f;
+#pragma unroll
+    for (int k = 0; k < CWFA_CHAIN_MAX; ++k) {
+        if (k < ch.n_stages) {
+            float s, t;
+            stage_st(ch.stage[k], b, off[k], s, t);
+            a = a - 2.f * s;
+        }
+    }
+    const int c = (int)(i / HW);
+    const int64_t pix = i - (int64_t)c * HW;
+    const float o = chain_var_out(var_low ? var_low[b * vl_bs + i] : 0.f, a, z_var, std_scale);
+    out[b * out_bs + (int64_t)(2 * c) * HW + pix] = o;
+    out[b * out_bs + (int64_t)(2 * c + 1) * HW + pix] = o;
+}
+
+// 16-byte form, under the conditions of chain_rows4_ok and laid out as chain_rows4_kernel: a thread owns four columns of one row, all
+// its s rows (and var_low) are in flight before the first use as non-temporal loads, s is read at the thread's own columns, and a
+// column permutation moves the travelling SUM between the threads of a row through the double-buffered LDS exchange.
+template <int NS>
+__global__ __launch_bounds__(CHAIN_THREADS) void chain_var_rows4_kernel(const float* __restrict__ var_low, float* __restrict__ out, cwfa_chain ch,
+                                                                        float z_var, float std_scale, int C, int H, int W, int64_t vl_bs,
+                                                                        int64_t out_bs) {
+    extern __shared__ float rows[];          // [2][row of the block][W]: exchange buffers of the travelling sums (column gathers)
+    const int tpr = W >> 2, RB = CHAIN_THREADS / tpr;
+    const int r = threadIdx.x / tpr, w4 = (threadIdx.x - r * tpr) * 4;
+    const int b = blockIdx.z, c = blockIdx.y, hh = blockIdx.x * RB + r;
+    const bool live = hh < H;
+    const int h = live ? hh : H - 1;         // rows beyond H in the last block: load row H - 1 (in bounds), take part in the barriers, store nothing
+    const int64_t HW = (int64_t)H * W;
+    const int n = ch.n_stages;
+    RowPos q[NS];
+    if (ch.src_c) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k)
+            if (k < n) q[k] = RowPos{ch.src_c[k * C + c], ch.src_h[k * H + h]};
+    } else {
+        RowPos src = RowPos{c, h};
+#pragma unroll
+        for (int k = NS - 1; k >= 0; --k)
+            if (k < n) {
+                q[k] = src;
+                src = row_gather(src, ch.stage[k].perm, ch.stage[k].perm_axis);
+            }
+    }
+    f32x4 sr[NS];
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        sr[k] = zero;
+        if (k < n && ch.stage[k].s_raw)
+            sr[k] = ld_stream(ch.stage[k].s_raw + b * ch.stage[k].s_bs + ((int64_t)q[k].c * H + q[k].h) * W + w4);
+    }
+    const int64_t oo = (int64_t)h * W + w4;
+    const f32x4 lo = var_low ? ld_stream(var_low + b * vl_bs + (int64_t)c * HW + oo) : zero;
+    f32x4 a = zero;
+    int nx = 0;
+#pragma unroll
+    for (int k = 0; k < NS; ++k)
+        if (k < n) {
+            if (ch.stage[k].perm && ch.stage[k].perm_axis == 3) {           // uniform over the block
+                float* buf = rows + (size_t)((nx & 1) * RB + r) * W;
+                ++nx;
+                *reinterpret_cast<f32x4*>(buf + w4) = a;
+                __syncthreads();
+                const int64_t* pk = ch.stage[k].perm + w4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a[j] = buf[(int)pk[j]];
+            }
+            f32x4 sv, tv;
+            stage_st4(ch.stage[k], sr[k], zero, sv, tv);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] = a[j] - 2.f * sv[j];
+        }
+    if (live) {
+        f32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = chain_var_out(lo[j], a[j], z_var, std_scale);
+        st_stream<true>(out + b * out_bs + (int64_t)(2 * c) * HW + oo, o);
+        st_stream<true>(out + b * out_bs + (int64_t)(2 * c + 1) * HW + oo, o);
+    }
+}
+
 // rows variant usable?  (LDS budget, grid limits)
 // Backward of  L = gscale * 0.5 * sum z^2  -  ldscale * sum_b logdet_b  (CWFA.py:970-978: gscale = 1/numel,
 // ldscale = 1/(B*numel)) through a whole forward chain in ONE launch and without stored activations: the flow is
@@ -1064,6 +1176,42 @@ extern "C" int cwfa_chain_inv_f32(const float* z, const float* low, float* x, co
     hipLaunchKernelGGL(chain_inv_kernel, grid, dim3(256), 0, (hipStream_t)stream, z, low, x, *ch, C, H, W, z_bs, low_bs, x_bs,
                        logdet);
     CWFA_LAUNCH_CHECK("cwfa_chain_inv_f32");
+    return CWFA_OK;
+}
+
+extern "C" int cwfa_chain_inv_var_f32(const float* var_low, float* out, const cwfa_chain* ch, float z_var, float std_scale, int B,
+                                      int C, int H, int W, int64_t var_low_bs, int64_t out_bs, void* stream) {
+    CWFA_REQUIRE(out, CWFA_E_INVAL, "cwfa_chain_inv_var_f32: null pointer");
+    CWFA_REQUIRE(B >= 0 && C >= 0 && H >= 0 && W >= 0 && B <= 65535, CWFA_E_SHAPE, "cwfa_chain_inv_var_f32: bad shape");
+    int rc = check_chain("cwfa_chain_inv_var_f32", ch);
+    if (rc) return rc;
+    CWFA_REQUIRE(std::isfinite(z_var) && z_var >= 0.f, CWFA_E_INVAL, "cwfa_chain_inv_var_f32: z_var %g is not a finite variance", (double)z_var);
+    CWFA_REQUIRE(std::isfinite(std_scale) && std_scale >= 0.f, CWFA_E_INVAL, "cwfa_chain_inv_var_f32: std_scale %g (0 = variance, > 0 = scaled std)",
+                 (double)std_scale);
+    const int64_t n = (int64_t)C * H * W;
+    if (B == 0 || n == 0) return CWFA_OK;
+    cwfa_chain sc = *ch;                      // the variance does not depend on the shifts: the kernels get no t pointer to read
+    for (int k = 0; k < sc.n_stages; ++k) {
+        sc.stage[k].t = nullptr;
+        sc.stage[k].t_bs = 0;
+    }
+    size_t lds;
+    if (chain_rows4_ok(&sc, C, H, W, B, &lds, var_low, out, nullptr, var_low ? var_low_bs : 0, out_bs, 0)) {
+        const int RB = CHAIN_THREADS * 4 / W;
+        const dim3 grid((H + RB - 1) / RB, C, B);
+        if (sc.n_stages <= 6)
+            hipLaunchKernelGGL((chain_var_rows4_kernel<6>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, var_low, out, sc, z_var, std_scale,
+                               C, H, W, var_low_bs, out_bs);
+        else
+            hipLaunchKernelGGL((chain_var_rows4_kernel<CWFA_CHAIN_MAX>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, var_low, out, sc, z_var,
+                               std_scale, C, H, W, var_low_bs, out_bs);
+        CWFA_LAUNCH_CHECK("cwfa_chain_inv_var_f32");
+        return CWFA_OK;
+    }
+    dim3 grid((unsigned)((n + 255) / 256), B);
+    hipLaunchKernelGGL(chain_inv_var_kernel, grid, dim3(256), 0, (hipStream_t)stream, var_low, out, sc, z_var, std_scale, C, H, W, var_low_bs,
+                       out_bs);
+    CWFA_LAUNCH_CHECK("cwfa_chain_inv_var_f32");
     return CWFA_OK;
 }
 

@@ -8,7 +8,7 @@ import torch
 from . import _lib
 from ._lib import AffineStage, Chain, ConvOpts, check
 
-__all__ = ["haar1d", "haar2d", "gather", "affine", "channel_affine", "chain_inv", "chain_fwd", "pack_conv_weight",
+__all__ = ["haar1d", "haar2d", "gather", "affine", "channel_affine", "chain_inv", "chain_inv_var", "chain_fwd", "pack_conv_weight",
            "conv2d", "conv2d_wgrad", "elu_bwd", "set_precision", "gelu_add", "gelu_bwd", "layernorm_bwd", "attention_bwd", "plane_affine", "bn_bwd_stats", "bn_act_bwd", "maxpool2_bwd", "chain_bwd", "chain_inv_bwd", "prelu_bwd", "conv3d_1k1_backward", "pack_1x1_panel", "pack_split_layer_weight", "subnet_layer", "conv3d_1k1", "channel_stats", "bn_fold", "bn_running_update", "maxpool", "sample_stats", "layernorm_apply",
            "attention_combine", "scale_channels", "axpby", "stage", "lion_step", "global_extrema", "wmse_loss"]
 
@@ -272,6 +272,32 @@ def chain_inv(z, low, stages, logdet=None, tables=None):
     if rec is not None:
         e1.record()
         rec.append(("inv", B, Cc, H, W, len(stages), z is not None, e0, e1))
+    return out
+
+
+def chain_inv_var(var_low, stages, z_var, shape=None, std_scale=0.0, tables=None):
+    """Per-voxel variance [B,2C,H,W] of ``chain_inv(z, low, stages)`` for independent latents of variance ``z_var`` and an
+    independent per-voxel variance ``var_low`` [B,C,H,W] of ``low`` (None = 0: then ``shape = (B, C, H, W)`` is needed and the
+    device is that of the stages' tensors).  The shifts of the stages are never read.  ``std_scale`` > 0 returns
+    ``std_scale * sqrt(variance)`` instead (see cwfa_chain_inv_var_f32).  ``tables`` as for ``chain_inv``."""
+    L = _lib.lib()
+    if var_low is not None:
+        var_low, vbs = planes(var_low, "var_low")
+        if shape is not None and tuple(shape) != tuple(var_low.shape):
+            raise ValueError(f"var_low {tuple(var_low.shape)} and shape {tuple(shape)} differ")
+        shape, dev = tuple(var_low.shape), var_low.device
+    else:
+        if shape is None or len(shape) != 4:
+            raise ValueError("chain_inv_var: without var_low the shape (B, C, H, W) must be given")
+        vbs = 0
+        dev = next((t.device for _, kp in stages for t in kp), None) if tables is None else tables[0].device
+        if dev is None:                     # a chain without a single tensor: the current device
+            dev = torch.device("cuda", torch.cuda.current_device())
+    B, Cc, H, W = (int(v) for v in shape)
+    ch, keep = _chain(stages, tables)
+    out = torch.empty((B, 2 * Cc, H, W), dtype=torch.float32, device=dev)
+    check(L.cwfa_chain_inv_var_f32(_p(var_low), _p(out), C.byref(ch), float(z_var), float(std_scale), B, Cc, H, W, vbs,
+                                   2 * Cc * H * W, _stream()), "chain_inv_var")
     return out
 
 

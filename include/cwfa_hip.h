@@ -175,6 +175,16 @@ typedef struct {
 int cwfa_chain_inv_f32(const float* z, const float* low, float* x, const cwfa_chain* ch, int B, int C, int H, int W,
                        int64_t z_bs, int64_t low_bs, int64_t x_bs, double* logdet, void* stream);
 
+/* Per-voxel variance of x = cwfa_chain_inv_f32(z, low, ...) when the elements of z are independent with variance z_var
+ * and low carries an independent per-voxel variance var_low [B,C,H,W] (NULL = 0).  `ch` as for cwfa_chain_inv_f32
+ * (execution order of the inverse; src_c / src_h honoured); t is never read.
+ *   a = 0;  for each stage: a <- gather_k(a) - 2*s_k;   var_v = z_var * exp(a)
+ *   out[2c] = out[2c+1] = (var_low[c] + var_v[c]) * 0.5            out [B,2C,H,W]
+ * std_scale == 0: out is the variance;  std_scale > 0: out = std_scale * sqrt(variance)  (the last step of a pyramid).
+ * z_var and std_scale must be finite and >= 0.  z_var == 0 gives exactly var_low * 0.5. */
+int cwfa_chain_inv_var_f32(const float* var_low, float* out, const cwfa_chain* ch, float z_var, float std_scale,
+                           int B, int C, int H, int W, int64_t var_low_bs, int64_t out_bs, void* stream);
+
 /* Forward (NLL direction) of one whole conditional step in ONE launch:
  *   (low, v) = Split(Haar1D(x));  for each stage: v <- A_k(gather_k(v));  z = gather_final(v)
  * final_perm (nullable) is the trailing PermuteRandom (networks.py:353-357).
