@@ -8,13 +8,14 @@ ops raise on non-HIP tensors and on a missing extension.
     cwfa_amd.install(precision="fp16")      # ... for its default --use_half_precision 1 (autocast)
     cwfa_amd.install(lion=True)             # ... and `from lion_pytorch import Lion` resolves to cwfa_amd.optim.Lion
     cwfa_amd.install(losses=True)           # ... and `import losses as Losses` resolves to cwfa_amd.losses (the fused wL2 loss)
+    cwfa_amd.install(utils=True)            # ... and `from utils import *` resolves to cwfa_amd.utils (XLFMDeconv, load_PSF_OTF, ...)
 """
 import sys
 
 __version__ = "0.1.0"
 
 
-def install(precision=None, lion=False, losses=False):
+def install(precision=None, lion=False, losses=False, utils=False):
     """Register this package's modules under the reference's top-level import names (FrEIA, INN_utils, networks, unet)
     so that code written against the reference (``import FrEIA.framework as Ff``, ``from networks import *``) runs on
     the HIP implementation unchanged.  Call before importing the reference's driver.
@@ -29,7 +30,12 @@ def install(precision=None, lion=False, losses=False):
 
     ``losses``: True also registers ``cwfa_amd.losses`` under the name ``losses``, so that the reference's ``import losses as Losses``
     (CWFA.py:27) and its ``Losses.weighted_mse_loss(curr_gt, upsampled_vol)`` calls (the `wL2` loss) run the fused HIP pass.  That
-    module holds only what CWFA.py uses from losses.py.  With the default False nothing is registered under that name."""
+    module holds only what CWFA.py uses from losses.py.  With the default False nothing is registered under that name.
+
+    ``utils``: True also registers ``cwfa_amd.utils`` under the name ``utils``, so that the ``from utils import *`` of the reference's
+    ``main_deconvolve_dataset.py`` finds ``XLFMDeconv``, ``load_PSF_OTF``, ``fft_conv_split`` and the other mirrors of that module
+    (DESIGN.md section 17).  The module holds no file readers (the reference's ``utils`` re-exports its dataset classes); with the
+    default False nothing is registered under that name."""
     from . import FrEIA, INN_utils, networks, unet
     if precision is not None:
         from . import ops
@@ -50,4 +56,7 @@ def install(precision=None, lion=False, losses=False):
     if losses:
         from . import losses as losses_mod
         sys.modules["losses"] = losses_mod
+    if utils:
+        from . import utils as utils_mod
+        sys.modules["utils"] = utils_mod
     return FrEIA, INN_utils, networks, unet

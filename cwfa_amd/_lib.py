@@ -71,6 +71,8 @@ PREP_MAX_BINS = 10239              # CWFA_PREP_MAX_BINS
 PREP_MOMENTS_WORKSPACE = 4096      # CWFA_PREP_MOMENTS_WORKSPACE (doubles)
 PREP_VOL = {"none": 0, "two": 1, "le": 2, "maxnorm": 3, "max_only": 4}          # CWFA_PREP_VOL_*
 PREP_APPLY = {"clamp_zero": 0, "sub_div": 1, "div_mul": 2}                      # CWFA_PREP_*
+DECONV_PRE = {None: 0, "none": 0, "relu": 1}                                    # CWFA_DECONV_PRE_*
+DECONV_POST = {None: 0, "none": 0, "abs": 1}                                    # CWFA_DECONV_POST_*
 
 # name -> (restype, argtypes); must list EVERY function declared in include/cwfa_hip.h (tests/test_boundary.py checks)
 i, i64, f, d, p = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_void_p
@@ -164,6 +166,12 @@ SIGNATURES = {
     "cwfa_lion_step_f32": (i, [C.POINTER(LionTable), f, f, f, f, p, p, p]),
     "cwfa_wmse_workspace_bytes": (i64, [i64]),
     "cwfa_wmse_loss_f32": (i, [p, p, p, f, f, p, p, p, i64, p]),
+    "cwfa_select_nonzero_f32": (i, [p, i, i64, i64, i64, p, p, p, p]),
+    "cwfa_deconv_spectrum_mul_c64": (i, [p, p, p, i, i64, i, i, p]),
+    "cwfa_deconv_project_f32": (i, [p, p, i, i, i, i, i, i, i, i, i, i, i, p]),
+    "cwfa_deconv_ratio_f32": (i, [p, p, p, p, i64, p]),
+    "cwfa_deconv_clamp_f32": (i, [p, i64, p, p, f, p]),
+    "cwfa_deconv_update_f32": (i, [p, p, i, i, i, i, p]),
 }
 del i, i64, f, d, p
 

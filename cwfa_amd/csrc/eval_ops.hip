@@ -518,12 +518,18 @@ extern "C" int cwfa_roi_means_f32(const float* x, const int32_t* boxes, double* 
 // first.  A pass counts, per value of its digit, the positive elements whose higher digits equal the prefix chosen so far -- an
 // LDS histogram per block (runs of equal digits are counted in registers first: real volumes share their exponent), then one
 // vector atomic add per bin and block; a one-block kernel then walks the 256 counts and extends the prefix.
+// NONZERO: the same selection over the elements != 0 of either sign (both zeros excluded), on the order-preserving key of the
+// bit pattern: negative values with every bit flipped, the others with the sign bit set.
 struct SelState {
     unsigned prefix;
     int bad;
     unsigned long long k, count;
 };
 
+__device__ __forceinline__ unsigned sel_key(unsigned u) { return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__device__ __forceinline__ unsigned sel_unkey(unsigned k) { return (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; }
+
+template <bool NONZERO>
 __global__ __launch_bounds__(256) void select_hist_kernel(const float* __restrict__ x, int64_t n, int64_t x_bs, int pass,
                                                           unsigned long long* __restrict__ hist, const SelState* __restrict__ st, int vec) {
     __shared__ unsigned long long lh[256];
@@ -535,8 +541,8 @@ __global__ __launch_bounds__(256) void select_hist_kernel(const float* __restric
     int cur = -1;
     unsigned long long run = 0;
     eval_stream<false>(x + blockIdx.y * x_bs, nullptr, n, vec, [&](float v, float) {
-        const unsigned u = f2u(v);
-        if ((int)u > 0 && (pass == 0 || (u >> (shift + 8)) == prefix)) {
+        const unsigned u = NONZERO ? sel_key(f2u(v)) : f2u(v);
+        if ((NONZERO ? v != 0.f : (int)u > 0) && (pass == 0 || (u >> (shift + 8)) == prefix)) {
             const int bin = (u >> shift) & 255;
             if (bin == cur) {
                 ++run;
@@ -552,7 +558,7 @@ __global__ __launch_bounds__(256) void select_hist_kernel(const float* __restric
 }
 
 __global__ void select_pick_kernel(const unsigned long long* __restrict__ hist, SelState* __restrict__ st, int pass, long long k_in,
-                                   float* __restrict__ value, long long* __restrict__ count) {
+                                   float* __restrict__ value, long long* __restrict__ count, int nonzero) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     if (pass == 0) {
         unsigned long long total = 0;
@@ -576,21 +582,22 @@ __global__ void select_pick_kernel(const unsigned long long* __restrict__ hist, 
         }
         k -= c;
     }
-    if (pass == 3) *value = u2f(st->prefix);
+    if (pass == 3) *value = u2f(nonzero ? sel_unkey(st->prefix) : st->prefix);
 }
 
-extern "C" int cwfa_select_positive_f32(const float* x, int B, int64_t n, int64_t x_bs, int64_t k, float* value, int64_t* count,
-                                        void* workspace, void* stream) {
-    CWFA_REQUIRE(x && value && count && workspace, CWFA_E_INVAL, "cwfa_select_positive_f32: null pointer");
-    CWFA_REQUIRE(B >= 0 && n >= 0 && B <= 65535 && n < ((int64_t)1 << 45), CWFA_E_SHAPE, "cwfa_select_positive_f32: bad shape");
-    CWFA_REQUIRE(x_bs >= 0 && (B <= 1 || x_bs >= n), CWFA_E_INVAL, "cwfa_select_positive_f32: batch stride smaller than a sample");
-    CWFA_REQUIRE(k >= -1, CWFA_E_INVAL, "cwfa_select_positive_f32: k must be >= 0, or -1 for the lower median");
-    CWFA_REQUIRE(k < (B * n > 0 ? B * n : 1), CWFA_E_INVAL, "cwfa_select_positive_f32: k = %lld is not below the element count %lld", (long long)k,
+template <bool NONZERO>
+static int select_run(const char* name, const float* x, int B, int64_t n, int64_t x_bs, int64_t k, float* value, int64_t* count,
+                      void* workspace, void* stream) {
+    CWFA_REQUIRE(x && value && count && workspace, CWFA_E_INVAL, "%s: null pointer", name);
+    CWFA_REQUIRE(B >= 0 && n >= 0 && B <= 65535 && n < ((int64_t)1 << 45), CWFA_E_SHAPE, "%s: bad shape", name);
+    CWFA_REQUIRE(x_bs >= 0 && (B <= 1 || x_bs >= n), CWFA_E_INVAL, "%s: batch stride smaller than a sample", name);
+    CWFA_REQUIRE(k >= -1, CWFA_E_INVAL, "%s: k must be >= 0, or -1 for the lower median", name);
+    CWFA_REQUIRE(k < (B * n > 0 ? B * n : 1), CWFA_E_INVAL, "%s: k = %lld is not below the element count %lld", name, (long long)k,
                  (long long)(B * n));
     if (B == 0 || n == 0) return CWFA_OK;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(workspace, 0, CWFA_SELECT_WORKSPACE_BYTES, st) != hipSuccess) {
-        cwfa_set_error("cwfa_select_positive_f32: clearing the workspace failed");
+        cwfa_set_error("%s: clearing the workspace failed", name);
         return CWFA_E_HIP;
     }
     unsigned long long* hist = reinterpret_cast<unsigned long long*>(workspace);
@@ -598,10 +605,22 @@ extern "C" int cwfa_select_positive_f32(const float* x, int B, int64_t n, int64_
     const int splits = eval_splits(n, B);
     const int vec = eval_vec(B, x, x_bs, nullptr, 0);
     for (int pass = 0; pass < 4; ++pass) {
-        hipLaunchKernelGGL(select_hist_kernel, dim3(splits, B), dim3(256), 0, st, x, n, x_bs, pass, hist, state, vec);
-        CWFA_LAUNCH_CHECK("cwfa_select_positive_f32");
-        hipLaunchKernelGGL(select_pick_kernel, dim3(1), dim3(64), 0, st, hist, state, pass, (long long)k, value, reinterpret_cast<long long*>(count));
-        CWFA_LAUNCH_CHECK("cwfa_select_positive_f32");
+        hipLaunchKernelGGL(select_hist_kernel<NONZERO>, dim3(splits, B), dim3(256), 0, st, x, n, x_bs, pass, hist, state, vec);
+        CWFA_LAUNCH_CHECK(name);
+        hipLaunchKernelGGL(select_pick_kernel, dim3(1), dim3(64), 0, st, hist, state, pass, (long long)k, value, reinterpret_cast<long long*>(count),
+                           (int)NONZERO);
+        CWFA_LAUNCH_CHECK(name);
     }
     return CWFA_OK;
+}
+
+extern "C" int cwfa_select_positive_f32(const float* x, int B, int64_t n, int64_t x_bs, int64_t k, float* value, int64_t* count,
+                                        void* workspace, void* stream) {
+    return select_run<false>("cwfa_select_positive_f32", x, B, n, x_bs, k, value, count, workspace, stream);
+}
+
+// Tmp[Tmp != 0].median() of the ratio image (utils.py:702-703), which is negative where the background-subtracted image is
+extern "C" int cwfa_select_nonzero_f32(const float* x, int B, int64_t n, int64_t x_bs, int64_t k, float* value, int64_t* count,
+                                       void* workspace, void* stream) {
+    return select_run<true>("cwfa_select_nonzero_f32", x, B, n, x_bs, k, value, count, workspace, stream);
 }

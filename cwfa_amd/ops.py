@@ -1758,3 +1758,119 @@ def wmse_loss(output, target, ths_perc=0.05, gscale=1.0, want_grad=True, extrema
         check(L.cwfa_wmse_loss_f32(_p(output), _p(target), _p(extrema), float(ths_perc), float(gscale), _p(grad), _p(out), _p(ws), n,
                                    _stream()), "wmse_loss")
     return out, grad
+
+
+# ------------------------------------------------------------------------------------------------ Richardson-Lucy deconvolution
+def _cdev(t, name):
+    """A contiguous complex64 tensor on the HIP device (the kernels read it as interleaved floats)."""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{name}: expected a torch.Tensor, got {type(t)}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: cwfa_amd runs on MI355X only -- got a {t.device} tensor (no CPU fallback exists)")
+    if t.dtype != torch.complex64:
+        raise TypeError(f"{name}: expected complex64, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous")
+    return t
+
+
+def _fdev(t, name):
+    _dev(t, name)
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous")
+    return t
+
+
+def select_nonzero(x, k=-1, out=None, workspace=None):
+    """(value float32[1], count int64[1]) on the device: the k-th smallest of the elements != 0 of the contiguous tensor x (both
+    zeros excluded, either sign), k = -1: their lower median -- torch's ``x[x != 0].median()``.  Exact; NaN if k >= count.  ``out``:
+    a (value, count) pair and ``workspace``: SELECT_WORKSPACE_BYTES device bytes to write into instead of allocating."""
+    L = _lib.lib()
+    _fdev(x, "select_nonzero")
+    value, count = out if out is not None else (torch.empty(1, dtype=torch.float32, device=x.device),
+                                                torch.empty(1, dtype=torch.int64, device=x.device))
+    ws = workspace if workspace is not None else torch.empty(_lib.SELECT_WORKSPACE_BYTES, dtype=torch.uint8, device=x.device)
+    n = x.numel()
+    if n == 0:
+        value.fill_(float("nan")), count.zero_()
+        return value, count
+    check(L.cwfa_select_nonzero_f32(_p(x), 1, n, n, int(k), _p(value), _p(count), _p(ws), _stream()), "select_nonzero")
+    return value, count
+
+
+def deconv_spectrum_mul(a, otf, conj=False, out=None):
+    """out[z] = a[z or 0] * otf[z] (``conj``: * conj(otf[z])) on contiguous complex64 tensors whose last two axes are a plane:
+    otf holds D planes, a holds D planes or one (broadcast).  ``out`` defaults to a new tensor of otf's shape; ``out=a`` works in
+    place when a holds D planes.  otf is never written."""
+    L = _lib.lib()
+    _cdev(a, "a"), _cdev(otf, "otf")
+    if otf.dim() < 2 or a.dim() < 2 or tuple(a.shape[-2:]) != tuple(otf.shape[-2:]):
+        raise ValueError(f"deconv_spectrum_mul: planes differ: {tuple(a.shape)} vs {tuple(otf.shape)}")
+    n = otf.shape[-2] * otf.shape[-1]
+    D, a_planes = (otf.numel() // n, a.numel() // n) if n else (0, 0)
+    if out is None:
+        out = torch.empty_like(otf)
+    _cdev(out, "out")
+    if out.numel() != otf.numel():
+        raise ValueError("deconv_spectrum_mul: out must have otf's size")
+    check(L.cwfa_deconv_spectrum_mul_c64(_p(a), _p(otf), _p(out), D, n, a_planes, int(bool(conj)), _stream()), "deconv_spectrum_mul")
+    return out
+
+
+def deconv_project(p, out=None, window=None, pre=None, post=None, accumulate=False):
+    """out[s, 0] (+)= post(sum_z pre(shift(p)[s, z])) over the window (oy, ox, Ho, Wo) of the plane (default: all of it), where
+    shift is the reference's ``batch_fftshift2d_real`` (source index = target index + ceil(size / 2)).  p: contiguous [N, D, H, W];
+    ``pre``: None / "relu"; ``post``: None / "abs".  Returns out [N, 1, Ho, Wo]."""
+    L = _lib.lib()
+    _fdev(p, "p")
+    if p.dim() != 4:
+        raise ValueError(f"deconv_project: expected [N,D,H,W], got {tuple(p.shape)}")
+    N, D, H, W = p.shape
+    oy, ox, Ho, Wo = (0, 0, H, W) if window is None else (int(v) for v in window)
+    if out is None:
+        if accumulate:
+            raise ValueError("deconv_project: accumulate needs the tensor to add to")
+        out = torch.empty(N, 1, Ho, Wo, dtype=torch.float32, device=p.device)
+    _fdev(out, "out")
+    if out.numel() != N * Ho * Wo:
+        raise ValueError(f"deconv_project: out {tuple(out.shape)} does not hold {N} windows of {Ho} x {Wo}")
+    check(L.cwfa_deconv_project_f32(_p(p), _p(out), N, D, H, W, Ho, Wo, oy, ox, _lib.DECONV_PRE[pre], _lib.DECONV_POST[post],
+                                    int(bool(accumulate)), _stream()), "deconv_project")
+    return out
+
+
+def deconv_ratio(img, est, out, flag):
+    """out = img / (est + 1e-8) on contiguous tensors of one size; the int32 device scalar ``flag`` is set to 1 (never cleared) when an
+    element of out is NaN or one of img is not finite."""
+    L = _lib.lib()
+    _fdev(img, "img"), _fdev(est, "est"), _fdev(out, "out")
+    if not (img.numel() == est.numel() == out.numel()):
+        raise ValueError("deconv_ratio: the tensors differ in size")
+    if not flag.is_cuda or flag.dtype != torch.int32 or flag.numel() != 1:
+        raise ValueError("deconv_ratio: flag must be a one-element int32 tensor on the HIP device")
+    check(L.cwfa_deconv_ratio_f32(_p(img), _p(est), _p(out), _p(flag), img.numel(), _stream()), "deconv_ratio")
+    return out
+
+
+def deconv_clamp(x, median, count, mult):
+    """In place clamp(x, 0, median * mult) with ``median`` (float32[1]) and ``count`` (int64[1]) on the device, as ``select_nonzero``
+    returns them; nothing happens when count is 0."""
+    L = _lib.lib()
+    _fdev(x, "x"), _dev(median, "median")
+    if not count.is_cuda or count.dtype != torch.int64 or count.numel() != 1 or median.numel() != 1:
+        raise ValueError("deconv_clamp: median / count must be one-element float32 / int64 tensors on the HIP device")
+    check(L.cwfa_deconv_clamp_f32(_p(x), x.numel(), _p(median), _p(count), float(mult), _stream()), "deconv_clamp")
+    return x
+
+
+def deconv_update(obj_pad, b, obj, po):
+    """obj_pad[..., po:po+obj, po:po+obj] *= shift(b)[..., po:po+obj, po:po+obj] in place on contiguous [.., D, F, F] tensors of one
+    shape (shift as in ``deconv_project``); nothing outside the window is read or written."""
+    L = _lib.lib()
+    _fdev(obj_pad, "obj_pad"), _fdev(b, "b")
+    if obj_pad.dim() < 2 or tuple(obj_pad.shape) != tuple(b.shape) or obj_pad.shape[-1] != obj_pad.shape[-2]:
+        raise ValueError(f"deconv_update: expected two [.., F, F] tensors of one shape, got {tuple(obj_pad.shape)} and {tuple(b.shape)}")
+    F = obj_pad.shape[-1]
+    D = obj_pad.numel() // (F * F) if F else 0
+    check(L.cwfa_deconv_update_f32(_p(obj_pad), _p(b), D, F, int(obj), int(po), _stream()), "deconv_update")
+    return obj_pad

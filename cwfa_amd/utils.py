@@ -3,7 +3,8 @@
 (:105-126), ``load_process_volume`` (:128-184) and ``prepare_XLFM_data``, the body of ``load_XLFM_data`` (:187-220) behind the
 dataset object.  The passes over volumes are HIP kernels (csrc/eval_ops.hip, csrc/prep_ops.hip); no torch operator runs on a volume.
 
-``cwfa_amd.install()`` does NOT register this module as ``utils``: the reference's ``utils`` also holds its dataset loaders.
+``cwfa_amd.install()`` does NOT register this module as ``utils`` (the reference's ``utils`` also holds its dataset loaders);
+``cwfa_amd.install(utils=True)`` does, for the ``from utils import *`` of ``main_deconvolve_dataset.py``.
 Inputs are assumed finite (the kernels do not propagate NaN)."""
 import numpy as np
 import torch
@@ -12,7 +13,8 @@ from . import _lib, ops
 from .amp import amp_function, amp_region
 
 __all__ = ["psnr", "volume_2_projections", "norm_data", "filter_data", "fast_quantile", "crop_volume_center", "load_process_volume",
-           "prepare_XLFM_data"]
+           "prepare_XLFM_data", "roll_n", "batch_fftshift2d_real", "fft_conv", "fft_conv_split", "load_PSF", "load_PSF_OTF",
+           "XLFMDeconv"]
 
 
 def _as_volume(t, name):
@@ -238,3 +240,232 @@ def prepare_XLFM_data(ds, vol_shape, volume_ths, volume_quantiles, img_ths, norm
     img_low = ops.volume_extrema(views.reshape(1, 1, 1, -1))[0, 1].cpu() * img_ths[0]       # fp32 scalar product, as there
     ds.stacked_views = ops.prep_apply(views, "clamp_zero", b=img_low, upper=False)
     return ds
+
+
+# ------------------------------------------------------------------------------------------------ Richardson-Lucy deconvolution
+def roll_n(X, axis, n):
+    """utils.py:451-463: X rolled along ``axis`` so that element n comes first (``torch.roll`` by -n); a torch operator, the
+    deconvolution itself does not go through it."""
+    return torch.roll(X, -int(n), axis)
+
+
+def batch_fftshift2d_real(x):
+    """utils.py:465-477 for a real float32 device tensor [B, C, H, W]: every plane rolled by ceil(size / 2) along both axes (the
+    source index is the target index plus the shift) -- one launch of the projection kernel with one depth per plane."""
+    if torch.is_tensor(x) and x.is_complex():
+        raise TypeError("batch_fftshift2d_real: real tensors only")
+    ops._dev(x, "x")
+    if x.dim() != 4:
+        raise ValueError(f"batch_fftshift2d_real: expected [B,C,H,W], got {tuple(x.shape)}")
+    B, Cc, H, W = x.shape
+    x = x if x.is_contiguous() else x.contiguous()
+    return ops.deconv_project(x.view(B * Cc, 1, H, W)).view(B, Cc, H, W)
+
+
+def _full_size(fullSize, what):
+    fh, fw = (int(v) for v in fullSize)
+    if fw % 2:
+        raise ValueError(f"{what}: the full width {fw} is odd: the reference's irfft2 returns {fw - 1} columns and its result is short")
+    return fh, fw
+
+
+def _pad_centre(A, fh, fw, what):
+    """F.pad of utils.py:492-498: ceil(d / 2) zeros in front and floor(d / 2) behind, on both axes."""
+    dh, dw = fh - A.shape[2], fw - A.shape[3]
+    if dh < 0 or dw < 0:
+        raise ValueError(f"{what}: a {A.shape[2]} x {A.shape[3]} plane does not fit the full size {fh} x {fw}")
+    return torch.nn.functional.pad(A, [(dw + 1) // 2, dw // 2, (dh + 1) // 2, dh // 2])
+
+
+def _conv_spectrum(A, B, fh, fw, B_precomputed, what):
+    """irfft2(rfft2(pad(A)) * OTF) of utils.py:498-510, unshifted: (real planes [Ba, n, fh, fw], OTF [1, n, fh, fw // 2 + 1])."""
+    ops._dev(A, "A")
+    if A.dim() != 4:
+        raise ValueError(f"{what}: expected [B,n,H,W], got {tuple(A.shape)}")
+    if B_precomputed:
+        otf = ops._cdev(B.detach(), "B")
+    else:
+        ops._dev(B, "B")
+        otf = torch.fft.rfft2(_pad_centre(B.detach(), fh, fw, what))
+    if otf.dim() != 4 or otf.shape[0] != 1 or tuple(otf.shape[1:]) != (A.shape[1], fh, fw // 2 + 1):
+        raise ValueError(f"{what}: the transfer function {tuple(otf.shape)} does not fit {A.shape[1]} planes of {fh} x {fw}")
+    spec = torch.fft.rfft2(_pad_centre(A, fh, fw, what))
+    for b in range(spec.shape[0]):
+        ops.deconv_spectrum_mul(spec[b], otf[0], out=spec[b])
+    return torch.fft.irfft2(spec, s=(fh, fw)), otf
+
+
+def fft_conv(A, B, fullSize, Bshape=[], B_precomputed=False):
+    """utils.py:480-510, same signature and both return forms: the shifted planes of irfft2(rfft2(pad A) * OTF), and the OTF too
+    when it is computed here (``B`` a PSF [1, n, h, w]) rather than given (``B_precomputed``).  float32 device tensors.
+    An odd full width raises ValueError (the reference's result comes out one column short)."""
+    fh, fw = _full_size(fullSize, "fft_conv")
+    real, otf = _conv_spectrum(A, B, fh, fw, B_precomputed, "fft_conv")
+    out = batch_fftshift2d_real(real)
+    return out if B_precomputed else (out, otf)
+
+
+def fft_conv_split(A, B, psf_shape, n_split, B_precomputed=False, device="cuda"):
+    """utils.py:513-550, same signature (``device`` is ignored: the tensors stay where they are): the image of a volume
+    A [Ba, D, h, w] under the PSF / OTF B, cropped to ``psf_shape``, in ``n_split`` depth chunks, |chunk sum| added per chunk.
+    Shift, crop, depth sum and abs are one kernel per chunk.  Returns the image [Ba, 1, psf, psf], and the OTF
+    [1, D, full_h, full_w // 2 + 1] when it is computed here.  As in the reference the chunks hold D // n_split depths and only
+    the first n_split chunks are used."""
+    if A.dim() != 4:
+        raise ValueError(f"fft_conv_split: expected [B,D,H,W], got {tuple(A.shape)}")
+    D = A.shape[1]
+    ph, pw = (int(v) for v in psf_shape)
+    n_split = int(n_split)
+    if n_split < 1 or n_split > D:
+        raise ValueError(f"fft_conv_split: n_split = {n_split} does not divide {D} depths into chunks")
+    fh, fw = _full_size((A.shape[2] + ph, A.shape[3] + pw), "fft_conv_split")
+    ops._dev(A, "A")
+    step = D // n_split
+    oy, ox = -((ph - fh) // 2), -((pw - fw) // 2)
+    img = torch.zeros(A.shape[0], 1, ph, pw, dtype=torch.float32, device=A.device)
+    otf_out = None if B_precomputed else torch.zeros(1, D, fh, fw // 2 + 1, dtype=torch.complex64, device=A.device)
+    for n in range(n_split):
+        sl = slice(n * step, (n + 1) * step)
+        real, otf = _conv_spectrum(A[:, sl], B[:, sl].contiguous(), fh, fw, B_precomputed, "fft_conv_split")
+        if not B_precomputed:
+            otf_out[:, sl] = otf
+        ops.deconv_project(real, out=img, window=(oy, ox, ph, pw), post="abs", accumulate=True)
+    return img if B_precomputed else (img, otf_out)
+
+
+def load_PSF(psf, depths_to_use=[], interleaved=True):
+    """utils.py:553-591 behind the file reading: ``psf`` is the tensor [1, D, H, W] the reference builds from the file.  Made square
+    (``pad_img_to_min``), the depths chosen (an int n: n interleaved depths, or the n central ones; -1: all; a list: those), every
+    depth divided by its sum.  Torch operators: this runs once per PSF."""
+    from .XLFMDataset import pad_img_to_min
+    if isinstance(psf, str):
+        raise NotImplementedError("load_PSF: reading a file is the reference's; pass the PSF tensor [1, D, H, W]")
+    psfIn = pad_img_to_min(psf)
+    if isinstance(depths_to_use, int):
+        if depths_to_use == -1:
+            depths_to_use = list(range(psfIn.shape[1]))
+        else:
+            n_depths = depths_to_use
+            if interleaved:
+                depths_to_use = torch.linspace(0, psfIn.shape[1], n_depths + 2).long()[1:-1]
+            else:
+                first = psfIn.shape[1] // 2 - n_depths // 2 + 1
+                depths_to_use = list(range(first, first + n_depths))
+    psfIn = psfIn[:, depths_to_use, ...]                                  # advanced indexing: a copy, as there
+    return psfIn / psfIn.sum((2, 3), keepdim=True)
+
+
+def load_PSF_OTF(psf, vol_size, n_split=20, downS=1, device="cuda", dark_current=106, calc_max=False, compute_OTF=False):
+    """utils.py:593-627 for a PSF tensor on the HIP device: (OTF, psf_shape) with OTF complex64 [1, D, full, full // 2 + 1] for a
+    volume of ``vol_size`` = [h, w, D], or [.., 2] with the conjugate behind it for ``compute_OTF``.  ``calc_max`` raises
+    NotImplementedError (the reference returns a name it never defines)."""
+    if calc_max:
+        raise NotImplementedError("load_PSF_OTF: calc_max=True is not supported (the reference fails there on an undefined name)")
+    n_depths = int(vol_size[-1])
+    if n_split == -1:
+        n_split = n_depths
+    psfIn = load_PSF(psf, n_depths).float()
+    psf_shape = torch.tensor(psfIn.shape[2:])
+    vol = torch.zeros(1, psfIn.shape[1], int(vol_size[0]), int(vol_size[1]), dtype=torch.float32, device=psfIn.device)
+    OTF = fft_conv_split(vol, psfIn.contiguous(), psf_shape, n_split=n_split)[1]       # the reference's random volume only sizes it
+    if compute_OTF:
+        OTF = torch.stack((OTF, OTF.conj().resolve_conj()), 4)
+    return OTF, psf_shape
+
+
+def _deconv_sizes(OTF, img, ObjSize):
+    """The shapes XLFMDeconv can run (the reference's pads come out short on the others), or ValueError naming the size."""
+    F = int(OTF.shape[2])
+    if F % 2:
+        raise ValueError(f"XLFMDeconv: the full size {F} is odd: irfft2 returns {F - 1} columns")
+    if OTF.shape[3] != F // 2 + 1:
+        raise ValueError(f"XLFMDeconv: the OTF's last axis is {OTF.shape[3]}, a square full size {F} needs {F // 2 + 1}")
+    obj = int(ObjSize[0])
+    if int(ObjSize[1]) != obj:
+        raise ValueError(f"XLFMDeconv: the object {list(ObjSize)} is not square")
+    if obj > F or (F - obj) % 2:
+        raise ValueError(f"XLFMDeconv: the object size {obj} cannot be padded evenly to the full size {F}")
+    if img.dim() != 4 or img.shape[0] != 1 or img.shape[1] != 1:
+        raise ValueError(f"XLFMDeconv: expected one image [1,1,H,W], got {tuple(img.shape)}")
+    ih = int(img.shape[2])
+    if int(img.shape[3]) != ih:
+        raise ValueError(f"XLFMDeconv: the image {ih} x {int(img.shape[3])} is not square")
+    if ih > F or (F - ih) % 2:
+        raise ValueError(f"XLFMDeconv: the image size {ih} cannot be padded evenly to the full size {F}")
+    return F, obj, (F - obj) // 2, (F - ih) // 2
+
+
+def XLFMDeconv(OTF, img, nIt, ObjSize=[512, 512], PSFShape=[2160, 2160], ROIsize=[512, 512, 90], errorMetric=torch.nn.functional.mse_loss,
+               n_split_fourier=1,
+               update_median_limit_multiplier=10, max_allowed=4500, device="cuda:0", all_in_device=False, verbose=False):
+    """Richardson-Lucy deconvolution of one image; utils.py:630-738, same signature and return forms.
+
+    OTF: complex64 [1, D, F, F // 2 + 1] (the conjugate is applied on the fly) or [1, D, F, F // 2 + 1, 2] (``OTF[..., 1]`` is used
+    for the back projection as given); img float32 [1, 1, H, W]; all on the HIP device, all results stay there.  Returns
+    (ObjRecon [1, D, obj, obj], 0, ImgEst [1, 1, F, F], [], padSize, padSizeImg); an image that sums to zero returns
+    (zeros, their composite projection on the CPU, img, []).  ``n_split_fourier`` depths go through the FFTs at a time (1: all).
+    Per iteration and chunk: rfft2 of the padded object, spectrum product, irfft2, shift + relu + depth sum (forward); ratio, median
+    of the non-zero elements, clamp; rfft2 of the ratio, product with the conjugate OTF, irfft2, shifted product into the object's
+    window (backward).  The object stays zero-padded throughout, every buffer is allocated before the loop.  A non-finite image
+    pixel makes the ratio NaN in the first iteration and stops the loop there, as the reference's ``0 * ImgExp`` start does.
+    ``device``, ``all_in_device``, ``errorMetric`` and ``max_allowed`` are accepted and unused; ``verbose`` raises
+    NotImplementedError (it plots).  img and OTF are left unchanged."""
+    if verbose:
+        raise NotImplementedError("XLFMDeconv: verbose=True plots every iteration with matplotlib; not supported")
+    if not torch.is_tensor(OTF) or OTF.dim() not in (4, 5) or (OTF.dim() == 5 and OTF.shape[4] != 2) or OTF.shape[0] != 1:
+        raise ValueError("XLFMDeconv: the OTF must be [1, D, F, F // 2 + 1] or [1, D, F, F // 2 + 1, 2]")
+    nDepths = int(OTF.shape[1])
+    step = nDepths if n_split_fourier == 1 else int(n_split_fourier)
+    if step < 1:
+        raise ValueError(f"XLFMDeconv: n_split_fourier = {n_split_fourier}")
+    F, obj, po, pi = _deconv_sizes(OTF, img, ObjSize)
+    ops._dev(img, "img")
+    dev = img.device
+    if float(img.sum()) == 0:
+        volOut = torch.zeros(img.shape[0], nDepths, obj, obj, dtype=torch.float32, device=dev)
+        return volOut, volume_2_projections(volOut.permute(0, 2, 3, 1).unsqueeze(1)), img, []
+    if OTF.dim() == 5:                                                     # the reference clones both halves too
+        otf_f, otf_b, conj = OTF[..., 0].contiguous(), OTF[..., 1].contiguous(), False
+    else:
+        otf_f = otf_b = OTF if OTF.is_contiguous() else OTF.contiguous()
+        conj = True
+    ops._cdev(otf_f, "OTF")
+    padSize, padSizeImg = 2 * [po] + 2 * [po], 2 * [pi] + 2 * [pi]
+    Fh = F // 2 + 1
+    with torch.no_grad():
+        ImgExp = torch.nn.functional.pad(img, padSizeImg).contiguous()
+        obj_pad = torch.zeros(1, nDepths, F, F, dtype=torch.float32, device=dev)
+        obj_pad[:, :, po:po + obj, po:po + obj] = 1.0
+        spec = torch.empty(1, min(step, nDepths), F, Fh, dtype=torch.complex64, device=dev)
+        real = torch.empty(1, min(step, nDepths), F, F, dtype=torch.float32, device=dev)
+        rspec = torch.empty(1, 1, F, Fh, dtype=torch.complex64, device=dev)
+        ImgEst = torch.zeros(1, 1, F, F, dtype=torch.float32, device=dev)
+        Tmp = torch.empty_like(ImgEst)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        median = (torch.empty(1, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.int64, device=dev))
+        ws = torch.empty(_lib.SELECT_WORKSPACE_BYTES, dtype=torch.uint8, device=dev)
+        chunks = [(jj, min(jj + step, nDepths)) for jj in range(0, nDepths, step)]
+        for ii in range(int(nIt)):
+            for jj, je in chunks:                                          # forward projection
+                sp, re = spec[:, :je - jj], real[:, :je - jj]
+                torch.fft.rfft2(obj_pad[:, jj:je], out=sp)
+                ops.deconv_spectrum_mul(sp, otf_f[:, jj:je], out=sp)
+                torch.fft.irfft2(sp, s=(F, F), out=re)
+                ops.deconv_project(re, out=ImgEst, pre="relu", accumulate=jj > 0)
+            ops.deconv_ratio(ImgExp, ImgEst, Tmp, flag)
+            ops.select_nonzero(Tmp, out=median, workspace=ws)
+            ops.deconv_clamp(Tmp, median[0], median[1], update_median_limit_multiplier)
+            if int(flag.item()):
+                print(F'nan found at it: {ii+1} ')
+                ImgEst += 0 * ImgExp                                       # the NaN the reference's estimate carries from its start
+                break
+            torch.fft.rfft2(Tmp, out=rspec)
+            for jj, je in chunks:                                          # back projection and update
+                sp, re = spec[:, :je - jj], real[:, :je - jj]
+                ops.deconv_spectrum_mul(rspec, otf_b[:, jj:je], conj=conj, out=sp)
+                torch.fft.irfft2(sp, s=(F, F), out=re)
+                ops.deconv_update(obj_pad[:, jj:je], re, obj, po)
+        ObjRecon = obj_pad[:, :, po:po + obj, po:po + obj].contiguous()
+    ObjRecon[:, 0:nDepths // 2 - ROIsize[2] // 2, ...] = 0
+    ObjRecon[:, nDepths // 2 + ROIsize[2] // 2:, ...] = 0
+    return ObjRecon, 0, ImgEst, [], padSize, padSizeImg

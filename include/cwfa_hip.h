@@ -552,7 +552,9 @@ int cwfa_attention_bwd_f32(const float* mean, const float* w1, const float* b1, 
  *                   [N][6], inside the volume; an empty box gives NaN).  x: [T, D, H, W] with time stride t_stride.
  *   select_positive: *value = the k-th smallest (k = 0 ..) of the strictly positive elements, k = -1: their lower median
  *                   (k = (count - 1) / 2, torch's convention); *count = the number of positive elements; k >= count gives NaN.
- *                   Radix selection on the bit patterns, 64-bit counters: exact.  workspace: CWFA_SELECT_WORKSPACE_BYTES device bytes. */
+ *                   Radix selection on the bit patterns, 64-bit counters: exact.  workspace: CWFA_SELECT_WORKSPACE_BYTES device bytes.
+ *   select_nonzero: the same over the elements != 0 of either sign (+0.0 and -0.0 are both excluded), ordered by value:
+ *                   `Tmp[Tmp != 0].median()` of utils.py:702-703.  Inputs are assumed free of NaN. */
 #define CWFA_EXTREMA_STRIDE 12
 #define CWFA_EVAL_MAX_SPLITS 2048
 #define CWFA_SELECT_WORKSPACE_BYTES 8448
@@ -580,6 +582,8 @@ int cwfa_roi_means_f32(const float* x, const int32_t* boxes, double* out, int T,
                        void* stream);
 int cwfa_select_positive_f32(const float* x, int B, int64_t n, int64_t x_bs, int64_t k, float* value, int64_t* count,
                              void* workspace, void* stream);
+int cwfa_select_nonzero_f32(const float* x, int B, int64_t n, int64_t x_bs, int64_t k, float* value, int64_t* count,
+                            void* workspace, void* stream);
 
 /* The data preparation pass in front of every run: load_XLFM_data (utils.py:187-220) with load_process_volume (:128-184),
  * crop_volume_center (:105-126) and fast_quantile (:84-102), the frame clean-up of XLFMDatasetFull (XLFMDataset.py:101-104,
@@ -664,6 +668,39 @@ int cwfa_lion_step_f32(const cwfa_lion_table* tab, float lr, float beta1, float 
 int64_t cwfa_wmse_workspace_bytes(int64_t n);
 int cwfa_wmse_loss_f32(const float* output, const float* target, const float* extrema, float ths_perc, float gscale, float* grad,
                        double* out, void* workspace, int64_t n, void* stream);
+
+/* Richardson-Lucy deconvolution: everything between the FFTs of XLFMDeconv (utils.py:630-738), fft_conv (:480-510) and
+ * fft_conv_split (:513-550) with batch_fftshift2d_real / roll_n (:451-477).  The FFTs stay with the caller (rocFFT).  Streaming
+ * kernels, 64-bit offsets, 16-byte accesses where every pointer is 16-byte aligned and the shapes allow, element by element
+ * otherwise.  Every fp32 operation is rounded separately.  Nothing is allocated, nothing synchronises.
+ *
+ *   spectrum_mul: out[z][i] = a[z or 0][i] * (conj ? conj(otf[z][i]) : otf[z][i]) on interleaved complex64, n complex values
+ *                 per plane, D planes of otf and out (utils.py:501,700,715).  a_planes == D: a plane per depth (out == a, in
+ *                 place, is allowed); a_planes == 1: one plane broadcast over the depths (the spectrum of the ratio image).
+ *                 conj != 0 multiplies with the conjugate, so one stored transfer function serves both directions (utils.py:663).
+ *                 otf is never written (out == otf is refused).
+ *   project:      out[s][y][x] (+)= post(sum_z pre(p[s][z][(y + oy + sy) mod H][(x + ox + sx) mod W])), sy = ceil(H / 2),
+ *                 sx = ceil(W / 2), for the Ho x Wo window at (oy, ox): batch_fftshift2d_real (the source index is the target index
+ *                 plus the shift) fused with the relu and depth sum of utils.py:700 (pre = RELU, accumulate over depth chunks) or
+ *                 the crop, depth sum and abs of utils.py:545-546 (post = ABS).  p: [N][D][H][W], out: [N][Ho][Wo].  The depths
+ *                 are added in order z = 0 .. D-1 by the one thread that owns the pixel: bitwise reproducible, no atomics.
+ *                 relu keeps NaN, as torch's.
+ *   ratio:        tmp = img / (est + 1e-8f) over n elements (utils.py:701); *flag (device int, never cleared here) is set to 1
+ *                 when an element of tmp is NaN or one of img is not finite -- the condition under which the reference, whose
+ *                 estimate starts as 0 * img (utils.py:677), leaves its loop (utils.py:707).
+ *   clamp:        in place min(max(tmp, 0), *median * mult), NaN kept (torch.clamp_, utils.py:703), bound and count read from
+ *                 device memory (the outputs of cwfa_select_nonzero_f32); nothing is written when *count == 0 (utils.py:702).
+ *   update:       obj_pad[z][po + y][po + x] *= b[z][(po + y + s) mod F][(po + x + s) mod F], s = ceil(F / 2), for the interior
+ *                 obj x obj window of D zero-padded F x F planes (utils.py:694,715: pad, product with the shifted back projection,
+ *                 crop).  Only the window of either tensor is touched: the border of obj_pad stays exactly 0. */
+enum { CWFA_DECONV_PRE_NONE = 0, CWFA_DECONV_PRE_RELU = 1 };
+enum { CWFA_DECONV_POST_NONE = 0, CWFA_DECONV_POST_ABS = 1 };
+int cwfa_deconv_spectrum_mul_c64(const float* a, const float* otf, float* out, int D, int64_t n, int a_planes, int conj, void* stream);
+int cwfa_deconv_project_f32(const float* p, float* out, int N, int D, int H, int W, int Ho, int Wo, int oy, int ox, int pre, int post,
+                            int accumulate, void* stream);
+int cwfa_deconv_ratio_f32(const float* img, const float* est, float* tmp, int* flag, int64_t n, void* stream);
+int cwfa_deconv_clamp_f32(float* tmp, int64_t n, const float* median, const int64_t* count, float mult, void* stream);
+int cwfa_deconv_update_f32(float* obj_pad, const float* b, int D, int F, int obj, int po, void* stream);
 
 #ifdef __cplusplus
 }
