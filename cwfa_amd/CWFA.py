@@ -19,7 +19,7 @@ __all__ = ["sample_z_truncated", "check_empty_depths", "evaluate_INN_forward", "
            "nll_terms", "allreduce_nll", "build_networks", "step_log_likelihoods", "allgather_scores", "detect_ood",
            "forward_nll_pass", "mean_volume_cache", "save_mean_volume_cache", "load_mean_volume_cache",
            "denormalise_prediction", "denormalise_ground_truth", "compute_INN_step_performance", "evaluate_step", "roi_boxes",
-           "corr_coeff_3D", "truncated_normal_variance", "posterior_moments", "posterior_samples"]
+           "corr_coeff_3D", "truncated_normal_variance", "posterior_moments", "posterior_samples", "posterior_roi_means"]
 
 
 def _no_grad_trunc_normal_(tensor, mean=0., std=1., a=-1., b=1.):
@@ -38,12 +38,17 @@ def _no_grad_trunc_normal_(tensor, mean=0., std=1., a=-1., b=1.):
         return tensor
 
 
-def sample_z_truncated(x, device="cpu", temperature=1):
+def sample_z_truncated(x, device="cpu", temperature=1, seed=None, stream=0, sample_offset=0):
     """Latent sample; ``temperature == 0`` (the default of main.py:109) returns zeros.  CWFA.py:47-64.
-    The fused inverse treats ``None`` as an all-zero z and never reads it (``inverse_pass`` does that itself)."""
+    The fused inverse treats ``None`` as an all-zero z and never reads it (``inverse_pass`` does that itself).
+    With ``seed`` the draw is ONE launch of the counter-based generator (``ops.rand_trunc_normal``: the first axis is its sample
+    axis; ``stream`` / ``sample_offset`` as there) on the HIP device instead of torch's five passes and global generator."""
     shape_like = torch.is_tensor(x)
     if temperature == 0:
         return torch.zeros_like(x, device=device) if shape_like else torch.zeros(x, device=device)
+    if seed is not None:
+        return ops.rand_trunc_normal(tuple(x.shape) if shape_like else tuple(x), temperature, seed, stream, sample_offset,
+                                     device=torch.device(device))
     base = torch.zeros_like(x, device=device) if shape_like else torch.zeros(x, device=device)
     return _no_grad_trunc_normal_(base, a=-temperature, b=temperature)
 
@@ -302,14 +307,19 @@ def posterior_moments(conv_inn, cond_nets, cond_input, mean_vols_cache, low=None
 @amp_function
 @torch.no_grad()
 def posterior_samples(conv_inn, cond_nets, cond_input, mean_vols_cache, n_samples, low=None, temperature=1.0,
-                      return_z=False):
+                      return_z=False, seed=None, sample_offset=0):
     """``n_samples`` genuine posterior samples [n_samples, B, D, H, W] of the reconstruction (every step all-CAT;
     NotImplementedError otherwise).  Every condition net and every sub-network runs ONCE per step; per sample only the
     latent draw (``sample_z_truncated``) and one ``ops.chain_inv`` follow.  Each sample carries its own coarser volume down
     the pyramid and nothing is averaged between the steps -- unlike ``inverse_pass(n_samples=...)``, which repeats the
     conditions, runs every network per sample and averages after every step (CWFA.py:913-914).  ``temperature = 0`` yields
     ``n_samples`` copies of the mean.  With ``return_z`` also the latents: a list over the steps in execution order (coarse
-    -> fine) of [n_samples, B, C_n, H, W] tensors (None per step at temperature 0)."""
+    -> fine) of [n_samples, B, C_n, H, W] tensors (None per step at temperature 0).
+
+    With ``seed`` (and temperature > 0) the latents come from the counter-based generator inside ONE ``ops.chain_inv_samples``
+    launch per step -- no separate draw, no ``torch.stack``; the step's execution index (0 = coarsest) is the generator's
+    stream and sample i draws at counter ``sample_offset + i``, so the call is reproducible and samples [k, n) of one call are
+    samples [0, n - k) of a call with ``sample_offset + k``.  Without ``seed`` the latents are torch's, as before."""
     plans = _affine_plans(conv_inn, "posterior_samples")
     n_samples = int(n_samples)
     if n_samples < 1:
@@ -317,6 +327,10 @@ def posterior_samples(conv_inn, cond_nets, cond_input, mean_vols_cache, n_sample
     if not float(temperature) >= 0.0:
         raise ValueError(f"temperature {temperature!r}: the truncation bound must be >= 0")
     S1 = len(conv_inn)
+    if seed is not None and temperature != 0:
+        up = _coarsest(conv_inn, cond_nets, cond_input, mean_vols_cache, low)
+        steps = _inverse_stage_lists(plans, cond_nets, cond_input, mean_vols_cache, tuple(up.shape[1:]), up.device)
+        return _seeded_samples(steps, up, n_samples, temperature, seed, sample_offset, return_z)
     ups = [_coarsest(conv_inn, cond_nets, cond_input, mean_vols_cache, low)] * n_samples
     latents = []
     from .networks import omega_first_scope
@@ -334,6 +348,67 @@ def posterior_samples(conv_inn, cond_nets, cond_input, mean_vols_cache, n_sample
             latents.append(zs)
     out = torch.stack(ups)
     return (out, latents) if return_z else out
+
+
+def _inverse_stage_lists(plans, cond_nets, cond_input, mean_vols_cache, shape, device):
+    """(stages, tables) of every step in execution order (coarse -> fine): every condition net and sub-network runs once.
+    ``shape`` = (C, H, W) of the coarsest volume; each step doubles the channels.  The coefficient tensors of all steps are alive
+    together while the list is (ten planes per detail channel)."""
+    from .networks import omega_first_scope
+    S1 = len(plans)
+    C0, H, W = shape
+    steps = []
+    with omega_first_scope(list(cond_nets[:S1]), cond_input):
+        for i, n in enumerate(range(S1 - 1, -1, -1)):
+            c = [cond_nets[n](cond_input)[-1], mean_vols_cache[n]]
+            steps.append(plans[n].inverse_stages(c, (C0 << i, H, W), device))
+    return steps
+
+
+def _seeded_samples(steps, up, n_samples, temperature, seed, sample_offset, return_z):
+    """One ``ops.chain_inv_samples`` launch per step: ``up`` [B,C,H,W] is shared at the coarsest step, afterwards every sample
+    carries its own volume."""
+    latents = []
+    for i, (stages, tabs) in enumerate(steps):
+        res = ops.chain_inv_samples(up, stages, n_samples, temperature, seed, stream=i, sample_offset=sample_offset, tables=tabs,
+                                    return_z=return_z)
+        up, z = res if return_z else (res, None)
+        latents.append(z)
+    return (up, latents) if return_z else up
+
+
+@amp_function
+@torch.no_grad()
+def posterior_roi_means(conv_inn, cond_nets, cond_input, mean_vols_cache, boxes, n_samples, low=None, temperature=1.0, seed=0,
+                        chunk=16):
+    """The ROI means (``corr_coeff_3D``'s traces, before its normalisation) of ``n_samples`` posterior samples: float64
+    [n_samples, B, n_roi] -- the distribution behind the error bar of a neuron's trace, which has no per-voxel closed form (the
+    two voxels of a Haar pair share a latent with opposite signs, coarse latents are shared by 2^k depths).  ``boxes``: the
+    integer [n_roi, 6] table of ``roi_boxes``.  Every network and stage list is built ONCE; the samples are then drawn ``chunk``
+    at a time (``posterior_samples(seed=seed, sample_offset=...)``: the same values whatever ``chunk`` is) and reduced by
+    ``ops.roi_means``, so the samples' memory is bounded by ``chunk`` volumes per level.  The price of building the networks once is
+    fixed: the s and t tensors of EVERY step stay alive for the whole call (ten planes per detail channel: about 1 GB at
+    96 x 512 x 512), where the unseeded ``posterior_samples`` frees a step's coefficients before the next step.  Every step
+    all-CAT; NotImplementedError otherwise."""
+    plans = _affine_plans(conv_inn, "posterior_roi_means")
+    n_samples, chunk = int(n_samples), int(chunk)
+    if n_samples < 1 or chunk < 1:
+        raise ValueError("posterior_roi_means: n_samples and chunk must be >= 1")
+    if not float(temperature) >= 0.0:
+        raise ValueError(f"temperature {temperature!r}: the truncation bound must be >= 0")
+    up = _coarsest(conv_inn, cond_nets, cond_input, mean_vols_cache, low)
+    steps = _inverse_stage_lists(plans, cond_nets, cond_input, mean_vols_cache, tuple(up.shape[1:]), up.device)
+    B = up.shape[0]
+    if temperature == 0:                             # every sample is the mean
+        for stages, tabs in steps:
+            up = ops.chain_inv(None, up, stages, tables=tabs)
+        return ops.roi_means(up, boxes).t().unsqueeze(0).repeat(n_samples, 1, 1)
+    out = []
+    for k in range(0, n_samples, chunk):
+        n = min(chunk, n_samples - k)
+        xs = _seeded_samples(steps, up, n, temperature, seed, k, False)
+        out.append(ops.roi_means(xs.view(n * B, *xs.shape[2:]), boxes).t().reshape(n, B, -1))
+    return torch.cat(out)
 
 
 def nll_step(graph, x, c, group=None):

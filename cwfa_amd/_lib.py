@@ -91,6 +91,10 @@ SIGNATURES = {
     "cwfa_channel_affine_f32": (i, [p, p, p, p, i, p, p, i, i, i64, i64, i64, p]),
     "cwfa_chain_inv_f32": (i, [p, p, p, C.POINTER(Chain), i, i, i, i, i64, i64, i64, p, p]),
     "cwfa_chain_inv_var_f32": (i, [p, p, C.POINTER(Chain), f, f, i, i, i, i, i64, i64, p]),
+    "cwfa_rand_uniform_f32": (i, [p, i, i64, i64, C.c_uint64, C.c_uint32, C.c_uint32, p]),
+    "cwfa_rand_trunc_normal_f32": (i, [p, i, i64, i64, f, C.c_uint64, C.c_uint32, C.c_uint32, p]),
+    "cwfa_chain_inv_samples_f32": (i, [p, p, p, C.POINTER(Chain), i, i, i, i, i, i64, i64, i64, i64, i64, i64, f, C.c_uint64, C.c_uint32,
+                                       C.c_uint32, p]),
     "cwfa_chain_fwd_f32": (i, [p, p, p, C.POINTER(Chain), p, i, i, i, i, i64, i64, i64, p, p, p]),
     "cwfa_conv2d_packed_floats": (i64, [i, i, i]),
     "cwfa_conv2d_pack_f32": (i, [p, p, i, i, i, i, p]),

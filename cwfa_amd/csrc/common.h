@@ -171,6 +171,38 @@ __device__ __forceinline__ float cwfa_soft_clamp(float a, int kind, float clamp)
     }
 }
 
+// ---- the device generator of the samplers (cwfa_rand_*_f32, cwfa_chain_inv_samples_f32).
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 known answers are in tests/test_sampler_cpu.py): ten rounds of
+//   (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)),   key += (0x9E3779B9, 0xBB67AE85)
+// The counter convention is part of the interface: element e (the contiguous linear index within one sample) of sample n takes
+// word e & 3 of the block with counter (g & 0xffffffff, g >> 32, sample_offset + n, stream_id), g = e >> 2, under the key
+// (seed & 0xffffffff, seed >> 32) -- so chunked, repeated and differently dispatched calls draw the same values.
+__device__ __forceinline__ u32x4 cwfa_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(M0, c0), l0 = M0 * c0, h1 = __umulhi(M1, c2), l1 = M1 * c2;
+        c0 = h1 ^ c1 ^ k0;
+        c1 = l1;
+        c2 = h0 ^ c3 ^ k1;
+        c3 = l0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return u32x4{c0, c1, c2, c3};
+}
+// the Philox block of group g of sample counter `sample` (= sample_offset + n, modulo 2^32)
+__device__ __forceinline__ u32x4 cwfa_rand_block(uint64_t g, uint32_t sample, uint32_t stream_id, uint32_t k0, uint32_t k1) {
+    return cwfa_philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), sample, stream_id, k0, k1);
+}
+// u = ((r >> 9) + 0.5) * 2^-23: an odd multiple of 2^-24 below 1, exact in fp32 and strictly inside (0, 1)
+__device__ __forceinline__ float cwfa_rand_u01(uint32_t r) { return ((float)(r >> 9) + 0.5f) * 1.1920928955078125e-07f; }
+// the map of _no_grad_trunc_normal_ (mean 0, std 1, bounds +-T): E = (float)erf(T / sqrt 2) from the host; 2u - 1 is exact
+__device__ __forceinline__ float cwfa_rand_trunc_normal(uint32_t r, float E, float T) {
+    const float a = E * (2.0f * cwfa_rand_u01(r) - 1.0f);
+    return fminf(fmaxf(CWFA_SQRT2_F * erfinvf(a), -T), T);
+}
+
 // a compile-time int argument (read as decltype(k)::value), and f(cwfa_ic<i>{}) for i = 0 .. N-1 unrolled at compile time
 template <int K>
 using cwfa_ic = std::integral_constant<int, K>;

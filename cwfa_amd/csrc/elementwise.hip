@@ -976,6 +976,189 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_var_rows4_kernel(const fl
     }
 }
 
+// ---- N samples of the inverse chain with the latents drawn in the kernel (cwfa_chain_inv_samples_f32).  The step is elementwise-
+// affine in z: v[p] = g[p] * z[start(p)] + o[p], where the pair travels like the value of the inverse chain from (1, 0):
+//     (g, o) <- gather_k(g, o);   g <- g * e_k;   o <- (o - t_k) * e_k            e_k = exp(-s_k)
+// The coefficient rows are read ONCE, the pair is formed once per thread, and the loop over the samples is one `low` plane in and
+// two planes out: x[n][2c], x[n][2c+1] = (low[n][c] +- (g z + o)) / sqrt 2.  The latent of output position p of sample n is element
+// e = lin(b, c, h, w) of [B,C,H,W] of the generator (common.h) -- indexed by where the value ARRIVES, so both forms draw the same
+// bits whatever the gathers are; z_out (nullable) receives it where it STARTS, so that cwfa_chain_inv_f32(z_out[n], low[n]) is
+// sample n.
+struct cwfa_sampler {
+    float E, T;                    // E = (float)erf(T / sqrt 2), T = the truncation bound (may be inf)
+    uint32_t k0, k1, stream_id, sample_offset;
+};
+
+// general form: one thread owns one final position and walks the gathers once (any shape, any alignment)
+__global__ __launch_bounds__(256) void chain_samples_kernel(const float* __restrict__ low, float* __restrict__ x, float* __restrict__ z_out,
+                                                            cwfa_chain ch, cwfa_sampler rs, int N, int C, int H, int W, int64_t low_ss,
+                                                            int64_t low_bs, int64_t x_ss, int64_t x_bs, int64_t z_ss, int64_t z_bs) {
+    const int64_t HW = (int64_t)H * W, n = (int64_t)C * HW;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    if (i >= n) return;
+    Pos p{(int)(i / HW), (int)((i / W) % H), (int)(i % W)};
+    int64_t off[CWFA_CHAIN_MAX];
+#pragma unroll
+    for (int k = CWFA_CHAIN_MAX - 1; k >= 0; --k) {
+        if (k < ch.n_stages) {
+            off[k] = lin(p, H, W);
+            p = gather_pos(p, ch.stage[k].perm, ch.stage[k].perm_axis);
+        }
+    }
+    float g = 1.f, o = 0.f;
+#pragma unroll
+    for (int k = 0; k < CWFA_CHAIN_MAX; ++k) {
+        if (k < ch.n_stages) {
+            float s, t;
+            stage_st(ch.stage[k], b, off[k], s, t);
+            const float e = expf(-s);
+            g = g * e;
+            o = (o - t) * e;
+        }
+    }
+    const int c = (int)(i / HW);
+    const int64_t pix = i - (int64_t)c * HW;
+    const uint64_t el = (uint64_t)b * (uint64_t)n + (uint64_t)i;
+    const int64_t zo = b * z_bs + lin(p, H, W);
+    const float* lp = low + b * low_bs + i;
+    float* xp = x + b * x_bs + (int64_t)(2 * c) * HW + pix;
+    for (int s = 0; s < N; ++s) {
+        const u32x4 blk = cwfa_rand_block(el >> 2, rs.sample_offset + (uint32_t)s, rs.stream_id, rs.k0, rs.k1);
+        const float z = cwfa_rand_trunc_normal(blk[el & 3], rs.E, rs.T);
+        const float v = g * z + o, l = lp[s * low_ss];
+        xp[s * x_ss] = (l + v) * CWFA_INV_SQRT2_F;
+        xp[s * x_ss + HW] = (l - v) * CWFA_INV_SQRT2_F;
+        if (z_out) z_out[s * z_ss + zo] = z;
+    }
+}
+
+// 16-byte form, under the conditions of chain_rows4_ok and laid out as chain_rows4_kernel.  A column permutation moves the PAIR
+// between the threads of a row through the double-buffered LDS exchange ([2][g | o][row of the block][W]: twice the bytes of the
+// variance kernel's, once per thread, never per sample).  A thread's four columns are one block of the generator (W is a multiple
+// of four, so e & 3 = 0 at its first column).
+template <int NS>
+__global__ __launch_bounds__(CHAIN_THREADS) void chain_samples_rows4_kernel(const float* __restrict__ low, float* __restrict__ x,
+                                                                            float* __restrict__ z_out, cwfa_chain ch, cwfa_sampler rs, int N,
+                                                                            int C, int H, int W, int64_t low_ss, int64_t low_bs, int64_t x_ss,
+                                                                            int64_t x_bs, int64_t z_ss, int64_t z_bs) {
+    extern __shared__ float rows[];
+    const int tpr = W >> 2, RB = CHAIN_THREADS / tpr;
+    const int r = threadIdx.x / tpr, w4 = (threadIdx.x - r * tpr) * 4;
+    const int b = blockIdx.z, c = blockIdx.y, hh = blockIdx.x * RB + r;
+    const bool live = hh < H;
+    const int h = live ? hh : H - 1;         // rows beyond H in the last block: load row H - 1 (in bounds), take part in the barriers, store nothing
+    const int64_t HW = (int64_t)H * W;
+    const int n = ch.n_stages;
+    RowPos q[NS], src = RowPos{c, h};
+    if (ch.src_c) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k)
+            if (k < n) q[k] = RowPos{ch.src_c[k * C + c], ch.src_h[k * H + h]};
+        src = RowPos{ch.src_c[n * C + c], ch.src_h[n * H + h]};
+    } else {
+#pragma unroll
+        for (int k = NS - 1; k >= 0; --k)
+            if (k < n) {
+                q[k] = src;
+                src = row_gather(src, ch.stage[k].perm, ch.stage[k].perm_axis);
+            }
+    }
+    f32x4 sr[NS], tr[NS];
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        sr[k] = tr[k] = zero;
+        if (k < n) {
+            const int64_t off = ((int64_t)q[k].c * H + q[k].h) * W + w4;
+            if (ch.stage[k].s_raw) sr[k] = ld_stream(ch.stage[k].s_raw + b * ch.stage[k].s_bs + off);
+            if (ch.stage[k].t) tr[k] = ld_stream(ch.stage[k].t + b * ch.stage[k].t_bs + off);
+        }
+    }
+    const int64_t oo = (int64_t)h * W + w4;
+    const float* lp = low + b * low_bs + (int64_t)c * HW + oo;
+    f32x4 lo = ld_stream(lp);               // sample 0's, and every sample's where they share it (low_ss == 0)
+    f32x4 g = {1.f, 1.f, 1.f, 1.f}, o = zero;
+    int nx = 0;
+#pragma unroll
+    for (int k = 0; k < NS; ++k)
+        if (k < n) {
+            if (ch.stage[k].perm && ch.stage[k].perm_axis == 3) {           // uniform over the block
+                float* bg = rows + (size_t)(nx & 1) * (2 * CHAIN_THREADS * 4) + (size_t)r * W;
+                float* bo = bg + CHAIN_THREADS * 4;
+                ++nx;
+                *reinterpret_cast<f32x4*>(bg + w4) = g;
+                *reinterpret_cast<f32x4*>(bo + w4) = o;
+                __syncthreads();
+                const int64_t* pk = ch.stage[k].perm + w4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int wj = (int)pk[j];
+                    g[j] = bg[wj];
+                    o[j] = bo[wj];
+                }
+            }
+            f32x4 sv, tv;
+            stage_st4(ch.stage[k], sr[k], tr[k], sv, tv);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float e = __expf(-sv[j]);
+                g[j] = g[j] * e;
+                o[j] = (o[j] - tv[j]) * e;
+            }
+        }
+    if (!live) return;                       // no barrier below
+    int64_t zo[4] = {0, 0, 0, 0};
+    if (z_out) {                             // where each of the four values starts: the column gathers walked backwards
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int w0 = w4 + j;
+#pragma unroll
+            for (int k = NS - 1; k >= 0; --k)
+                if (k < n && ch.stage[k].perm && ch.stage[k].perm_axis == 3) w0 = (int)ch.stage[k].perm[w0];
+            zo[j] = b * z_bs + ((int64_t)src.c * H + src.h) * W + w0;
+        }
+    }
+    const uint64_t grp = ((uint64_t)b * (uint64_t)C * (uint64_t)HW + (uint64_t)c * (uint64_t)HW + (uint64_t)oo) >> 2;
+    float* xp = x + b * x_bs + (int64_t)(2 * c) * HW + oo;
+    for (int s = 0; s < N; ++s) {
+        if (s > 0 && low_ss != 0) lo = ld_stream(lp + s * low_ss);
+        const u32x4 blk = cwfa_rand_block(grp, rs.sample_offset + (uint32_t)s, rs.stream_id, rs.k0, rs.k1);
+        f32x4 z;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z[j] = cwfa_rand_trunc_normal(blk[j], rs.E, rs.T);
+        const f32x4 v = g * z + o;
+        st_stream<true>(xp + s * x_ss, (lo + v) * CWFA_INV_SQRT2_F);
+        st_stream<true>(xp + s * x_ss + HW, (lo - v) * CWFA_INV_SQRT2_F);
+        if (z_out) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) z_out[s * z_ss + zo[j]] = z[j];
+        }
+    }
+}
+
+// ---- the generator alone: out[n][e] for e < len (cwfa_rand_uniform_f32, cwfa_rand_trunc_normal_f32).  A thread owns one block of
+// four elements of one sample; 16-byte stores where the host found every sample's row on the 16-byte grid.
+template <bool NORMAL>
+__global__ __launch_bounds__(256) void rand_kernel(float* __restrict__ out, int N, int64_t len, int64_t out_ss, cwfa_sampler rs, int vec) {
+    const int64_t groups = (len + 3) >> 2;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= groups * N) return;
+    const int64_t s = i / groups, grp = i - s * groups;
+    const u32x4 blk = cwfa_rand_block((uint64_t)grp, rs.sample_offset + (uint32_t)s, rs.stream_id, rs.k0, rs.k1);
+    f32x4 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = NORMAL ? cwfa_rand_trunc_normal(blk[j], rs.E, rs.T) : cwfa_rand_u01(blk[j]);
+    float* dst = out + s * out_ss + 4 * grp;
+    if (vec && 4 * grp + 4 <= len) {
+        *reinterpret_cast<f32x4*>(dst) = v;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * grp + j < len) dst[j] = v[j];
+    }
+}
+
 // rows variant usable?  (LDS budget, grid limits)
 // Backward of  L = gscale * 0.5 * sum z^2  -  ldscale * sum_b logdet_b  (CWFA.py:970-978: gscale = 1/numel,
 // ldscale = 1/(B*numel)) through a whole forward chain in ONE launch and without stored activations: the flow is
@@ -1212,6 +1395,96 @@ extern "C" int cwfa_chain_inv_var_f32(const float* var_low, float* out, const cw
     hipLaunchKernelGGL(chain_inv_var_kernel, grid, dim3(256), 0, (hipStream_t)stream, var_low, out, sc, z_var, std_scale, C, H, W, var_low_bs,
                        out_bs);
     CWFA_LAUNCH_CHECK("cwfa_chain_inv_var_f32");
+    return CWFA_OK;
+}
+
+// the generator's parameters of a call; temperature > 0 (inf allowed), NaN refused
+static int make_sampler(const char* name, float temperature, uint64_t seed, uint32_t stream_id, uint32_t sample_offset, cwfa_sampler* rs) {
+    CWFA_REQUIRE(temperature > 0.f, CWFA_E_INVAL, "%s: temperature %g must be > 0 (the truncation bound; 0 is the mean: no draw)", name,
+                 (double)temperature);
+    rs->E = (float)std::erf((double)temperature / std::sqrt(2.0));
+    rs->T = temperature;
+    rs->k0 = (uint32_t)(seed & 0xffffffffu);
+    rs->k1 = (uint32_t)(seed >> 32);
+    rs->stream_id = stream_id;
+    rs->sample_offset = sample_offset;
+    return CWFA_OK;
+}
+
+static int launch_rand(const char* name, bool normal, float* out, int N, int64_t n, int64_t out_ss, const cwfa_sampler& rs, void* stream) {
+    CWFA_REQUIRE(out, CWFA_E_INVAL, "%s: null pointer", name);
+    CWFA_REQUIRE(N >= 0 && n >= 0, CWFA_E_SHAPE, "%s: bad shape", name);
+    CWFA_REQUIRE(N <= 1 || out_ss >= n, CWFA_E_INVAL, "%s: sample stride %lld below the %lld elements of a sample", name, (long long)out_ss,
+                 (long long)n);
+    if (N == 0 || n == 0) return CWFA_OK;
+    const int64_t threads = ((n + 3) >> 2) * N, blocks = (threads + 255) / 256;
+    CWFA_REQUIRE(blocks <= 0x7fffffff, CWFA_E_SHAPE, "%s: %lld samples of %lld elements exceed one launch", name, (long long)N, (long long)n);
+    const int vec = cwfa_aligned16(out) && (N == 1 || (out_ss & 3) == 0);
+    if (normal)
+        hipLaunchKernelGGL((rand_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, N, n, out_ss, rs, vec);
+    else
+        hipLaunchKernelGGL((rand_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, out, N, n, out_ss, rs, vec);
+    CWFA_LAUNCH_CHECK(name);
+    return CWFA_OK;
+}
+
+extern "C" int cwfa_rand_uniform_f32(float* out, int N, int64_t n, int64_t out_ss, uint64_t seed, uint32_t stream_id, uint32_t sample_offset,
+                                     void* stream) {
+    cwfa_sampler rs;
+    int rc = make_sampler("cwfa_rand_uniform_f32", 1.f, seed, stream_id, sample_offset, &rs);
+    if (rc) return rc;
+    return launch_rand("cwfa_rand_uniform_f32", false, out, N, n, out_ss, rs, stream);
+}
+
+extern "C" int cwfa_rand_trunc_normal_f32(float* out, int N, int64_t n, int64_t out_ss, float temperature, uint64_t seed, uint32_t stream_id,
+                                          uint32_t sample_offset, void* stream) {
+    cwfa_sampler rs;
+    int rc = make_sampler("cwfa_rand_trunc_normal_f32", temperature, seed, stream_id, sample_offset, &rs);
+    if (rc) return rc;
+    return launch_rand("cwfa_rand_trunc_normal_f32", true, out, N, n, out_ss, rs, stream);
+}
+
+extern "C" int cwfa_chain_inv_samples_f32(const float* low, float* x, float* z_out, const cwfa_chain* ch, int N, int B, int C, int H, int W,
+                                          int64_t low_ss, int64_t low_bs, int64_t x_ss, int64_t x_bs, int64_t z_ss, int64_t z_bs,
+                                          float temperature, uint64_t seed, uint32_t stream_id, uint32_t sample_offset, void* stream) {
+    CWFA_REQUIRE(low && x, CWFA_E_INVAL, "cwfa_chain_inv_samples_f32: null pointer");
+    CWFA_REQUIRE(N >= 0 && B >= 0 && C >= 0 && H >= 0 && W >= 0 && B <= 65535, CWFA_E_SHAPE, "cwfa_chain_inv_samples_f32: bad shape");
+    int rc = check_chain("cwfa_chain_inv_samples_f32", ch);
+    if (rc) return rc;
+    cwfa_sampler rs;
+    rc = make_sampler("cwfa_chain_inv_samples_f32", temperature, seed, stream_id, sample_offset, &rs);
+    if (rc) return rc;
+    CWFA_REQUIRE(low_ss >= 0 && x_ss >= 0 && z_ss >= 0, CWFA_E_INVAL, "cwfa_chain_inv_samples_f32: negative sample stride");
+    const int64_t n = (int64_t)C * H * W;
+    if (N == 0 || B == 0 || n == 0) return CWFA_OK;
+    CWFA_REQUIRE(B == 1 || (low_bs >= n && x_bs >= 2 * n && (!z_out || z_bs >= n)), CWFA_E_INVAL,
+                 "cwfa_chain_inv_samples_f32: a batch stride is below the elements of one sample's batch entry");
+    const int64_t low_ext = (B - 1) * low_bs + n, x_ext = (B - 1) * x_bs + 2 * n, z_ext = (B - 1) * z_bs + n;      // elements one sample spans
+    CWFA_REQUIRE(N == 1 || ((low_ss == 0 || low_ss >= low_ext) && x_ss >= x_ext && (!z_out || z_ss >= z_ext)), CWFA_E_INVAL,
+                 "cwfa_chain_inv_samples_f32: a sample stride is below the elements of one sample (low_ss = 0 shares low)");
+    if (z_out) {
+        const float *x_end = x + (N - 1) * x_ss + x_ext, *z_end = z_out + (N - 1) * z_ss + z_ext;
+        CWFA_REQUIRE(z_end <= x || x_end <= z_out, CWFA_E_INVAL, "cwfa_chain_inv_samples_f32: z_out overlaps x");
+    }
+    size_t lds;
+    // z_out is written with scalar stores (its positions scatter): it need not sit on the 16-byte grid
+    if (chain_rows4_ok(ch, C, H, W, B, &lds, low, x, nullptr, low_bs, x_bs, 0) && (low_ss & 3) == 0 && (x_ss & 3) == 0) {
+        const int RB = CHAIN_THREADS * 4 / W;
+        const dim3 grid((H + RB - 1) / RB, C, B);
+        lds *= 2;                              // the exchange carries the pair (g, o)
+        if (ch->n_stages <= 6)
+            hipLaunchKernelGGL((chain_samples_rows4_kernel<6>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, low, x, z_out, *ch, rs, N, C,
+                               H, W, low_ss, low_bs, x_ss, x_bs, z_ss, z_bs);
+        else
+            hipLaunchKernelGGL((chain_samples_rows4_kernel<CWFA_CHAIN_MAX>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, low, x, z_out,
+                               *ch, rs, N, C, H, W, low_ss, low_bs, x_ss, x_bs, z_ss, z_bs);
+        CWFA_LAUNCH_CHECK("cwfa_chain_inv_samples_f32");
+        return CWFA_OK;
+    }
+    dim3 grid((unsigned)((n + 255) / 256), B);
+    hipLaunchKernelGGL(chain_samples_kernel, grid, dim3(256), 0, (hipStream_t)stream, low, x, z_out, *ch, rs, N, C, H, W, low_ss, low_bs, x_ss,
+                       x_bs, z_ss, z_bs);
+    CWFA_LAUNCH_CHECK("cwfa_chain_inv_samples_f32");
     return CWFA_OK;
 }
 

@@ -8,7 +8,7 @@ import torch
 from . import _lib
 from ._lib import AffineStage, Chain, ConvOpts, check
 
-__all__ = ["haar1d", "haar2d", "gather", "affine", "channel_affine", "chain_inv", "chain_inv_var", "chain_fwd", "pack_conv_weight",
+__all__ = ["haar1d", "haar2d", "gather", "affine", "channel_affine", "chain_inv", "chain_inv_var", "chain_inv_samples", "rand_uniform", "rand_trunc_normal", "chain_fwd", "pack_conv_weight",
            "conv2d", "conv2d_wgrad", "elu_bwd", "set_precision", "gelu_add", "gelu_bwd", "layernorm_bwd", "attention_bwd", "plane_affine", "bn_bwd_stats", "bn_act_bwd", "maxpool2_bwd", "chain_bwd", "chain_inv_bwd", "prelu_bwd", "conv3d_1k1_backward", "pack_1x1_panel", "pack_split_layer_weight", "subnet_layer", "conv3d_1k1", "channel_stats", "bn_fold", "bn_running_update", "maxpool", "sample_stats", "layernorm_apply",
            "attention_combine", "scale_channels", "axpby", "stage", "lion_step", "global_extrema", "wmse_loss"]
 
@@ -299,6 +299,86 @@ def chain_inv_var(var_low, stages, z_var, shape=None, std_scale=0.0, tables=None
     check(L.cwfa_chain_inv_var_f32(_p(var_low), _p(out), C.byref(ch), float(z_var), float(std_scale), B, Cc, H, W, vbs,
                                    2 * Cc * H * W, _stream()), "chain_inv_var")
     return out
+
+
+def _rand_args(seed, stream, sample_offset, name):
+    seed, stream, sample_offset = int(seed), int(stream), int(sample_offset)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"{name}: seed {seed} is not an unsigned 64-bit number")
+    if not 0 <= stream < 1 << 32 or not 0 <= sample_offset < 1 << 32:
+        raise ValueError(f"{name}: stream {stream} / sample_offset {sample_offset} are not unsigned 32-bit numbers")
+    return C.c_uint64(seed), C.c_uint32(stream), C.c_uint32(sample_offset)
+
+
+def _rand_out(shape, device, name):
+    shape = tuple(int(v) for v in shape)
+    if len(shape) < 1 or any(v < 0 for v in shape):
+        raise ValueError(f"{name}: shape {shape} needs a leading sample axis and no negative size")
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    out = torch.empty(shape, dtype=torch.float32, device=device)
+    _dev(out, name)
+    n = 1
+    for v in shape[1:]:
+        n *= v
+    return out, shape[0], n
+
+
+def rand_uniform(shape, seed, stream=0, sample_offset=0, device=None):
+    """Uniforms in (0, 1) of the counter-based generator (cwfa_rand_uniform_f32): ``shape[0]`` is the SAMPLE axis, the rest is one
+    sample.  Sample n of a call equals sample 0 of a call with ``sample_offset + n``; ``stream`` separates independent uses of
+    one seed."""
+    out, N, n = _rand_out(shape, device, "rand_uniform")
+    if out.numel() == 0:
+        return out
+    check(_lib.lib().cwfa_rand_uniform_f32(_p(out), N, n, n, *_rand_args(seed, stream, sample_offset, "rand_uniform"), _stream()),
+          "rand_uniform")
+    return out
+
+
+def rand_trunc_normal(shape, temperature, seed, stream=0, sample_offset=0, device=None):
+    """Standard normals truncated to [-temperature, temperature] (the draw of ``CWFA.sample_z_truncated``) from the same generator
+    and counters as ``rand_uniform``, in one launch.  ``temperature`` > 0 (inf allowed)."""
+    out, N, n = _rand_out(shape, device, "rand_trunc_normal")
+    seed, stream, sample_offset = _rand_args(seed, stream, sample_offset, "rand_trunc_normal")
+    if out.numel() == 0 and float(temperature) > 0.0:
+        return out
+    check(_lib.lib().cwfa_rand_trunc_normal_f32(_p(out), N, n, n, float(temperature), seed, stream, sample_offset, _stream()),
+          "rand_trunc_normal")
+    return out
+
+
+def chain_inv_samples(low, stages, n_samples, temperature, seed, stream=0, sample_offset=0, tables=None, return_z=False):
+    """``n_samples`` draws [N,B,2C,H,W] of ``chain_inv(z, low, stages)`` in ONE launch, z drawn in the kernel as by
+    ``rand_trunc_normal((N,B,C,H,W), temperature, seed, stream, sample_offset)`` and indexed by the position at which a latent
+    ARRIVES at the end of the chain.  ``low``: [B,C,H,W] (shared by all samples) or [N,B,C,H,W] (each sample its own).  With
+    ``return_z`` also z [N,B,C,H,W] laid out where the latents START, so that ``chain_inv(z[n], low[n], stages)`` reproduces sample
+    n.  ``temperature`` must be > 0: at 0 every sample is ``chain_inv(None, low, stages)``.  ``tables`` as for ``chain_inv``."""
+    L = _lib.lib()
+    N = int(n_samples)
+    if N < 1:
+        raise ValueError("chain_inv_samples: n_samples must be >= 1")
+    if not float(temperature) > 0.0:
+        raise ValueError(f"chain_inv_samples: temperature {temperature!r} must be > 0 (use chain_inv(None, ...) for the mean)")
+    _dev(low, "low")
+    if low.dim() == 5:
+        if low.shape[0] != N:
+            raise ValueError(f"chain_inv_samples: low holds {low.shape[0]} samples, n_samples = {N}")
+        low = low.contiguous()
+        _, B, Cc, H, W = low.shape
+        lss, lbs = B * Cc * H * W, Cc * H * W
+    else:
+        low, lbs = planes(low, "low")
+        B, Cc, H, W = low.shape
+        lss = 0
+    ch, keep = _chain(stages, tables)
+    out = torch.empty((N, B, 2 * Cc, H, W), dtype=torch.float32, device=low.device)
+    z = torch.empty((N, B, Cc, H, W), dtype=torch.float32, device=low.device) if return_z else None
+    n = Cc * H * W
+    seed, stream, sample_offset = _rand_args(seed, stream, sample_offset, "chain_inv_samples")
+    check(L.cwfa_chain_inv_samples_f32(_p(low), _p(out), _p(z), C.byref(ch), N, B, Cc, H, W, lss, lbs, 2 * B * n, 2 * n, B * n, n,
+                                       float(temperature), seed, stream, sample_offset, _stream()), "chain_inv_samples")
+    return (out, z) if return_z else out
 
 
 def chain_fwd(x, stages, final_perm=None, logdet=None, sumsq=None, tables=None):

@@ -185,6 +185,31 @@ int cwfa_chain_inv_f32(const float* z, const float* low, float* x, const cwfa_ch
 int cwfa_chain_inv_var_f32(const float* var_low, float* out, const cwfa_chain* ch, float z_var, float std_scale,
                            int B, int C, int H, int W, int64_t var_low_bs, int64_t out_bs, void* stream);
 
+/* The counter-based generator of the samplers: Philox4x32-10 under the key (seed & 0xffffffff, seed >> 32).  Element e (the
+ * contiguous linear index within ONE sample) of sample n takes word e & 3 of the block with counter
+ * (g & 0xffffffff, g >> 32, sample_offset + n, stream_id), g = e >> 2; as a uniform, u = ((word >> 9) + 0.5) * 2^-23 (exact in
+ * fp32, strictly inside (0, 1)).  A call over samples [0, N) therefore equals calls over [0, k) and, with sample_offset + k,
+ * [k, N), whatever kernel form runs.  out [N][n] with sample stride out_ss (elements, >= n). */
+int cwfa_rand_uniform_f32(float* out, int N, int64_t n, int64_t out_ss, uint64_t seed, uint32_t stream_id, uint32_t sample_offset,
+                          void* stream);
+/* The latent draw of sample_z_truncated (CWFA.py:47-64; utils.py:42-82 with mean 0, std 1, bounds +-temperature) in one launch:
+ *   z = clamp(sqrt2f * erfinvf(E * (2u - 1)), -T, T),   E = (float)erf(T / sqrt 2) formed in double on the host
+ * temperature must be > 0 (inf allowed: E = 1 and |z| stays below about 5.2). */
+int cwfa_rand_trunc_normal_f32(float* out, int N, int64_t n, int64_t out_ss, float temperature, uint64_t seed, uint32_t stream_id,
+                               uint32_t sample_offset, void* stream);
+
+/* N posterior samples of one conditional step in ONE launch, the latents drawn in the kernel:
+ *   x[n] = cwfa_chain_inv_f32(z[n], low[n], ch)   with z[n] drawn as by cwfa_rand_trunc_normal_f32
+ * The coefficient rows of `ch` (as for cwfa_chain_inv_f32; src_c / src_h honoured) are read once for all samples; per sample one
+ * low plane is read and two planes are written.  low [N][B,C,H,W] with sample stride low_ss (0: every sample shares one low, as
+ * at the coarsest step), x [N][B,2C,H,W], z_out (nullable) [N][B,C,H,W]; all sample and batch strides in elements, 64-bit.
+ * The latent that ARRIVES at position (b, c, h, w) of the chain's output is element e = ((b*C + c)*H + h)*W + w of the generator
+ * above; z_out receives it at the position where it STARTS, so that cwfa_chain_inv_f32(z_out[n], low[n], ..) reproduces x[n]
+ * (to rounding: the kernel evaluates g*z + o with the chain collapsed to one pair per element).  temperature must be > 0. */
+int cwfa_chain_inv_samples_f32(const float* low, float* x, float* z_out, const cwfa_chain* ch, int N, int B, int C, int H, int W,
+                               int64_t low_ss, int64_t low_bs, int64_t x_ss, int64_t x_bs, int64_t z_ss, int64_t z_bs,
+                               float temperature, uint64_t seed, uint32_t stream_id, uint32_t sample_offset, void* stream);
+
 /* Forward (NLL direction) of one whole conditional step in ONE launch:
  *   (low, v) = Split(Haar1D(x));  for each stage: v <- A_k(gather_k(v));  z = gather_final(v)
  * final_perm (nullable) is the trailing PermuteRandom (networks.py:353-357).
