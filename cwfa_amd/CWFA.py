@@ -411,6 +411,54 @@ def posterior_roi_means(conv_inn, cond_nets, cond_input, mean_vols_cache, boxes,
     return torch.cat(out)
 
 
+@amp_function
+@torch.no_grad()
+def nll_maps(conv_inn, cond_nets, gt_volume, cond_input, mean_vols_cache, want_z=False):
+    """WHERE a volume disagrees with the flow (every step all-CAT, NotImplementedError otherwise: only there
+    does the density factorise over the coefficients).  With the conditions of ``forward_nll_pass`` every Haar detail coefficient
+    of every step is an independent Gaussian g z + o, so its standardised residual z = (d - o) / g and its share
+    nll = z^2 / 2 + log g of the step's negative log-likelihood are exact.  One ``ops.chain_nll_map`` launch per step, fine ->
+    coarse, each fed by the previous step's low band, then one ``ops.nll_compose``.  Returns
+
+        (volume_map [B,D,H,W], maps, z_maps, sums, low)
+
+    ``maps[n]`` [B, D / 2^(n+1), H, W]: the step-n coefficients' shares, each at the coefficient's own position; a coefficient covers
+    2^(n+1) adjacent depths at its pixel and ``volume_map`` spreads it evenly over them, so its total is the pyramid's NLL.
+    ``z_maps``: the z-scores laid out likewise (None unless ``want_z``): for a volume drawn from the posterior they are the latents
+    that were drawn -- see ``zscore_coverage``.  ``sums`` float64 [B, S]: per sample and step the sum of ``maps[n]``
+    = 0.5 * sum z^2 - logdet, what ``nll_terms`` reduces.  ``low``: the coarsest low band, as ``forward_nll_pass`` returns it."""
+    plans = _affine_plans(conv_inn, "nll_maps")
+    S1 = len(conv_inn)
+    B = gt_volume.shape[0]
+    sums = [torch.zeros(B, dtype=torch.float64, device=gt_volume.device) for _ in range(S1)]
+    maps, z_maps = [], [] if want_z else None
+    gt = gt_volume
+    from .networks import omega_first_scope
+    with omega_first_scope(list(cond_nets[:S1]), cond_input):
+        for n in range(S1):
+            c = [cond_nets[n](cond_input)[-1], mean_vols_cache[n]]
+            stages, tabs = plans[n].inverse_stages(c, (gt.shape[1] // 2,) + tuple(gt.shape[2:]), gt.device)
+            nll, gt, z = ops.chain_nll_map(gt, stages, tables=tabs, want_low=True, want_z=want_z, want_nll=True, nll_sum=sums[n])
+            maps.append(nll)
+            if want_z:
+                z_maps.append(z)
+    return ops.nll_compose(maps), maps, z_maps, torch.stack(sums, dim=1), gt
+
+
+def zscore_coverage(z_levels, ks=(1.0, 2.0, 3.0)):
+    """The calibration readout of the posterior: per level of z-scores (``nll_maps(..., want_z=True)[2]``, or any tensors) the
+    fraction of |z| <= k beside the standard normal's erf(k / sqrt 2).  Returns (observed float64 [levels, len(ks)] on the
+    z-scores' device, expected float64 [len(ks)]); a posterior that is too narrow for the volumes it is shown covers less than
+    expected, one that is too wide more.  Torch reductions on the device; nothing waits for it."""
+    z_levels = list(z_levels)
+    ks = [float(k) for k in ks]
+    if not z_levels or not ks:
+        raise ValueError("zscore_coverage: needs at least one level and one k")
+    rows = [torch.stack([(z.abs() <= k).sum().to(torch.float64) / z.numel() for k in ks]) for z in z_levels]
+    expected = torch.tensor([math.erf(k / math.sqrt(2.0)) for k in ks], dtype=torch.float64)
+    return torch.stack(rows), expected
+
+
 def nll_step(graph, x, c, group=None):
     """Training-time NLL of one step, CWFA.py:966-978:  (0.5*||Z0||^2 - mean_b logdet) / numel(batch volume),
     with the norm taken over the WHOLE (global) batch.  The divisor is ``upsampled_vol.numel()`` = B*D_n*H*W, the step's

@@ -65,6 +65,13 @@ class LionTable(C.Structure):
     _fields_ = [("n", C.c_int), ("t", LionTensor * LION_MAX_TENSORS)]
 
 
+NLL_MAX_LEVELS = 8                 # CWFA_NLL_MAX_LEVELS
+
+
+class NllLevels(C.Structure):
+    _fields_ = [("n", C.c_int), ("level", c_f32p * NLL_MAX_LEVELS), ("bs", C.c_int64 * NLL_MAX_LEVELS)]
+
+
 EXTREMA_STRIDE = 12                # CWFA_EXTREMA_STRIDE
 SELECT_WORKSPACE_BYTES = 8448      # CWFA_SELECT_WORKSPACE_BYTES
 PREP_MAX_BINS = 10239              # CWFA_PREP_MAX_BINS
@@ -95,6 +102,8 @@ SIGNATURES = {
     "cwfa_rand_trunc_normal_f32": (i, [p, i, i64, i64, f, C.c_uint64, C.c_uint32, C.c_uint32, p]),
     "cwfa_chain_inv_samples_f32": (i, [p, p, p, C.POINTER(Chain), i, i, i, i, i, i64, i64, i64, i64, i64, i64, f, C.c_uint64, C.c_uint32,
                                        C.c_uint32, p]),
+    "cwfa_chain_nll_map_f32": (i, [p, p, p, p, C.POINTER(Chain), i, i, i, i, i64, i64, i64, i64, p, p]),
+    "cwfa_nll_compose_f32": (i, [C.POINTER(NllLevels), p, i, i, i64, i64, p]),
     "cwfa_chain_fwd_f32": (i, [p, p, p, C.POINTER(Chain), p, i, i, i, i, i64, i64, i64, p, p, p]),
     "cwfa_conv2d_packed_floats": (i64, [i, i, i]),
     "cwfa_conv2d_pack_f32": (i, [p, p, i, i, i, i, p]),

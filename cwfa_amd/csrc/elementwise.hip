@@ -1488,6 +1488,253 @@ extern "C" int cwfa_chain_inv_samples_f32(const float* low, float* x, float* z_o
     return CWFA_OK;
 }
 
+// ---- per-coefficient z-scores and NLL shares of a given volume (cwfa_chain_nll_map_f32).  Given the conditions the detail d[p] of a
+// CAT step is the Gaussian g[p] * z + o[p] (the pair of chain_samples_kernel): its standardised residual is z = (d - o) / g and its
+// share of the step's NLL is z^2 / 2 + log g.  The kernels carry a = -log g as a SUM, a <- gather_k(a) + s_k, beside the offset
+// o <- (gather_k(o) - t_k) * exp(-s_k): |a| reaches stages * clamp, so it takes ONE precise expf(a) per element (as the variance
+// kernel does), and log g is never formed from a product.  Everything is read and written at the thread's own position.
+__device__ __forceinline__ void nll_map_out(float e, float od, float o, float a, float& lowv, float& z, float& nv) {
+    lowv = (e + od) * CWFA_INV_SQRT2_F;
+    z = ((e - od) * CWFA_INV_SQRT2_F - o) * expf(a);
+    nv = 0.5f * z * z - a;
+}
+
+// general form: one thread owns one volume-side position and walks the gathers once (any shape, any alignment)
+__global__ __launch_bounds__(256) void chain_nll_map_kernel(const float* __restrict__ x, float* __restrict__ low, float* __restrict__ zout,
+                                                            float* __restrict__ nll, cwfa_chain ch, int C, int H, int W, int64_t x_bs,
+                                                            int64_t low_bs, int64_t z_bs, int64_t nll_bs, double* __restrict__ nll_sum) {
+    __shared__ double red[16];
+    const int64_t HW = (int64_t)H * W, n = (int64_t)C * HW;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    float nv = 0.f;
+    if (i < n) {
+        Pos p{(int)(i / HW), (int)((i / W) % H), (int)(i % W)};
+        int64_t off[CWFA_CHAIN_MAX];
+#pragma unroll
+        for (int k = CWFA_CHAIN_MAX - 1; k >= 0; --k) {
+            if (k < ch.n_stages) {
+                off[k] = lin(p, H, W);
+                p = gather_pos(p, ch.stage[k].perm, ch.stage[k].perm_axis);
+            }
+        }
+        float a = 0.f, o = 0.f;
+#pragma unroll
+        for (int k = 0; k < CWFA_CHAIN_MAX; ++k) {
+            if (k < ch.n_stages) {
+                float s, t;
+                stage_st(ch.stage[k], b, off[k], s, t);
+                o = (o - t) * expf(-s);
+                a = a + s;
+            }
+        }
+        const int c = (int)(i / HW);
+        const int64_t pix = i - (int64_t)c * HW;
+        const float* xp = x + b * x_bs + (int64_t)(2 * c) * HW + pix;
+        float lowv, z;
+        nll_map_out(xp[0], xp[HW], o, a, lowv, z, nv);
+        if (low) low[b * low_bs + i] = lowv;
+        if (zout) zout[b * z_bs + i] = z;
+        if (nll) nll[b * nll_bs + i] = nv;
+    }
+    if (nll_sum) {
+        const double tot = cwfa_block_sum((double)nv, red);
+        if (threadIdx.x == 0) atomicAdd(&nll_sum[b], tot);
+    }
+}
+
+// 16-byte form, under the conditions of chain_rows4_ok and laid out as chain_samples_rows4_kernel: a thread owns four columns of one
+// row, its x pair (read ONCE here, at the thread's own position) and all its coefficient rows are in flight before the first use as
+// non-temporal loads, and a column permutation moves the pair (a, o) between the threads of a row through the double-buffered LDS
+// exchange ([2][a | o][row of the block][W]).  The x pair is loaded FIRST, so that d and low are formed -- and low stored -- while the
+// coefficient rows are still on their way: the pair's eight registers are free before the chain starts (80 VGPRs = six waves per
+// SIMD; with the pair kept to the end it was 82 = five).  Dead rows of the last block take part in the barriers and store nothing.
+template <int NS>
+__global__ __launch_bounds__(CHAIN_THREADS) void chain_nll_map_rows4_kernel(const float* __restrict__ x, float* __restrict__ low,
+                                                                            float* __restrict__ zout, float* __restrict__ nll, cwfa_chain ch,
+                                                                            int C, int H, int W, int64_t x_bs, int64_t low_bs, int64_t z_bs,
+                                                                            int64_t nll_bs, double* __restrict__ nll_sum) {
+    extern __shared__ float rows[];
+    __shared__ double red[16];
+    const int tpr = W >> 2, RB = CHAIN_THREADS / tpr;
+    const int r = threadIdx.x / tpr, w4 = (threadIdx.x - r * tpr) * 4;
+    const int b = blockIdx.z, c = blockIdx.y, hh = blockIdx.x * RB + r;
+    const bool live = hh < H;
+    const int h = live ? hh : H - 1;         // rows beyond H in the last block: load row H - 1 (in bounds), take part in the barriers, store nothing
+    const int64_t HW = (int64_t)H * W;
+    const int n = ch.n_stages;
+    RowPos q[NS];
+    if (ch.src_c) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k)
+            if (k < n) q[k] = RowPos{ch.src_c[k * C + c], ch.src_h[k * H + h]};
+    } else {
+        RowPos src = RowPos{c, h};
+#pragma unroll
+        for (int k = NS - 1; k >= 0; --k)
+            if (k < n) {
+                q[k] = src;
+                src = row_gather(src, ch.stage[k].perm, ch.stage[k].perm_axis);
+            }
+    }
+    const int64_t oo = (int64_t)h * W + w4, po = (int64_t)c * HW + oo;
+    const f32x4 xe = ld_stream(x + b * x_bs + (int64_t)(2 * c) * HW + oo);          // the oldest loads: the first to be waited for
+    const f32x4 xo = ld_stream(x + b * x_bs + (int64_t)(2 * c + 1) * HW + oo);
+    f32x4 sr[NS], tr[NS];
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        sr[k] = tr[k] = zero;
+        if (k < n) {
+            const int64_t off = ((int64_t)q[k].c * H + q[k].h) * W + w4;
+            if (ch.stage[k].s_raw) sr[k] = ld_stream(ch.stage[k].s_raw + b * ch.stage[k].s_bs + off);
+            if (ch.stage[k].t) tr[k] = ld_stream(ch.stage[k].t + b * ch.stage[k].t_bs + off);
+        }
+    }
+    // the pair is done with once d is formed: low leaves while the coefficient rows are still on their way
+    const f32x4 d = (xe - xo) * CWFA_INV_SQRT2_F;
+    if (live && low) st_stream<false>(low + b * low_bs + po, (xe + xo) * CWFA_INV_SQRT2_F);          // the next step's input: left in the cache
+    f32x4 a = zero, o = zero;
+    int nx = 0;
+#pragma unroll
+    for (int k = 0; k < NS; ++k)
+        if (k < n) {
+            if (ch.stage[k].perm && ch.stage[k].perm_axis == 3) {           // uniform over the block
+                float* ba = rows + (size_t)(nx & 1) * (2 * CHAIN_THREADS * 4) + (size_t)r * W;
+                float* bo = ba + CHAIN_THREADS * 4;
+                ++nx;
+                *reinterpret_cast<f32x4*>(ba + w4) = a;
+                *reinterpret_cast<f32x4*>(bo + w4) = o;
+                __syncthreads();
+                const int64_t* pk = ch.stage[k].perm + w4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int wj = (int)pk[j];
+                    a[j] = ba[wj];
+                    o[j] = bo[wj];
+                }
+            }
+            f32x4 sv, tv;
+            stage_st4(ch.stage[k], sr[k], tr[k], sv, tv);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                o[j] = (o[j] - tv[j]) * __expf(-sv[j]);        // |s| <= clamp: the fast exponential, as in the chain kernels
+                a[j] = a[j] + sv[j];
+            }
+        }
+    double nsum = 0.0;
+    if (live) {
+        f32x4 z, nv;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            z[j] = (d[j] - o[j]) * expf(a[j]);
+            nv[j] = 0.5f * z[j] * z[j] - a[j];
+        }
+        if (zout) st_stream<true>(zout + b * z_bs + po, z);
+        if (nll) st_stream<true>(nll + b * nll_bs + po, nv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) nsum += (double)nv[j];
+    }
+    if (nll_sum) {
+        const double tot = cwfa_block_sum(nsum, red);
+        if (threadIdx.x == 0) atomicAdd(&nll_sum[b], tot);
+    }
+}
+
+extern "C" int cwfa_chain_nll_map_f32(const float* x, float* low, float* z, float* nll, const cwfa_chain* ch, int B, int C, int H, int W,
+                                      int64_t x_bs, int64_t low_bs, int64_t z_bs, int64_t nll_bs, double* nll_sum, void* stream) {
+    CWFA_REQUIRE(x, CWFA_E_INVAL, "cwfa_chain_nll_map_f32: null pointer");
+    CWFA_REQUIRE(low || z || nll || nll_sum, CWFA_E_INVAL, "cwfa_chain_nll_map_f32: no output requested (low, z, nll and nll_sum are all null)");
+    CWFA_REQUIRE(B >= 0 && C >= 0 && H >= 0 && W >= 0 && B <= 65535, CWFA_E_SHAPE, "cwfa_chain_nll_map_f32: bad shape");
+    int rc = check_chain("cwfa_chain_nll_map_f32", ch);
+    if (rc) return rc;
+    const int64_t n = (int64_t)C * H * W;
+    if (B == 0 || n == 0) return CWFA_OK;
+    CWFA_REQUIRE(B == 1 || (x_bs >= 2 * n && (!low || low_bs >= n) && (!z || z_bs >= n) && (!nll || nll_bs >= n)), CWFA_E_INVAL,
+                 "cwfa_chain_nll_map_f32: a batch stride is below the elements of one batch entry");
+    size_t lds;
+    if (chain_rows4_ok(ch, C, H, W, B, &lds, x, low, z, x_bs, low ? low_bs : 0, z_bs) && cwfa_aligned16(nll) && (!nll || (nll_bs & 3) == 0)) {
+        const int RB = CHAIN_THREADS * 4 / W;
+        const dim3 grid((H + RB - 1) / RB, C, B);
+        lds *= 2;                              // the exchange carries the pair (a, o)
+        if (ch->n_stages <= 6)
+            hipLaunchKernelGGL((chain_nll_map_rows4_kernel<6>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, x, low, z, nll, *ch, C, H, W,
+                               x_bs, low_bs, z_bs, nll_bs, nll_sum);
+        else
+            hipLaunchKernelGGL((chain_nll_map_rows4_kernel<CWFA_CHAIN_MAX>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, x, low, z, nll,
+                               *ch, C, H, W, x_bs, low_bs, z_bs, nll_bs, nll_sum);
+        CWFA_LAUNCH_CHECK("cwfa_chain_nll_map_f32");
+        return CWFA_OK;
+    }
+    CWFA_REQUIRE((n + 255) / 256 <= 0x7fffffff, CWFA_E_SHAPE, "cwfa_chain_nll_map_f32: %lld positions exceed one launch", (long long)n);
+    dim3 grid((unsigned)((n + 255) / 256), B);
+    hipLaunchKernelGGL(chain_nll_map_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, low, z, nll, *ch, C, H, W, x_bs, low_bs, z_bs, nll_bs,
+                       nll_sum);
+    CWFA_LAUNCH_CHECK("cwfa_chain_nll_map_f32");
+    return CWFA_OK;
+}
+
+// ---- the per-step maps as one full-resolution volume (cwfa_nll_compose_f32): out[d] = sum_n 2^-(n+1) level_n[d >> (n+1)], finest
+// first.  One streaming pass: a thread owns four pixels (VEC) or one of one output plane; level n's plane is shared by 2^(n+1)
+// adjacent output planes, so only the first of them reads it from HBM (plain loads: the others hit the caches); the output is
+// written once (non-temporal).
+template <bool VEC>
+__global__ __launch_bounds__(256) void nll_compose_kernel(cwfa_nll_levels lv, float* __restrict__ out, int64_t HW, int64_t out_bs) {
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * (VEC ? 4 : 1);
+    if (i >= HW) return;
+    const int d = blockIdx.y, b = blockIdx.z;
+    float* op = out + b * out_bs + (int64_t)d * HW + i;
+    float fac = 0.5f;
+    if constexpr (VEC) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < CWFA_NLL_MAX_LEVELS; ++k)
+            if (k < lv.n) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(lv.level[k] + b * lv.bs[k] + (int64_t)(d >> (k + 1)) * HW + i);
+                acc = k == 0 ? v * fac : acc + v * fac;
+                fac *= 0.5f;
+            }
+        st_stream<true>(op, acc);
+    } else {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < CWFA_NLL_MAX_LEVELS; ++k)
+            if (k < lv.n) {
+                const float v = lv.level[k][b * lv.bs[k] + (int64_t)(d >> (k + 1)) * HW + i];
+                acc = k == 0 ? v * fac : acc + v * fac;
+                fac *= 0.5f;
+            }
+        *op = acc;
+    }
+}
+
+extern "C" int cwfa_nll_compose_f32(const cwfa_nll_levels* levels, float* out, int B, int D, int64_t HW, int64_t out_bs, void* stream) {
+    CWFA_REQUIRE(levels && out, CWFA_E_INVAL, "cwfa_nll_compose_f32: null pointer");
+    CWFA_REQUIRE(levels->n >= 1 && levels->n <= CWFA_NLL_MAX_LEVELS, CWFA_E_INVAL, "cwfa_nll_compose_f32: %d levels (1 .. %d)", levels->n,
+                 CWFA_NLL_MAX_LEVELS);
+    CWFA_REQUIRE(B >= 0 && D >= 0 && HW >= 0 && B <= 65535 && D <= 65535, CWFA_E_SHAPE, "cwfa_nll_compose_f32: bad shape");
+    CWFA_REQUIRE(D % (1 << levels->n) == 0, CWFA_E_SHAPE, "cwfa_nll_compose_f32: %d depths are not divisible by 2^%d", D, levels->n);
+    for (int k = 0; k < levels->n; ++k)
+        CWFA_REQUIRE(levels->level[k], CWFA_E_INVAL, "cwfa_nll_compose_f32: level %d is null", k);
+    if (B == 0 || D == 0 || HW == 0) return CWFA_OK;
+    bool vec = (HW & 3) == 0 && cwfa_aligned16(out) && (out_bs & 3) == 0;
+    for (int k = 0; k < levels->n; ++k) {
+        CWFA_REQUIRE(B == 1 || levels->bs[k] >= (int64_t)(D >> (k + 1)) * HW, CWFA_E_INVAL,
+                     "cwfa_nll_compose_f32: the batch stride of level %d is below the elements of one batch entry", k);
+        vec = vec && cwfa_aligned16(levels->level[k]) && (levels->bs[k] & 3) == 0;
+    }
+    CWFA_REQUIRE(B == 1 || out_bs >= (int64_t)D * HW, CWFA_E_INVAL, "cwfa_nll_compose_f32: the batch stride of out is below the elements of one batch entry");
+    const int64_t threads = vec ? HW >> 2 : HW, blocks = (threads + 255) / 256;
+    CWFA_REQUIRE(blocks <= 0x7fffffff, CWFA_E_SHAPE, "cwfa_nll_compose_f32: %lld pixels exceed one launch", (long long)HW);
+    const dim3 grid((unsigned)blocks, D, B);
+    if (vec)
+        hipLaunchKernelGGL((nll_compose_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, *levels, out, HW, out_bs);
+    else
+        hipLaunchKernelGGL((nll_compose_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, *levels, out, HW, out_bs);
+    CWFA_LAUNCH_CHECK("cwfa_nll_compose_f32");
+    return CWFA_OK;
+}
+
 extern "C" int cwfa_chain_fwd_f32(const float* x, float* low, float* z, const cwfa_chain* ch, const int64_t* final_perm,
                                   int B, int C, int H, int W, int64_t x_bs, int64_t low_bs, int64_t z_bs, double* logdet,
                                   double* sumsq, void* stream) {

@@ -8,7 +8,7 @@ import torch
 from . import _lib
 from ._lib import AffineStage, Chain, ConvOpts, check
 
-__all__ = ["haar1d", "haar2d", "gather", "affine", "channel_affine", "chain_inv", "chain_inv_var", "chain_inv_samples", "rand_uniform", "rand_trunc_normal", "chain_fwd", "pack_conv_weight",
+__all__ = ["haar1d", "haar2d", "gather", "affine", "channel_affine", "chain_inv", "chain_inv_var", "chain_inv_samples", "rand_uniform", "rand_trunc_normal", "chain_nll_map", "nll_compose", "chain_fwd", "pack_conv_weight",
            "conv2d", "conv2d_wgrad", "elu_bwd", "set_precision", "gelu_add", "gelu_bwd", "layernorm_bwd", "attention_bwd", "plane_affine", "bn_bwd_stats", "bn_act_bwd", "maxpool2_bwd", "chain_bwd", "chain_inv_bwd", "prelu_bwd", "conv3d_1k1_backward", "pack_1x1_panel", "pack_split_layer_weight", "subnet_layer", "conv3d_1k1", "channel_stats", "bn_fold", "bn_running_update", "maxpool", "sample_stats", "layernorm_apply",
            "attention_combine", "scale_channels", "axpby", "stage", "lion_step", "global_extrema", "wmse_loss"]
 
@@ -379,6 +379,61 @@ def chain_inv_samples(low, stages, n_samples, temperature, seed, stream=0, sampl
     check(L.cwfa_chain_inv_samples_f32(_p(low), _p(out), _p(z), C.byref(ch), N, B, Cc, H, W, lss, lbs, 2 * B * n, 2 * n, B * n, n,
                                        float(temperature), seed, stream, sample_offset, _stream()), "chain_inv_samples")
     return (out, z) if return_z else out
+
+
+def chain_nll_map(x, stages, tables=None, want_low=True, want_z=False, want_nll=True, nll_sum=None):
+    """(nll, low, z) of the volume ``x`` [B,2C,H,W] under one CAT step (cwfa_chain_nll_map_f32), each
+    [B,C,H,W] or None where not wanted.  ``stages`` are the INVERSE-direction stages (``_CatStepPlan.inverse_stages``), ``tables``
+    as for ``chain_inv``.  With d = (x[2c] - x[2c+1]) / sqrt 2 and the step's posterior d = g z + o:  z = (d - o) / g is the
+    standardised residual of the coefficient AT ITS OWN POSITION, nll = z^2 / 2 + log g its share of the step's negative
+    log-likelihood (no log 2 pi term) and low = (x[2c] + x[2c+1]) / sqrt 2 the next step's input, bit-equal to ``chain_fwd``'s.
+    ``nll_sum``: float64 [B] on the device, onto which the per-sample sums of nll are ACCUMULATED.  One launch."""
+    L = _lib.lib()
+    x, xbs = planes(x, "x")
+    B, D, H, W = x.shape
+    if D % 2:
+        raise ValueError(f"chain_nll_map: x has {D} channels, an odd number")
+    Cc = D // 2
+    if nll_sum is not None:
+        if not torch.is_tensor(nll_sum) or not nll_sum.is_cuda or nll_sum.dtype != torch.float64:
+            raise TypeError("chain_nll_map: nll_sum must be a float64 tensor on the HIP device")
+        if tuple(nll_sum.shape) != (B,) or not nll_sum.is_contiguous() or nll_sum.device != x.device:
+            raise ValueError(f"chain_nll_map: nll_sum must be a contiguous [{B}] tensor on x's device, got {tuple(nll_sum.shape)}")
+    ch, keep = _chain(stages, tables)
+    mk = lambda on: torch.empty((B, Cc, H, W), dtype=torch.float32, device=x.device) if on else None    # noqa: E731
+    nll, low, z = mk(want_nll), mk(want_low), mk(want_z)
+    n = Cc * H * W
+    check(L.cwfa_chain_nll_map_f32(_p(x), _p(low), _p(z), _p(nll), C.byref(ch), B, Cc, H, W, xbs, n, n, n, _p(nll_sum), _stream()),
+          "chain_nll_map")
+    return nll, low, z
+
+
+def nll_compose(levels):
+    """The per-step maps of a pyramid (finest first; level n is [B, D >> (n+1), H, W]) as one volume [B,D,H,W]:
+    out[b,d] = sum_n 2^-(n+1) level_n[b, d >> (n+1)], added finest first in fp32 (cwfa_nll_compose_f32), so that a sample's total
+    is the total of its levels.  One launch."""
+    L = _lib.lib()
+    levels = list(levels)
+    if not 1 <= len(levels) <= _lib.NLL_MAX_LEVELS:
+        raise ValueError(f"nll_compose: {len(levels)} levels (1 .. {_lib.NLL_MAX_LEVELS})")
+    tab = _lib.NllLevels()
+    tab.n = len(levels)
+    keep = []
+    for k, lv in enumerate(levels):
+        lv, bs = planes(lv, f"levels[{k}]")
+        if k == 0:
+            B, C0, H, W = lv.shape
+            D = 2 * C0
+            if D % (1 << len(levels)):
+                raise ValueError(f"nll_compose: {D} depths are not divisible by 2^{len(levels)}")
+        if tuple(lv.shape) != (B, D >> (k + 1), H, W) or lv.device != levels[0].device:
+            raise ValueError(f"nll_compose: levels[{k}] is {tuple(lv.shape)} on {lv.device}, expected {(B, D >> (k + 1), H, W)} on "
+                             f"{levels[0].device}")
+        tab.level[k], tab.bs[k] = lv.data_ptr(), bs
+        keep.append(lv)
+    out = torch.empty((B, D, H, W), dtype=torch.float32, device=keep[0].device)
+    check(L.cwfa_nll_compose_f32(C.byref(tab), _p(out), B, D, H * W, D * H * W, _stream()), "nll_compose")
+    return out
 
 
 def chain_fwd(x, stages, final_perm=None, logdet=None, sumsq=None, tables=None):

@@ -210,6 +210,33 @@ int cwfa_chain_inv_samples_f32(const float* low, float* x, float* z_out, const c
                                int64_t low_ss, int64_t low_bs, int64_t x_ss, int64_t x_bs, int64_t z_ss, int64_t z_bs,
                                float temperature, uint64_t seed, uint32_t stream_id, uint32_t sample_offset, void* stream);
 
+/* Per-coefficient z-scores and NLL shares of a volume x [B,2C,H,W] under one conditional step, in ONE launch.  `ch` holds the stages
+ * of the INVERSE direction, as for cwfa_chain_inv_f32 (src_c / src_h honoured).  The step gives the detail d = (x[2c] - x[2c+1]) /
+ * sqrt 2 at volume position p the density of  g * z + o  with z standard normal; the pair is collapsed once per position:
+ *   (a, o) = (0, 0);  for each stage: (a, o) <- gather_k(a, o);  o <- (o - t_k) * exp(-s_k);  a <- a + s_k         (g = exp(-a))
+ *   z[p] = (d[p] - o[p]) * exp(a[p])        the latent that the inverse chain carries to p: the standardised residual of d[p]
+ *   nll[p] = z[p]^2 / 2 - a[p]              its share of 0.5 * sum z^2 - logdet of cwfa_chain_fwd_f32 (no log 2 pi term)
+ *   low[p] = (x[2c] + x[2c+1]) * fl(1 / sqrt 2)     bit-equal to cwfa_chain_fwd_f32's low
+ * low, z, nll [B,C,H,W] are written at the coefficient's OWN position (nothing scatters); each is nullable and has its own batch
+ * stride.  nll_sum (nullable, double [B]) ACCUMULATES the per-sample sum of nll.  At least one of the four must be given; the
+ * outputs must not overlap x or one another. */
+int cwfa_chain_nll_map_f32(const float* x, float* low, float* z, float* nll, const cwfa_chain* ch, int B, int C, int H, int W,
+                           int64_t x_bs, int64_t low_bs, int64_t z_bs, int64_t nll_bs, double* nll_sum, void* stream);
+
+/* The per-step maps of a pyramid as one full-resolution volume: a coefficient of level n (0 = finest) covers 2^(n+1) adjacent
+ * depths at one pixel and gives each of them an equal share,
+ *   out[b, d, h, w] = sum_{n < L} 2^-(n+1) * level_n[b, d >> (n+1), h, w]          level_n [B, D >> (n+1), H, W], out [B, D, H, W]
+ * added finest first in fp32 (the factors are powers of two: every product is exact, so the same fp32 expression gives the same
+ * bits anywhere), so that the sum of out over a sample is the sum of all levels.  1 <= L <= CWFA_NLL_MAX_LEVELS, D divisible by
+ * 2^L; the levels have contiguous planes (channel stride HW) and their own batch strides. */
+#define CWFA_NLL_MAX_LEVELS 8
+typedef struct {
+    int n;
+    const float* level[CWFA_NLL_MAX_LEVELS];   /* finest first */
+    int64_t bs[CWFA_NLL_MAX_LEVELS];           /* batch strides, elements */
+} cwfa_nll_levels;
+int cwfa_nll_compose_f32(const cwfa_nll_levels* levels, float* out, int B, int D, int64_t HW, int64_t out_bs, void* stream);
+
 /* Forward (NLL direction) of one whole conditional step in ONE launch:
  *   (low, v) = Split(Haar1D(x));  for each stage: v <- A_k(gather_k(v));  z = gather_final(v)
  * final_perm (nullable) is the trailing PermuteRandom (networks.py:353-357).
