@@ -36,7 +36,8 @@ class ConvOpts(C.Structure):
     _fields_ = [("bias", c_f32p), ("act", C.c_int), ("prelu_alpha", c_f32p), ("residual", c_f32p), ("res_bs", C.c_int64),
                 ("act2", C.c_int), ("in_scale", c_f32p), ("in_shift", c_f32p), ("in_affine_bs", C.c_int), ("in_add", c_f32p),
                 ("in_add_bs", C.c_int64), ("upshuffle2", C.c_int), ("in_blocked8", C.c_int), ("out_blocked8", C.c_int),
-                ("in_cat", c_f32p), ("in_cat_bs", C.c_int64), ("in_cat_from", C.c_int), ("in_cat_c1", C.c_int), ("out_stats", c_f64p), ("prelu_per_channel", C.c_int)]
+                ("in_cat", c_f32p), ("in_cat_bs", C.c_int64), ("in_cat_from", C.c_int), ("in_cat_c1", C.c_int), ("out_stats", c_f64p), ("prelu_per_channel", C.c_int),
+                ("out_sample_stats", c_f64p)]
 
 
 class Couple(C.Structure):
@@ -118,6 +119,7 @@ SIGNATURES = {
     "cwfa_maxpool_f32": (i, [p, p, p, p, p, i, i, i, i, i, i, p]),
     "cwfa_sample_stats_f32": (i, [p, p, i, i64, p]),
     "cwfa_layernorm_apply_f32": (i, [p, p, p, p, f, p, i, i64, p]),
+    "cwfa_convnext_tail_f32": (i, [p, p, p, p, f, p, p, p, p, p, p, p, i, p, i, i, i64, i64, i64, i64, i64, p]),
     "cwfa_attention_combine_f32": (i, [p, p, p, p, p, p, p, p, i, i, i64, p]),
     "cwfa_scale_channels_f32": (i, [p, p, p, i, i, i64, p]),
     "cwfa_axpby_f32": (i, [p, p, f, f, p, i64, p]),

@@ -665,6 +665,7 @@ int fill_params(ConvParams& p, const char* name, const float* x, const float* w_
     CWFA_REQUIRE(B >= 0 && Cin > 0 && Cout > 0 && H >= 0 && W >= 0, CWFA_E_INVAL, "%s: bad size", name);
     if (B == 0 || H == 0 || W == 0) return 1;                                    // empty: nothing to do
     CWFA_REQUIRE(x && w_packed && y, CWFA_E_INVAL, "%s: null pointer", name);
+    CWFA_REQUIRE(!opts || !opts->out_sample_stats, CWFA_E_INVAL, "%s: out_sample_stats is a feature of the few-channel cwfa_conv7x7_split_f32", name);
     CWFA_REQUIRE((int64_t)Cin * H * W < (1ll << 30) && (int64_t)Cout * H * W * (p.o.upshuffle2 ? 1 : 1) < (1ll << 30), CWFA_E_SHAPE, "%s: C*H*W exceeds the 32-bit byte offsets of a tile (2^30 elements per image)", name);
     CWFA_REQUIRE(cwfa_aligned16(w_packed), CWFA_E_ALIGN, "%s: packed weights must be 16-byte aligned", name);
     p.x = x; p.wp = w_packed; p.y = y;

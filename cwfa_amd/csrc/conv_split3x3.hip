@@ -722,6 +722,10 @@ __global__ __launch_bounds__(512, 2) void conv7x7_few_split_kernel(SParams p) {
     const auto rb = CWFA_RSRC(p.o.bias ? p.o.bias : p.y, p.o.bias ? p.Cout * 4 : 0);
     const int cwave = wm * MPW * 16;
     const unsigned glane = (unsigned)(4 * g) * (unsigned)plane;
+    // cwfa_conv_opts.out_sample_stats: (sum, sum of squares) of the values stored below, for the LayerNorm over (C,H,W) behind this
+    // convolution -- float64 from the first addition (32 values per thread), pixels outside the image and channels >= Cout left out
+    const bool want_stats = p.o.out_sample_stats != nullptr;       // (uniform)
+    double ssum = 0.0, ssq = 0.0;
 #pragma unroll
     for (int mt = 0; mt < MPW; ++mt) {
         float bias[4];
@@ -732,10 +736,41 @@ __global__ __launch_bounds__(512, 2) void conv7x7_few_split_kernel(SParams p) {
         for (int nt = 0; nt < NT; ++nt) {
             const int row = row0 + wn * RW + (nt >> 1), col = col0 + 16 * (nt & 1) + c16;
             const unsigned po = (row < p.H && col < p.W) ? (unsigned)((row * p.W + col) * 4) + glane : OOB;
+            float v[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, acc[mt][nt][r] + bias[r]), ry, po, (cwave + mt * 16 + r) * plane, 0);
+            for (int r = 0; r < 4; ++r) {
+                v[r] = acc[mt][nt][r] + bias[r];
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[r]), ry, po, (cwave + mt * 16 + r) * plane, 0);
+            }
+            if (want_stats) {                             // one uniform branch per n-tile; the masks are selects
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const double dv = (po != OOB && cwave + mt * 16 + 4 * g + r < p.Cout) ? (double)v[r] : 0.0;
+                    ssum += dv;
+                    ssq += dv * dv;
+                }
+            }
             CWFA_FENCE();
+        }
+    }
+    if (want_stats) {                                     // block sum -> one float64 atomic pair per block
+        ssum = cwfa_wave_sum(ssum);
+        ssq = cwfa_wave_sum(ssq);
+        double* red = reinterpret_cast<double*>(lds);      // the operand buffers are dead (every wave passed the loop's last barrier)
+        if (lane == 0) {
+            red[2 * wave] = ssum;
+            red[2 * wave + 1] = ssq;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double t1 = 0.0, t2 = 0.0;
+#pragma unroll
+            for (int w = 0; w < 8; ++w) {
+                t1 += red[2 * w];
+                t2 += red[2 * w + 1];
+            }
+            atomicAdd(&p.o.out_sample_stats[2 * b], t1);
+            atomicAdd(&p.o.out_sample_stats[2 * b + 1], t2);
         }
     }
 }
@@ -970,6 +1005,7 @@ extern "C" int cwfa_conv3x3_split_f32(const float* x, const void* w_packed, floa
     p.B = B; p.Cin = Cin; p.H = H; p.W = W; p.Cout = Cout; p.x_bs = x_bs; p.y_bs = y_bs;
     if (opts) p.o = *opts;
     CWFA_REQUIRE(!p.o.upshuffle2 && !p.o.in_cat, CWFA_E_SHAPE, "cwfa_conv3x3_split_f32: upshuffle2 / in_cat are 1x1 features");
+    CWFA_REQUIRE(!p.o.out_sample_stats, CWFA_E_INVAL, "cwfa_conv3x3_split_f32: out_sample_stats is a feature of the few-channel cwfa_conv7x7_split_f32");
     CWFA_REQUIRE(!p.o.in_blocked8 || (Cin % 8 == 0 && cwfa_aligned16(x) && (x_bs & 3) == 0 && !p.o.in_add), CWFA_E_ALIGN,
                  "cwfa_conv3x3_split_f32: blocked input needs Cin %% 8 == 0, 16-byte alignment and no added tensor");
     CWFA_REQUIRE(!p.o.out_blocked8 || (Cout % 8 == 0 && cwfa_aligned16(y) && (y_bs & 3) == 0 && !p.o.residual && p.o.act2 == CWFA_ACT_NONE &&
@@ -1068,6 +1104,7 @@ extern "C" int cwfa_conv7x7_split_f32(const float* x, const void* w_packed, floa
     CWFA_REQUIRE(!p.o.upshuffle2 && !p.o.in_cat && !p.o.in_scale && !p.o.in_add && !p.o.in_blocked8 && !p.o.out_blocked8 && !p.o.residual && !p.o.out_stats &&
                      p.o.act == CWFA_ACT_NONE && p.o.act2 == CWFA_ACT_NONE,
                  CWFA_E_INVAL, "cwfa_conv7x7_split_f32: bias-only epilogue, no load-side prologue, NCHW maps");
+    CWFA_REQUIRE(!p.o.out_sample_stats || Cin <= 8, CWFA_E_INVAL, "cwfa_conv7x7_split_f32: out_sample_stats is written by the few-channel form (Cin <= 8) only");
     p.nchunks = (Cin + 15) / 16;
     p.nsteps = nsteps_of(Cin, 49);
     // a single 16-channel chunk (9 .. 16 inputs): the odd chunk of the one period is all zeros (zero-filled in steps 0 .. 2, zero weights) and

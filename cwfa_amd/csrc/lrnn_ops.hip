@@ -326,18 +326,29 @@ extern "C" int cwfa_sample_stats_f32(const float* x, double* stats, int B, int64
     return CWFA_OK;
 }
 
+// The LayerNorm expression, shared by the apply kernel and the fused ConvNeXt tail (convnext_tail_kernel) so that both form the
+// same bits: mean and rstd of sample b from its float64 (sum, sum of squares), the mean rounded to fp32, rstd from a float64 sqrt
+__device__ __forceinline__ void cwfa_ln_coefs(const double* __restrict__ stats, int b, int64_t CHW, float eps, float& mean_f, float& rstd) {
+    const double mean = stats[2 * b] / (double)CHW;
+    double var = stats[2 * b + 1] / (double)CHW - mean * mean;
+    if (var < 0.0) var = 0.0;
+    rstd = (float)(1.0 / sqrt(var + (double)eps));
+    mean_f = (float)mean;
+}
+__device__ __forceinline__ float cwfa_ln_apply(float x, float mean, float rstd, float w, float b) {
+    const float v = (x - mean) * rstd;
+    return v * w + b;
+}
+
 __global__ __launch_bounds__(256) void layernorm_apply_kernel(const float* __restrict__ x, const double* __restrict__ stats,
                                                               const float* __restrict__ w, const float* __restrict__ bsh,
                                                               float eps, float* __restrict__ y, int64_t CHW) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= CHW) return;
     const int b = blockIdx.y;
-    const double mean = stats[2 * b] / (double)CHW;
-    double var = stats[2 * b + 1] / (double)CHW - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float v = (x[(int64_t)b * CHW + i] - (float)mean) * rstd;
-    y[(int64_t)b * CHW + i] = v * (w ? w[i] : 1.f) + (bsh ? bsh[i] : 0.f);
+    float mean, rstd;
+    cwfa_ln_coefs(stats, b, CHW, eps, mean, rstd);
+    y[(int64_t)b * CHW + i] = cwfa_ln_apply(x[(int64_t)b * CHW + i], mean, rstd, w ? w[i] : 1.f, bsh ? bsh[i] : 0.f);
 }
 
 extern "C" int cwfa_layernorm_apply_f32(const float* x, const double* stats, const float* w, const float* b, float eps,
@@ -348,6 +359,198 @@ extern "C" int cwfa_layernorm_apply_f32(const float* x, const double* stats, con
     hipLaunchKernelGGL(layernorm_apply_kernel, dim3((unsigned)((CHW + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, x,
                        stats, w, b, eps, y, CHW);
     CWFA_LAUNCH_CHECK("cwfa_layernorm_apply_f32");
+    return CWFA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the ConvNeXt block's tail
+// y[b,co,p] = GELU(b1[co] + sum_ci W1[co,ci] LN(v)[b,ci,p]) + gate[b] u[b,co,p]        (networks.py:490-503; C <= 64)
+// in ONE pass: LayerNorm apply, the 1x1, GELU, the drop-path gate and the residual -- what layernorm_apply, scale_channels and the
+// fp32 1x1 launch did with three more trips of the map through memory.  fp32 on v_mfma_f32_32x32x2_f32, k ascending from a zero
+// accumulator: the fmaf chain of conv2d_mfma_kernel, so the result is that sequence's bit for bit.
+//   M = output channels (MT = 1 or 2 tiles of 32), N = 32 consecutive pixels of the flattened plane, K = channel pairs.
+//   B operand: lane (k = lane >> 5, pixel = lane & 31) loads v, the LayerNorm weight and bias of its (channel, pixel) from global
+//   memory -- 128 contiguous bytes per half-wave and channel -- and normalises in registers: no LDS staging, no barrier in the loop.
+//   Channels >= C and pixels >= HW are out of range of the buffer descriptors (0.0, never read); K is padded to whole chunks of 16
+//   channels with zero weights.
+//   A operand: W1 in torch layout [co][ci], copied once per block into LDS rows of KP + 1 floats (odd stride: the 32 rows of a
+//   fragment read fall on different banks), zero beyond C.  A block (four waves) walks pixel tiles blockIdx.x * 4 + wave + k * grid.
+//   Loads run one chunk (8 k-steps: 24 values per lane) ahead of the MFMAs; a tile's first chunk is requested in front of the
+//   epilogue of the tile before it (the first one in front of the LDS fill), so a wave always has loads in flight.
+//   Residual: u from memory, or (XRES, c_in <= 8) formed here as the fp32 1x1 kernel forms it: fmaf over ci ascending from 0.0f,
+//   then + b0.  gate * u is a rounded product and the sum a rounded sum (scale_channels stored the product).
+struct TailParams {
+    const float *v, *lw, *lb, *w1, *b1, *u, *gate, *x, *w0, *b0;
+    const double* stats;
+    float* y;
+    float eps;
+    int C, c_in, KP;
+    int64_t HW, v_bs, u_bs, x_bs, y_bs, ntiles;
+};
+
+template <int MT, bool XRES>
+__global__ __launch_bounds__(256, 4) void convnext_tail_kernel(TailParams p) {
+    constexpr int KC = 8;                                     // k-steps per chunk
+    constexpr unsigned OOB = 0x80000000u;
+    __shared__ float Ws[MT * 32 * 65];
+    __shared__ float Es[MT * 32 * 10];                        // per output channel: W0[co][0..7], b0[co], b1[co]
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, kh = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.y, C = p.C, LS = p.KP + 1;
+    const int plane = (int)(p.HW * 4);
+    const int cbytes = C * plane;
+    const auto rv = CWFA_RSRC(p.v + (int64_t)b * p.v_bs, cbytes);
+    const auto rlw = CWFA_RSRC(p.lw, cbytes);
+    const auto rlb = CWFA_RSRC(p.lb, cbytes);
+    const auto ru = CWFA_RSRC(XRES ? p.v : p.u + (int64_t)b * p.u_bs, XRES ? 0 : cbytes);
+    const auto rx = CWFA_RSRC(XRES ? p.x + (int64_t)b * p.x_bs : p.v, XRES ? p.c_in * plane : 0);
+    const auto ry = CWFA_RSRC(p.y + (int64_t)b * p.y_bs, cbytes);
+    auto ldf = [](decltype(rv) r, unsigned vo, int so) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, vo, so, 0)); };
+    // (32-bit indices: the entry point holds (C + 23) * HW * 4 below 2^31)
+    const int HW = (int)p.HW, ntiles = (int)p.ntiles, tstep = (int)gridDim.x * 4;
+    float xa[KC], wa[KC], ba[KC], xb[KC], wb[KC], bb[KC];
+    // B operand offset of a tile: channel 2 kk + kh of pixel tile * 32 + l31 (out of range beyond the plane)
+    auto vo_of = [&](int tile) { const int px = tile * 32 + l31; return px < HW ? (unsigned)(px + kh * HW) * 4u : OOB; };
+    auto load = [&](float (&xv)[KC], float (&wv)[KC], float (&bv)[KC], unsigned vo, int c) {
+#pragma unroll
+        for (int j = 0; j < KC; ++j) {
+            const int so = (c * KC + j) * 2 * plane;
+            xv[j] = ldf(rv, vo, so);
+            wv[j] = ldf(rlw, vo, so);
+            bv[j] = ldf(rlb, vo, so);
+        }
+    };
+    // the first tile's first chunk is requested before the weights are staged: the fill and its barrier run under those loads
+    int tile = (int)blockIdx.x * 4 + wave;
+    unsigned vo = vo_of(tile);
+    if (tile < ntiles) load(xa, wa, ba, vo, 0);
+    CWFA_FENCE();
+
+    for (int co = tid >> 6, ci = tid & 63; co < MT * 32; co += 4)      // a wave per row: 256 contiguous bytes of W1, no division
+        if (ci < p.KP) Ws[co * LS + ci] = (co < C && ci < C) ? p.w1[co * C + ci] : 0.f;
+    for (int e = tid; e < MT * 32 * 10; e += 256) {
+        const int co = e / 10, j = e % 10;
+        float val = 0.f;
+        if (co < C) {
+            if (j < 8) val = (XRES && j < p.c_in) ? p.w0[co * p.c_in + j] : 0.f;
+            else if (j == 8) val = (XRES && p.b0) ? p.b0[co] : 0.f;
+            else val = p.b1 ? p.b1[co] : 0.f;
+        }
+        Es[e] = val;
+    }
+    __syncthreads();
+
+    float mean, rstd;
+    cwfa_ln_coefs(p.stats, b, (int64_t)C * p.HW, p.eps, mean, rstd);
+    const float gate = p.gate ? p.gate[b] : 1.f;
+    const bool gated = p.gate != nullptr;
+    const float* wl = Ws + l31 * LS + kh;
+    const float* el = Es + 4 * kh * 10;                       // this lane half's rows of Es
+    const int nch = p.KP / (2 * KC);
+    auto run = [&](f32x16 (&acc)[MT], const float (&xv)[KC], const float (&wv)[KC], const float (&bv)[KC], int c) {
+#pragma unroll
+        for (int j = 0; j < KC; ++j) {
+            const float bq = cwfa_ln_apply(xv[j], mean, rstd, wv[j], bv[j]);
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+                acc[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(wl[m * 32 * LS + (c * KC + j) * 2], bq, acc[m], 0, 0, 0);
+        }
+    };
+
+    while (tile < ntiles) {                                   // (wave-uniform) chunk 0 of this tile is in flight in xa / wa / ba
+        const int px = tile * 32 + l31;
+        const bool ok = px < HW;
+        f32x16 acc[MT];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
+#pragma unroll 1
+        for (int c = 0; c < nch; c += 2) {
+            if (c + 1 < nch) load(xb, wb, bb, vo, c + 1);
+            CWFA_FENCE();
+            run(acc, xa, wa, ba, c);
+            CWFA_FENCE();
+            if (c + 1 < nch) {
+                if (c + 2 < nch) load(xa, wa, ba, vo, c + 2);
+                CWFA_FENCE();
+                run(acc, xb, wb, bb, c + 1);
+                CWFA_FENCE();
+            }
+        }
+
+        // ---- epilogue: register r of tile m = channel m*32 + row(r, kh) of pixel px; rows >= C are out of the descriptors' range
+        const unsigned eo = ok ? (unsigned)(px + 4 * kh * HW) * 4u : OOB;
+        float xin[8];
+        if constexpr (XRES) {
+            const unsigned pb = ok ? (unsigned)px * 4u : OOB;                               // this lane's pixel, channel 0
+#pragma unroll
+            for (int ci = 0; ci < 8; ++ci) xin[ci] = ldf(rx, pb, ci * plane);
+        }
+        // the next tile's first chunk goes out in front of the epilogue's vector work (xa / wa / ba are free: the chunk loop has consumed them)
+        tile += tstep;
+        vo = vo_of(tile);
+        if (tile < ntiles) load(xa, wa, ba, vo, 0);
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            float uu[XRES ? 1 : 16];
+            if constexpr (!XRES) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (m * 32 + cwfa_acc_row(r, 0) < C) uu[r] = ldf(ru, eo, (m * 32 + cwfa_acc_row(r, 0)) * plane);
+            }
+            CWFA_FENCE();
+            // (fenced per element: unfenced, hipcc hoists the LDS reads and erf polynomials of all 16 and spills)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int c0 = m * 32 + cwfa_acc_row(r, 0);
+                if (c0 >= C) continue;                     // (uniform) rows of both lane halves past the last channel: no GELU for nothing
+                float ur;
+                if constexpr (XRES) {
+                    float a = 0.0f;
+#pragma unroll
+                    for (int ci = 0; ci < 8; ++ci) a = fmaf(el[c0 * 10 + ci], xin[ci], a);
+                    ur = a + el[c0 * 10 + 8];
+                } else {
+                    ur = uu[r];
+                }
+                const float t = cwfa_gelu(acc[m][r] + el[c0 * 10 + 9]);
+                const float res = gated ? __fmul_rn(ur, gate) : ur;
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, __fadd_rn(t, res)), ry, eo, c0 * plane, 0);
+                CWFA_FENCE();
+            }
+        }
+    }
+}
+
+extern "C" int cwfa_convnext_tail_f32(const float* v, const double* stats, const float* lw, const float* lb, float eps,
+                                      const float* w1, const float* b1, const float* u, const float* gate, const float* x,
+                                      const float* w0, const float* b0, int c_in, float* y, int B, int C, int64_t HW,
+                                      int64_t v_bs, int64_t u_bs, int64_t x_bs, int64_t y_bs, void* stream) {
+    CWFA_REQUIRE(B >= 0 && B <= 65535 && C > 0 && C <= 64 && HW >= 0, CWFA_E_SHAPE, "cwfa_convnext_tail_f32: bad shape (C <= 64)");
+    if (B == 0 || HW == 0) return CWFA_OK;
+    CWFA_REQUIRE(v && stats && lw && lb && w1 && y, CWFA_E_INVAL, "cwfa_convnext_tail_f32: null pointer");
+    CWFA_REQUIRE((u != nullptr) != (x != nullptr), CWFA_E_INVAL, "cwfa_convnext_tail_f32: exactly one of u (the residual) and x (the block input it is formed from)");
+    CWFA_REQUIRE(!x || (w0 && c_in > 0 && c_in <= 8), CWFA_E_INVAL, "cwfa_convnext_tail_f32: the residual is formed from at most 8 input channels and needs w0");
+    CWFA_REQUIRE((int64_t)(C + 15 + 8) * HW * 4 < (1ll << 31), CWFA_E_SHAPE, "cwfa_convnext_tail_f32: one sample's map must stay below 2 GiB (32-bit buffer offsets)");
+    TailParams p{};
+    p.v = v; p.lw = lw; p.lb = lb; p.w1 = w1; p.b1 = b1; p.u = u; p.gate = gate; p.x = x; p.w0 = w0; p.b0 = b0;
+    p.stats = stats; p.y = y; p.eps = eps; p.C = C; p.c_in = c_in; p.KP = (C + 15) / 16 * 16;
+    p.HW = HW; p.v_bs = v_bs; p.u_bs = u_bs; p.x_bs = x_bs; p.y_bs = y_bs;
+    p.ntiles = (HW + 31) / 32;
+    // four blocks of four waves per CU over the chip; at least one tile per wave
+    int64_t gx = (p.ntiles + 3) / 4;
+    const int64_t cap = B >= 1024 ? 1 : 1024 / B;
+    if (gx > cap) gx = cap;
+    const dim3 grid((unsigned)gx, B);
+    hipStream_t st = (hipStream_t)stream;
+    if (C <= 32) {
+        if (x) hipLaunchKernelGGL((convnext_tail_kernel<1, true>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((convnext_tail_kernel<1, false>), grid, dim3(256), 0, st, p);
+    } else {
+        if (x) hipLaunchKernelGGL((convnext_tail_kernel<2, true>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((convnext_tail_kernel<2, false>), grid, dim3(256), 0, st, p);
+    }
+    CWFA_LAUNCH_CHECK("cwfa_convnext_tail_f32");
     return CWFA_OK;
 }
 

@@ -537,11 +537,16 @@ def drop_path(x, drop_prob: float = 0., training: bool = False):
     """Per-sample stochastic depth: x/keep * Bernoulli(keep).  networks.py:370-385."""
     if drop_prob == 0. or not training:
         return x
-    keep = 1 - drop_prob
     B, C = x.shape[0], x.shape[1]
-    # floor(keep + U) is Bernoulli(keep) (networks.py:381-383): drawn directly, two tiny launches instead of four
-    gate = torch.empty(B, 1, dtype=x.dtype, device=x.device).bernoulli_(keep).div_(keep)
+    gate = _drop_gate(B, drop_prob, x)
     return ops.scale_channels(x, gate.expand(B, C).contiguous())
+
+
+def _drop_gate(B, drop_prob, like):
+    """the [B,1] factor of drop_path: Bernoulli(keep) / keep"""
+    keep = 1 - drop_prob
+    # floor(keep + U) is Bernoulli(keep) (networks.py:381-383): drawn directly, two tiny launches instead of four
+    return torch.empty(B, 1, dtype=like.dtype, device=like.device).bernoulli_(keep).div_(keep)
 
 
 class ConvNeXt(nn.Module):
@@ -567,19 +572,38 @@ class ConvNeXt(nn.Module):
     @amp_entry
     def forward(self, input):
         P = self._packed.get
-        u = ops.conv2d(input, P(self.input), bias=self.input.bias)     # (the residual; memory-bound either way)
-        if ops.convnext_composed(self.input.in_channels, self.m[0].out_channels, self.input.bias is not None and self.m[0].bias is not None):
+        composed = ops.convnext_composed(self.input.in_channels, self.m[0].out_channels, self.input.bias is not None and self.m[0].bias is not None)
+        pc2 = P(self.m[2])
+        # the fused tail stands in for the fp32 MFMA 1x1 launch and what runs in front of it: only where m[2] goes to that kernel
+        fused = ops.CONVNEXT_TAIL_FUSED and not pc2.split and pc2.cout <= 64
+        # in the composed form nothing but the residual reads u: with few inputs the tail forms it from the block input itself
+        fused_u = fused and composed and ops.CONVNEXT_RESIDUAL_FUSED and self.input.in_channels <= 8
+        u = None if fused_u else ops.conv2d(input, P(self.input), bias=self.input.bias)     # (the residual; memory-bound either way)
+        st = None
+        if composed:
             # the 7x7 over the block's few inputs and a ones channel instead of over the c_out-channel map u (K = 49 x 8 or 16, not 49 x c_out)
-            v = ops.conv2d(ops.with_ones(input), self._composed(), bias=self.m[0].bias)
+            pc = self._composed()
+            if fused and ops.conv_writes_sample_stats(pc):       # the LayerNorm statistics from the 7x7's epilogue
+                st = torch.zeros(2 * input.shape[0], dtype=torch.float64, device=input.device)
+            v = ops.conv2d(ops.with_ones(input), pc, bias=self.m[0].bias, out_sample_stats=st)
         else:
             v = ops.conv2d(u, P(self.m[0]), bias=self.m[0].bias)
         ln = self.m[1]
         if tuple(v.shape[1:]) != tuple(ln.normalized_shape):
             raise RuntimeError(f"Given normalized_shape={list(ln.normalized_shape)}, expected input with shape "
                                f"[*, {', '.join(map(str, ln.normalized_shape))}], but got input of size{list(v.shape)}")
-        v = ops.layernorm_apply(v, ops.sample_stats(v), ln.weight, ln.bias, ln.eps)
+        if st is None:
+            st = ops.sample_stats(v)
+        if fused:
+            # LayerNorm apply, 1x1, GELU, drop-path gate and residual in one launch (the same RNG draw as drop_path)
+            gate = _drop_gate(v.shape[0], self.drop_prob, v) if (self.training and self.drop_prob != 0.) else None
+            if fused_u:
+                return ops.convnext_tail(v, st, ln.weight, ln.bias, ln.eps, self.m[2].weight, self.m[2].bias, gate=gate,
+                                         x=input, w0=self.input.weight, b0=self.input.bias)
+            return ops.convnext_tail(v, st, ln.weight, ln.bias, ln.eps, self.m[2].weight, self.m[2].bias, u=u, gate=gate)
+        v = ops.layernorm_apply(v, st, ln.weight, ln.bias, ln.eps)
         res = drop_path(u, self.drop_prob, training=self.training)
-        return ops.conv2d(v, P(self.m[2]), bias=self.m[2].bias, act="gelu", residual=res)
+        return ops.conv2d(v, pc2, bias=self.m[2].bias, act="gelu", residual=res)
 
 
 class LRNN(nn.Module):

@@ -10,7 +10,7 @@ from ._lib import AffineStage, Chain, ConvOpts, check
 
 __all__ = ["haar1d", "haar2d", "gather", "affine", "channel_affine", "chain_inv", "chain_inv_var", "chain_inv_samples", "rand_uniform", "rand_trunc_normal", "chain_nll_map", "nll_compose", "chain_fwd", "pack_conv_weight",
            "conv2d", "conv2d_wgrad", "elu_bwd", "set_precision", "gelu_add", "gelu_bwd", "layernorm_bwd", "attention_bwd", "plane_affine", "bn_bwd_stats", "bn_act_bwd", "maxpool2_bwd", "chain_bwd", "chain_inv_bwd", "prelu_bwd", "conv3d_1k1_backward", "pack_1x1_panel", "pack_split_layer_weight", "subnet_layer", "conv3d_1k1", "channel_stats", "bn_fold", "bn_running_update", "maxpool", "sample_stats", "layernorm_apply",
-           "attention_combine", "scale_channels", "axpby", "stage", "lion_step", "global_extrema", "wmse_loss"]
+           "convnext_tail", "conv_writes_sample_stats", "attention_combine", "scale_channels", "axpby", "stage", "lion_step", "global_extrema", "wmse_loss"]
 
 
 def _stream():
@@ -599,11 +599,20 @@ def conv_writes_stats(pc, act=None, residual=None, act2=None, out_blocked=False,
                 and not (in_add and act is None))
 
 
+def conv_writes_sample_stats(pc):
+    """True when conv2d(..., out_sample_stats=) is available for this bank: the few-channel form of the split 7x7 kernel (at most 8
+    inputs with the ones channel: the composed ConvNeXt bank) adds the per-sample (sum, sum of squares) of its output from its
+    epilogue.  The 9 .. 16-input form, the 64-channel 7x7 and the fp32 kernels do not; ops.sample_stats stays for them."""
+    return bool(pc.split and pc.ks == 7 and pc.cin <= 8)
+
+
 def conv2d(x, pc, bias=None, act=None, prelu_alpha=None, residual=None, act2=None, in_scale=None, in_shift=None,
-           in_add=None, out=None, in_blocked=False, out_blocked=False, cat=None, out_stats=None):
+           in_add=None, out=None, in_blocked=False, out_blocked=False, cat=None, out_stats=None, out_sample_stats=None):
     """y = act2(act(conv(x') + bias) + residual), x' = x*in_scale[c] + in_shift[c] + in_add.  Transposed banks
     (ConvTranspose2d k2 s2) write the pixel-shuffled [B,Co,2H,2W] output.  ``out_stats`` (float64 [2*Cout], see
-    conv_writes_stats): the launch adds (sum y, sum y^2) per channel -- the statistics of a BatchNorm behind the convolution."""
+    conv_writes_stats): the launch adds (sum y, sum y^2) per channel -- the statistics of a BatchNorm behind the convolution.
+    ``out_sample_stats`` (float64 [2*B], see conv_writes_sample_stats): the launch adds (sum y, sum y^2) per sample -- the
+    statistics of a LayerNorm over (C,H,W) behind the convolution."""
     L = _lib.lib()
     x, xbs = planes(x, "x")
     B, Cin, H, W = x.shape
@@ -678,6 +687,12 @@ def conv2d(x, pc, bias=None, act=None, prelu_alpha=None, residual=None, act2=Non
         if out_stats.dtype != torch.float64 or out_stats.numel() != 2 * pc.cout or not out_stats.is_cuda:
             raise ValueError("conv2d: out_stats must be a float64 [2*Cout] tensor on the HIP device")
         o.out_stats = out_stats.data_ptr()
+    if out_sample_stats is not None:
+        if not conv_writes_sample_stats(pc):
+            raise ValueError("conv2d: out_sample_stats needs the few-channel split 7x7 kernel (a composed ConvNeXt bank with <= 8 inputs)")
+        if out_sample_stats.dtype != torch.float64 or out_sample_stats.numel() != 2 * B or not out_sample_stats.is_cuda:
+            raise ValueError("conv2d: out_sample_stats must be a float64 [2*B] tensor on the HIP device")
+        o.out_sample_stats = out_sample_stats.data_ptr()
     rec = conv_event_sink
     if rec is not None:                    # bench.py: HIP events around selected launches, on the launch stream
         # the last field names the kernel instantiation the C side dispatches to (prologue / epilogue variant)
@@ -1383,6 +1398,56 @@ def layernorm_apply(x, stats, weight, bias, eps):
     out = torch.empty_like(x)
     check(L.cwfa_layernorm_apply_f32(_p(x), _p(stats), _p(weight), _p(bias), float(eps), _p(out), x.shape[0],
                                      x[0].numel(), _stream()), "layernorm_apply")
+    return out
+
+
+CONVNEXT_TAIL_FUSED = True        # (tuning / ablation) False: ConvNeXt.forward runs layernorm_apply, scale_channels and the fp32 1x1 launch
+CONVNEXT_RESIDUAL_FUSED = True    # (tuning / ablation) False: the composed block still writes u = conv1x1(x) + b0 for the tail to read
+
+
+def convnext_tail(v, stats, ln_weight, ln_bias, eps, w1, b1, u=None, gate=None, x=None, w0=None, b0=None, out=None):
+    """The tail of a ConvNeXt block in one launch: GELU(conv1x1(LayerNorm(v), w1) + b1) + gate[b] * u, bit for bit what
+    layernorm_apply -> scale_channels -> conv2d(act="gelu", residual=) give.  v [B,C <= 64,H,W]; stats: float64 [2B] (sample_stats,
+    or conv2d(out_sample_stats=)); w1 [C,C,1,1]; gate: [B] or None (= 1).  The residual is ``u`` [B,C,H,W], or with ``u`` None it is
+    formed in the launch from the block input ``x`` [B,c_in <= 8,H,W] as conv1x1(x, w0) + b0 (the fp32 1x1 kernel's bits)."""
+    L = _lib.lib()
+    v, vbs = planes(v, "v")
+    B, Cc, H, W = v.shape
+    HW = H * W
+    if stats.dtype != torch.float64 or stats.numel() != 2 * B or not stats.is_cuda:
+        raise ValueError("convnext_tail: stats must be a float64 [2*B] tensor on the HIP device")
+    ln_weight, ln_bias = _dev(ln_weight, "ln_weight").contiguous(), _dev(ln_bias, "ln_bias").contiguous()
+    w1 = _dev(w1, "w1").detach().contiguous()
+    if Cc > 64 or ln_weight.numel() != Cc * HW or ln_bias.numel() != Cc * HW or w1.numel() != Cc * Cc:
+        raise ValueError("convnext_tail: C <= 64, LayerNorm tables of C*H*W values and a [C,C,1,1] bank are needed")
+    if b1 is not None and _dev(b1, "b1").numel() != Cc:
+        raise ValueError("convnext_tail: b1 must hold C values")
+    if (u is None) == (x is None):
+        raise ValueError("convnext_tail: pass the residual u, or the block input x it is formed from")
+    ubs = xbs = cin = 0
+    if u is not None:
+        u, ubs = planes(u, "u")
+        if tuple(u.shape) != (B, Cc, H, W):
+            raise ValueError(f"convnext_tail: residual {tuple(u.shape)} != {(B, Cc, H, W)}")
+    else:
+        x, xbs = planes(x, "x")
+        cin = x.shape[1]
+        w0 = _dev(w0, "w0").detach().contiguous()
+        if tuple(x.shape) != (B, cin, H, W) or cin > 8 or w0.numel() != Cc * cin or (b0 is not None and _dev(b0, "b0").numel() != Cc):
+            raise ValueError("convnext_tail: x [B,c_in <= 8,H,W] with w0 [C,c_in,1,1] and b0 [C] is needed")
+    if gate is not None:
+        gate = _dev(gate, "gate").reshape(-1).contiguous()
+        if gate.numel() != B:
+            raise ValueError("convnext_tail: gate must hold one factor per sample")
+    if out is None:
+        out = torch.empty((B, Cc, H, W), dtype=torch.float32, device=v.device)
+        ybs = Cc * HW
+    else:
+        out_c, ybs = planes(out, "out")
+        if tuple(out.shape) != (B, Cc, H, W) or out_c.data_ptr() != out.data_ptr():
+            raise ValueError("convnext_tail: `out` must be [B,C,H,W] with contiguous planes")
+    check(L.cwfa_convnext_tail_f32(_p(v), _p(stats), _p(ln_weight), _p(ln_bias), float(eps), _p(w1), _p(b1), _p(u), _p(gate), _p(x),
+                                   _p(w0), _p(b0), cin, _p(out), B, Cc, HW, vbs, ubs, xbs, ybs, _stream()), "convnext_tail")
     return out
 
 

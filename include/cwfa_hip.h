@@ -295,6 +295,11 @@ typedef struct {
                                  (slope 1.0 = no activation on that channel): several filter banks that read the same
                                  input -- conv1 (+ PReLU) and downsample (plain) of the condition nets' ResidualBlocks,
                                  networks.py:212-219,229-233 -- run as ONE convolution                                 */
+    double* out_sample_stats; /* cwfa_conv7x7_split_f32 with Cin <= 8 only (the few-channel form): nullable [2*B]; the launch
+                                 ADDS (sum y, sum y^2) of sample b's output over (C,H,W) to entries 2b, 2b + 1 -- the
+                                 statistics of the nn.LayerNorm([C,H,W]) behind the ConvNeXt block's 7x7 (networks.py:490),
+                                 float64 from the first addition, taken from the values the epilogue stores instead of a
+                                 second pass over y (cwfa_sample_stats_f32).  Every other entry point and form rejects it */
 } cwfa_conv_opts;
 
 int cwfa_conv2d_f32(const float* x, const float* w_packed, float* y, int B, int Cin, int H, int W, int Cout, int ks,
@@ -362,6 +367,19 @@ int cwfa_sample_stats_f32(const float* x, double* stats, int B, int64_t CHW, voi
 /* y = (x - mean_b) * rstd_b * w[chw] + b[chw]   networks.py:490 (eps 1e-5) */
 int cwfa_layernorm_apply_f32(const float* x, const double* stats, const float* w, const float* b, float eps,
                              float* y, int B, int64_t CHW, void* stream);
+/* The tail of a ConvNeXt block (networks.py:490-503) in one pass, C <= 64, fp32 (v_mfma_f32_32x32x2_f32, k ascending):
+ *   y[b,co,p] = GELU(b1[co] + sum_ci w1[co,ci] * LN(v)[b,ci,p]) + gate[b] * u[b,co,p]
+ *   LN(v)[b,ci,p] = (v[b,ci,p] - mean_b) * rstd_b * lw[ci,p] + lb[ci,p], mean_b / rstd_b from stats[2b], stats[2b+1] (the float64
+ *   (sum, sum of squares) over (C,H,W): cwfa_sample_stats_f32 or cwfa_conv_opts.out_sample_stats) -- cwfa_layernorm_apply_f32's bits.
+ * lw, lb: the LayerNorm tables [C*HW] (required).  w1: [C][C] (torch layout, no packed image), b1 nullable.  gate: nullable [B] (drop-path factor; null = 1).  The residual u is read
+ * from memory ([B,C,HW] planes, batch stride u_bs), or, with u null, formed from the block input x [B,c_in <= 8,HW]:
+ *   u[b,co,p] = b0[co] + sum_ci w0[co,ci] * x[b,ci,p]   (fmaf over ci ascending from 0.0f: the fp32 1x1 kernel's bits).
+ * The result equals cwfa_layernorm_apply_f32 -> cwfa_scale_channels_f32 -> cwfa_conv2d_f32 (1x1, GELU, residual) bit for bit.
+ * v, u, x, y: contiguous planes with batch strides; channels beyond C (c_in) are never read or written. */
+int cwfa_convnext_tail_f32(const float* v, const double* stats, const float* lw, const float* lb, float eps,
+                           const float* w1, const float* b1, const float* u, const float* gate, const float* x,
+                           const float* w0, const float* b0, int c_in, float* y, int B, int C, int64_t HW,
+                           int64_t v_bs, int64_t u_bs, int64_t x_bs, int64_t y_bs, void* stream);
 /* GlobalAttention (networks.py:249-262) fused with the LRNN combine (networks.py:552-554):
  *   att = sigmoid(W2 . relu(conv1d_k3(mean over the flattened H*W sequence) ) )
  *   out = x + m * 2 * (att - 0.5)            (m, x nullable -> out = att) */
