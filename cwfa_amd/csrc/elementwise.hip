@@ -6,6 +6,7 @@
 #include <cmath>
 #include <stdarg.h>
 #include <stdio.h>
+#include <type_traits>
 
 // ------------------------------------------------------------------------------------------------ error plumbing
 static thread_local char g_err[512] = "";
@@ -490,6 +491,18 @@ extern "C" int cwfa_channel_affine_f32(const float* x, float* y, const float* sc
 // visited by exactly one thread, so block-reducing the s values gives the exact per-sample log-det.
 __device__ __forceinline__ int64_t lin(Pos p, int H, int W) { return ((int64_t)p.c * H + p.h) * W + p.w; }
 
+// the backwards walk from the final position p: off[k] = where stage k reads its s,t; returns where the value starts
+__device__ __forceinline__ Pos chain_pos_walk(const cwfa_chain& ch, Pos p, int H, int W, int64_t (&off)[CWFA_CHAIN_MAX]) {
+#pragma unroll
+    for (int k = CWFA_CHAIN_MAX - 1; k >= 0; --k) {
+        if (k < ch.n_stages) {
+            off[k] = lin(p, H, W);
+            p = gather_pos(p, ch.stage[k].perm, ch.stage[k].perm_axis);
+        }
+    }
+    return p;
+}
+
 __global__ __launch_bounds__(256) void chain_inv_kernel(const float* __restrict__ z, const float* __restrict__ low,
                                                         float* __restrict__ x, cwfa_chain ch, int C, int H, int W,
                                                         int64_t z_bs, int64_t low_bs, int64_t x_bs,
@@ -500,15 +513,8 @@ __global__ __launch_bounds__(256) void chain_inv_kernel(const float* __restrict_
     const int b = blockIdx.y;
     float ssum = 0.f;
     if (i < n) {
-        Pos p{(int)(i / HW), (int)((i / W) % H), (int)(i % W)};
         int64_t off[CWFA_CHAIN_MAX];
-#pragma unroll
-        for (int k = CWFA_CHAIN_MAX - 1; k >= 0; --k) {
-            if (k < ch.n_stages) {
-                off[k] = lin(p, H, W);
-                p = gather_pos(p, ch.stage[k].perm, ch.stage[k].perm_axis);
-            }
-        }
+        const Pos p = chain_pos_walk(ch, Pos{(int)(i / HW), (int)((i / W) % H), (int)(i % W)}, H, W, off);
         float v = z ? z[b * z_bs + lin(p, H, W)] : 0.f;
 #pragma unroll
         for (int k = 0; k < CWFA_CHAIN_MAX; ++k) {
@@ -548,15 +554,8 @@ __global__ __launch_bounds__(256) void chain_fwd_kernel(const float* __restrict_
             const float e = x[b * x_bs + (int64_t)(2 * p.c) * HW + pix], o = x[b * x_bs + (int64_t)(2 * p.c + 1) * HW + pix];
             low[b * low_bs + i] = (e + o) * CWFA_INV_SQRT2_F;
         }
-        p = gather_pos(p, final_perm, 1);
         int64_t off[CWFA_CHAIN_MAX];
-#pragma unroll
-        for (int k = CWFA_CHAIN_MAX - 1; k >= 0; --k) {
-            if (k < ch.n_stages) {
-                off[k] = lin(p, H, W);
-                p = gather_pos(p, ch.stage[k].perm, ch.stage[k].perm_axis);
-            }
-        }
+        p = chain_pos_walk(ch, gather_pos(p, final_perm, 1), H, W, off);
         {   // the detail half where this thread's value starts
             const int64_t pix = (int64_t)p.h * W + p.w;
             const float e = x[b * x_bs + (int64_t)(2 * p.c) * HW + pix], o = x[b * x_bs + (int64_t)(2 * p.c + 1) * HW + pix];
@@ -752,6 +751,68 @@ __device__ __forceinline__ void stage_st4(const cwfa_affine_stage& st, const f32
 }
 
 constexpr int CHAIN_THREADS = 256;     // threads per block of chain_rows4_kernel: a block covers CHAIN_THREADS * 4 pixels = whole image rows
+
+// ---- the skeleton that the 16-byte kernels share (chain, variance, sampler, likelihood map).  A new one supplies its own loads and
+// stores, the value(s) it carries and what a stage does to them; where the rows come from, how they are loaded and how a column
+// permutation is served are these three.
+// Where the block's row (c, h) reads: q[k] = the row of stage k's s,t, returned = the row where the value starts.  `start` is (c, h),
+// or its final_perm gather for the forward chain.  Composed by the caller (ch.src_c): independent loads instead of a dependent walk.
+template <int NS>
+__device__ __forceinline__ RowPos chain_row_walk(const cwfa_chain& ch, int c, int h, RowPos start, int C, int H, RowPos (&q)[NS]) {
+    const int n = ch.n_stages;
+    if (ch.src_c) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k)
+            if (k < n) q[k] = RowPos{ch.src_c[k * C + c], ch.src_h[k * H + h]};
+        return RowPos{ch.src_c[n * C + c], ch.src_h[n * H + h]};
+    }
+#pragma unroll
+    for (int k = NS - 1; k >= 0; --k)
+        if (k < n) {
+            q[k] = start;
+            start = row_gather(start, ch.stage[k].perm, ch.stage[k].perm_axis);
+        }
+    return start;
+}
+
+// Every coefficient row of the thread, back to back (zeros where a stage has no s or no t).  Read ONCE: non-temporal, see above.
+template <int NS>
+__device__ __forceinline__ void chain_load_rows(const cwfa_chain& ch, const RowPos (&q)[NS], int b, int H, int W, int w4, f32x4 (&sr)[NS],
+                                                f32x4 (&tr)[NS]) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        sr[k] = tr[k] = zero;
+        if (k < ch.n_stages) {
+            const int64_t off = ((int64_t)q[k].c * H + q[k].h) * W + w4;
+            if (ch.stage[k].s_raw) sr[k] = ld_stream(ch.stage[k].s_raw + b * ch.stage[k].s_bs + off);
+            if (ch.stage[k].t) tr[k] = ld_stream(ch.stage[k].t + b * ch.stage[k].t_bs + off);
+        }
+    }
+}
+
+// A column permutation (uniform over the block) moves the travelling values v... between the threads of a row: each value through one
+// LDS row, double-buffered ([nx & 1][value][row of the block][W], RB * W = CHAIN_THREADS * 4), so ONE barrier per column permutation.
+// Channel and row permutations only changed which rows were loaded.  Every thread of the block comes here, dead rows included.
+template <typename... V>
+__device__ __forceinline__ void chain_col_gather(const cwfa_affine_stage& st, float* rows, int& nx, int r, int W, int w4, V&... v) {
+    if (!(st.perm && st.perm_axis == 3)) return;
+    constexpr int K = sizeof...(V);
+    f32x4* const val[K] = {&v...};
+    float* buf = rows + (size_t)(nx & 1) * (K * CHAIN_THREADS * 4) + (size_t)r * W;
+    ++nx;
+#pragma unroll
+    for (int i = 0; i < K; ++i) *reinterpret_cast<f32x4*>(buf + i * CHAIN_THREADS * 4 + w4) = *val[i];
+    __syncthreads();
+    const int64_t* pk = st.perm + w4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int wj = (int)pk[j];
+#pragma unroll
+        for (int i = 0; i < K; ++i) (*val[i])[j] = buf[i * CHAIN_THREADS * 4 + wj];
+    }
+}
+
 // NS: stages the register arrays are sized for (6 covers a CAT step: five conditional affines + the trailing permutation; sized for
 // CWFA_CHAIN_MAX = 8 the kernel held 87 registers = five waves per SIMD -- with <= 80 it holds six, i.e. 1536 resident blocks, which the
 // 1536 x 2^k blocks of the 6 / 12 / 24 / 48-channel levels at 512 x 512 fill in whole rounds)
@@ -771,32 +832,12 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_rows4_kernel(const float*
     const int h = live ? hh : H - 1;
     const int64_t HW = (int64_t)H * W;
     const int n = ch.n_stages;
-    RowPos q[NS], src = INV ? RowPos{c, h} : row_gather(RowPos{c, h}, final_perm, 1);
-    if (ch.src_c) {                          // composed by the caller: independent loads instead of a dependent walk
-#pragma unroll
-        for (int k = 0; k < NS; ++k)
-            if (k < n) q[k] = RowPos{ch.src_c[k * C + c], ch.src_h[k * H + h]};
-        src = RowPos{ch.src_c[n * C + c], ch.src_h[n * H + h]};
-    } else {
-#pragma unroll
-        for (int k = NS - 1; k >= 0; --k)
-            if (k < n) {
-                q[k] = src;
-                src = row_gather(src, ch.stage[k].perm, ch.stage[k].perm_axis);
-            }
-    }
+    RowPos q[NS];
+    const RowPos src = chain_row_walk(ch, c, h, INV ? RowPos{c, h} : row_gather(RowPos{c, h}, final_perm, 1), C, H, q);
     // ---- every global load of this thread, back to back
     f32x4 sr[NS], tr[NS];
+    chain_load_rows(ch, q, b, H, W, w4, sr, tr);
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        sr[k] = tr[k] = zero;
-        if (k < n) {
-            const int64_t off = ((int64_t)q[k].c * H + q[k].h) * W + w4;
-            if (ch.stage[k].s_raw) sr[k] = ld_stream(ch.stage[k].s_raw + b * ch.stage[k].s_bs + off);
-            if (ch.stage[k].t) tr[k] = ld_stream(ch.stage[k].t + b * ch.stage[k].t_bs + off);
-        }
-    }
     f32x4 v0 = zero, lo = zero, own0 = zero, own1 = zero;
     const int64_t so = ((int64_t)src.h) * W + w4, oo = (int64_t)h * W + w4;
     if constexpr (INV) {
@@ -809,9 +850,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_rows4_kernel(const float*
         own1 = *reinterpret_cast<const f32x4*>(a0 + b * bs0 + (int64_t)(2 * c + 1) * HW + oo);
         v0 = (e0 - e1) * CWFA_INV_SQRT2_F;
     }
-    // ---- coefficients at the thread's OWN four columns, then the chain.  A column permutation moves the travelling values
-    // between the threads of a row (through one LDS row, double-buffered: one barrier per column permutation); channel and
-    // row permutations only changed which rows were loaded above.
+    // ---- coefficients at the thread's OWN four columns, then the chain
     f32x4 ev[NS], tv[NS];
     float ssum = 0.f;
 #pragma unroll
@@ -830,15 +869,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_rows4_kernel(const float*
 #pragma unroll
     for (int k = 0; k < NS; ++k)
         if (k < n) {
-            if (ch.stage[k].perm && ch.stage[k].perm_axis == 3) {           // uniform over the block
-                float* buf = rows + (size_t)((nx & 1) * RB + r) * W;
-                ++nx;
-                *reinterpret_cast<f32x4*>(buf + w4) = v;
-                __syncthreads();
-                const int64_t* pk = ch.stage[k].perm + w4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = buf[(int)pk[j]];
-            }
+            chain_col_gather(ch.stage[k], rows, nx, r, W, w4, v);
             v = INV ? (v - tv[k]) * ev[k] : ev[k] * v + tv[k];
         }
     double sq = 0.0;
@@ -884,15 +915,8 @@ __global__ __launch_bounds__(256) void chain_inv_var_kernel(const float* __restr
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int b = blockIdx.y;
     if (i >= n) return;
-    Pos p{(int)(i / HW), (int)((i / W) % H), (int)(i % W)};
     int64_t off[CWFA_CHAIN_MAX];
-#pragma unroll
-    for (int k = CWFA_CHAIN_MAX - 1; k >= 0; --k) {
-        if (k < ch.n_stages) {
-            off[k] = lin(p, H, W);
-            p = gather_pos(p, ch.stage[k].perm, ch.stage[k].perm_axis);
-        }
-    }
+    chain_pos_walk(ch, Pos{(int)(i / HW), (int)((i / W) % H), (int)(i % W)}, H, W, off);
     float a = 0.f;
 #pragma unroll
     for (int k = 0; k < CWFA_CHAIN_MAX; ++k) {
@@ -925,27 +949,10 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_var_rows4_kernel(const fl
     const int64_t HW = (int64_t)H * W;
     const int n = ch.n_stages;
     RowPos q[NS];
-    if (ch.src_c) {
-#pragma unroll
-        for (int k = 0; k < NS; ++k)
-            if (k < n) q[k] = RowPos{ch.src_c[k * C + c], ch.src_h[k * H + h]};
-    } else {
-        RowPos src = RowPos{c, h};
-#pragma unroll
-        for (int k = NS - 1; k >= 0; --k)
-            if (k < n) {
-                q[k] = src;
-                src = row_gather(src, ch.stage[k].perm, ch.stage[k].perm_axis);
-            }
-    }
-    f32x4 sr[NS];
+    chain_row_walk(ch, c, h, RowPos{c, h}, C, H, q);
+    f32x4 sr[NS], tr[NS];                    // tr stays unused: the host nulled the t pointers, and its loads are not even compiled
+    chain_load_rows(ch, q, b, H, W, w4, sr, tr);
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        sr[k] = zero;
-        if (k < n && ch.stage[k].s_raw)
-            sr[k] = ld_stream(ch.stage[k].s_raw + b * ch.stage[k].s_bs + ((int64_t)q[k].c * H + q[k].h) * W + w4);
-    }
     const int64_t oo = (int64_t)h * W + w4;
     const f32x4 lo = var_low ? ld_stream(var_low + b * vl_bs + (int64_t)c * HW + oo) : zero;
     f32x4 a = zero;
@@ -953,15 +960,7 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_var_rows4_kernel(const fl
 #pragma unroll
     for (int k = 0; k < NS; ++k)
         if (k < n) {
-            if (ch.stage[k].perm && ch.stage[k].perm_axis == 3) {           // uniform over the block
-                float* buf = rows + (size_t)((nx & 1) * RB + r) * W;
-                ++nx;
-                *reinterpret_cast<f32x4*>(buf + w4) = a;
-                __syncthreads();
-                const int64_t* pk = ch.stage[k].perm + w4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) a[j] = buf[(int)pk[j]];
-            }
+            chain_col_gather(ch.stage[k], rows, nx, r, W, w4, a);
             f32x4 sv, tv;
             stage_st4(ch.stage[k], sr[k], zero, sv, tv);
 #pragma unroll
@@ -997,15 +996,8 @@ __global__ __launch_bounds__(256) void chain_samples_kernel(const float* __restr
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int b = blockIdx.y;
     if (i >= n) return;
-    Pos p{(int)(i / HW), (int)((i / W) % H), (int)(i % W)};
     int64_t off[CWFA_CHAIN_MAX];
-#pragma unroll
-    for (int k = CWFA_CHAIN_MAX - 1; k >= 0; --k) {
-        if (k < ch.n_stages) {
-            off[k] = lin(p, H, W);
-            p = gather_pos(p, ch.stage[k].perm, ch.stage[k].perm_axis);
-        }
-    }
+    const Pos p = chain_pos_walk(ch, Pos{(int)(i / HW), (int)((i / W) % H), (int)(i % W)}, H, W, off);
     float g = 1.f, o = 0.f;
 #pragma unroll
     for (int k = 0; k < CWFA_CHAIN_MAX; ++k) {
@@ -1050,54 +1042,19 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_samples_rows4_kernel(cons
     const int h = live ? hh : H - 1;         // rows beyond H in the last block: load row H - 1 (in bounds), take part in the barriers, store nothing
     const int64_t HW = (int64_t)H * W;
     const int n = ch.n_stages;
-    RowPos q[NS], src = RowPos{c, h};
-    if (ch.src_c) {
-#pragma unroll
-        for (int k = 0; k < NS; ++k)
-            if (k < n) q[k] = RowPos{ch.src_c[k * C + c], ch.src_h[k * H + h]};
-        src = RowPos{ch.src_c[n * C + c], ch.src_h[n * H + h]};
-    } else {
-#pragma unroll
-        for (int k = NS - 1; k >= 0; --k)
-            if (k < n) {
-                q[k] = src;
-                src = row_gather(src, ch.stage[k].perm, ch.stage[k].perm_axis);
-            }
-    }
+    RowPos q[NS];
+    const RowPos src = chain_row_walk(ch, c, h, RowPos{c, h}, C, H, q);
     f32x4 sr[NS], tr[NS];
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        sr[k] = tr[k] = zero;
-        if (k < n) {
-            const int64_t off = ((int64_t)q[k].c * H + q[k].h) * W + w4;
-            if (ch.stage[k].s_raw) sr[k] = ld_stream(ch.stage[k].s_raw + b * ch.stage[k].s_bs + off);
-            if (ch.stage[k].t) tr[k] = ld_stream(ch.stage[k].t + b * ch.stage[k].t_bs + off);
-        }
-    }
+    chain_load_rows(ch, q, b, H, W, w4, sr, tr);
     const int64_t oo = (int64_t)h * W + w4;
     const float* lp = low + b * low_bs + (int64_t)c * HW + oo;
     f32x4 lo = ld_stream(lp);               // sample 0's, and every sample's where they share it (low_ss == 0)
-    f32x4 g = {1.f, 1.f, 1.f, 1.f}, o = zero;
+    f32x4 g = {1.f, 1.f, 1.f, 1.f}, o = {0.f, 0.f, 0.f, 0.f};
     int nx = 0;
 #pragma unroll
     for (int k = 0; k < NS; ++k)
         if (k < n) {
-            if (ch.stage[k].perm && ch.stage[k].perm_axis == 3) {           // uniform over the block
-                float* bg = rows + (size_t)(nx & 1) * (2 * CHAIN_THREADS * 4) + (size_t)r * W;
-                float* bo = bg + CHAIN_THREADS * 4;
-                ++nx;
-                *reinterpret_cast<f32x4*>(bg + w4) = g;
-                *reinterpret_cast<f32x4*>(bo + w4) = o;
-                __syncthreads();
-                const int64_t* pk = ch.stage[k].perm + w4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int wj = (int)pk[j];
-                    g[j] = bg[wj];
-                    o[j] = bo[wj];
-                }
-            }
+            chain_col_gather(ch.stage[k], rows, nx, r, W, w4, g, o);
             f32x4 sv, tv;
             stage_st4(ch.stage[k], sr[k], tr[k], sv, tv);
 #pragma unroll
@@ -1159,7 +1116,6 @@ __global__ __launch_bounds__(256) void rand_kernel(float* __restrict__ out, int 
     }
 }
 
-// rows variant usable?  (LDS budget, grid limits)
 // Backward of  L = gscale * 0.5 * sum z^2  -  ldscale * sum_b logdet_b  (CWFA.py:970-978: gscale = 1/numel,
 // ldscale = 1/(B*numel)) through a whole forward chain in ONE launch and without stored activations: the flow is
 // invertible, so the thread that owns a latent position walks the stages backwards, recovering each stage's input from
@@ -1247,15 +1203,8 @@ __global__ __launch_bounds__(256) void chain_inv_bwd_kernel(const float* __restr
     const int b = blockIdx.y;
     double lsum = 0.0;
     if (i < n) {
-        Pos p{(int)(i / HW), (int)((i / W) % H), (int)(i % W)};
         int64_t off[CWFA_CHAIN_MAX];
-#pragma unroll
-        for (int k = CWFA_CHAIN_MAX - 1; k >= 0; --k) {
-            if (k < ch.n_stages) {
-                off[k] = lin(p, H, W);
-                p = gather_pos(p, ch.stage[k].perm, ch.stage[k].perm_axis);
-            }
-        }
+        const Pos p = chain_pos_walk(ch, Pos{(int)(i / HW), (int)((i / W) % H), (int)(i % W)}, H, W, off);
         const int64_t pix = (int64_t)p.h * W + p.w;
         const float x0 = xhat[b * xhat_bs + (int64_t)(2 * p.c) * HW + pix], x1 = xhat[b * xhat_bs + (int64_t)(2 * p.c + 1) * HW + pix];
         const float q0 = gt[b * gt_bs + (int64_t)(2 * p.c) * HW + pix], q1 = gt[b * gt_bs + (int64_t)(2 * p.c + 1) * HW + pix];
@@ -1293,10 +1242,7 @@ __global__ __launch_bounds__(256) void chain_inv_bwd_kernel(const float* __restr
     }
 }
 
-extern "C" int cwfa_chain_bwd_f32(const float* z, const float* gz, const cwfa_chain* ch, const cwfa_chain_grads* grads,
-                                  const int64_t* final_perm, float* gv0, int B, int C, int H, int W, int64_t z_bs, int64_t gz_bs,
-                                  int64_t gv0_bs, float gscale, float ldscale, int accumulate, const float* gld, void* stream);
-
+// rows variant usable?  (LDS budget, grid limits)
 static bool chain_rows_ok(const cwfa_chain* ch, int C, int H, int W, int B, size_t* lds) {
     *lds = (size_t)(2 * ch->n_stages + 1) * W * sizeof(float);
     return *lds <= 60 * 1024 && C <= 65535 && B <= 65535 && W >= 64;
@@ -1329,26 +1275,40 @@ static int check_chain(const char* name, const cwfa_chain* ch) {
     return CWFA_OK;
 }
 
+// The front that the chain entry points share: the pointers the entry needs (`ptrs`), the sizes (N = samples, 1 where there is no
+// sample axis) and the chain.  *n = positions of one batch entry; the caller returns at once where B, N or *n is zero, after its own
+// argument checks.
+static int chain_front(const char* name, bool ptrs, int N, int B, int C, int H, int W, const cwfa_chain* ch, int64_t* n) {
+    CWFA_REQUIRE(ptrs, CWFA_E_INVAL, "%s: null pointer", name);
+    CWFA_REQUIRE(N >= 0 && B >= 0 && C >= 0 && H >= 0 && W >= 0 && B <= 65535, CWFA_E_SHAPE, "%s: bad shape", name);
+    *n = (int64_t)C * H * W;
+    return check_chain(name, ch);
+}
+
+// Launch of a 16-byte kernel: a block covers RB whole rows of one channel, and the register arrays are sized for six stages where the
+// chain has no more (see chain_rows4_kernel).  `launch(ns, grid)` issues the kernel for NS = decltype(ns)::value.
+template <class F>
+static int chain_rows4_launch(const char* name, const cwfa_chain& ch, int B, int C, int H, int W, F launch) {
+    const int RB = CHAIN_THREADS * 4 / W;
+    const dim3 grid((H + RB - 1) / RB, C, B);
+    if (ch.n_stages <= 6) launch(std::integral_constant<int, 6>{}, grid);
+    else launch(std::integral_constant<int, CWFA_CHAIN_MAX>{}, grid);
+    CWFA_LAUNCH_CHECK(name);
+    return CWFA_OK;
+}
+
 extern "C" int cwfa_chain_inv_f32(const float* z, const float* low, float* x, const cwfa_chain* ch, int B, int C, int H,
                                   int W, int64_t z_bs, int64_t low_bs, int64_t x_bs, double* logdet, void* stream) {
-    CWFA_REQUIRE(low && x, CWFA_E_INVAL, "cwfa_chain_inv_f32: null pointer");
-    CWFA_REQUIRE(B >= 0 && C >= 0 && H >= 0 && W >= 0 && B <= 65535, CWFA_E_SHAPE, "cwfa_chain_inv_f32: bad shape");
-    int rc = check_chain("cwfa_chain_inv_f32", ch);
+    int64_t n;
+    int rc = chain_front("cwfa_chain_inv_f32", low && x, 1, B, C, H, W, ch, &n);
     if (rc) return rc;
-    const int64_t n = (int64_t)C * H * W;
     if (B == 0 || n == 0) return CWFA_OK;
     size_t lds;
-    if (chain_rows4_ok(ch, C, H, W, B, &lds, low, x, z, low_bs, x_bs, z_bs)) {
-        const int RB = CHAIN_THREADS * 4 / W;
-        if (ch->n_stages <= 6)
-            hipLaunchKernelGGL((chain_rows4_kernel<true, 6>), dim3((H + RB - 1) / RB, C, B), dim3(CHAIN_THREADS), lds, (hipStream_t)stream, low, x,
+    if (chain_rows4_ok(ch, C, H, W, B, &lds, low, x, z, low_bs, x_bs, z_bs))
+        return chain_rows4_launch("cwfa_chain_inv_f32", *ch, B, C, H, W, [&](auto ns, dim3 grid) {
+            hipLaunchKernelGGL((chain_rows4_kernel<true, decltype(ns)::value>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, low, x,
                                const_cast<float*>(z), *ch, (const int64_t*)nullptr, C, H, W, low_bs, x_bs, z_bs, logdet, (double*)nullptr);
-        else
-            hipLaunchKernelGGL((chain_rows4_kernel<true, CWFA_CHAIN_MAX>), dim3((H + RB - 1) / RB, C, B), dim3(CHAIN_THREADS), lds, (hipStream_t)stream, low, x,
-                               const_cast<float*>(z), *ch, (const int64_t*)nullptr, C, H, W, low_bs, x_bs, z_bs, logdet, (double*)nullptr);
-        CWFA_LAUNCH_CHECK("cwfa_chain_inv_f32");
-        return CWFA_OK;
-    }
+        });
     if (chain_rows_ok(ch, C, H, W, B, &lds)) {
         hipLaunchKernelGGL(chain_inv_rows_kernel, dim3(H, C, B), dim3(256), lds, (hipStream_t)stream, z, low, x, *ch, C, H, W,
                            z_bs, low_bs, x_bs, logdet);
@@ -1364,14 +1324,12 @@ extern "C" int cwfa_chain_inv_f32(const float* z, const float* low, float* x, co
 
 extern "C" int cwfa_chain_inv_var_f32(const float* var_low, float* out, const cwfa_chain* ch, float z_var, float std_scale, int B,
                                       int C, int H, int W, int64_t var_low_bs, int64_t out_bs, void* stream) {
-    CWFA_REQUIRE(out, CWFA_E_INVAL, "cwfa_chain_inv_var_f32: null pointer");
-    CWFA_REQUIRE(B >= 0 && C >= 0 && H >= 0 && W >= 0 && B <= 65535, CWFA_E_SHAPE, "cwfa_chain_inv_var_f32: bad shape");
-    int rc = check_chain("cwfa_chain_inv_var_f32", ch);
+    int64_t n;
+    int rc = chain_front("cwfa_chain_inv_var_f32", out, 1, B, C, H, W, ch, &n);
     if (rc) return rc;
     CWFA_REQUIRE(std::isfinite(z_var) && z_var >= 0.f, CWFA_E_INVAL, "cwfa_chain_inv_var_f32: z_var %g is not a finite variance", (double)z_var);
     CWFA_REQUIRE(std::isfinite(std_scale) && std_scale >= 0.f, CWFA_E_INVAL, "cwfa_chain_inv_var_f32: std_scale %g (0 = variance, > 0 = scaled std)",
                  (double)std_scale);
-    const int64_t n = (int64_t)C * H * W;
     if (B == 0 || n == 0) return CWFA_OK;
     cwfa_chain sc = *ch;                      // the variance does not depend on the shifts: the kernels get no t pointer to read
     for (int k = 0; k < sc.n_stages; ++k) {
@@ -1379,18 +1337,11 @@ extern "C" int cwfa_chain_inv_var_f32(const float* var_low, float* out, const cw
         sc.stage[k].t_bs = 0;
     }
     size_t lds;
-    if (chain_rows4_ok(&sc, C, H, W, B, &lds, var_low, out, nullptr, var_low ? var_low_bs : 0, out_bs, 0)) {
-        const int RB = CHAIN_THREADS * 4 / W;
-        const dim3 grid((H + RB - 1) / RB, C, B);
-        if (sc.n_stages <= 6)
-            hipLaunchKernelGGL((chain_var_rows4_kernel<6>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, var_low, out, sc, z_var, std_scale,
-                               C, H, W, var_low_bs, out_bs);
-        else
-            hipLaunchKernelGGL((chain_var_rows4_kernel<CWFA_CHAIN_MAX>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, var_low, out, sc, z_var,
-                               std_scale, C, H, W, var_low_bs, out_bs);
-        CWFA_LAUNCH_CHECK("cwfa_chain_inv_var_f32");
-        return CWFA_OK;
-    }
+    if (chain_rows4_ok(&sc, C, H, W, B, &lds, var_low, out, nullptr, var_low ? var_low_bs : 0, out_bs, 0))
+        return chain_rows4_launch("cwfa_chain_inv_var_f32", sc, B, C, H, W, [&](auto ns, dim3 grid) {
+            hipLaunchKernelGGL((chain_var_rows4_kernel<decltype(ns)::value>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, var_low, out, sc,
+                               z_var, std_scale, C, H, W, var_low_bs, out_bs);
+        });
     dim3 grid((unsigned)((n + 255) / 256), B);
     hipLaunchKernelGGL(chain_inv_var_kernel, grid, dim3(256), 0, (hipStream_t)stream, var_low, out, sc, z_var, std_scale, C, H, W, var_low_bs,
                        out_bs);
@@ -1447,15 +1398,13 @@ extern "C" int cwfa_rand_trunc_normal_f32(float* out, int N, int64_t n, int64_t 
 extern "C" int cwfa_chain_inv_samples_f32(const float* low, float* x, float* z_out, const cwfa_chain* ch, int N, int B, int C, int H, int W,
                                           int64_t low_ss, int64_t low_bs, int64_t x_ss, int64_t x_bs, int64_t z_ss, int64_t z_bs,
                                           float temperature, uint64_t seed, uint32_t stream_id, uint32_t sample_offset, void* stream) {
-    CWFA_REQUIRE(low && x, CWFA_E_INVAL, "cwfa_chain_inv_samples_f32: null pointer");
-    CWFA_REQUIRE(N >= 0 && B >= 0 && C >= 0 && H >= 0 && W >= 0 && B <= 65535, CWFA_E_SHAPE, "cwfa_chain_inv_samples_f32: bad shape");
-    int rc = check_chain("cwfa_chain_inv_samples_f32", ch);
+    int64_t n;
+    int rc = chain_front("cwfa_chain_inv_samples_f32", low && x, N, B, C, H, W, ch, &n);
     if (rc) return rc;
     cwfa_sampler rs;
     rc = make_sampler("cwfa_chain_inv_samples_f32", temperature, seed, stream_id, sample_offset, &rs);
     if (rc) return rc;
     CWFA_REQUIRE(low_ss >= 0 && x_ss >= 0 && z_ss >= 0, CWFA_E_INVAL, "cwfa_chain_inv_samples_f32: negative sample stride");
-    const int64_t n = (int64_t)C * H * W;
     if (N == 0 || B == 0 || n == 0) return CWFA_OK;
     CWFA_REQUIRE(B == 1 || (low_bs >= n && x_bs >= 2 * n && (!z_out || z_bs >= n)), CWFA_E_INVAL,
                  "cwfa_chain_inv_samples_f32: a batch stride is below the elements of one sample's batch entry");
@@ -1469,17 +1418,11 @@ extern "C" int cwfa_chain_inv_samples_f32(const float* low, float* x, float* z_o
     size_t lds;
     // z_out is written with scalar stores (its positions scatter): it need not sit on the 16-byte grid
     if (chain_rows4_ok(ch, C, H, W, B, &lds, low, x, nullptr, low_bs, x_bs, 0) && (low_ss & 3) == 0 && (x_ss & 3) == 0) {
-        const int RB = CHAIN_THREADS * 4 / W;
-        const dim3 grid((H + RB - 1) / RB, C, B);
         lds *= 2;                              // the exchange carries the pair (g, o)
-        if (ch->n_stages <= 6)
-            hipLaunchKernelGGL((chain_samples_rows4_kernel<6>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, low, x, z_out, *ch, rs, N, C,
-                               H, W, low_ss, low_bs, x_ss, x_bs, z_ss, z_bs);
-        else
-            hipLaunchKernelGGL((chain_samples_rows4_kernel<CWFA_CHAIN_MAX>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, low, x, z_out,
-                               *ch, rs, N, C, H, W, low_ss, low_bs, x_ss, x_bs, z_ss, z_bs);
-        CWFA_LAUNCH_CHECK("cwfa_chain_inv_samples_f32");
-        return CWFA_OK;
+        return chain_rows4_launch("cwfa_chain_inv_samples_f32", *ch, B, C, H, W, [&](auto ns, dim3 grid) {
+            hipLaunchKernelGGL((chain_samples_rows4_kernel<decltype(ns)::value>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, low, x,
+                               z_out, *ch, rs, N, C, H, W, low_ss, low_bs, x_ss, x_bs, z_ss, z_bs);
+        });
     }
     dim3 grid((unsigned)((n + 255) / 256), B);
     hipLaunchKernelGGL(chain_samples_kernel, grid, dim3(256), 0, (hipStream_t)stream, low, x, z_out, *ch, rs, N, C, H, W, low_ss, low_bs, x_ss,
@@ -1509,15 +1452,8 @@ __global__ __launch_bounds__(256) void chain_nll_map_kernel(const float* __restr
     const int b = blockIdx.y;
     float nv = 0.f;
     if (i < n) {
-        Pos p{(int)(i / HW), (int)((i / W) % H), (int)(i % W)};
         int64_t off[CWFA_CHAIN_MAX];
-#pragma unroll
-        for (int k = CWFA_CHAIN_MAX - 1; k >= 0; --k) {
-            if (k < ch.n_stages) {
-                off[k] = lin(p, H, W);
-                p = gather_pos(p, ch.stage[k].perm, ch.stage[k].perm_axis);
-            }
-        }
+        chain_pos_walk(ch, Pos{(int)(i / HW), (int)((i / W) % H), (int)(i % W)}, H, W, off);
         float a = 0.f, o = 0.f;
 #pragma unroll
         for (int k = 0; k < CWFA_CHAIN_MAX; ++k) {
@@ -1564,56 +1500,21 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_nll_map_rows4_kernel(cons
     const int64_t HW = (int64_t)H * W;
     const int n = ch.n_stages;
     RowPos q[NS];
-    if (ch.src_c) {
-#pragma unroll
-        for (int k = 0; k < NS; ++k)
-            if (k < n) q[k] = RowPos{ch.src_c[k * C + c], ch.src_h[k * H + h]};
-    } else {
-        RowPos src = RowPos{c, h};
-#pragma unroll
-        for (int k = NS - 1; k >= 0; --k)
-            if (k < n) {
-                q[k] = src;
-                src = row_gather(src, ch.stage[k].perm, ch.stage[k].perm_axis);
-            }
-    }
+    chain_row_walk(ch, c, h, RowPos{c, h}, C, H, q);
     const int64_t oo = (int64_t)h * W + w4, po = (int64_t)c * HW + oo;
     const f32x4 xe = ld_stream(x + b * x_bs + (int64_t)(2 * c) * HW + oo);          // the oldest loads: the first to be waited for
     const f32x4 xo = ld_stream(x + b * x_bs + (int64_t)(2 * c + 1) * HW + oo);
     f32x4 sr[NS], tr[NS];
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < NS; ++k) {
-        sr[k] = tr[k] = zero;
-        if (k < n) {
-            const int64_t off = ((int64_t)q[k].c * H + q[k].h) * W + w4;
-            if (ch.stage[k].s_raw) sr[k] = ld_stream(ch.stage[k].s_raw + b * ch.stage[k].s_bs + off);
-            if (ch.stage[k].t) tr[k] = ld_stream(ch.stage[k].t + b * ch.stage[k].t_bs + off);
-        }
-    }
+    chain_load_rows(ch, q, b, H, W, w4, sr, tr);
     // the pair is done with once d is formed: low leaves while the coefficient rows are still on their way
     const f32x4 d = (xe - xo) * CWFA_INV_SQRT2_F;
     if (live && low) st_stream<false>(low + b * low_bs + po, (xe + xo) * CWFA_INV_SQRT2_F);          // the next step's input: left in the cache
-    f32x4 a = zero, o = zero;
+    f32x4 a = {0.f, 0.f, 0.f, 0.f}, o = a;
     int nx = 0;
 #pragma unroll
     for (int k = 0; k < NS; ++k)
         if (k < n) {
-            if (ch.stage[k].perm && ch.stage[k].perm_axis == 3) {           // uniform over the block
-                float* ba = rows + (size_t)(nx & 1) * (2 * CHAIN_THREADS * 4) + (size_t)r * W;
-                float* bo = ba + CHAIN_THREADS * 4;
-                ++nx;
-                *reinterpret_cast<f32x4*>(ba + w4) = a;
-                *reinterpret_cast<f32x4*>(bo + w4) = o;
-                __syncthreads();
-                const int64_t* pk = ch.stage[k].perm + w4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int wj = (int)pk[j];
-                    a[j] = ba[wj];
-                    o[j] = bo[wj];
-                }
-            }
+            chain_col_gather(ch.stage[k], rows, nx, r, W, w4, a, o);
             f32x4 sv, tv;
             stage_st4(ch.stage[k], sr[k], tr[k], sv, tv);
 #pragma unroll
@@ -1645,26 +1546,19 @@ extern "C" int cwfa_chain_nll_map_f32(const float* x, float* low, float* z, floa
                                       int64_t x_bs, int64_t low_bs, int64_t z_bs, int64_t nll_bs, double* nll_sum, void* stream) {
     CWFA_REQUIRE(x, CWFA_E_INVAL, "cwfa_chain_nll_map_f32: null pointer");
     CWFA_REQUIRE(low || z || nll || nll_sum, CWFA_E_INVAL, "cwfa_chain_nll_map_f32: no output requested (low, z, nll and nll_sum are all null)");
-    CWFA_REQUIRE(B >= 0 && C >= 0 && H >= 0 && W >= 0 && B <= 65535, CWFA_E_SHAPE, "cwfa_chain_nll_map_f32: bad shape");
-    int rc = check_chain("cwfa_chain_nll_map_f32", ch);
+    int64_t n;
+    int rc = chain_front("cwfa_chain_nll_map_f32", true, 1, B, C, H, W, ch, &n);        // (x: checked above, before the outputs)
     if (rc) return rc;
-    const int64_t n = (int64_t)C * H * W;
     if (B == 0 || n == 0) return CWFA_OK;
     CWFA_REQUIRE(B == 1 || (x_bs >= 2 * n && (!low || low_bs >= n) && (!z || z_bs >= n) && (!nll || nll_bs >= n)), CWFA_E_INVAL,
                  "cwfa_chain_nll_map_f32: a batch stride is below the elements of one batch entry");
     size_t lds;
     if (chain_rows4_ok(ch, C, H, W, B, &lds, x, low, z, x_bs, low ? low_bs : 0, z_bs) && cwfa_aligned16(nll) && (!nll || (nll_bs & 3) == 0)) {
-        const int RB = CHAIN_THREADS * 4 / W;
-        const dim3 grid((H + RB - 1) / RB, C, B);
         lds *= 2;                              // the exchange carries the pair (a, o)
-        if (ch->n_stages <= 6)
-            hipLaunchKernelGGL((chain_nll_map_rows4_kernel<6>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, x, low, z, nll, *ch, C, H, W,
-                               x_bs, low_bs, z_bs, nll_bs, nll_sum);
-        else
-            hipLaunchKernelGGL((chain_nll_map_rows4_kernel<CWFA_CHAIN_MAX>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, x, low, z, nll,
-                               *ch, C, H, W, x_bs, low_bs, z_bs, nll_bs, nll_sum);
-        CWFA_LAUNCH_CHECK("cwfa_chain_nll_map_f32");
-        return CWFA_OK;
+        return chain_rows4_launch("cwfa_chain_nll_map_f32", *ch, B, C, H, W, [&](auto ns, dim3 grid) {
+            hipLaunchKernelGGL((chain_nll_map_rows4_kernel<decltype(ns)::value>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, x, low, z,
+                               nll, *ch, C, H, W, x_bs, low_bs, z_bs, nll_bs, nll_sum);
+        });
     }
     CWFA_REQUIRE((n + 255) / 256 <= 0x7fffffff, CWFA_E_SHAPE, "cwfa_chain_nll_map_f32: %lld positions exceed one launch", (long long)n);
     dim3 grid((unsigned)((n + 255) / 256), B);
@@ -1738,24 +1632,16 @@ extern "C" int cwfa_nll_compose_f32(const cwfa_nll_levels* levels, float* out, i
 extern "C" int cwfa_chain_fwd_f32(const float* x, float* low, float* z, const cwfa_chain* ch, const int64_t* final_perm,
                                   int B, int C, int H, int W, int64_t x_bs, int64_t low_bs, int64_t z_bs, double* logdet,
                                   double* sumsq, void* stream) {
-    CWFA_REQUIRE(x && low && z, CWFA_E_INVAL, "cwfa_chain_fwd_f32: null pointer");
-    CWFA_REQUIRE(B >= 0 && C >= 0 && H >= 0 && W >= 0 && B <= 65535, CWFA_E_SHAPE, "cwfa_chain_fwd_f32: bad shape");
-    int rc = check_chain("cwfa_chain_fwd_f32", ch);
+    int64_t n;
+    int rc = chain_front("cwfa_chain_fwd_f32", x && low && z, 1, B, C, H, W, ch, &n);
     if (rc) return rc;
-    const int64_t n = (int64_t)C * H * W;
     if (B == 0 || n == 0) return CWFA_OK;
     size_t lds;
-    if (chain_rows4_ok(ch, C, H, W, B, &lds, x, low, z, x_bs, low_bs, z_bs)) {
-        const int RB = CHAIN_THREADS * 4 / W;
-        if (ch->n_stages <= 6)
-            hipLaunchKernelGGL((chain_rows4_kernel<false, 6>), dim3((H + RB - 1) / RB, C, B), dim3(CHAIN_THREADS), lds, (hipStream_t)stream, x, low, z,
-                               *ch, final_perm, C, H, W, x_bs, low_bs, z_bs, logdet, sumsq);
-        else
-            hipLaunchKernelGGL((chain_rows4_kernel<false, CWFA_CHAIN_MAX>), dim3((H + RB - 1) / RB, C, B), dim3(CHAIN_THREADS), lds, (hipStream_t)stream, x, low, z,
-                               *ch, final_perm, C, H, W, x_bs, low_bs, z_bs, logdet, sumsq);
-        CWFA_LAUNCH_CHECK("cwfa_chain_fwd_f32");
-        return CWFA_OK;
-    }
+    if (chain_rows4_ok(ch, C, H, W, B, &lds, x, low, z, x_bs, low_bs, z_bs))
+        return chain_rows4_launch("cwfa_chain_fwd_f32", *ch, B, C, H, W, [&](auto ns, dim3 grid) {
+            hipLaunchKernelGGL((chain_rows4_kernel<false, decltype(ns)::value>), grid, dim3(CHAIN_THREADS), lds, (hipStream_t)stream, x, low, z, *ch,
+                               final_perm, C, H, W, x_bs, low_bs, z_bs, logdet, sumsq);
+        });
     if (chain_rows_ok(ch, C, H, W, B, &lds)) {
         hipLaunchKernelGGL(chain_fwd_rows_kernel, dim3(H, C, B), dim3(256), lds, (hipStream_t)stream, x, low, z, *ch, final_perm,
                            C, H, W, x_bs, low_bs, z_bs, logdet, sumsq);
@@ -1917,7 +1803,6 @@ extern "C" int cwfa_affine_bwd_f32(const float* x, const float* g, const cwfa_af
     return CWFA_OK;
 }
 
-static int check_chain(const char* name, const cwfa_chain* ch);
 extern "C" int cwfa_chain_bwd_f32(const float* z, const float* gz, const cwfa_chain* ch, const cwfa_chain_grads* grads,
                                   const int64_t* final_perm, float* gv0, int B, int C, int H, int W, int64_t z_bs, int64_t gz_bs,
                                   int64_t gv0_bs, float gscale, float ldscale, int accumulate, const float* gld, void* stream) {
