@@ -382,8 +382,10 @@ def _seeded_samples(steps, up, n_samples, temperature, seed, sample_offset, retu
 def posterior_roi_means(conv_inn, cond_nets, cond_input, mean_vols_cache, boxes, n_samples, low=None, temperature=1.0, seed=0,
                         chunk=16):
     """The ROI means (``corr_coeff_3D``'s traces, before its normalisation) of ``n_samples`` posterior samples: float64
-    [n_samples, B, n_roi] -- the distribution behind the error bar of a neuron's trace, which has no per-voxel closed form (the
-    two voxels of a Haar pair share a latent with opposite signs, coarse latents are shared by 2^k depths).  ``boxes``: the
+    [n_samples, B, n_roi] -- the DISTRIBUTION behind the error bar of a neuron's trace (quantiles, tails, any non-linear
+    statistic).  Its first two moments need no samples: the mean, the variance and the covariance of any two ROI means are exact
+    in ``posterior_roi_moments`` (the two voxels of a Haar pair share a latent with opposite signs and coarse latents are shared by
+    2^k depths, which the closed form there accounts for).  ``boxes``: the
     integer [n_roi, 6] table of ``roi_boxes``.  Every network and stage list is built ONCE; the samples are then drawn ``chunk``
     at a time (``posterior_samples(seed=seed, sample_offset=...)``: the same values whatever ``chunk`` is) and reduced by
     ``ops.roi_means``, so the samples' memory is bounded by ``chunk`` volumes per level.  The price of building the networks once is
@@ -409,6 +411,54 @@ def posterior_roi_means(conv_inn, cond_nets, cond_input, mean_vols_cache, boxes,
         xs = _seeded_samples(steps, up, n, temperature, seed, k, False)
         out.append(ops.roi_means(xs.view(n * B, *xs.shape[2:]), boxes).t().reshape(n, B, -1))
     return torch.cat(out)
+
+
+@amp_function
+@torch.no_grad()
+def posterior_roi_moments(conv_inn, cond_nets, cond_input, mean_vols_cache, boxes, low=None, temperature=1.0, pairs=None,
+                          std_scale=1.0, return_volume=False):
+    """Exact first and second moments of the ROI means (``corr_coeff_3D``'s traces, before its normalisation) under the posterior
+    ``posterior_samples`` draws from: ``(mean [B, R], std [B, R], cov [B, P] or None)``, float64, plus the mean volume with
+    ``return_volume``.  ``boxes``: the integer [R, 6] table of ``roi_boxes``; ``pairs``: integer [P, 2] box indices whose covariance
+    is wanted (None: ``cov`` is None).  Every step all-CAT; NotImplementedError otherwise (as ``posterior_moments``).
+
+    The loop of ``posterior_moments``: per step the sub-networks run once, one ``ops.chain_inv`` with z = None carries the mean
+    volume down (the mean of an ROI mean is the ROI mean of that volume: E z = 0) and one ``ops.chain_inv_roi_cov`` adds the step's
+    term of
+        Cov(mean_r1, mean_r2) = z_var / (cnt_r1 cnt_r2) * sum_m 2^-m sum_c q_r1,m(c) q_r2,m(c) sum_{(y,x) in both footprints} exp(a_m[c,y,x])
+    where step m (1 = finest) spreads its detail v[c] over the 2^m depths of block c with opposite signs on the two halves,
+    q_r,m(c) counts the box's depths in the first half minus those in the second, and z_var exp(a_m) is the variance of v.  Depths
+    that cover a whole block cancel exactly: a box over all depths has variance 0.  A step's coefficients are free before the
+    next step runs.  An empty box gives NaN, as in ``ops.roi_means``.
+
+    ``std_scale`` as in ``posterior_moments`` (std_vols * 2**len(batch) for the de-normalised volume): it multiplies ``mean`` and
+    ``std`` and its square multiplies ``cov``, in float64 on the results; the returned volume is unscaled."""
+    import numpy as np
+    plans = _affine_plans(conv_inn, "posterior_roi_moments")
+    if not float(std_scale) > 0.0:
+        raise ValueError(f"std_scale {std_scale!r} must be > 0")
+    z_var = truncated_normal_variance(temperature)
+    S1 = len(conv_inn)
+    bx = np.asarray(boxes, dtype=np.int32).reshape(-1, 6)
+    R = len(bx)
+    diag = np.repeat(np.arange(R, dtype=np.int32)[:, None], 2, 1)
+    pr = diag if pairs is None else np.concatenate([diag, np.asarray(pairs, dtype=np.int32).reshape(-1, 2)])
+    up = _coarsest(conv_inn, cond_nets, cond_input, mean_vols_cache, low)
+    table = ops.RoiPairs(bx, pr, up.device)          # the variances first, then the requested pairs: one launch per step
+    acc = torch.zeros(up.shape[0], len(pr), dtype=torch.float64, device=up.device)
+    from .networks import omega_first_scope
+    with omega_first_scope(list(cond_nets[:S1]), cond_input):
+        for n in range(S1 - 1, -1, -1):
+            c = [cond_nets[n](cond_input)[-1], mean_vols_cache[n]]
+            stages, tabs = plans[n].inverse_stages(c, tuple(up.shape[1:]), up.device)
+            shape = tuple(up.shape)
+            up = ops.chain_inv(None, up, stages, tables=tabs)
+            ops.chain_inv_roi_cov(acc, stages, z_var, shape, n + 1, table)      # step n is level m = n + 1 (n = 0: the finest)
+    scale = float(std_scale)
+    mean = ops.roi_means(up, bx).t() * scale
+    std = acc[:, :R].sqrt() * scale
+    cov = None if pairs is None else acc[:, R:] * (scale * scale)
+    return (mean, std, cov, up) if return_volume else (mean, std, cov)
 
 
 @amp_function

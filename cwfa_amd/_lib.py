@@ -99,6 +99,7 @@ SIGNATURES = {
     "cwfa_channel_affine_f32": (i, [p, p, p, p, i, p, p, i, i, i64, i64, i64, p]),
     "cwfa_chain_inv_f32": (i, [p, p, p, C.POINTER(Chain), i, i, i, i, i64, i64, i64, p, p]),
     "cwfa_chain_inv_var_f32": (i, [p, p, C.POINTER(Chain), f, f, i, i, i, i, i64, i64, p]),
+    "cwfa_chain_inv_roi_cov_f32": (i, [p, C.POINTER(Chain), f, i, i, i, i, i, p, i, p, i, p, i64, p]),
     "cwfa_rand_uniform_f32": (i, [p, i, i64, i64, C.c_uint64, C.c_uint32, C.c_uint32, p]),
     "cwfa_rand_trunc_normal_f32": (i, [p, i, i64, i64, f, C.c_uint64, C.c_uint32, C.c_uint32, p]),
     "cwfa_chain_inv_samples_f32": (i, [p, p, p, C.POINTER(Chain), i, i, i, i, i, i64, i64, i64, i64, i64, i64, f, C.c_uint64, C.c_uint32,

@@ -1349,6 +1349,132 @@ extern "C" int cwfa_chain_inv_var_f32(const float* var_low, float* out, const cw
     return CWFA_OK;
 }
 
+// ---- exact covariance of ROI means under the posterior of a CAT pyramid (cwfa_chain_inv_roi_cov_f32).  The
+// detail v[c,y,x] of the step at level m (m = 1: the finest step) reaches the 2^m final depths [c 2^m, (c+1) 2^m) at the same (y,x)
+// with weight +2^(-m/2) on the first half of that block and -2^(-m/2) on the second, and the v are independent with variance
+// z_var * exp(a) (the travelling sum of chain_inv_var_kernel).  A box over depths [z0, z1) therefore sees v[c] with the integer weight
+// q(c) = (depths in the first half) - (depths in the second half): zero for every block wholly inside or outside the range, so at most
+// the two blocks that hold an end of the range count.  The boxes of a pair travel as twelve ints, in the kernel arguments (ROI_COV_CHUNK
+// pairs per launch) or in a device table (one launch).
+#define ROI_COV_CHUNK 64
+struct RoiPairChunk {
+    int box[ROI_COV_CHUNK][12];
+};
+
+__host__ __device__ static inline int64_t roi_overlap(int z0, int z1, int64_t lo, int64_t hi) {
+    const int64_t a = z0 > lo ? z0 : lo, b = z1 < hi ? z1 : hi;
+    return b > a ? b - a : 0;
+}
+// q of the depth range [z0, z1) in block c of level m
+__host__ __device__ static inline int64_t roi_q(int z0, int z1, int c, int m) {
+    const int64_t lo = (int64_t)c << m, half = (int64_t)1 << (m - 1);
+    return roi_overlap(z0, z1, lo, lo + half) - roi_overlap(z0, z1, lo + half, lo + 2 * half);
+}
+
+// one block per (pair, batch sample); the threads stride over the footprint intersection of each counted channel.  No atomics: the
+// block's owner adds its term to out[b][p], and the steps of a pyramid accumulate in stream order.
+__global__ __launch_bounds__(256) void chain_roi_cov_kernel(double* __restrict__ out, cwfa_chain ch, float z_var, int H, int W, int m,
+                                                            RoiPairChunk ck, const int* __restrict__ table, int64_t out_bs) {
+    __shared__ double red[16];
+    const int p = blockIdx.x, b = blockIdx.y;
+    int bx[12];
+    if (table) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) bx[k] = table[(int64_t)p * 12 + k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) bx[k] = ck.box[p][k];
+    }
+    double* o = out + b * out_bs + p;
+    const int64_t cnt1 = (int64_t)(bx[1] - bx[0]) * (bx[3] - bx[2]) * (bx[5] - bx[4]);
+    const int64_t cnt2 = (int64_t)(bx[7] - bx[6]) * (bx[9] - bx[8]) * (bx[11] - bx[10]);
+    if (cnt1 == 0 || cnt2 == 0) {                              // the mean of an empty box is NaN (roi_means_kernel)
+        if (threadIdx.x == 0) *o = (double)NAN;
+        return;
+    }
+    const int ya = max(bx[2], bx[8]), xa = max(bx[4], bx[10]);
+    const int ny = min(bx[3], bx[9]) - ya, nx = min(bx[5], bx[11]) - xa;
+    if (z_var == 0.f || ny <= 0 || nx <= 0) return;            // the term is exactly zero: out keeps its value
+    const int64_t npos = (int64_t)ny * nx;
+    const int c_first = bx[0] >> m, c_last = (bx[1] - 1) >> m; // the blocks that hold an end of box 1's range: every other q1 is 0
+    double acc = 0.0;
+    for (int j = 0; j < 2; ++j) {
+        if (j == 1 && c_last == c_first) break;
+        const int c = j ? c_last : c_first;
+        const double qq = (double)roi_q(bx[0], bx[1], c, m) * (double)roi_q(bx[6], bx[7], c, m);
+        if (qq == 0.0) continue;                               // skipped before any load
+        double part = 0.0;
+        for (int64_t i = threadIdx.x; i < npos; i += 256) {
+            int64_t off[CWFA_CHAIN_MAX];
+            chain_pos_walk(ch, Pos{c, ya + (int)(i / nx), xa + (int)(i % nx)}, H, W, off);
+            float a = 0.f;
+#pragma unroll
+            for (int k = 0; k < CWFA_CHAIN_MAX; ++k) {
+                if (k < ch.n_stages) {
+                    float s, t;
+                    stage_st(ch.stage[k], b, off[k], s, t);
+                    a = a - 2.f * s;
+                }
+            }
+            part += (double)expf(a);                           // the precise one, as chain_var_out
+        }
+        acc += qq * part;
+    }
+    const double tot = cwfa_block_sum(acc, red);
+    if (threadIdx.x == 0) *o += (double)z_var * ldexp(1.0, -m) / ((double)cnt1 * (double)cnt2) * tot;
+}
+
+extern "C" int cwfa_chain_inv_roi_cov_f32(double* out, const cwfa_chain* ch, float z_var, int B, int C, int H, int W, int level,
+                                          const int32_t* boxes, int R, const int32_t* pairs, int P, const int32_t* dev_table,
+                                          int64_t out_bs, void* stream) {
+    const char* name = "cwfa_chain_inv_roi_cov_f32";
+    int64_t n;
+    int rc = chain_front(name, out || B == 0 || P == 0, 1, B, C, H, W, ch, &n);          // (an empty out has no address)
+    if (rc) return rc;
+    CWFA_REQUIRE(std::isfinite(z_var) && z_var >= 0.f, CWFA_E_INVAL, "%s: z_var %g is not a finite variance", name, (double)z_var);
+    CWFA_REQUIRE(level >= 1 && level <= 30, CWFA_E_INVAL, "%s: level %d not in 1..30 (1 = the finest step)", name, level);
+    const int64_t D = (int64_t)C << level;
+    CWFA_REQUIRE(D < ((int64_t)1 << 31) && (int64_t)H * W < ((int64_t)1 << 31), CWFA_E_SHAPE, "%s: volume too large", name);
+    CWFA_REQUIRE(R >= 0 && P >= 0 && (boxes || R == 0), CWFA_E_INVAL, "%s: bad box table", name);
+    CWFA_REQUIRE(pairs || P == R, CWFA_E_INVAL, "%s: without a pair table P (%d) must be the number of boxes (%d)", name, P, R);
+    CWFA_REQUIRE(out_bs >= P, CWFA_E_INVAL, "%s: batch stride %lld of out is smaller than a row of %d pairs", name, (long long)out_bs, P);
+    for (int i = 0; i < R; ++i) {
+        const int32_t* b = boxes + 6 * i;
+        CWFA_REQUIRE(0 <= b[0] && b[0] <= b[1] && b[1] <= D && 0 <= b[2] && b[2] <= b[3] && b[3] <= H && 0 <= b[4] && b[4] <= b[5] && b[5] <= W,
+                     CWFA_E_INVAL, "%s: box %d [%d,%d) x [%d,%d) x [%d,%d) is not inside the %lld x %d x %d volume", name, i, b[0], b[1], b[2],
+                     b[3], b[4], b[5], (long long)D, H, W);
+    }
+    for (int i = 0; pairs && i < P; ++i)
+        CWFA_REQUIRE(pairs[2 * i] >= 0 && pairs[2 * i] < R && pairs[2 * i + 1] >= 0 && pairs[2 * i + 1] < R, CWFA_E_INVAL,
+                     "%s: pair %d (%d, %d) names a box outside [0, %d)", name, i, pairs[2 * i], pairs[2 * i + 1], R);
+    if (B == 0 || P == 0) return CWFA_OK;
+    cwfa_chain sc = *ch;                      // as cwfa_chain_inv_var_f32: no t pointer for the kernel to read
+    for (int k = 0; k < sc.n_stages; ++k) {
+        sc.stage[k].t = nullptr;
+        sc.stage[k].t_bs = 0;
+    }
+    RoiPairChunk ck = {};
+    if (dev_table) {                          // the caller's device copy of the [P][12] pair table: one launch
+        hipLaunchKernelGGL(chain_roi_cov_kernel, dim3(P, B), dim3(256), 0, (hipStream_t)stream, out, sc, z_var, H, W, level, ck, dev_table, out_bs);
+        CWFA_LAUNCH_CHECK(name);
+        return CWFA_OK;
+    }
+    for (int p0 = 0; p0 < P; p0 += ROI_COV_CHUNK) {
+        const int np = P - p0 < ROI_COV_CHUNK ? P - p0 : ROI_COV_CHUNK;
+        for (int i = 0; i < ROI_COV_CHUNK; ++i) {
+            const int r1 = i >= np ? -1 : pairs ? pairs[2 * (p0 + i)] : p0 + i, r2 = i >= np ? -1 : pairs ? pairs[2 * (p0 + i) + 1] : p0 + i;
+            for (int k = 0; k < 6; ++k) {
+                ck.box[i][k] = r1 < 0 ? 0 : boxes[6 * r1 + k];
+                ck.box[i][6 + k] = r2 < 0 ? 0 : boxes[6 * r2 + k];
+            }
+        }
+        hipLaunchKernelGGL(chain_roi_cov_kernel, dim3(np, B), dim3(256), 0, (hipStream_t)stream, out + p0, sc, z_var, H, W, level, ck,
+                           (const int*)nullptr, out_bs);
+        CWFA_LAUNCH_CHECK(name);
+    }
+    return CWFA_OK;
+}
+
 // the generator's parameters of a call; temperature > 0 (inf allowed), NaN refused
 static int make_sampler(const char* name, float temperature, uint64_t seed, uint32_t stream_id, uint32_t sample_offset, cwfa_sampler* rs) {
     CWFA_REQUIRE(temperature > 0.f, CWFA_E_INVAL, "%s: temperature %g must be > 0 (the truncation bound; 0 is the mean: no draw)", name,

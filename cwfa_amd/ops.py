@@ -8,7 +8,7 @@ import torch
 from . import _lib
 from ._lib import AffineStage, Chain, ConvOpts, check
 
-__all__ = ["haar1d", "haar2d", "gather", "affine", "channel_affine", "chain_inv", "chain_inv_var", "chain_inv_samples", "rand_uniform", "rand_trunc_normal", "chain_nll_map", "nll_compose", "chain_fwd", "pack_conv_weight",
+__all__ = ["haar1d", "haar2d", "gather", "affine", "channel_affine", "chain_inv", "chain_inv_var", "chain_inv_roi_cov", "chain_inv_samples", "rand_uniform", "rand_trunc_normal", "chain_nll_map", "nll_compose", "chain_fwd", "pack_conv_weight",
            "conv2d", "conv2d_wgrad", "elu_bwd", "set_precision", "gelu_add", "gelu_bwd", "layernorm_bwd", "attention_bwd", "plane_affine", "bn_bwd_stats", "bn_act_bwd", "maxpool2_bwd", "chain_bwd", "chain_inv_bwd", "prelu_bwd", "conv3d_1k1_backward", "pack_1x1_panel", "pack_split_layer_weight", "subnet_layer", "conv3d_1k1", "channel_stats", "bn_fold", "bn_running_update", "maxpool", "sample_stats", "layernorm_apply",
            "convnext_tail", "conv_writes_sample_stats", "attention_combine", "scale_channels", "axpby", "stage", "lion_step", "global_extrema", "wmse_loss"]
 
@@ -298,6 +298,55 @@ def chain_inv_var(var_low, stages, z_var, shape=None, std_scale=0.0, tables=None
     out = torch.empty((B, 2 * Cc, H, W), dtype=torch.float32, device=dev)
     check(L.cwfa_chain_inv_var_f32(_p(var_low), _p(out), C.byref(ch), float(z_var), float(std_scale), B, Cc, H, W, vbs,
                                    2 * Cc * H * W, _stream()), "chain_inv_var")
+    return out
+
+
+ROI_COV_ARG_PAIRS = 64        # ROI_COV_CHUNK of csrc/elementwise.hip: up to this many pairs travel in one launch's kernel arguments
+
+
+class RoiPairs:
+    """The box / pair tables of ``chain_inv_roi_cov`` prepared once for the steps of a pyramid: the int32 host tables the library
+    validates and, with ``device_table``, the device copy [P, 12] of the pairs' boxes (one upload for every step)."""
+
+    def __init__(self, boxes, pairs=None, device=None, device_table=None):
+        import numpy as np
+        self.boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 6))
+        self.pairs = None if pairs is None else np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        self.n_pairs = len(self.boxes) if self.pairs is None else len(self.pairs)
+        if device_table is None:                 # beyond one launch's worth of kernel arguments (DESIGN.md section 19)
+            device_table = self.n_pairs > ROI_COV_ARG_PAIRS
+        self.table = None
+        if device_table and self.n_pairs:
+            R = len(self.boxes)
+            idx = np.repeat(np.arange(R)[:, None], 2, 1) if self.pairs is None else self.pairs
+            if idx.size and (idx.min() < 0 or idx.max() >= R):
+                raise ValueError(f"chain_inv_roi_cov: a pair names a box outside [0, {R})")
+            tab = np.ascontiguousarray(self.boxes[idx].reshape(-1, 12))
+            self.table = torch.from_numpy(tab).to(device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+
+
+def chain_inv_roi_cov(out, stages, z_var, shape, level, boxes, pairs=None, tables=None):
+    """Accumulate into ``out`` (float64 [B, P] on the device, zeroed by the caller; returned) one step's term of the covariance of
+    the ROI means of the final volume (cwfa_chain_inv_roi_cov_f32).  ``stages``: the step's inverse chain with coefficients of
+    ``shape = (B, C, H, W)``; ``level`` = m: 1 for the finest step, so that the final volume has C * 2^m depths; ``boxes``: the
+    integer [R, 6] host table of ``roi_means`` in the final volume's coordinates, ``pairs``: integer [P, 2] box indices (None = the
+    R diagonal pairs: the variances) -- or a prepared ``RoiPairs`` as ``boxes``.  A pair with an empty box becomes NaN.  ``tables``
+    is accepted for symmetry with the other chain ops; the kernel walks the gathers itself."""
+    L = _lib.lib()
+    if not torch.is_tensor(out) or not out.is_cuda:
+        raise RuntimeError("chain_inv_roi_cov: cwfa_amd runs on MI355X only -- `out` must be a device tensor (no CPU fallback exists)")
+    if out.dtype != torch.float64 or out.dim() != 2 or not out.is_contiguous():
+        raise TypeError("chain_inv_roi_cov: `out` must be a contiguous float64 [B, P] tensor")
+    rp = boxes if isinstance(boxes, RoiPairs) else RoiPairs(boxes, pairs, out.device)
+    if isinstance(boxes, RoiPairs) and pairs is not None:
+        raise ValueError("chain_inv_roi_cov: a prepared RoiPairs already holds its pairs")
+    B, Cc, H, W = (int(v) for v in shape)
+    if tuple(out.shape) != (B, rp.n_pairs):
+        raise ValueError(f"chain_inv_roi_cov: out {tuple(out.shape)} is not [B, P] = {(B, rp.n_pairs)}")
+    ch, keep = _chain(stages, None)
+    check(L.cwfa_chain_inv_roi_cov_f32(_p(out), C.byref(ch), float(z_var), B, Cc, H, W, int(level), C.c_void_p(rp.boxes.ctypes.data),
+                                       len(rp.boxes), None if rp.pairs is None else C.c_void_p(rp.pairs.ctypes.data), rp.n_pairs,
+                                       _p(rp.table), rp.n_pairs, _stream()), "chain_inv_roi_cov")
     return out
 
 

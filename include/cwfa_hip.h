@@ -185,6 +185,22 @@ int cwfa_chain_inv_f32(const float* z, const float* low, float* x, const cwfa_ch
 int cwfa_chain_inv_var_f32(const float* var_low, float* out, const cwfa_chain* ch, float z_var, float std_scale,
                            int B, int C, int H, int W, int64_t var_low_bs, int64_t out_bs, void* stream);
 
+/* One step's term of the exact covariance of ROI means of the volume a CAT pyramid reconstructs.  `ch` is the
+ * step's chain as for cwfa_chain_inv_var_f32 ([B,C,H,W] coefficients, execution order of the inverse; t, src_c, src_h never read),
+ * `level` = m in 1..30 counts the steps from the finest (m = 1) so that the final volume has D = C * 2^m depths.  boxes: HOST int32
+ * [R][6] = {z0,z1,y0,y1,x0,x1}, half-open, inside D x H x W (as cwfa_roi_means_f32); pairs: HOST int32 [P][2] box indices, NULL = the
+ * R diagonal pairs (then P must be R).  For every pair and batch sample
+ *   out[b][p] += z_var * 2^-m / (cnt1 * cnt2) * sum_c q1(c) q2(c) * sum_{(y,x) in both footprints} exp(a[b,c,y,x])
+ * with a the travelling sum of cwfa_chain_inv_var_f32 and q(c) = (depths of the box in the first half of [c 2^m, (c+1) 2^m)) - (depths
+ * in its second half).  out: DEVICE double [B][P], batch stride out_bs >= P, zeroed by the caller; the calls of a pyramid's steps
+ * accumulate in stream order and no atomics are used, so a call is bitwise repeatable.  A pair with an empty box is set to NaN; an
+ * empty footprint intersection, a channel with q1 q2 = 0 (never read) and z_var = 0 add exactly nothing.
+ * dev_table (nullable): a DEVICE int32 [P][12] copy of the pairs' boxes (box of pairs[p][0], then box of pairs[p][1]): one launch for
+ * any P.  NULL: the boxes travel in the kernel arguments, 64 pairs per launch.  The host tables are validated either way. */
+int cwfa_chain_inv_roi_cov_f32(double* out, const cwfa_chain* ch, float z_var, int B, int C, int H, int W, int level,
+                               const int32_t* boxes, int R, const int32_t* pairs, int P, const int32_t* dev_table, int64_t out_bs,
+                               void* stream);
+
 /* The counter-based generator of the samplers: Philox4x32-10 under the key (seed & 0xffffffff, seed >> 32).  Element e (the
  * contiguous linear index within ONE sample) of sample n takes word e & 3 of the block with counter
  * (g & 0xffffffff, g >> 32, sample_offset + n, stream_id), g = e >> 2; as a uniform, u = ((word >> 9) + 0.5) * 2^-23 (exact in
