@@ -162,6 +162,9 @@ SIGNATURES = {
     "cwfa_subnet_layer_split_pack_f32": (i, [p, p, p, p]),
     "cwfa_subnet_layer_split_f32": (i, [p, p, p, p, p, i, i, i, i64, i64, i, p]),
     "cwfa_subnet_layer_split_tape_f32": (i, [p, p, p, p, p, p, i, i, i, i64, i64, i64, p]),
+    "cwfa_conv3x3_out_split_packed_bytes": (i64, [i]),
+    "cwfa_conv3x3_out_split_pack_f32": (i, [p, p, i, p]),
+    "cwfa_conv3x3_out_split_f32": (i, [p, p, p, p, i, i, i, i, i64, i64, i, p]),
     "cwfa_subnet_layer_first_packed_bytes": (i64, []),
     "cwfa_subnet_layer_first_pack_f32": (i, [p, p, p, i, p, p]),
     "cwfa_subnet_layer_first_f32": (i, [p, p, p, p, p, p, i, i, i, i, i64, i64, i64, i, p]),

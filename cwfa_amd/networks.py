@@ -186,7 +186,7 @@ class wavelet_flow_subnetwork(nn.Module):
         # ([8][H][W][8]: 16-byte accesses in the layer kernel, see cwfa_subnet_layer_split_f32) whenever their consumer reads
         # that layout -- the next layer, and the last convolution if it runs on the split-bf16 3x3 kernel
         pc_out = None if couple is not None else P(conv_out)
-        last_reads_blocked = split_layers and ops.BLOCKED_MAPS and (couple is not None or (pc_out.split and pc_out.ks == 3))
+        last_reads_blocked = split_layers and ops.BLOCKED_MAPS and (couple is not None or (pc_out.split and pc_out.ks == 3) or ops.out_walk_selected(pc_out, H_, W_))
         for i, blk in enumerate((self.block2, self.block4, self.block6)):
             if fused:       # 3x3 -> ELU -> 1x1 -> +b -> ELU in one launch, hidden map stays in registers
                 if split_layers and i == 0 and first_form:

@@ -576,18 +576,31 @@ def chain_bwd(z, stages, grads, final_perm=None, gscale=0.0, ldscale=0.0, gz=Non
 class PackedConv:
     """Kernel-layout image of one filter bank (built once per weight version on the device)."""
     __slots__ = ("packed", "cout", "cin", "ks", "transposed", "version", "src_ptr", "split", "epoch", "version1", "src_ptr1", "cat_c1",
-                 "cat_from", "short")
+                 "cat_from", "short", "walk")
 
     def __init__(self, packed, cout, cin, ks, transposed, version, src_ptr, split=False):
         self.packed, self.cout, self.cin, self.ks = packed, cout, cin, ks
         self.transposed, self.version, self.src_ptr = transposed, version, src_ptr
         self.split = split          # weights held as three bf16 pieces for the split-bf16 kernels (set_precision)
         self.epoch = _pack_epoch    # set_option() generation this image was built under (caches re-pack on a change)
+        self.walk = None            # second image of the bank for the persistent output convolution (out_walk_bank), or None
 
 
 def pack_conv_weight(w, transposed=False, direct=False):
     """w: [Cout,Cin,k,k] (k in 1,3,7), or with transposed=True a ConvTranspose2d weight [Cin,Co,2,2].  ``direct``: the fp32 MFMA
-    kernels' layout whatever the precision mode (banks whose launch is bound by its output stores, not by the matrix pipe)."""
+    kernels' layout whatever the precision mode (banks whose launch is bound by its output stores, not by the matrix pipe).
+    A bank of the persistent output convolution (out_walk_bank) carries that kernel's image as well (``walk``): both belong to the
+    one PackedConv and so go stale together."""
+    pc = _pack_conv_weight(w, transposed, direct)
+    if not direct and out_walk_bank(pc.cout, pc.cin, pc.ks, transposed):
+        L = _lib.lib()
+        wc = _dev(w, "weight").detach().contiguous()
+        pc.walk = torch.empty(L.cwfa_conv3x3_out_split_packed_bytes(pc.cout), dtype=torch.uint8, device=wc.device)
+        check(L.cwfa_conv3x3_out_split_pack_f32(_p(wc), _p(pc.walk), pc.cout, _stream()), "conv3x3_out_split_pack")
+    return pc
+
+
+def _pack_conv_weight(w, transposed, direct):
     L = _lib.lib()
     w = _dev(w, "weight").detach().contiguous()
     if transposed:
@@ -667,6 +680,8 @@ def conv2d(x, pc, bias=None, act=None, prelu_alpha=None, residual=None, act2=Non
     B, Cin, H, W = x.shape
     o = ConvOpts()
     keep = [x]
+    walk = out_walk_selected(pc, H, W, act=act, prelu_alpha=prelu_alpha, residual=residual, act2=act2, in_scale=in_scale, in_add=in_add,
+                             out_blocked=out_blocked, cat=cat, out_stats=out_stats, out_sample_stats=out_sample_stats)
     if cat is not None:                     # the input is cat(x, cat) read from its two tensors (pack_conv_weight_cat)
         cat, cbs = planes(cat, "cat")
         c1 = getattr(pc, "cat_c1", None)
@@ -719,8 +734,8 @@ def conv2d(x, pc, bias=None, act=None, prelu_alpha=None, residual=None, act2=Non
         keep.append(in_add)
     o.upshuffle2 = int(up)
     if in_blocked:                          # x is a channel-blocked map of the fused layer kernel (subnet_layer, layout bit 1)
-        if not (pc.split and pc.ks == 3):
-            raise ValueError("conv2d: channel-blocked input is read by the split-bf16 3x3 kernel only")
+        if not (walk or (pc.split and pc.ks == 3)):
+            raise ValueError("conv2d: channel-blocked input is read by the split-bf16 3x3 kernels only")
         o.in_blocked8 = 1
     if out_blocked:                         # y leaves channel-blocked: the split-bf16 3x3 kernel (bias / PReLU epilogue), or plain 1x1
         ok3 = (pc.split and pc.ks == 3 and pc.cout % 8 == 0 and residual is None and act2 is None and act in (None, "prelu")
@@ -752,7 +767,11 @@ def conv2d(x, pc, bias=None, act=None, prelu_alpha=None, residual=None, act2=Non
         if rec.want(key):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-    if pc.split and pc.ks == 7:
+    if walk:
+        # 64 -> <= 48 channels, bias only: the conv phase of the layer kernel, persistent (csrc/conv_split_out.hip)
+        check(L.cwfa_conv3x3_out_split_f32(_p(x), _p(pc.walk), _p(bias), _p(out), B, H, W, pc.cout, xbs, ybs, int(bool(in_blocked)),
+                                           _stream()), "conv3x3_out_split")
+    elif pc.split and pc.ks == 7:
         # the same kernel with a 3-pixel halo and 49 taps (bias-only epilogue, no prologue: what the ConvNeXt block needs)
         if act or act2 or residual is not None or in_scale is not None or in_add is not None:
             raise ValueError("conv2d: the split-bf16 7x7 kernel has a bias-only epilogue and no load-side prologue")
@@ -878,6 +897,28 @@ SPLIT_3X3_NARROW_MAX = 16   # banks with <= this many outputs (and >= 29 inputs)
 #                             outputs stay on the fp32 Winograd kernel.  Measured @512^2 (tools/small_conv_time.py, fp32 Winograd vs split): 64 -> 24:
 #                             71 vs 76 us, 64 -> 12: 66 vs 58, 64 -> 6: 62 vs 56, 29 -> 12: 38 vs 32, 29 -> 6: 35 vs 31, 24 -> 24: 34 vs 39, 6 -> 6: 15 vs 29
 #                             -- with so few MFMAs per step the per-step costs of the kernel (barrier, weight DMA, operand reads) decide
+OUT_WALK = True             # (tuning / ablation) False: today's dispatch -- no bank takes the persistent output convolution.  Read when a bank is
+#                             packed AND at every launch: switch it off at any time; switch it on before the banks are packed (or invalidate_packs())
+OUT_WALK_MT = (1, 2, 3)     # widths, in 16-channel m-tiles, that take it (DESIGN.md section 9.1 lists a width that was sent back)
+
+
+def out_walk_bank(cout, cin, ks, transposed=False):
+    """Bank side of the rule for the persistent output convolution (cwfa_conv3x3_out_split_f32): split / bf16 / fp16 precision, a 3x3
+    bank over exactly 64 inputs with at most 48 outputs -- the last convolution of a coupling sub-network."""
+    return bool(OUT_WALK and _split_bf16 >= 2 and ks == 3 and not transposed and cin == 64 and 1 <= cout <= 48
+                and (cout + 15) // 16 in OUT_WALK_MT)
+
+
+def out_walk_selected(pc, H, W, act=None, prelu_alpha=None, residual=None, act2=None, in_scale=None, in_add=None, out_blocked=False,
+                      cat=None, out_stats=None, out_sample_stats=None):
+    """Launch side: conv2d(x, pc, bias=..., out=..., in_blocked=...) takes that kernel when the bank carries its image and the call
+    has a bias-only epilogue, no load-side affine or add, no second source, an NCHW output and no statistics.  Everything else keeps
+    its kernel."""
+    return bool(OUT_WALK and getattr(pc, "walk", None) is not None and act is None and prelu_alpha is None
+                and residual is None and act2 is None and in_scale is None and in_add is None and not out_blocked and cat is None
+                and out_stats is None and out_sample_stats is None and 64 * H * W * 4 < 2 ** 31)
+
+
 conv_event_sink = None      # object with want(key)->bool and add(key, start_event, end_event); set by bench.py only
 
 

@@ -494,6 +494,16 @@ int cwfa_subnet_layer_first_f32(const float* u, const float* x, const void* pack
  * h = ELU(conv3x3(x) + b3) [B,64,H,W] the backward needs, from the registers that hold it as the 1x1's operand.  NCHW maps. */
 int cwfa_subnet_layer_split_tape_f32(const float* x, const void* packed, const float* b3, const float* b1, float* y, float* hid, int B,
                                      int H, int W, int64_t x_bs, int64_t y_bs, int64_t hid_bs, void* stream);
+/* The OUTPUT convolution of a coupling sub-network, y = conv3x3(x, w) + bias with 64 -> Cout <= 48 channels (networks.py:632, 666),
+ * as the conv phase of the layer above: the same persistent tile walk, LDS image and weight ring, ceil(Cout / 16) m-tiles wide,
+ * with a plain NCHW store (csrc/conv_split_out.hip).  packed = cwfa_conv3x3_out_split_pack_f32(w [Cout,64,3,3]):
+ * cwfa_conv3x3_out_split_packed_bytes(Cout) bytes (-1: Cout not in 1..48), 16-byte aligned, in the operand format active at pack
+ * time.  bias [Cout] may be NULL.  y: Cout planes per sample, batch stride y_bs (a channel slice of a larger tensor is fine: nothing
+ * outside those planes is written); in_blocked: x is a channel-blocked map (see `layout` below). */
+int64_t cwfa_conv3x3_out_split_packed_bytes(int Cout);
+int cwfa_conv3x3_out_split_pack_f32(const float* w, void* packed, int Cout, void* stream);
+int cwfa_conv3x3_out_split_f32(const float* x, const void* packed, const float* bias, float* y, int B, int H, int W, int Cout,
+                               int64_t x_bs, int64_t y_bs, int in_blocked, void* stream);
 /* layout: bit 0 = x, bit 1 = y is CHANNEL-BLOCKED, [B][8 blocks][H][W][8 channels] (same size and batch strides as NCHW, 16-byte
  * aligned), instead of NCHW planes.  The maps between the layers of one sub-network are private to it; blocked, a staging entry
  * of the kernel (8 channels of a pixel) is two 16-byte loads instead of eight 4-byte ones and the four channels a lane holds for
