@@ -81,6 +81,8 @@ PREP_VOL = {"none": 0, "two": 1, "le": 2, "maxnorm": 3, "max_only": 4}          
 PREP_APPLY = {"clamp_zero": 0, "sub_div": 1, "div_mul": 2}                      # CWFA_PREP_*
 DECONV_PRE = {None: 0, "none": 0, "relu": 1}                                    # CWFA_DECONV_PRE_*
 DECONV_POST = {None: 0, "none": 0, "abs": 1}                                    # CWFA_DECONV_POST_*
+DECONV_ACCEL_UNITS = 1024          # CWFA_DECONV_ACCEL_UNITS
+DECONV_NLL_WORKSPACE_BYTES = 8192  # CWFA_DECONV_NLL_WORKSPACE_BYTES
 
 # name -> (restype, argtypes); must list EVERY function declared in include/cwfa_hip.h (tests/test_boundary.py checks)
 i, i64, f, d, p = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_void_p
@@ -191,6 +193,10 @@ SIGNATURES = {
     "cwfa_deconv_ratio_f32": (i, [p, p, p, p, i64, p]),
     "cwfa_deconv_clamp_f32": (i, [p, i64, p, p, f, p]),
     "cwfa_deconv_update_f32": (i, [p, p, i, i, i, i, p]),
+    "cwfa_deconv_update_accel_f32": (i, [p, p, p, p, p, p, i64, i, i, i, i, p]),
+    "cwfa_deconv_alpha_f64": (i, [p, i64, d, p, p]),
+    "cwfa_deconv_predict_f32": (i, [p, p, p, p, i, i, i, i, p]),
+    "cwfa_deconv_poisson_nll_f32": (i, [p, p, i64, p, i64, i64, p, p]),
 }
 del i, i64, f, d, p
 

@@ -240,3 +240,241 @@ extern "C" int cwfa_deconv_update_f32(float* obj_pad, const float* b, int D, int
     CWFA_LAUNCH_CHECK("cwfa_deconv_update_f32");
     return CWFA_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ vector extrapolation
+// Biggs-Andrews acceleration of the iteration above.  The padded object holds the prediction y_k; the iterates
+// x_k, x_{k+1} and the step g live in window-sized buffers [D][obj][obj].  A block owns DC_THREADS * 4 units of V window elements of
+// one depth (CWFA_DECONV_ACCEL_UNITS); the window has fewer than 2^31 elements per depth, so its indices are 32-bit.
+#define DC_ALPHA_THREADS 1024
+
+// x_new = y * shifted(b) (the one fp32 product of update_kernel), g = x_new - y; slab row (depth in chunk, block) += the float64
+// partials of sum g * g_prev and sum g_prev^2.  The chunks of one iteration run one after the other on the stream, so a row receives
+// its chunks' partials in chunk order; no atomics.  g == g_prev is safe: a thread reads its elements before it writes them.
+template <int V>
+__global__ __launch_bounds__(DC_THREADS) void update_accel_kernel(const float* __restrict__ obj_pad, const float* __restrict__ b, const float* g_prev,
+                                                                  float* __restrict__ x_new, float* g, double* __restrict__ slab, int F, int obj,
+                                                                  int po, int shift) {
+    typedef float vec __attribute__((ext_vector_type(V)));
+    __shared__ double red[16];
+    const unsigned gw = obj / V, units = (unsigned)obj * gw;
+    const unsigned base = blockIdx.x * (DC_THREADS * 4) + threadIdx.x;
+    const int64_t plane = (int64_t)blockIdx.y * F * F, win = (int64_t)blockIdx.y * obj * obj;
+    vec vy[4], vm[4], vp[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const unsigned i = base + u * DC_THREADS;
+        if (i >= units) continue;
+        const int y = po + (int)(i / gw), x = po + (int)(i % gw) * V;
+        int srow = y + shift, scol = x + shift;
+        if (srow >= F) srow -= F;
+        if (scol >= F) scol -= F;
+        vy[u] = *reinterpret_cast<const vec*>(obj_pad + plane + (int64_t)y * F + x);
+        vm[u] = *reinterpret_cast<const vec*>(b + plane + (int64_t)srow * F + scol);
+        vp[u] = *reinterpret_cast<const vec*>(g_prev + win + (int64_t)i * V);
+    }
+    double dot = 0.0, nrm = 0.0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const unsigned i = base + u * DC_THREADS;
+        if (i >= units) continue;
+        vec xn, gn;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            xn[j] = vy[u][j] * vm[u][j];
+            gn[j] = xn[j] - vy[u][j];
+            dot += (double)gn[j] * (double)vp[u][j];               // fp32 x fp32 is exact in float64
+            nrm += (double)vp[u][j] * (double)vp[u][j];
+        }
+        *reinterpret_cast<vec*>(x_new + win + (int64_t)i * V) = xn;
+        *reinterpret_cast<vec*>(g + win + (int64_t)i * V) = gn;
+    }
+    dot = cwfa_block_sum(dot, red);
+    nrm = cwfa_block_sum(nrm, red);
+    if (threadIdx.x == 0) {
+        const int64_t row = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+        slab[2 * row] += dot;
+        slab[2 * row + 1] += nrm;
+    }
+}
+
+// the window in 16-byte groups: every row of either tensor starts on a 16-byte boundary and no group straddles the wrap column
+static inline bool accel_vec(int F, int obj, int po) { return (F & 3) == 0 && (obj & 3) == 0 && (po & 3) == 0; }
+
+static inline int64_t accel_blocks(int obj, bool vec) {
+    const int64_t units = (int64_t)obj * (vec ? obj / 4 : obj);
+    return (units + CWFA_DECONV_ACCEL_UNITS - 1) / CWFA_DECONV_ACCEL_UNITS;
+}
+
+extern "C" int cwfa_deconv_update_accel_f32(const float* obj_pad, const float* b, const float* g_prev, float* x_new, float* g, double* slab,
+                                            int64_t slab_rows, int D, int F, int obj, int po, void* stream) {
+    CWFA_REQUIRE(obj_pad && b && g_prev && x_new && g && slab, CWFA_E_INVAL, "cwfa_deconv_update_accel_f32: null pointer");
+    CWFA_REQUIRE(D >= 0 && F >= 0 && obj >= 0 && D <= 65535 && (int64_t)F * F < ((int64_t)1 << 31), CWFA_E_SHAPE,
+                 "cwfa_deconv_update_accel_f32: bad shape");
+    CWFA_REQUIRE(po >= 0 && (int64_t)po + obj <= F, CWFA_E_INVAL,
+                 "cwfa_deconv_update_accel_f32: the %d x %d window at %d is not inside the %d x %d plane", obj, obj, po, F, F);
+    CWFA_REQUIRE(obj_pad != b, CWFA_E_INVAL, "cwfa_deconv_update_accel_f32: the object and the back projection are the same tensor");
+    CWFA_REQUIRE(x_new != g && x_new != g_prev && (const float*)x_new != obj_pad && (const float*)x_new != b && (const float*)g != obj_pad &&
+                     (const float*)g != b,
+                 CWFA_E_INVAL, "cwfa_deconv_update_accel_f32: x_new and g are written: they share no buffer with an input or each other");
+    CWFA_REQUIRE((reinterpret_cast<uintptr_t>(slab) & 7u) == 0, CWFA_E_ALIGN, "cwfa_deconv_update_accel_f32: the slab is not 8-byte aligned");
+    if (D == 0 || obj == 0) return CWFA_OK;
+    const int shift = (F + 1) / 2;
+    const bool vec = accel_vec(F, obj, po) && (shift & 3) == 0 && cwfa_aligned16(obj_pad) && cwfa_aligned16(b) && cwfa_aligned16(g_prev) &&
+                     cwfa_aligned16(x_new) && cwfa_aligned16(g);
+    const int64_t blocks = accel_blocks(obj, vec);
+    CWFA_REQUIRE(slab_rows >= blocks * D, CWFA_E_INVAL, "cwfa_deconv_update_accel_f32: the slab holds %lld rows, %d depths need %lld",
+                 (long long)slab_rows, D, (long long)(blocks * D));
+    const dim3 grid((unsigned)blocks, D);
+    if (vec)
+        hipLaunchKernelGGL(update_accel_kernel<4>, grid, dim3(DC_THREADS), 0, (hipStream_t)stream, obj_pad, b, g_prev, x_new, g, slab, F, obj, po,
+                           shift);
+    else
+        hipLaunchKernelGGL(update_accel_kernel<1>, grid, dim3(DC_THREADS), 0, (hipStream_t)stream, obj_pad, b, g_prev, x_new, g, slab, F, obj, po,
+                           shift);
+    CWFA_LAUNCH_CHECK("cwfa_deconv_update_accel_f32");
+    return CWFA_OK;
+}
+
+// *alpha = clamp(sum of column 0 / sum of column 1, 0, alpha_max), 0 when the quotient is not finite (an empty or zero denominator
+// included); each thread adds its rows in ascending order, then the block sum: one fixed order.  The slab is left zeroed.
+__global__ __launch_bounds__(DC_ALPHA_THREADS) void alpha_kernel(double* __restrict__ slab, int64_t rows, double alpha_max,
+                                                                 float* __restrict__ alpha) {
+    __shared__ double red[16];
+    double num = 0.0, den = 0.0;
+    for (int64_t i = threadIdx.x; i < rows; i += DC_ALPHA_THREADS) {
+        num += slab[2 * i];
+        den += slab[2 * i + 1];
+        slab[2 * i] = 0.0;
+        slab[2 * i + 1] = 0.0;
+    }
+    num = cwfa_block_sum(num, red);
+    den = cwfa_block_sum(den, red);
+    if (threadIdx.x == 0) {
+        const double q = num / den;
+        *alpha = (float)(isfinite(q) ? (q < 0.0 ? 0.0 : (q > alpha_max ? alpha_max : q)) : 0.0);
+    }
+}
+
+extern "C" int cwfa_deconv_alpha_f64(double* slab, int64_t rows, double alpha_max, float* alpha, void* stream) {
+    CWFA_REQUIRE(slab && alpha, CWFA_E_INVAL, "cwfa_deconv_alpha_f64: null pointer");
+    CWFA_REQUIRE(rows >= 0, CWFA_E_SHAPE, "cwfa_deconv_alpha_f64: negative size");
+    CWFA_REQUIRE(alpha_max >= 0.0 && alpha_max < 1.0, CWFA_E_INVAL, "cwfa_deconv_alpha_f64: alpha_max = %g is not in [0, 1)", alpha_max);
+    CWFA_REQUIRE((reinterpret_cast<uintptr_t>(slab) & 7u) == 0 && (reinterpret_cast<uintptr_t>(alpha) & 3u) == 0, CWFA_E_ALIGN,
+                 "cwfa_deconv_alpha_f64: the slab is not 8-byte or alpha not 4-byte aligned");
+    hipLaunchKernelGGL(alpha_kernel, dim3(1), dim3(DC_ALPHA_THREADS), 0, (hipStream_t)stream, slab, rows, alpha_max, alpha);
+    CWFA_LAUNCH_CHECK("cwfa_deconv_alpha_f64");
+    return CWFA_OK;
+}
+
+// obj_pad window = max(x_new + *alpha * (x_new - x_prev), 0): difference, product and sum are rounded one by one; NaN is kept.
+template <int V>
+__global__ __launch_bounds__(DC_THREADS) void predict_kernel(float* __restrict__ obj_pad, const float* __restrict__ x_new,
+                                                             const float* __restrict__ x_prev, const float* __restrict__ alpha, int F, int obj,
+                                                             int po) {
+    typedef float vec __attribute__((ext_vector_type(V)));
+    const float a = *alpha;
+    const unsigned gw = obj / V, units = (unsigned)obj * gw;
+    const unsigned base = blockIdx.x * (DC_THREADS * 4) + threadIdx.x;
+    const int64_t plane = (int64_t)blockIdx.y * F * F, win = (int64_t)blockIdx.y * obj * obj;
+    vec vn[4], vo[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const unsigned i = base + u * DC_THREADS;
+        if (i >= units) continue;
+        vn[u] = *reinterpret_cast<const vec*>(x_new + win + (int64_t)i * V);
+        vo[u] = *reinterpret_cast<const vec*>(x_prev + win + (int64_t)i * V);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const unsigned i = base + u * DC_THREADS;
+        if (i >= units) continue;
+        vec r;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float d = vn[u][j] - vo[u][j];
+            const float t = a * d;
+            const float s = vn[u][j] + t;
+            r[j] = s > 0.f ? s : (s != s ? s : 0.f);
+        }
+        const int y = po + (int)(i / gw), x = po + (int)(i % gw) * V;
+        *reinterpret_cast<vec*>(obj_pad + plane + (int64_t)y * F + x) = r;
+    }
+}
+
+extern "C" int cwfa_deconv_predict_f32(float* obj_pad, const float* x_new, const float* x_prev, const float* alpha, int D, int F, int obj, int po,
+                                       void* stream) {
+    CWFA_REQUIRE(obj_pad && x_new && x_prev && alpha, CWFA_E_INVAL, "cwfa_deconv_predict_f32: null pointer");
+    CWFA_REQUIRE(D >= 0 && F >= 0 && obj >= 0 && D <= 65535 && (int64_t)F * F < ((int64_t)1 << 31), CWFA_E_SHAPE,
+                 "cwfa_deconv_predict_f32: bad shape");
+    CWFA_REQUIRE(po >= 0 && (int64_t)po + obj <= F, CWFA_E_INVAL, "cwfa_deconv_predict_f32: the %d x %d window at %d is not inside the %d x %d plane",
+                 obj, obj, po, F, F);
+    CWFA_REQUIRE((const float*)obj_pad != x_new && (const float*)obj_pad != x_prev, CWFA_E_INVAL,
+                 "cwfa_deconv_predict_f32: the padded object and an iterate are the same tensor");
+    if (D == 0 || obj == 0) return CWFA_OK;
+    const bool vec = accel_vec(F, obj, po) && cwfa_aligned16(obj_pad) && cwfa_aligned16(x_new) && cwfa_aligned16(x_prev);
+    const dim3 grid((unsigned)accel_blocks(obj, vec), D);
+    if (vec)
+        hipLaunchKernelGGL(predict_kernel<4>, grid, dim3(DC_THREADS), 0, (hipStream_t)stream, obj_pad, x_new, x_prev, alpha, F, obj, po);
+    else
+        hipLaunchKernelGGL(predict_kernel<1>, grid, dim3(DC_THREADS), 0, (hipStream_t)stream, obj_pad, x_new, x_prev, alpha, F, obj, po);
+    CWFA_LAUNCH_CHECK("cwfa_deconv_predict_f32");
+    return CWFA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ Poisson likelihood
+// sum over the image of est - img * log(est + 1e-8), every term and every sum in float64: per-block partials, then one block adds
+// them in ascending order and writes one element of the trace.
+#define DC_NLL_BLOCKS (CWFA_DECONV_NLL_WORKSPACE_BYTES / 8)
+
+template <int V>
+__global__ __launch_bounds__(DC_THREADS) void nll_kernel(const float* __restrict__ img, const float* __restrict__ est, double* __restrict__ partial,
+                                                         int64_t units) {
+    typedef float vec __attribute__((ext_vector_type(V)));
+    __shared__ double red[16];
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * DC_THREADS + threadIdx.x; i < units; i += (int64_t)gridDim.x * DC_THREADS) {
+        const vec a = reinterpret_cast<const vec*>(img)[i], e = reinterpret_cast<const vec*>(est)[i];
+#pragma unroll
+        for (int j = 0; j < V; ++j) acc += (double)e[j] - (double)a[j] * log((double)e[j] + 1e-8);
+    }
+    acc = cwfa_block_sum(acc, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
+}
+
+__global__ __launch_bounds__(DC_THREADS) void nll_finish_kernel(const double* __restrict__ partial, int blocks, double* __restrict__ out) {
+    __shared__ double red[16];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < blocks; i += DC_THREADS) acc += partial[i];
+    acc = cwfa_block_sum(acc, red);
+    if (threadIdx.x == 0) *out = acc;
+}
+
+extern "C" int cwfa_deconv_poisson_nll_f32(const float* img, const float* est, int64_t n, double* trace, int64_t index, int64_t trace_len,
+                                           void* workspace, void* stream) {
+    CWFA_REQUIRE(img && est && trace && workspace, CWFA_E_INVAL, "cwfa_deconv_poisson_nll_f32: null pointer");
+    CWFA_REQUIRE(n >= 0, CWFA_E_SHAPE, "cwfa_deconv_poisson_nll_f32: negative size");
+    CWFA_REQUIRE(index >= 0 && index < trace_len, CWFA_E_INVAL, "cwfa_deconv_poisson_nll_f32: element %lld is not inside a trace of %lld",
+                 (long long)index, (long long)trace_len);
+    CWFA_REQUIRE(((reinterpret_cast<uintptr_t>(trace) | reinterpret_cast<uintptr_t>(workspace)) & 7u) == 0, CWFA_E_ALIGN,
+                 "cwfa_deconv_poisson_nll_f32: the trace or the workspace is not 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        if (hipMemsetAsync(trace + index, 0, sizeof(double), st) != hipSuccess) {
+            cwfa_set_error("cwfa_deconv_poisson_nll_f32: clearing the element failed");
+            return CWFA_E_HIP;
+        }
+        return CWFA_OK;
+    }
+    double* partial = static_cast<double*>(workspace);
+    const bool vec = (n & 3) == 0 && cwfa_aligned16(img) && cwfa_aligned16(est);
+    const int64_t units = vec ? n >> 2 : n;
+    const unsigned want = deconv_blocks(units), blocks = want > DC_NLL_BLOCKS ? DC_NLL_BLOCKS : want;
+    if (vec)
+        hipLaunchKernelGGL(nll_kernel<4>, dim3(blocks), dim3(DC_THREADS), 0, st, img, est, partial, units);
+    else
+        hipLaunchKernelGGL(nll_kernel<1>, dim3(blocks), dim3(DC_THREADS), 0, st, img, est, partial, units);
+    CWFA_LAUNCH_CHECK("cwfa_deconv_poisson_nll_f32");
+    hipLaunchKernelGGL(nll_finish_kernel, dim3(1), dim3(DC_THREADS), 0, st, partial, (int)blocks, trace + index);
+    CWFA_LAUNCH_CHECK("cwfa_deconv_poisson_nll_f32");
+    return CWFA_OK;
+}

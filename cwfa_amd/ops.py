@@ -2164,3 +2164,90 @@ def deconv_update(obj_pad, b, obj, po):
     D = obj_pad.numel() // (F * F) if F else 0
     check(L.cwfa_deconv_update_f32(_p(obj_pad), _p(b), D, F, int(obj), int(po), _stream()), "deconv_update")
     return obj_pad
+
+
+def deconv_accel_slab(D, obj, device):
+    """The zeroed float64 slab [rows, 2] ``deconv_update_accel`` adds its block partials to, for chunks of at most D depths of an
+    obj x obj window; ``deconv_alpha`` leaves it zeroed again."""
+    rows = int(D) * ((int(obj) * int(obj) + _lib.DECONV_ACCEL_UNITS - 1) // _lib.DECONV_ACCEL_UNITS)
+    return torch.zeros(max(rows, 1), 2, dtype=torch.float64, device=device)
+
+
+def _slab(slab, name):
+    if not torch.is_tensor(slab) or not slab.is_cuda or slab.dtype != torch.float64 or not slab.is_contiguous() or slab.numel() % 2:
+        raise ValueError(f"{name}: slab must be a contiguous float64 tensor [rows, 2] on the HIP device (deconv_accel_slab)")
+    return slab
+
+
+def _scalar(t, dtype, name, what):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or t.numel() != 1:
+        raise ValueError(f"{name}: {what} must be a one-element {str(dtype)[6:]} tensor on the HIP device")
+    return t
+
+
+def _window(obj_pad, wins, obj, name):
+    """(D, F) of a contiguous padded tensor [.., D, F, F] and window tensors [.., D, obj, obj] of as many depths."""
+    _fdev(obj_pad, "obj_pad")
+    if obj_pad.dim() < 2 or obj_pad.shape[-1] != obj_pad.shape[-2]:
+        raise ValueError(f"{name}: expected a padded tensor [.., F, F], got {tuple(obj_pad.shape)}")
+    F, obj = obj_pad.shape[-1], int(obj)
+    D = obj_pad.numel() // (F * F) if F else 0
+    for w_name, w in wins:
+        _fdev(w, w_name)
+        if w.dim() < 2 or tuple(w.shape[-2:]) != (obj, obj) or w.numel() != D * obj * obj:
+            raise ValueError(f"{name}: {w_name} {tuple(w.shape)} does not hold {D} windows of {obj} x {obj}")
+    return D, F
+
+
+def deconv_update_accel(obj_pad, b, g, x_new, slab, obj, po):
+    """The accelerated form of ``deconv_update`` for one depth chunk: x_new = window(obj_pad) * window(shift(b)), the same fp32
+    product; the step x_new - window(obj_pad) replaces the previous step in ``g`` (in place), and the float64 partials of
+    sum(step * previous step) and sum(previous step^2) are added to ``slab``.  obj_pad and b [.., D, F, F] are only read; g and
+    x_new are contiguous [.., D, obj, obj]."""
+    L = _lib.lib()
+    _fdev(b, "b")
+    D, F = _window(obj_pad, (("g", g), ("x_new", x_new)), obj, "deconv_update_accel")
+    if tuple(obj_pad.shape) != tuple(b.shape):
+        raise ValueError(f"deconv_update_accel: expected two [.., F, F] tensors of one shape, got {tuple(obj_pad.shape)} and {tuple(b.shape)}")
+    _slab(slab, "deconv_update_accel")
+    check(L.cwfa_deconv_update_accel_f32(_p(obj_pad), _p(b), _p(g), _p(x_new), _p(g), _p(slab), slab.numel() // 2, D, F, int(obj), int(po),
+                                         _stream()), "deconv_update_accel")
+    return x_new
+
+
+def deconv_alpha(slab, alpha_max, alpha):
+    """alpha (float32[1] on the device) = clamp(sum(slab[:, 0]) / sum(slab[:, 1]), 0, alpha_max), 0 where that quotient is not
+    finite; the slab is zeroed.  Nothing comes back to the host."""
+    L = _lib.lib()
+    _slab(slab, "deconv_alpha"), _scalar(alpha, torch.float32, "deconv_alpha", "alpha")
+    check(L.cwfa_deconv_alpha_f64(_p(slab), slab.numel() // 2, float(alpha_max), _p(alpha), _stream()), "deconv_alpha")
+    return alpha
+
+
+def deconv_predict(obj_pad, x_new, x_prev, alpha, obj, po):
+    """obj_pad[..., po:po+obj, po:po+obj] = max(x_new + alpha * (x_new - x_prev), 0) with ``alpha`` a float32[1] on the device and
+    three separately rounded fp32 operations; nothing outside the window is written."""
+    L = _lib.lib()
+    D, F = _window(obj_pad, (("x_new", x_new), ("x_prev", x_prev)), obj, "deconv_predict")
+    _scalar(alpha, torch.float32, "deconv_predict", "alpha")
+    check(L.cwfa_deconv_predict_f32(_p(obj_pad), _p(x_new), _p(x_prev), _p(alpha), D, F, int(obj), int(po), _stream()), "deconv_predict")
+    return obj_pad
+
+
+def deconv_poisson_nll(img, est, trace, index, workspace=None):
+    """trace[index] = sum(est - img * log(est + 1e-8)) in float64 over two contiguous float32 tensors of one size; ``trace`` a
+    contiguous float64 vector on the device, ``workspace`` DECONV_NLL_WORKSPACE_BYTES device bytes to use instead of allocating."""
+    L = _lib.lib()
+    _fdev(img, "img"), _fdev(est, "est")
+    if img.numel() != est.numel():
+        raise ValueError("deconv_poisson_nll: the tensors differ in size")
+    if not torch.is_tensor(trace) or not trace.is_cuda or trace.dtype != torch.float64 or not trace.is_contiguous():
+        raise ValueError("deconv_poisson_nll: trace must be a contiguous float64 tensor on the HIP device")
+    if not 0 <= int(index) < trace.numel():
+        raise ValueError(f"deconv_poisson_nll: element {index} is not inside a trace of {trace.numel()}")
+    ws = workspace if workspace is not None else torch.empty(_lib.DECONV_NLL_WORKSPACE_BYTES, dtype=torch.uint8, device=img.device)
+    if not ws.is_cuda or ws.numel() * ws.element_size() < _lib.DECONV_NLL_WORKSPACE_BYTES:
+        raise ValueError(f"deconv_poisson_nll: the workspace needs {_lib.DECONV_NLL_WORKSPACE_BYTES} device bytes")
+    check(L.cwfa_deconv_poisson_nll_f32(_p(img), _p(est), img.numel(), _p(trace), int(index), trace.numel(), _p(ws), _stream()),
+          "deconv_poisson_nll")
+    return trace

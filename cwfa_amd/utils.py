@@ -397,7 +397,8 @@ def _deconv_sizes(OTF, img, ObjSize):
 
 def XLFMDeconv(OTF, img, nIt, ObjSize=[512, 512], PSFShape=[2160, 2160], ROIsize=[512, 512, 90], errorMetric=torch.nn.functional.mse_loss,
                n_split_fourier=1,
-               update_median_limit_multiplier=10, max_allowed=4500, device="cuda:0", all_in_device=False, verbose=False):
+               update_median_limit_multiplier=10, max_allowed=4500, device="cuda:0", all_in_device=False, verbose=False, *,
+               accelerate=False, alpha_max=0.999, trace=False, tol=None, check_every=5):
     """Richardson-Lucy deconvolution of one image; utils.py:630-738, same signature and return forms.
 
     OTF: complex64 [1, D, F, F // 2 + 1] (the conjugate is applied on the fly) or [1, D, F, F // 2 + 1, 2] (``OTF[..., 1]`` is used
@@ -409,9 +410,26 @@ def XLFMDeconv(OTF, img, nIt, ObjSize=[512, 512], PSFShape=[2160, 2160], ROIsize
     window (backward).  The object stays zero-padded throughout, every buffer is allocated before the loop.  A non-finite image
     pixel makes the ratio NaN in the first iteration and stops the loop there, as the reference's ``0 * ImgExp`` start does.
     ``device``, ``all_in_device``, ``errorMetric`` and ``max_allowed`` are accepted and unused; ``verbose`` raises
-    NotImplementedError (it plots).  img and OTF are left unchanged."""
+    NotImplementedError (it plots).  img and OTF are left unchanged.
+
+    Beyond the reference, all off by default (the default call issues the launches and returns the bits it always did):
+    ``accelerate``: Biggs-Andrews vector extrapolation.  The padded object holds a prediction y_k, the
+    iteration above is applied to it (x_{k+1}), the step g_k = x_{k+1} - y_k gives alpha = sum(g_k g_{k-1}) / sum(g_{k-1}^2) in
+    float64 over the whole window, clamped to [0, ``alpha_max``] (0 without a previous step or a finite quotient), and
+    y_{k+1} = max(x_{k+1} + alpha (x_{k+1} - x_k), 0).  Two more streaming passes over the window per iteration, no FFT; alpha never
+    leaves the device.  The volume returned is the last x, ImgEst the projection of the last y.
+    ``trace``: the fourth slot holds the Poisson negative log-likelihood sum(est - img log(est + 1e-8)) of every iteration run, as
+    Python floats (float64 on the device, copied once after the loop).
+    ``tol``: every ``check_every`` iterations the likelihood is read; when (previous checked - this) / |this| < tol the iteration
+    is completed and the loop ends."""
     if verbose:
         raise NotImplementedError("XLFMDeconv: verbose=True plots every iteration with matplotlib; not supported")
+    if not 0.0 <= float(alpha_max) < 1.0:
+        raise ValueError(f"XLFMDeconv: alpha_max = {alpha_max} is not in [0, 1)")
+    if tol is not None and not float(tol) > 0.0:
+        raise ValueError(f"XLFMDeconv: tol = {tol} is not positive")
+    if int(check_every) < 1:
+        raise ValueError(f"XLFMDeconv: check_every = {check_every} is below 1")
     if not torch.is_tensor(OTF) or OTF.dim() not in (4, 5) or (OTF.dim() == 5 and OTF.shape[4] != 2) or OTF.shape[0] != 1:
         raise ValueError("XLFMDeconv: the OTF must be [1, D, F, F // 2 + 1] or [1, D, F, F // 2 + 1, 2]")
     nDepths = int(OTF.shape[1])
@@ -445,7 +463,16 @@ def XLFMDeconv(OTF, img, nIt, ObjSize=[512, 512], PSFShape=[2160, 2160], ROIsize
         median = (torch.empty(1, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.int64, device=dev))
         ws = torch.empty(_lib.SELECT_WORKSPACE_BYTES, dtype=torch.uint8, device=dev)
         chunks = [(jj, min(jj + step, nDepths)) for jj in range(0, nDepths, step)]
-        for ii in range(int(nIt)):
+        nIt, done, stop, checked = int(nIt), 0, False, None
+        if accelerate:                                                     # x_k (ones), x_{k+1}, g_{k-1} (none: zeros), the sums, alpha
+            x_prev = torch.ones(1, nDepths, obj, obj, dtype=torch.float32, device=dev)
+            x_new, g = torch.empty_like(x_prev), torch.zeros_like(x_prev)
+            slab = ops.deconv_accel_slab(min(step, nDepths), obj, dev)
+            alpha = torch.zeros(1, dtype=torch.float32, device=dev)
+        if trace or tol is not None:
+            nll = torch.zeros(max(nIt, 1), dtype=torch.float64, device=dev)
+            nll_ws = torch.empty(_lib.DECONV_NLL_WORKSPACE_BYTES, dtype=torch.uint8, device=dev)
+        for ii in range(nIt):
             for jj, je in chunks:                                          # forward projection
                 sp, re = spec[:, :je - jj], real[:, :je - jj]
                 torch.fft.rfft2(obj_pad[:, jj:je], out=sp)
@@ -455,17 +482,35 @@ def XLFMDeconv(OTF, img, nIt, ObjSize=[512, 512], PSFShape=[2160, 2160], ROIsize
             ops.deconv_ratio(ImgExp, ImgEst, Tmp, flag)
             ops.select_nonzero(Tmp, out=median, workspace=ws)
             ops.deconv_clamp(Tmp, median[0], median[1], update_median_limit_multiplier)
+            if trace or tol is not None:
+                ops.deconv_poisson_nll(ImgExp, ImgEst, nll, ii, nll_ws)
             if int(flag.item()):
                 print(F'nan found at it: {ii+1} ')
                 ImgEst += 0 * ImgExp                                       # the NaN the reference's estimate carries from its start
                 break
+            if tol is not None and (ii + 1) % int(check_every) == 0:
+                now = float(nll[ii].item())
+                stop = checked is not None and (checked - now) / abs(now) < float(tol)
+                checked = now
             torch.fft.rfft2(Tmp, out=rspec)
             for jj, je in chunks:                                          # back projection and update
                 sp, re = spec[:, :je - jj], real[:, :je - jj]
                 ops.deconv_spectrum_mul(rspec, otf_b[:, jj:je], conj=conj, out=sp)
                 torch.fft.irfft2(sp, s=(F, F), out=re)
-                ops.deconv_update(obj_pad[:, jj:je], re, obj, po)
-        ObjRecon = obj_pad[:, :, po:po + obj, po:po + obj].contiguous()
+                if accelerate:
+                    ops.deconv_update_accel(obj_pad[:, jj:je], re, g[:, jj:je], x_new[:, jj:je], slab, obj, po)
+                else:
+                    ops.deconv_update(obj_pad[:, jj:je], re, obj, po)
+            done = ii + 1
+            if accelerate:
+                ops.deconv_alpha(slab, alpha_max, alpha)
+                if done < nIt and not stop:
+                    ops.deconv_predict(obj_pad, x_new, x_prev, alpha, obj, po)
+                x_new, x_prev = x_prev, x_new                              # x_prev is the latest iterate from here on
+            if stop:
+                break
+        ObjRecon = x_prev if accelerate else obj_pad[:, :, po:po + obj, po:po + obj].contiguous()
+        losses = nll[:done].tolist() if trace else []
     ObjRecon[:, 0:nDepths // 2 - ROIsize[2] // 2, ...] = 0
     ObjRecon[:, nDepths // 2 + ROIsize[2] // 2:, ...] = 0
-    return ObjRecon, 0, ImgEst, [], padSize, padSizeImg
+    return ObjRecon, 0, ImgEst, losses, padSize, padSizeImg

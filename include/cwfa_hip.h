@@ -798,6 +798,39 @@ int cwfa_deconv_ratio_f32(const float* img, const float* est, float* tmp, int* f
 int cwfa_deconv_clamp_f32(float* tmp, int64_t n, const float* median, const int64_t* count, float mult, void* stream);
 int cwfa_deconv_update_f32(float* obj_pad, const float* b, int D, int F, int obj, int po, void* stream);
 
+/* Vector extrapolation (Biggs & Andrews, Appl. Opt. 36, 1997) of the iteration above, a convergence trace for either loop
+ * (DESIGN.md section 20).  The padded object holds the prediction y_k the FFTs read; the Richardson-Lucy iterates x_k, x_{k+1} and
+ * the step g_k = x_{k+1} - y_k live in window-sized buffers [D][obj][obj].  Same conventions as the block above; the sums are
+ * float64 block partials in a slab, added in a fixed order: no atomics, bitwise repeatable.  Nothing is allocated, nothing
+ * synchronises, the host reads nothing back.
+ *
+ *   update_accel: in place of update, per depth chunk: x_new = obj_pad window * shifted(b) (the same single fp32 product), g =
+ *                 x_new - obj_pad window; obj_pad and b are only read.  g_prev is read before g is written: g == g_prev, in place,
+ *                 is allowed.  x_new and g share no buffer with an input or each other.  Slab row (depth within the chunk, block)
+ *                 += (sum g * g_prev, sum g_prev^2) over the block's elements, products exact in float64; the rows of the chunks of
+ *                 one iteration coincide and are added to in launch order.  slab: 2 * slab_rows doubles, 8-byte aligned, zero
+ *                 before the first chunk of an iteration; slab_rows >= D * ceil(units / CWFA_DECONV_ACCEL_UNITS), units = obj * obj
+ *                 window elements (obj * obj / 4 sixteen-byte groups where F, obj, po and ceil(F / 2) are multiples of 4 and every
+ *                 pointer is 16-byte aligned): D * ceil(obj * obj / CWFA_DECONV_ACCEL_UNITS) rows always suffice.
+ *   alpha:        one block: *alpha = float(clamp(sum of column 0 / sum of column 1, 0, alpha_max)) over `rows` rows of the slab, 0
+ *                 when the quotient is not finite (zero denominator: no previous step; NaN).  The rows are zeroed for the next
+ *                 iteration.  alpha_max in [0, 1).
+ *   predict:      obj_pad window = max(x_new + *alpha * (x_new - x_prev), 0) over all D depths, alpha read from device memory;
+ *                 difference, product and sum are three separately rounded fp32 operations, NaN is kept.  Only the window of
+ *                 obj_pad is written: its border stays exactly 0.
+ *   poisson_nll:  trace[index] = sum over n elements of est - img * log(est + 1e-8), terms and sums in float64: one pass, at most
+ *                 CWFA_DECONV_NLL_WORKSPACE_BYTES / 8 block partials in `workspace` (that many device bytes, 8-byte aligned, no
+ *                 clearing needed), then one block adds them in ascending order.  0 <= index < trace_len.  n == 0 writes 0. */
+#define CWFA_DECONV_ACCEL_UNITS 1024
+#define CWFA_DECONV_NLL_WORKSPACE_BYTES 8192
+int cwfa_deconv_update_accel_f32(const float* obj_pad, const float* b, const float* g_prev, float* x_new, float* g, double* slab,
+                                 int64_t slab_rows, int D, int F, int obj, int po, void* stream);
+int cwfa_deconv_alpha_f64(double* slab, int64_t rows, double alpha_max, float* alpha, void* stream);
+int cwfa_deconv_predict_f32(float* obj_pad, const float* x_new, const float* x_prev, const float* alpha, int D, int F, int obj, int po,
+                            void* stream);
+int cwfa_deconv_poisson_nll_f32(const float* img, const float* est, int64_t n, double* trace, int64_t index, int64_t trace_len,
+                                void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
