@@ -82,6 +82,7 @@ PREP_APPLY = {"clamp_zero": 0, "sub_div": 1, "div_mul": 2}                      
 DECONV_PRE = {None: 0, "none": 0, "relu": 1}                                    # CWFA_DECONV_PRE_*
 DECONV_POST = {None: 0, "none": 0, "abs": 1}                                    # CWFA_DECONV_POST_*
 DECONV_ACCEL_UNITS = 1024          # CWFA_DECONV_ACCEL_UNITS
+DECONV_UPDATE_UNITS = 256          # CWFA_DECONV_UPDATE_UNITS
 DECONV_NLL_WORKSPACE_BYTES = 8192  # CWFA_DECONV_NLL_WORKSPACE_BYTES
 
 # name -> (restype, argtypes); must list EVERY function declared in include/cwfa_hip.h (tests/test_boundary.py checks)
@@ -197,6 +198,9 @@ SIGNATURES = {
     "cwfa_deconv_alpha_f64": (i, [p, i64, d, p, p]),
     "cwfa_deconv_predict_f32": (i, [p, p, p, p, i, i, i, i, p]),
     "cwfa_deconv_poisson_nll_f32": (i, [p, p, i64, p, i64, i64, p, p]),
+    "cwfa_deconv_update_map_f32": (i, [p, p, p, p, p, i64, i, i, i, i, p]),
+    "cwfa_deconv_update_accel_map_f32": (i, [p, p, p, p, p, p, p, p, i64, p, i64, i, i, i, i, p]),
+    "cwfa_deconv_penalty_f64": (i, [p, i64, p, i64, i64, p]),
 }
 del i, i64, f, d, p
 

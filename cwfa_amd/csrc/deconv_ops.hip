@@ -421,6 +421,214 @@ extern "C" int cwfa_deconv_predict_f32(float* obj_pad, const float* x_new, const
     return CWFA_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ MAP update under a Gaussian prior
+// The EM M-step of a Poisson likelihood with an independent prior N(mu, 1 / w) per voxel: the x > 0 that
+// maximises -x + a log x - w / 2 (x - mu)^2, a the plain Richardson-Lucy update, i.e. the positive root of w x^2 + c x - a = 0,
+// c = 1 - w mu, in the form that only adds terms of one sign.  Nine fp32 operations, each rounded once.  Square root and division are
+// sqrtf and /, which hipcc expands to the correctly rounded sequences by default (-fhip-fp32-correctly-rounded-divide-sqrt); the
+// __fsqrt_rn intrinsic is the native approximation in this toolchain and is not used.  The tests compare bits with IEEE arithmetic.
+// w == 0 gives c = 1, r = 1 and 2a / 2 = a: the plain update's bits.  The test is c > 0, not >=: c == 0 with a == 0 would be 0 / 0
+// in the first form.  a < 0 (a back projection's rounding noise below zero) can make the discriminant negative; it is held at 0
+// there, which changes nothing for a >= 0.  NaN is kept.
+__device__ __forceinline__ float map_step(float a, float mu, float w) {
+    const float wm = w * mu;
+    const float c = 1.0f - wm;
+    const float wa = w * a;
+    const float cc = c * c;
+    const float t = cc + 4.0f * wa;                                  // the product with 4 is exact
+    const float r = sqrtf(t < 0.f ? 0.f : t);
+    return c > 0.f ? (2.0f * a) / (c + r) : (r - c) / (2.0f * w);
+}
+
+// the prior's penalty of one input element, 0.5 w (y - mu)^2, every operation in float64
+__device__ __forceinline__ double map_penalty(float y, float mu, float w) {
+    const double d = (double)y - (double)mu;
+    return 0.5 * (double)w * (d * d);
+}
+
+// update_kernel's walk: the window of obj_pad becomes M(window * shifted(b), mu, w); mu and w are window-sized [D][obj][obj].
+// With a penalty slab, row (depth in chunk, block) += the block's float64 sum of the penalty of the window as it was read.
+static_assert(CWFA_DECONV_UPDATE_UNITS == DC_THREADS, "one unit per thread");
+
+template <int V>
+__global__ __launch_bounds__(DC_THREADS) void update_map_kernel(float* __restrict__ obj_pad, const float* __restrict__ b,
+                                                                const float* __restrict__ mu, const float* __restrict__ w,
+                                                                double* __restrict__ pen, int F, int obj, int po, int shift) {
+    typedef float vec __attribute__((ext_vector_type(V)));
+    __shared__ double red[16];
+    const int gw = obj / V;
+    const int64_t g = (int64_t)blockIdx.x * DC_THREADS + threadIdx.x;
+    double acc = 0.0;
+    if (g < (int64_t)obj * gw) {
+        const int y = po + (int)(g / gw), x = po + (int)(g % gw) * V;
+        int srow = y + shift, scol = x + shift;
+        if (srow >= F) srow -= F;
+        if (scol >= F) scol -= F;
+        const int64_t plane = (int64_t)blockIdx.y * F * F, win = (int64_t)blockIdx.y * obj * obj + g * V;
+        vec* dst = reinterpret_cast<vec*>(obj_pad + plane + (int64_t)y * F + x);
+        const vec m = *reinterpret_cast<const vec*>(b + plane + (int64_t)srow * F + scol);
+        const vec vm = *reinterpret_cast<const vec*>(mu + win), vw = *reinterpret_cast<const vec*>(w + win);
+        vec v = *dst;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            acc += map_penalty(v[j], vm[j], vw[j]);
+            v[j] = map_step(v[j] * m[j], vm[j], vw[j]);
+        }
+        *dst = v;
+    }
+    if (pen == nullptr) return;                                      // uniform over the block
+    acc = cwfa_block_sum(acc, red);
+    if (threadIdx.x == 0) pen[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] += acc;
+}
+
+extern "C" int cwfa_deconv_update_map_f32(float* obj_pad, const float* b, const float* mu, const float* w, double* pen_slab, int64_t pen_rows,
+                                          int D, int F, int obj, int po, void* stream) {
+    CWFA_REQUIRE(obj_pad && b && mu && w, CWFA_E_INVAL, "cwfa_deconv_update_map_f32: null pointer");
+    CWFA_REQUIRE(D >= 0 && F >= 0 && obj >= 0 && D <= 65535 && (int64_t)F * F < ((int64_t)1 << 31), CWFA_E_SHAPE,
+                 "cwfa_deconv_update_map_f32: bad shape");
+    CWFA_REQUIRE(po >= 0 && (int64_t)po + obj <= F, CWFA_E_INVAL, "cwfa_deconv_update_map_f32: the %d x %d window at %d is not inside the %d x %d plane",
+                 obj, obj, po, F, F);
+    CWFA_REQUIRE(obj_pad != b, CWFA_E_INVAL, "cwfa_deconv_update_map_f32: the object and the back projection are the same tensor");
+    CWFA_REQUIRE((const float*)obj_pad != mu && (const float*)obj_pad != w, CWFA_E_INVAL,
+                 "cwfa_deconv_update_map_f32: the object is written: it shares no buffer with the prior");
+    CWFA_REQUIRE((reinterpret_cast<uintptr_t>(pen_slab) & 7u) == 0, CWFA_E_ALIGN, "cwfa_deconv_update_map_f32: the penalty slab is not 8-byte aligned");
+    if (D == 0 || obj == 0) return CWFA_OK;
+    const int shift = (F + 1) / 2;
+    const bool vec = accel_vec(F, obj, po) && (shift & 3) == 0 && cwfa_aligned16(obj_pad) && cwfa_aligned16(b) && cwfa_aligned16(mu) &&
+                     cwfa_aligned16(w);
+    const int64_t groups = (int64_t)obj * (vec ? obj / 4 : obj);
+    const int64_t blocks = (groups + DC_THREADS - 1) / DC_THREADS;
+    CWFA_REQUIRE(pen_slab == nullptr || pen_rows >= blocks * D, CWFA_E_INVAL,
+                 "cwfa_deconv_update_map_f32: the penalty slab holds %lld rows, %d depths need %lld", (long long)pen_rows, D, (long long)(blocks * D));
+    const dim3 grid((unsigned)blocks, D);
+    if (vec)
+        hipLaunchKernelGGL(update_map_kernel<4>, grid, dim3(DC_THREADS), 0, (hipStream_t)stream, obj_pad, b, mu, w, pen_slab, F, obj, po, shift);
+    else
+        hipLaunchKernelGGL(update_map_kernel<1>, grid, dim3(DC_THREADS), 0, (hipStream_t)stream, obj_pad, b, mu, w, pen_slab, F, obj, po, shift);
+    CWFA_LAUNCH_CHECK("cwfa_deconv_update_map_f32");
+    return CWFA_OK;
+}
+
+// update_accel_kernel's walk: x_new = M(y * shifted(b), mu, w), g = x_new - y, the same two float64 slab columns for alpha_kernel;
+// with a penalty slab, row (depth in chunk, block) += the block's float64 sum of the penalty of y.
+template <int V>
+__global__ __launch_bounds__(DC_THREADS) void update_accel_map_kernel(const float* __restrict__ obj_pad, const float* __restrict__ b,
+                                                                      const float* g_prev, const float* __restrict__ mu,
+                                                                      const float* __restrict__ w, float* __restrict__ x_new, float* g,
+                                                                      double* __restrict__ slab, double* __restrict__ pen, int F, int obj, int po,
+                                                                      int shift) {
+    typedef float vec __attribute__((ext_vector_type(V)));
+    __shared__ double red[16];
+    const unsigned gw = obj / V, units = (unsigned)obj * gw;
+    const unsigned base = blockIdx.x * (DC_THREADS * 4) + threadIdx.x;
+    const int64_t plane = (int64_t)blockIdx.y * F * F, win = (int64_t)blockIdx.y * obj * obj;
+    vec vy[4], vm[4], vp[4], vmu[4], vw[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const unsigned i = base + u * DC_THREADS;
+        if (i >= units) continue;
+        const int y = po + (int)(i / gw), x = po + (int)(i % gw) * V;
+        int srow = y + shift, scol = x + shift;
+        if (srow >= F) srow -= F;
+        if (scol >= F) scol -= F;
+        vy[u] = *reinterpret_cast<const vec*>(obj_pad + plane + (int64_t)y * F + x);
+        vm[u] = *reinterpret_cast<const vec*>(b + plane + (int64_t)srow * F + scol);
+        vp[u] = *reinterpret_cast<const vec*>(g_prev + win + (int64_t)i * V);
+        vmu[u] = *reinterpret_cast<const vec*>(mu + win + (int64_t)i * V);
+        vw[u] = *reinterpret_cast<const vec*>(w + win + (int64_t)i * V);
+    }
+    double dot = 0.0, nrm = 0.0, acc = 0.0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const unsigned i = base + u * DC_THREADS;
+        if (i >= units) continue;
+        vec xn, gn;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            xn[j] = map_step(vy[u][j] * vm[u][j], vmu[u][j], vw[u][j]);
+            gn[j] = xn[j] - vy[u][j];
+            dot += (double)gn[j] * (double)vp[u][j];
+            nrm += (double)vp[u][j] * (double)vp[u][j];
+            acc += map_penalty(vy[u][j], vmu[u][j], vw[u][j]);
+        }
+        *reinterpret_cast<vec*>(x_new + win + (int64_t)i * V) = xn;
+        *reinterpret_cast<vec*>(g + win + (int64_t)i * V) = gn;
+    }
+    dot = cwfa_block_sum(dot, red);
+    nrm = cwfa_block_sum(nrm, red);
+    if (pen != nullptr) acc = cwfa_block_sum(acc, red);
+    if (threadIdx.x == 0) {
+        const int64_t row = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+        slab[2 * row] += dot;
+        slab[2 * row + 1] += nrm;
+        if (pen != nullptr) pen[row] += acc;
+    }
+}
+
+extern "C" int cwfa_deconv_update_accel_map_f32(const float* obj_pad, const float* b, const float* g_prev, const float* mu, const float* w,
+                                                float* x_new, float* g, double* slab, int64_t slab_rows, double* pen_slab, int64_t pen_rows, int D,
+                                                int F, int obj, int po, void* stream) {
+    CWFA_REQUIRE(obj_pad && b && g_prev && mu && w && x_new && g && slab, CWFA_E_INVAL, "cwfa_deconv_update_accel_map_f32: null pointer");
+    CWFA_REQUIRE(D >= 0 && F >= 0 && obj >= 0 && D <= 65535 && (int64_t)F * F < ((int64_t)1 << 31), CWFA_E_SHAPE,
+                 "cwfa_deconv_update_accel_map_f32: bad shape");
+    CWFA_REQUIRE(po >= 0 && (int64_t)po + obj <= F, CWFA_E_INVAL,
+                 "cwfa_deconv_update_accel_map_f32: the %d x %d window at %d is not inside the %d x %d plane", obj, obj, po, F, F);
+    CWFA_REQUIRE(obj_pad != b, CWFA_E_INVAL, "cwfa_deconv_update_accel_map_f32: the object and the back projection are the same tensor");
+    CWFA_REQUIRE(x_new != g && x_new != g_prev && (const float*)x_new != obj_pad && (const float*)x_new != b && (const float*)x_new != mu &&
+                     (const float*)x_new != w && (const float*)g != obj_pad && (const float*)g != b && (const float*)g != mu &&
+                     (const float*)g != w,
+                 CWFA_E_INVAL, "cwfa_deconv_update_accel_map_f32: x_new and g are written: they share no buffer with an input or each other");
+    CWFA_REQUIRE(((reinterpret_cast<uintptr_t>(slab) | reinterpret_cast<uintptr_t>(pen_slab)) & 7u) == 0, CWFA_E_ALIGN,
+                 "cwfa_deconv_update_accel_map_f32: a slab is not 8-byte aligned");
+    CWFA_REQUIRE(slab != pen_slab, CWFA_E_INVAL, "cwfa_deconv_update_accel_map_f32: the two slabs are the same buffer");
+    if (D == 0 || obj == 0) return CWFA_OK;
+    const int shift = (F + 1) / 2;
+    const bool vec = accel_vec(F, obj, po) && (shift & 3) == 0 && cwfa_aligned16(obj_pad) && cwfa_aligned16(b) && cwfa_aligned16(g_prev) &&
+                     cwfa_aligned16(mu) && cwfa_aligned16(w) && cwfa_aligned16(x_new) && cwfa_aligned16(g);
+    const int64_t blocks = accel_blocks(obj, vec);
+    CWFA_REQUIRE(slab_rows >= blocks * D, CWFA_E_INVAL, "cwfa_deconv_update_accel_map_f32: the slab holds %lld rows, %d depths need %lld",
+                 (long long)slab_rows, D, (long long)(blocks * D));
+    CWFA_REQUIRE(pen_slab == nullptr || pen_rows >= blocks * D, CWFA_E_INVAL,
+                 "cwfa_deconv_update_accel_map_f32: the penalty slab holds %lld rows, %d depths need %lld", (long long)pen_rows, D,
+                 (long long)(blocks * D));
+    const dim3 grid((unsigned)blocks, D);
+    if (vec)
+        hipLaunchKernelGGL(update_accel_map_kernel<4>, grid, dim3(DC_THREADS), 0, (hipStream_t)stream, obj_pad, b, g_prev, mu, w, x_new, g, slab,
+                           pen_slab, F, obj, po, shift);
+    else
+        hipLaunchKernelGGL(update_accel_map_kernel<1>, grid, dim3(DC_THREADS), 0, (hipStream_t)stream, obj_pad, b, g_prev, mu, w, x_new, g, slab,
+                           pen_slab, F, obj, po, shift);
+    CWFA_LAUNCH_CHECK("cwfa_deconv_update_accel_map_f32");
+    return CWFA_OK;
+}
+
+// trace[index] += the sum of the penalty slab's rows: each thread adds its rows in ascending order, then the block sum, one fixed
+// order, onto the likelihood cwfa_deconv_poisson_nll_f32 wrote there.  The slab is left zeroed.
+__global__ __launch_bounds__(DC_ALPHA_THREADS) void penalty_kernel(double* __restrict__ slab, int64_t rows, double* __restrict__ out) {
+    __shared__ double red[16];
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < rows; i += DC_ALPHA_THREADS) {
+        acc += slab[i];
+        slab[i] = 0.0;
+    }
+    acc = cwfa_block_sum(acc, red);
+    if (threadIdx.x == 0) *out += acc;
+}
+
+extern "C" int cwfa_deconv_penalty_f64(double* slab, int64_t rows, double* trace, int64_t index, int64_t trace_len, void* stream) {
+    CWFA_REQUIRE(slab && trace, CWFA_E_INVAL, "cwfa_deconv_penalty_f64: null pointer");
+    CWFA_REQUIRE(rows >= 0, CWFA_E_SHAPE, "cwfa_deconv_penalty_f64: negative size");
+    CWFA_REQUIRE(index >= 0 && index < trace_len, CWFA_E_INVAL, "cwfa_deconv_penalty_f64: element %lld is not inside a trace of %lld",
+                 (long long)index, (long long)trace_len);
+    CWFA_REQUIRE(((reinterpret_cast<uintptr_t>(slab) | reinterpret_cast<uintptr_t>(trace)) & 7u) == 0, CWFA_E_ALIGN,
+                 "cwfa_deconv_penalty_f64: the slab or the trace is not 8-byte aligned");
+    CWFA_REQUIRE(slab != trace, CWFA_E_INVAL, "cwfa_deconv_penalty_f64: the slab and the trace are the same buffer");
+    if (rows == 0) return CWFA_OK;
+    hipLaunchKernelGGL(penalty_kernel, dim3(1), dim3(DC_ALPHA_THREADS), 0, (hipStream_t)stream, slab, rows, trace + index);
+    CWFA_LAUNCH_CHECK("cwfa_deconv_penalty_f64");
+    return CWFA_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ Poisson likelihood
 // sum over the image of est - img * log(est + 1e-8), every term and every sum in float64: per-block partials, then one block adds
 // them in ascending order and writes one element of the trace.

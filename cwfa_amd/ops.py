@@ -2234,6 +2234,77 @@ def deconv_predict(obj_pad, x_new, x_prev, alpha, obj, po):
     return obj_pad
 
 
+def deconv_penalty_slab(D, obj, device):
+    """The zeroed float64 slab [rows] ``deconv_update_map`` and ``deconv_update_accel_map`` add the block partials of the prior's
+    penalty to, for chunks of at most D depths of an obj x obj window; ``deconv_penalty`` leaves it zeroed again."""
+    # sized for the plain kernel's element-by-element walk, the most rows either kernel can use: a launch picks its 16-byte path
+    # from the pointers' alignment, and that path and the accelerated walk (1024 units per block) fill only the front of the slab
+    rows = int(D) * ((int(obj) * int(obj) + _lib.DECONV_UPDATE_UNITS - 1) // _lib.DECONV_UPDATE_UNITS)
+    return torch.zeros(max(rows, 1), dtype=torch.float64, device=device)
+
+
+def _pen_slab(slab, name):
+    if slab is None:
+        return None, 0
+    if not torch.is_tensor(slab) or not slab.is_cuda or slab.dtype != torch.float64 or not slab.is_contiguous():
+        raise ValueError(f"{name}: penalty_slab must be a contiguous float64 tensor on the HIP device (deconv_penalty_slab)")
+    return _p(slab), slab.numel()
+
+
+def _trace(trace, index, name):
+    if not torch.is_tensor(trace) or not trace.is_cuda or trace.dtype != torch.float64 or not trace.is_contiguous():
+        raise ValueError(f"{name}: trace must be a contiguous float64 tensor on the HIP device")
+    if not 0 <= int(index) < trace.numel():
+        raise ValueError(f"{name}: element {index} is not inside a trace of {trace.numel()}")
+    return trace
+
+
+def deconv_update_map(obj_pad, b, mu, w, obj, po, penalty_slab=None):
+    """``deconv_update`` under a Gaussian prior N(mu, 1 / w) per voxel, for one depth chunk, in place: the window of obj_pad becomes
+    M(window * window(shift(b)), mu, w), the positive root of w x^2 + (1 - w mu) x - a = 0 in its cancellation-free fp32 form
+    (DESIGN.md section 21); w = 0 gives ``deconv_update``'s bits.  mu and w are contiguous [.., D, obj, obj] and only read.  With
+    ``penalty_slab`` (``deconv_penalty_slab``) the float64 partials of sum(0.5 w (window - mu)^2) of the window as read are added
+    to it."""
+    L = _lib.lib()
+    _fdev(b, "b")
+    D, F = _window(obj_pad, (("mu", mu), ("w", w)), obj, "deconv_update_map")
+    if tuple(obj_pad.shape) != tuple(b.shape):
+        raise ValueError(f"deconv_update_map: expected two [.., F, F] tensors of one shape, got {tuple(obj_pad.shape)} and {tuple(b.shape)}")
+    pen, pen_rows = _pen_slab(penalty_slab, "deconv_update_map")
+    check(L.cwfa_deconv_update_map_f32(_p(obj_pad), _p(b), _p(mu), _p(w), pen, pen_rows, D, F, int(obj), int(po), _stream()),
+          "deconv_update_map")
+    return obj_pad
+
+
+def deconv_update_accel_map(obj_pad, b, g, x_new, mu, w, slab, obj, po, penalty_slab=None):
+    """``deconv_update_accel`` under the prior of ``deconv_update_map``: x_new = M(window(obj_pad) * window(shift(b)), mu, w), the
+    step x_new - window(obj_pad) replaces the previous step in ``g``, ``slab`` receives the same two sums; ``penalty_slab`` as in
+    ``deconv_update_map`` (the penalty of window(obj_pad))."""
+    L = _lib.lib()
+    _fdev(b, "b")
+    D, F = _window(obj_pad, (("g", g), ("x_new", x_new), ("mu", mu), ("w", w)), obj, "deconv_update_accel_map")
+    if tuple(obj_pad.shape) != tuple(b.shape):
+        raise ValueError(f"deconv_update_accel_map: expected two [.., F, F] tensors of one shape, got {tuple(obj_pad.shape)} and "
+                         f"{tuple(b.shape)}")
+    _slab(slab, "deconv_update_accel_map")
+    pen, pen_rows = _pen_slab(penalty_slab, "deconv_update_accel_map")
+    check(L.cwfa_deconv_update_accel_map_f32(_p(obj_pad), _p(b), _p(g), _p(mu), _p(w), _p(x_new), _p(g), _p(slab), slab.numel() // 2, pen,
+                                             pen_rows, D, F, int(obj), int(po), _stream()), "deconv_update_accel_map")
+    return x_new
+
+
+def deconv_penalty(penalty_slab, trace, index):
+    """trace[index] += the sum of ``penalty_slab`` in one fixed order (on top of the likelihood ``deconv_poisson_nll`` wrote there);
+    the slab is zeroed.  Nothing comes back to the host."""
+    L = _lib.lib()
+    if penalty_slab is None:
+        raise ValueError("deconv_penalty: penalty_slab must be a contiguous float64 tensor on the HIP device (deconv_penalty_slab)")
+    pen, pen_rows = _pen_slab(penalty_slab, "deconv_penalty")
+    _trace(trace, index, "deconv_penalty")
+    check(L.cwfa_deconv_penalty_f64(pen, pen_rows, _p(trace), int(index), trace.numel(), _stream()), "deconv_penalty")
+    return trace
+
+
 def deconv_poisson_nll(img, est, trace, index, workspace=None):
     """trace[index] = sum(est - img * log(est + 1e-8)) in float64 over two contiguous float32 tensors of one size; ``trace`` a
     contiguous float64 vector on the device, ``workspace`` DECONV_NLL_WORKSPACE_BYTES device bytes to use instead of allocating."""

@@ -373,6 +373,9 @@ def load_PSF_OTF(psf, vol_size, n_split=20, downS=1, device="cuda", dark_current
     return OTF, psf_shape
 
 
+MAP_PRIOR_BOUND = 2.0 ** 60      # XLFMDeconv refuses a prior whose w or w |mean| lies above it (the fp32 M-step would overflow)
+
+
 def _deconv_sizes(OTF, img, ObjSize):
     """The shapes XLFMDeconv can run (the reference's pads come out short on the others), or ValueError naming the size."""
     F = int(OTF.shape[2])
@@ -398,7 +401,8 @@ def _deconv_sizes(OTF, img, ObjSize):
 def XLFMDeconv(OTF, img, nIt, ObjSize=[512, 512], PSFShape=[2160, 2160], ROIsize=[512, 512, 90], errorMetric=torch.nn.functional.mse_loss,
                n_split_fourier=1,
                update_median_limit_multiplier=10, max_allowed=4500, device="cuda:0", all_in_device=False, verbose=False, *,
-               accelerate=False, alpha_max=0.999, trace=False, tol=None, check_every=5):
+               accelerate=False, alpha_max=0.999, trace=False, tol=None, check_every=5, prior_mean=None, prior_std=None, prior_weight=1.0,
+               init=None):
     """Richardson-Lucy deconvolution of one image; utils.py:630-738, same signature and return forms.
 
     OTF: complex64 [1, D, F, F // 2 + 1] (the conjugate is applied on the fly) or [1, D, F, F // 2 + 1, 2] (``OTF[..., 1]`` is used
@@ -421,7 +425,19 @@ def XLFMDeconv(OTF, img, nIt, ObjSize=[512, 512], PSFShape=[2160, 2160], ROIsize
     ``trace``: the fourth slot holds the Poisson negative log-likelihood sum(est - img log(est + 1e-8)) of every iteration run, as
     Python floats (float64 on the device, copied once after the loop).
     ``tol``: every ``check_every`` iterations the likelihood is read; when (previous checked - this) / |this| < tol the iteration
-    is completed and the loop ends."""
+    is completed and the loop ends.
+    ``prior_mean``, ``prior_std`` (both or neither; float32 [1, D, obj, obj] on the device, e.g. from ``prior_from_posterior``),
+    ``prior_weight`` >= 0: MAP Richardson-Lucy under an independent Gaussian prior N(prior_mean, prior_std^2) per voxel (DESIGN.md
+    section 21).  With a the plain update of a voxel and w = prior_weight / prior_std^2 (formed once, in fp32), the new value is
+    the maximiser of -x + a log x - w / 2 (x - mean)^2: c = 1 - w mean, r = sqrt(c^2 + 4 w a), x = 2a / (c + r) where c > 0 and
+    (r - c) / (2w) elsewhere.  ``prior_std = inf`` is "no prior here", w = 0 everywhere returns the plain call's bits; the mean may
+    be negative.  Works with ``accelerate`` (x_{k+1} is the MAP update of y_k).  ValueError, once before the loop, for a std that is
+    not > 0 (NaN included), a mean that is not finite, and w or w |mean| above 2^60 (then c^2 <= 2^121 and 2w <= 2^61 are finite
+    in fp32, and 4 w a is for every a below 2^64; a std of 1e-9 at weight 1 is still inside).  With a prior, ``trace`` and ``tol``
+    see the objective: the likelihood plus sum(w / 2 (y_k - mean)^2) of the point y_k that was projected, in float64; it is complete
+    once the iteration's update has run, so that is where ``tol`` reads it.
+    ``init``: float32 [1, D, obj, obj] on the device, finite and >= 0: the start object in place of the ones (x_0 = y_0 = init with
+    ``accelerate``); usable without a prior.  A voxel that starts at 0 stays 0 without a prior."""
     if verbose:
         raise NotImplementedError("XLFMDeconv: verbose=True plots every iteration with matplotlib; not supported")
     if not 0.0 <= float(alpha_max) < 1.0:
@@ -437,8 +453,36 @@ def XLFMDeconv(OTF, img, nIt, ObjSize=[512, 512], PSFShape=[2160, 2160], ROIsize
     if step < 1:
         raise ValueError(f"XLFMDeconv: n_split_fourier = {n_split_fourier}")
     F, obj, po, pi = _deconv_sizes(OTF, img, ObjSize)
+    if (prior_mean is None) != (prior_std is None):
+        raise ValueError("XLFMDeconv: prior_mean and prior_std are given together or not at all")
+    if not float(prior_weight) >= 0.0 or float(prior_weight) == float("inf"):
+        raise ValueError(f"XLFMDeconv: prior_weight = {prior_weight} is not a finite number >= 0")
+    for name, t in (("prior_mean", prior_mean), ("prior_std", prior_std), ("init", init)):
+        if t is not None and (not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (1, nDepths, obj, obj)):
+            raise ValueError(f"XLFMDeconv: {name} must be a float32 tensor [1, {nDepths}, {obj}, {obj}], got "
+                             f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t)}")
     ops._dev(img, "img")
     dev = img.device
+    prior = prior_mean is not None
+    for name, t in (("prior_mean", prior_mean), ("prior_std", prior_std), ("init", init)):
+        if t is not None and ops._dev(t, name).device != dev:
+            raise ValueError(f"XLFMDeconv: {name} is on {t.device}, the image on {dev}")
+    if prior or init is not None:                                          # one read-back for every refusal, before the loop
+        with torch.no_grad():
+            bad = []
+            if prior:
+                mu, std = prior_mean.contiguous(), prior_std.contiguous()
+                w_map = float(prior_weight) / (std * std)
+                bad += [~(std > 0), ~torch.isfinite(mu), ~(w_map <= MAP_PRIOR_BOUND), ~(w_map * mu.abs() <= MAP_PRIOR_BOUND)]
+            if init is not None:
+                bad += [~torch.isfinite(init) | ~(init >= 0)]
+            bad = torch.stack([b.any() for b in bad]).tolist()
+        reasons = (["prior_std is not > 0 everywhere (NaN included; +inf switches the prior off)", "prior_mean is not finite everywhere",
+                    "prior_weight / prior_std^2 exceeds 2^60", "prior_weight / prior_std^2 * |prior_mean| exceeds 2^60"] if prior else []) + \
+                  (["init is not finite and >= 0 everywhere"] if init is not None else [])
+        for flag_, reason in zip(bad, reasons):
+            if flag_:
+                raise ValueError(f"XLFMDeconv: {reason}")
     if float(img.sum()) == 0:
         volOut = torch.zeros(img.shape[0], nDepths, obj, obj, dtype=torch.float32, device=dev)
         return volOut, volume_2_projections(volOut.permute(0, 2, 3, 1).unsqueeze(1)), img, []
@@ -453,7 +497,7 @@ def XLFMDeconv(OTF, img, nIt, ObjSize=[512, 512], PSFShape=[2160, 2160], ROIsize
     with torch.no_grad():
         ImgExp = torch.nn.functional.pad(img, padSizeImg).contiguous()
         obj_pad = torch.zeros(1, nDepths, F, F, dtype=torch.float32, device=dev)
-        obj_pad[:, :, po:po + obj, po:po + obj] = 1.0
+        obj_pad[:, :, po:po + obj, po:po + obj] = 1.0 if init is None else init
         spec = torch.empty(1, min(step, nDepths), F, Fh, dtype=torch.complex64, device=dev)
         real = torch.empty(1, min(step, nDepths), F, F, dtype=torch.float32, device=dev)
         rspec = torch.empty(1, 1, F, Fh, dtype=torch.complex64, device=dev)
@@ -465,13 +509,15 @@ def XLFMDeconv(OTF, img, nIt, ObjSize=[512, 512], PSFShape=[2160, 2160], ROIsize
         chunks = [(jj, min(jj + step, nDepths)) for jj in range(0, nDepths, step)]
         nIt, done, stop, checked = int(nIt), 0, False, None
         if accelerate:                                                     # x_k (ones), x_{k+1}, g_{k-1} (none: zeros), the sums, alpha
-            x_prev = torch.ones(1, nDepths, obj, obj, dtype=torch.float32, device=dev)
+            x_prev = torch.ones(1, nDepths, obj, obj, dtype=torch.float32, device=dev) if init is None else init.clone().contiguous()
             x_new, g = torch.empty_like(x_prev), torch.zeros_like(x_prev)
             slab = ops.deconv_accel_slab(min(step, nDepths), obj, dev)
             alpha = torch.zeros(1, dtype=torch.float32, device=dev)
         if trace or tol is not None:
             nll = torch.zeros(max(nIt, 1), dtype=torch.float64, device=dev)
             nll_ws = torch.empty(_lib.DECONV_NLL_WORKSPACE_BYTES, dtype=torch.uint8, device=dev)
+        # with a prior the trace holds the objective: the update kernels add the penalty of what they read to a slab of its own
+        pen = ops.deconv_penalty_slab(min(step, nDepths), obj, dev) if prior and (trace or tol is not None) else None
         for ii in range(nIt):
             for jj, je in chunks:                                          # forward projection
                 sp, re = spec[:, :je - jj], real[:, :je - jj]
@@ -488,7 +534,7 @@ def XLFMDeconv(OTF, img, nIt, ObjSize=[512, 512], PSFShape=[2160, 2160], ROIsize
                 print(F'nan found at it: {ii+1} ')
                 ImgEst += 0 * ImgExp                                       # the NaN the reference's estimate carries from its start
                 break
-            if tol is not None and (ii + 1) % int(check_every) == 0:
+            if tol is not None and pen is None and (ii + 1) % int(check_every) == 0:
                 now = float(nll[ii].item())
                 stop = checked is not None and (checked - now) / abs(now) < float(tol)
                 checked = now
@@ -497,10 +543,21 @@ def XLFMDeconv(OTF, img, nIt, ObjSize=[512, 512], PSFShape=[2160, 2160], ROIsize
                 sp, re = spec[:, :je - jj], real[:, :je - jj]
                 ops.deconv_spectrum_mul(rspec, otf_b[:, jj:je], conj=conj, out=sp)
                 torch.fft.irfft2(sp, s=(F, F), out=re)
-                if accelerate:
+                if prior and accelerate:
+                    ops.deconv_update_accel_map(obj_pad[:, jj:je], re, g[:, jj:je], x_new[:, jj:je], mu[:, jj:je], w_map[:, jj:je], slab, obj,
+                                                po, pen)
+                elif prior:
+                    ops.deconv_update_map(obj_pad[:, jj:je], re, mu[:, jj:je], w_map[:, jj:je], obj, po, pen)
+                elif accelerate:
                     ops.deconv_update_accel(obj_pad[:, jj:je], re, g[:, jj:je], x_new[:, jj:je], slab, obj, po)
                 else:
                     ops.deconv_update(obj_pad[:, jj:je], re, obj, po)
+            if pen is not None:                                            # the objective of y_k is complete only now
+                ops.deconv_penalty(pen, nll, ii)
+                if tol is not None and (ii + 1) % int(check_every) == 0:
+                    now = float(nll[ii].item())
+                    stop = checked is not None and (checked - now) / abs(now) < float(tol)
+                    checked = now
             done = ii + 1
             if accelerate:
                 ops.deconv_alpha(slab, alpha_max, alpha)
@@ -514,3 +571,24 @@ def XLFMDeconv(OTF, img, nIt, ObjSize=[512, 512], PSFShape=[2160, 2160], ROIsize
     ObjRecon[:, 0:nDepths // 2 - ROIsize[2] // 2, ...] = 0
     ObjRecon[:, nDepths // 2 + ROIsize[2] // 2:, ...] = 0
     return ObjRecon, 0, ImgEst, losses, padSize, padSizeImg
+
+
+def prior_from_posterior(mean, std, n_depths, obj_size, scale=1.0, offset=0.0):
+    """(prior_mean, prior_std) for ``XLFMDeconv``: the flow's per-voxel posterior moments [1, d, h, w] (``CWFA.posterior_moments``)
+    centre-embedded into [1, n_depths, obj_size, obj_size].  Inside: ``mean * scale + offset`` and ``std * scale``; outside: mean 0 and
+    std +inf, "no prior here".  The embedding uses ``crop_offsets`` on the three axes, so with scale 1 and offset 0
+    ``crop_volume_center`` of either result (and the same centre crop of its depths) gives the input back bit for bit.  Plain torch, on
+    whatever device the moments are on.
+    Units: ``posterior_moments(std_scale=...)`` and ``denormalise_prediction`` bring the moments back to the dataset's volume units
+    (a de-normalised mean may be negative, which the deconvolution accepts); any further factor between the dataset's normalisation
+    and the photon units the deconvolution's volume is in is the caller's ``scale``."""
+    if not torch.is_tensor(mean) or not torch.is_tensor(std) or mean.dim() != 4 or mean.shape[0] != 1 or tuple(mean.shape) != tuple(std.shape):
+        raise ValueError("prior_from_posterior: mean and std must be two [1, d, h, w] tensors of one shape")
+    n_depths, obj_size = int(n_depths), int(obj_size)
+    (d0, d1), (h0, h1), (w0, w1) = (crop_offsets(full, int(crop)) for full, crop in zip((n_depths, obj_size, obj_size), mean.shape[1:]))
+    prior_mean = torch.zeros(1, n_depths, obj_size, obj_size, dtype=mean.dtype, device=mean.device)
+    prior_std = torch.full_like(prior_mean, float("inf"))
+    neutral = float(scale) == 1.0 and float(offset) == 0.0
+    prior_mean[:, d0:d1, h0:h1, w0:w1] = mean if neutral else mean * scale + offset
+    prior_std[:, d0:d1, h0:h1, w0:w1] = std if neutral else std * scale
+    return prior_mean, prior_std

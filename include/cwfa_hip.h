@@ -831,6 +831,33 @@ int cwfa_deconv_predict_f32(float* obj_pad, const float* x_new, const float* x_p
 int cwfa_deconv_poisson_nll_f32(const float* img, const float* est, int64_t n, double* trace, int64_t index, int64_t trace_len,
                                 void* workspace, void* stream);
 
+/* MAP Richardson-Lucy: the two updates above under an independent Gaussian prior N(mu, 1 / w) per voxel.
+ * With a the plain update (window * shifted(b)), the new value is M(a, mu, w), the x > 0 that maximises
+ * -x + a log x - w / 2 (x - mu)^2:
+ *     c = 1 - w * mu,  r = sqrt(max(c * c + 4 * (w * a), 0)),  x = c > 0 ? 2a / (c + r) : (r - c) / (2w)
+ * in fp32, one rounding per operation, square root and division correctly rounded.  w == 0 returns a's bits (a below 2^127);
+ * a == 0 with c <= 0 returns mu - 1 / w; the maximum with 0 only acts for a < 0 and keeps NaN.  The caller keeps w and w * |mu|
+ * small enough that c * c, 4 * w * a and 2 * w stay finite.  mu, w: [D][obj][obj] contiguous like g / x_new, only read, no buffer
+ * shared with an output.  Same conventions as the blocks above.
+ *
+ *   update_map:        update's walk, in place: obj_pad window = M(obj_pad window * shifted(b), mu, w).
+ *   update_accel_map:  update_accel's walk and slab: x_new = M(obj_pad window * shifted(b), mu, w), g = x_new - obj_pad window.
+ *   Both, when pen_slab is not NULL: pen_slab row (depth within the chunk, block) += the block's sum of
+ *                      0.5 * w * (y - mu)^2 over the window y as read, every operation in float64; the rows of the chunks of one
+ *                      iteration coincide and are added to in launch order.  pen_slab: pen_rows doubles, 8-byte aligned, zero
+ *                      before the first chunk; pen_rows >= D * ceil(units / CWFA_DECONV_UPDATE_UNITS) for update_map and
+ *                      D * ceil(units / CWFA_DECONV_ACCEL_UNITS) for update_accel_map, units as for update_accel:
+ *                      D * ceil(obj * obj / CWFA_DECONV_UPDATE_UNITS) rows always suffice for either.
+ *   penalty:           one block: trace[index] += the sum of `rows` rows of pen_slab, each thread adding its rows in ascending
+ *                      order, then the block sum (one fixed order), onto what poisson_nll wrote there; the rows are zeroed. */
+#define CWFA_DECONV_UPDATE_UNITS 256
+int cwfa_deconv_update_map_f32(float* obj_pad, const float* b, const float* mu, const float* w, double* pen_slab, int64_t pen_rows, int D,
+                               int F, int obj, int po, void* stream);
+int cwfa_deconv_update_accel_map_f32(const float* obj_pad, const float* b, const float* g_prev, const float* mu, const float* w,
+                                     float* x_new, float* g, double* slab, int64_t slab_rows, double* pen_slab, int64_t pen_rows, int D,
+                                     int F, int obj, int po, void* stream);
+int cwfa_deconv_penalty_f64(double* pen_slab, int64_t rows, double* trace, int64_t index, int64_t trace_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
