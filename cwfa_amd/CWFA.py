@@ -19,7 +19,8 @@ __all__ = ["sample_z_truncated", "check_empty_depths", "evaluate_INN_forward", "
            "nll_terms", "allreduce_nll", "build_networks", "step_log_likelihoods", "allgather_scores", "detect_ood",
            "forward_nll_pass", "mean_volume_cache", "save_mean_volume_cache", "load_mean_volume_cache",
            "denormalise_prediction", "denormalise_ground_truth", "compute_INN_step_performance", "evaluate_step", "roi_boxes",
-           "corr_coeff_3D", "truncated_normal_variance", "posterior_moments", "posterior_samples", "posterior_roi_means"]
+           "corr_coeff_3D", "truncated_normal_variance", "posterior_moments", "posterior_samples", "posterior_roi_means",
+           "ActivityMap", "find_neurons", "read_neural_coordinates_from_file", "write_neural_coordinates_to_file"]
 
 
 def _no_grad_trunc_normal_(tensor, mean=0., std=1., a=-1., b=1.):
@@ -816,3 +817,108 @@ def corr_coeff_3D(stack_gt, pred_3D, coords, r12, r3, n_time_steps=None, start_p
     median_scaled = np.float32(median.cpu().numpy()[0]) / m_gt                         # fp32 division: the median of stack / max
     return correlate_traces(coords, boxes, tr_gt.cpu().numpy() / np.float64(m_gt), tr_pred.cpu().numpy() / np.float64(m_pred),
                             median_scaled, stack_gt.shape[1] // 2 + start_plane_offset, n_time_steps, minmax_ths, filter_width)
+
+
+# ---------------------------------------------------------------------------------------------------- neuron detection
+# The producer of the ``coords`` that corr_coeff_3D, roi_boxes and the ROI posterior moments take.  The reference
+# reads them from a hand-annotated file (``read_neural_coordinates_from_file``, CWFA.py:223-238) or falls back to thirteen fixed pixel
+# pairs (CWFA.py:45); here they come from the recording itself: frames -> volumes -> activity map -> local maxima -> that file.
+class ActivityMap:
+    """Per-voxel temporal statistics of a series of [D,H,W] volumes, accumulated as the volumes are produced (by ``inverse_pass``
+    or ``XLFMDeconv``), so the series never has to be resident: mean, unbiased std, maximum and minimum over time.  ``finish``'s
+    mean and std are bit for bit ``ops.stack_mean_std`` of the whole series, for any chunking (the same float64 additions per voxel in
+    the same order).  The state costs 28 bytes per voxel -- the first sample, two float64 sums, maximum, minimum: about 700 MB at
+    96 x 512 x 512."""
+
+    def __init__(self, shape, device):
+        self.shape = tuple(int(s) for s in shape)
+        if len(self.shape) != 3 or min(self.shape) < 0:
+            raise ValueError(f"ActivityMap: shape is (D, H, W), got {shape!r}")
+        self.state = ops.activity_state(self.shape, device)
+        self.count = 0
+
+    def update(self, volumes):
+        """Add ``volumes``: [T',D,H,W] or one [D,H,W] volume, float32 on the device."""
+        ops._dev(volumes, "volumes")
+        if volumes.dim() == 3:
+            volumes = volumes.unsqueeze(0)
+        if volumes.dim() != 4 or tuple(volumes.shape[1:]) != self.shape:
+            raise ValueError(f"ActivityMap.update: volumes of shape {self.shape} are expected, got {tuple(volumes.shape)}")
+        if volumes.shape[0]:
+            ops.activity_update(volumes, self.state, first=self.count == 0)
+            self.count += volumes.shape[0]
+        return self
+
+    def finish(self, kind="std"):
+        """(score, mean, std, vmax, vmin), float32 [D,H,W].  ``kind`` chooses the score: "std", "range" = vmax - vmin, "peak" =
+        vmax - mean, "snr" = (vmax - mean) / std with 0 where std == 0.  The state is kept: more volumes may follow (vmax and vmin
+        are the state's own tensors, which a later ``update`` writes)."""
+        if self.count < 1:
+            raise ValueError("ActivityMap.finish: no volume has been added")
+        score, mean, std = ops.activity_finish(self.state, self.count, kind)
+        return score, mean, std, self.state[3], self.state[4]
+
+
+def find_neurons(score, r12=5, r3=3, n_max=None, thr=None, rel_thr=0.1, start_plane_offset=-25 // 2, margin=None, dist=None):
+    """Neuron positions as the 3-D local maxima of an activity map: ``(coords, scores)``.
+
+    ``score``: a float32 device map [D,H,W], or an ``ActivityMap`` (finished with ``kind="std"``).  A voxel is kept when it is at
+    least ``thr`` (default ``rel_thr`` times the map's maximum), at least ``margin`` (default ``(r3, r12, r12)``) from every face and
+    the maximum of the box of half-widths ``dist`` (default ``(2 r3 - 1, 2 r12 - 1, 2 r12 - 1)``) around it, ties going to the
+    lowest linear index (``ops.local_maxima``); the ``n_max`` highest are returned, by descending score.  With the default ``dist`` two
+    detections differ by at least 2 r on one axis, so their ROIs [c - r, c + r) are disjoint.
+
+    ``coords`` is a list of ``[x, y, z - (D // 2 + start_plane_offset)]`` (x indexes W, y indexes H): the convention of the
+    reference's coordinates file, which ``roi_boxes(coords, shape, r12, r3, start_plane_offset)``, ``corr_coeff_3D`` and
+    ``posterior_roi_moments`` take as it is.  ``scores``: float32 numpy array, the map's values at the peaks."""
+    r12, r3 = int(r12), int(r3)
+    if r12 < 1 or r3 < 1:
+        raise ValueError("find_neurons: r12 and r3 are positive ROI half-widths")
+    dist = (2 * r3 - 1, 2 * r12 - 1, 2 * r12 - 1) if dist is None else dist
+    margin = (r3, r12, r12) if margin is None else margin
+    dist, margin, n_max, _ = ops.local_maxima_args(dist, margin, n_max, 0, "find_neurons")
+    if thr is None and not 0.0 <= float(rel_thr) <= 1.0:
+        raise ValueError(f"find_neurons: rel_thr = {rel_thr} is not in [0, 1]")
+    if isinstance(score, ActivityMap):
+        score = score.finish("std")[0]
+    ops._dev(score, "score")
+    if score.dim() != 3:
+        raise ValueError(f"find_neurons: a [D,H,W] map is expected, got {tuple(score.shape)}")
+    if thr is None:
+        thr = float(rel_thr) * float(ops.volume_extrema(score.unsqueeze(0))[0, 1].cpu()) if score.numel() else 0.0
+    zyx, scores, _ = ops.local_maxima(score, thr, dist, margin, n_max)
+    shift = score.shape[0] // 2 + int(start_plane_offset)
+    return [[int(x), int(y), int(z) - shift] for z, y, x in zyx], scores
+
+
+def read_neural_coordinates_from_file(filename):
+    """CWFA.py:223-238, same signature: the ``[x, y, z]`` rows with ``is_gt == 1`` of a coordinates CSV, or of a list of them.
+    One departure: for a list the reference drops the result of ``dataframe.append`` (and pandas 2 has no such method), so it returns
+    the first file's rows only; here the rows of all files are returned, in order."""
+    import pandas as pd
+    if isinstance(filename, str):
+        dataframe = pd.read_csv(filename)
+    else:
+        dataframe = pd.concat([pd.read_csv(F) for F in filename], ignore_index=True)
+    rows = dataframe[dataframe['is_gt'] == 1]
+    cols = [rows[axis].tolist() for axis in ('coord_x', 'coord_y', 'coord_z')]
+    return [[cols[0][ix], cols[1][ix], cols[2][ix]] for ix in range(len(cols[0]))]
+
+
+def write_neural_coordinates_to_file(coords, filename, scores=None):
+    """Write ``coords`` (``[x, y, z]`` integer rows, as ``find_neurons`` returns them) as the CSV the reference's
+    ``read_neural_coordinates_from_file`` reads back exactly: columns patch_n, coord_x, coord_y, coord_z, corr_coeff (0), is_gt (1),
+    and ``score`` when ``scores`` are given."""
+    import pandas as pd
+    rows = [[int(v) for v in c] for c in coords]
+    if any(len(r) != 3 for r in rows) or any(a != b for r, c in zip(rows, coords) for a, b in zip(r, c)):
+        raise ValueError("write_neural_coordinates_to_file: coords are [x, y, z] integer rows")
+    data = {'patch_n': list(range(len(rows))), 'coord_x': [r[0] for r in rows], 'coord_y': [r[1] for r in rows],
+            'coord_z': [r[2] for r in rows], 'corr_coeff': [0] * len(rows), 'is_gt': [1] * len(rows)}
+    if scores is not None:
+        scores = [float(s) for s in scores]
+        if len(scores) != len(rows):
+            raise ValueError("write_neural_coordinates_to_file: one score per coordinate")
+        data['score'] = scores
+    pd.DataFrame(data).to_csv(filename, index=False)
+    return filename

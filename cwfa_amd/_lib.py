@@ -84,6 +84,8 @@ DECONV_POST = {None: 0, "none": 0, "abs": 1}                                    
 DECONV_ACCEL_UNITS = 1024          # CWFA_DECONV_ACCEL_UNITS
 DECONV_UPDATE_UNITS = 256          # CWFA_DECONV_UPDATE_UNITS
 DECONV_NLL_WORKSPACE_BYTES = 8192  # CWFA_DECONV_NLL_WORKSPACE_BYTES
+ACTIVITY_KIND = {"std": 0, "range": 1, "peak": 2, "snr": 3}                     # CWFA_ACTIVITY_*
+NMAX_MAX_DIST = 16                 # CWFA_NMAX_MAX_DIST
 
 # name -> (restype, argtypes); must list EVERY function declared in include/cwfa_hip.h (tests/test_boundary.py checks)
 i, i64, f, d, p = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_void_p
@@ -201,6 +203,9 @@ SIGNATURES = {
     "cwfa_deconv_update_map_f32": (i, [p, p, p, p, p, i64, i, i, i, i, p]),
     "cwfa_deconv_update_accel_map_f32": (i, [p, p, p, p, p, p, p, p, i64, p, i64, i, i, i, i, p]),
     "cwfa_deconv_penalty_f64": (i, [p, i64, p, i64, i64, p]),
+    "cwfa_activity_update_f32": (i, [p, p, p, p, p, p, i, i64, i64, i, p]),
+    "cwfa_activity_finish_f32": (i, [p, p, p, p, p, i64, i, p, p, p, i64, p]),
+    "cwfa_local_maxima_f32": (i, [p, i, i, i, f, i, i, i, i, i, i, p, p, i64, p, p]),
 }
 del i, i64, f, d, p
 

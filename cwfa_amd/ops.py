@@ -2322,3 +2322,125 @@ def deconv_poisson_nll(img, est, trace, index, workspace=None):
     check(L.cwfa_deconv_poisson_nll_f32(_p(img), _p(est), img.numel(), _p(trace), int(index), trace.numel(), _p(ws), _stream()),
           "deconv_poisson_nll")
     return trace
+
+
+# ------------------------------------------------------------------------------------------------ neuron detection
+def activity_state(shape, device):
+    """The per-voxel state of a streaming activity map for volumes of ``shape``: (x0 fp32, s1 float64, s2 float64, vmax fp32,
+    vmin fp32), 28 bytes per voxel, uninitialised -- the first ``activity_update`` (``first=True``) writes all of it."""
+    f = lambda dt: torch.empty(tuple(shape), dtype=dt, device=device)
+    return f(torch.float32), f(torch.float64), f(torch.float64), f(torch.float32), f(torch.float32)
+
+
+def _activity(state, what):
+    if len(state) != 5:
+        raise ValueError(f"{what}: the state is (x0, s1, s2, vmax, vmin)")
+    for t, dt in zip(state, (torch.float32, torch.float64, torch.float64, torch.float32, torch.float32)):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous() or t.shape != state[0].shape:
+            raise ValueError(f"{what}: the state is five contiguous tensors of one shape on the HIP device (ops.activity_state)")
+    return state[0].numel()
+
+
+def activity_update(x, state, first):
+    """Add the chunk ``x`` [T', ...] (float32; contiguous volumes, any time stride of at least a volume) to ``state``
+    (``activity_state``).  ``first``: the state is initialised from x[0].  Per voxel the additions are those of ``stack_mean_std`` in
+    its order, however the series is chunked."""
+    L = _lib.lib()
+    _dev(x, "x")
+    m = _activity(state, "activity_update")
+    if x.dim() < 1 or tuple(x.shape[1:]) != tuple(state[0].shape):
+        raise ValueError(f"activity_update: a chunk [T', {', '.join(str(s) for s in state[0].shape)}] is expected, got {tuple(x.shape)}")
+    T = x.shape[0]
+    if first and T < 1:
+        raise ValueError("activity_update: the first chunk needs at least one volume")
+    if T and m and (not x[0].is_contiguous() or (T > 1 and x.stride(0) < m)):
+        x = x.contiguous()
+    ss = x.stride(0) if T > 1 else m
+    check(L.cwfa_activity_update_f32(_p(x), *(_p(t) for t in state), T, m, ss, int(bool(first)), _stream()), "activity_update")
+    return state
+
+
+def activity_finish(state, count, kind="std"):
+    """(score, mean, std) float32 maps from ``state`` after ``count`` samples: mean and std are the bits of ``stack_mean_std`` on the
+    whole series (unbiased, NaN for one sample); ``kind``: "std", "range" (vmax - vmin), "peak" (vmax - mean) or "snr"
+    ((vmax - mean) / std, 0 where std == 0), in separately rounded fp32 operations."""
+    L = _lib.lib()
+    if kind not in _lib.ACTIVITY_KIND:
+        raise ValueError(f"activity_finish: kind is one of {sorted(_lib.ACTIVITY_KIND)}, got {kind!r}")
+    m = _activity(state, "activity_finish")
+    if int(count) < 1:
+        raise ValueError("activity_finish: needs at least one sample")
+    score, mean, std = (torch.empty_like(state[0]) for _ in range(3))
+    check(L.cwfa_activity_finish_f32(*(_p(t) for t in state), int(count), _lib.ACTIVITY_KIND[kind], _p(mean), _p(std), _p(score), m,
+                                     _stream()), "activity_finish")
+    return score, mean, std
+
+
+def _triple(v, name, what):
+    try:
+        t = tuple(int(a) for a in v)
+    except (TypeError, ValueError):
+        t = ()
+    if len(t) != 3 or any(a != b for a, b in zip(t, v)):
+        raise ValueError(f"{what}: {name} is three integers (z, y, x), got {v!r}")
+    return t
+
+
+def local_maxima_args(dist, margin, n_max, capacity, what):
+    """``local_maxima``'s host-side arguments, checked before anything touches the device: (dist, margin, n_max, capacity)."""
+    dist, margin = _triple(dist, "dist", what), _triple(margin, "margin", what)
+    if any(d < 0 or d > _lib.NMAX_MAX_DIST for d in dist):
+        raise ValueError(f"{what}: half-widths {dist} are not in 0 .. {_lib.NMAX_MAX_DIST}")
+    if any(v < 0 for v in margin) or int(capacity) < 0 or (n_max is not None and int(n_max) < 0):
+        raise ValueError(f"{what}: margin, capacity and n_max are not negative")
+    return dist, margin, None if n_max is None else int(n_max), int(capacity)
+
+
+def peak_order(bits, lin):
+    """The order of ``local_maxima``'s result: the 64-bit keys ord(score) << 32 | (0xFFFFFFFF - index) of numpy arrays of fp32 bit
+    patterns (uint32) and linear indices, formed from the pair alone; peaks are listed by descending key."""
+    import numpy as np
+    s = bits.astype(np.uint32).view(np.float32) + np.float32(0.0)
+    u = s.view(np.uint32)
+    o = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+    o = np.where(np.isnan(s), np.uint32(0), o)
+    return (o.astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - lin.astype(np.uint64))
+
+
+def local_maxima(score, thr, dist, margin=(0, 0, 0), n_max=None, capacity=1 << 20):
+    """The 3-D local maxima of a float32 device map [D,H,W]: the voxels that are not NaN, at least ``thr``, at least ``margin``
+    (z, y, x) from every face and the maximum of the box of half-widths ``dist`` (z, y, x; 0 .. 16 each) around them under the total
+    order "by value, ties to the lower linear index" (a plateau gives one voxel per window).  Returns, on the host,
+    (zyx int32 [K,3], scores float32 [K], total): ordered by score descending, then index ascending, the first ``n_max`` of ``total``
+    peaks.  ``capacity``: entries of the device buffer of the first run; if there are more peaks the kernels run once more with
+    room for all of them -- the candidate set is never truncated."""
+    import numpy as np
+    dist, margin, n_max, capacity = local_maxima_args(dist, margin, n_max, capacity, "local_maxima")
+    L = _lib.lib()
+    _dev(score, "score")
+    if score.dim() != 3:
+        raise ValueError(f"local_maxima: a [D,H,W] map is expected, got {tuple(score.shape)}")
+    score = score if score.is_contiguous() else score.contiguous()
+    D, H, W = score.shape
+    n = score.numel()
+    if n > 1 << 32:
+        raise ValueError(f"local_maxima: {D} x {H} x {W} voxels do not fit a 32-bit linear index")
+    ws = torch.empty(max(n, 1), dtype=torch.int64, device=score.device)
+    count = torch.empty(1, dtype=torch.int64, device=score.device)
+    cap = min(int(capacity), n)
+    while True:
+        out = torch.empty(max(cap, 1), 2, dtype=torch.int32, device=score.device)
+        check(L.cwfa_local_maxima_f32(_p(score), D, H, W, _f32(thr), *dist, *margin, _p(ws), _p(out), cap, _p(count), _stream()),
+              "local_maxima")
+        total = int(count.cpu()[0])
+        if total <= cap:
+            break
+        cap = total
+    pairs = out[:total].cpu().numpy().view(np.uint32)
+    bits, lin = pairs[:, 0], pairs[:, 1].astype(np.int64)
+    order = np.argsort(peak_order(bits, lin))[::-1]
+    if n_max is not None:
+        order = order[:int(n_max)]
+    lin = lin[order]
+    zyx = np.stack([lin // (H * W), lin // W % H, lin % W], axis=1).astype(np.int32) if len(lin) else np.zeros((0, 3), dtype=np.int32)
+    return zyx, bits[order].view(np.float32).copy(), total

@@ -858,6 +858,43 @@ int cwfa_deconv_update_accel_map_f32(const float* obj_pad, const float* b, const
                                      int F, int obj, int po, void* stream);
 int cwfa_deconv_penalty_f64(double* pen_slab, int64_t rows, double* trace, int64_t index, int64_t trace_len, void* stream);
 
+/* Neuron detection behind a reconstructed time series: the producer of the `coords` / `boxes` that roi_means,
+ * corr_coeff_3D and the ROI posterior moments take (the reference reads them from a hand-annotated file, CWFA.py:223-238).  Every
+ * floating-point operation is rounded separately.  Arguments are checked before any device work.
+ *
+ *   activity_update: adds the chunk x [T, m] (fp32, time stride x_ss >= m elements) to a per-voxel state of m voxels, 28 bytes each:
+ *                    x0 (fp32, the first sample ever seen), s1 / s2 (float64 sums of d = (double)x - (double)x0 and of d * d, added in
+ *                    time order), vmax / vmin (fp32; NaN propagates, as in torch.amax / amin).  first != 0: the state is initialised
+ *                    from the chunk's first volume (T >= 1) and not read.  The additions per voxel happen in the same order however
+ *                    the series is cut into chunks, and they are those of stack_mean_std.  One thread owns a group of voxels and walks
+ *                    the chunk's time axis: no atomics; 16-byte accesses where m, x_ss and every pointer allow, element by element
+ *                    otherwise.  T == 0 (first == 0) or m == 0: no launch.
+ *   activity_finish: mean[m], std[m] (fp32) from the state of N samples by stack_mean_std's formulae -- bit for bit its results on the
+ *                    concatenated series; unbiased std, N = 1 gives NaN -- and score[m] from the fp32 maps, each operation rounded to
+ *                    fp32: ACTIVITY_STD: std; ACTIVITY_RANGE: vmax - vmin; ACTIVITY_PEAK: vmax - mean; ACTIVITY_SNR: (vmax - mean) / std,
+ *                    0 where std == 0.
+ *   local_maxima:    the 3-D local maxima of score [D, H, W] under the total order
+ *                        key(v) = ord(S[v]) << 32 | (0xFFFFFFFF - lin(v)),
+ *                    ord the order-preserving unsigned image of the fp32 bits of S[v] + 0.0f (-0 and +0 are one value; NaN -> 0), lin
+ *                    the linear index (D * H * W <= 2^32, CWFA_E_SHAPE otherwise).  v is a peak iff S[v] is not NaN, S[v] >= thr, v
+ *                    lies at least (mz, my, mx) voxels from every face, and key(v) is the maximum of the keys over the box |z'| <= dz,
+ *                    |y'| <= dy, |x'| <= dx around it, clipped by the volume (voxels inside the margin still suppress their
+ *                    neighbours).  A plateau yields the voxel of lowest linear index in each window; two peaks differ by more than the
+ *                    half-width on at least one axis.  Half-widths 0 .. CWFA_NMAX_MAX_DIST, CWFA_E_SHAPE beyond.  Two launches: the
+ *                    in-plane maximum of the keys from a haloed tile in the LDS into `workspace` (8 * D * H * W device bytes, 8-byte
+ *                    aligned), then a walk along z per pixel.  Peaks are appended to `out` (`capacity` entries of 8 bytes: the fp32
+ *                    score's bits, then the 32-bit linear index) through the device counter *count (int64, cleared by the call),
+ *                    which keeps counting past `capacity`: *count is the number of peaks, min(*count, capacity) entries are
+ *                    written, in no particular order -- order them by key.  Nothing synchronises: the caller reads *count. */
+#define CWFA_NMAX_MAX_DIST 16
+enum { CWFA_ACTIVITY_STD = 0, CWFA_ACTIVITY_RANGE = 1, CWFA_ACTIVITY_PEAK = 2, CWFA_ACTIVITY_SNR = 3 };
+int cwfa_activity_update_f32(const float* x, float* x0, double* s1, double* s2, float* vmax, float* vmin, int T, int64_t m, int64_t x_ss,
+                             int first, void* stream);
+int cwfa_activity_finish_f32(const float* x0, const double* s1, const double* s2, const float* vmax, const float* vmin, int64_t N, int kind,
+                             float* mean, float* std, float* score, int64_t m, void* stream);
+int cwfa_local_maxima_f32(const float* score, int D, int H, int W, float thr, int dz, int dy, int dx, int mz, int my, int mx,
+                          void* workspace, void* out, int64_t capacity, int64_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
