@@ -1,13 +1,14 @@
 """The pieces of the reference's XLFMDataset.py around the hot path: cropping the 29 lenslet views out of the sensor frame
 (SURVEY.md section 8f, row 2), the clean-up and centre crop of the raw frames (XLFMDataset.py:15-40,101-104,160-162) and the
-statistics / normalisation of ``ConcatDataset`` (:251-395) on device tensors.  File reading stays the
+statistics / normalisation of ``ConcatDataset`` (:251-395) on device tensors, and the shot-noise augmentation
+the reference documents (:397-405) but never defines per dataset.  File reading stays the
 reference's.  Not registered by cwfa_amd.install(); a maintainer patches the calls, see INTEGRATION.md."""
 import torch
 
 from . import ops
 from .amp import amp_function
 
-__all__ = ["XLFMDatasetFull", "ConcatDataset", "extract_views", "pad_img_to_min", "center_crop", "prepare_frames"]
+__all__ = ["XLFMDatasetFull", "ConcatDataset", "extract_views", "pad_img_to_min", "center_crop", "prepare_frames", "shot_noise_scales", "add_random_shot_noise_to_datasets"]
 
 
 def extract_views(image, lenslet_coords, subimage_shape, debug=False):
@@ -74,6 +75,20 @@ def _max(t):
     return ops.volume_extrema(t.reshape(1, 1, 1, -1) if t.is_contiguous() else t.contiguous().reshape(1, 1, 1, -1))[0, 1].cpu()
 
 
+def shot_noise_scales(m, u, signal_power_range):
+    """(pre, post) of the shot-noise augmentation for image maxima ``m`` and uniforms ``u`` (two tensors of one shape, any device):
+    the signal power P = lo + (hi - lo) u photons at the image's maximum, pre = P / m and post = m / P, both 0 where m <= 0 (an
+    all-zero image stays all zero instead of becoming NaN).  Plain torch, fp32."""
+    lo, hi = (float(v) for v in signal_power_range)
+    if not 0.0 < lo <= hi or hi == float("inf"):
+        raise ValueError(f"add_random_shot_noise_to_dataset: signal_power_range {list(signal_power_range)} is not 0 < lo <= hi < inf")
+    P = lo + (hi - lo) * u
+    lit = m > 0
+    safe = torch.where(lit, m, torch.ones_like(m))
+    zero = torch.zeros_like(m)
+    return torch.where(lit, P / safe, zero), torch.where(lit, safe / P, zero)
+
+
 class XLFMDatasetFull:
     """The tensor side of the reference's dataset class: ``stacked_views`` (fp32 [N,H,W]) and ``vols`` on the HIP device."""
     extract_views = staticmethod(extract_views)
@@ -114,6 +129,32 @@ class XLFMDatasetFull:
         self.stacked_views = self.standarize_sample(self.stacked_views, mean_imgs, std_imgs)
         self.vols = self.standarize_sample(self.vols, mean_vols, std_vols)
 
+    @amp_function
+    def add_random_shot_noise_to_dataset(self, signal_power_range=[32**2, 32**2], seed=None, sample_offset=0):
+        """Photon shot noise on every image of ``stacked_views`` ([N,H,W]), in place, on the device, nothing read back: image i is
+        scaled so that its maximum m_i holds P_i photons, P_i uniform in ``signal_power_range`` (photons at the brightest pixel; the
+        default 32^2 gives a peak signal-to-noise ratio of 32), every pixel is replaced by a Poisson draw at that rate, and the
+        image is scaled back:  views[i] <- Poisson(views[i] * P_i / m_i) * m_i / P_i.  An all-zero image stays all zero.
+        Meant for NON-NEGATIVE images, i.e. before ``standarize``: a negative pixel becomes NaN.
+        ``seed``: the draw is a pure function of (seed, sample_offset + i, pixel): u_i is ``ops.rand_uniform`` on stream 1, the
+        Poisson draw ``ops.rand_poisson`` on stream 0.  None takes a seed from torch's generator, so ``set_all_seeds`` governs it.
+        ``sample_offset``: the number of images in front of this dataset (``add_random_shot_noise_to_datasets`` passes it), so that the noise of an
+        image does not depend on how the datasets were split."""
+        v = self.stacked_views
+        if v.dim() != 3:
+            raise ValueError(f"add_random_shot_noise_to_dataset: expected stacked_views [N,H,W], got {tuple(v.shape)}")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())          # torch's CPU generator: no device read-back
+        if v.dtype != torch.float32 or not v.is_contiguous():
+            v = self.stacked_views = v.float().contiguous()
+        N = int(v.shape[0])
+        if v.numel() == 0:
+            return
+        m = ops.volume_extrema(v.reshape(N, 1, 1, -1))[:, 1]
+        u = ops.rand_uniform((N, 1), seed, stream=1, sample_offset=sample_offset, device=v.device)[:, 0]
+        pre, post = shot_noise_scales(m, u, signal_power_range)
+        ops.rand_poisson(v, seed, stream=0, sample_offset=sample_offset, pre=pre.contiguous(), post=post.contiguous(), out=v)
+
     @staticmethod
     def standarize_sample(sample, mean, std):
         """(sample - mean) / std in fp32, in place where ``sample`` is contiguous."""
@@ -128,7 +169,9 @@ class XLFMDatasetFull:
 class ConcatDataset:
     """XLFMDataset.py:251-395 over datasets whose ``stacked_views`` and ``vols`` are fp32 tensors on the HIP device.  The statistics
     are float64 device sums accumulated over the datasets (nothing is concatenated) and come back as 0-dim float32 CPU tensors,
-    rounded once.  ``add_random_shot_noise_to_dataset`` is left out: it calls a dataset method the reference does not define."""
+    rounded once.  ``add_random_shot_noise_to_dataset`` (:397-405) calls a dataset method the reference does not define, so the class
+    does not carry it; the augmentation it documents is the module's ``add_random_shot_noise_to_datasets(concat, ...)`` over
+    ``XLFMDatasetFull.add_random_shot_noise_to_dataset``."""
 
     def __init__(self, *datasets):
         self.datasets = datasets
@@ -212,3 +255,16 @@ class ConcatDataset:
             stats = self.get_statistics()
         for d in self.datasets:
             d.standarize(stats)
+
+
+def add_random_shot_noise_to_datasets(datasets, signal_power_range=[32**2, 32**2], seed=None):
+    """What the reference's ``ConcatDataset.add_random_shot_noise_to_dataset`` (:397-405) is documented to do, as a function of a
+    ``ConcatDataset`` or a sequence of ``XLFMDatasetFull``: shot noise on every dataset under ONE seed (None: from torch's
+    generator), each with ``sample_offset`` set to the number of images in front of it, so that the result is that of the unsplit
+    stack, bit for bit."""
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
+    offset = 0
+    for d in getattr(datasets, "datasets", datasets):
+        d.add_random_shot_noise_to_dataset(signal_power_range=signal_power_range, seed=seed, sample_offset=offset)
+        offset += len(d)

@@ -206,6 +206,7 @@ SIGNATURES = {
     "cwfa_activity_update_f32": (i, [p, p, p, p, p, p, i, i64, i64, i, p]),
     "cwfa_activity_finish_f32": (i, [p, p, p, p, p, i64, i, p, p, p, i64, p]),
     "cwfa_local_maxima_f32": (i, [p, i, i, i, f, i, i, i, i, i, i, p, p, i64, p, p]),
+    "cwfa_rand_poisson_f32": (i, [p, p, i, i64, i64, i64, p, p, C.c_uint64, C.c_uint32, C.c_uint32, p]),
 }
 del i, i64, f, d, p
 

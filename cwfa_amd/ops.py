@@ -8,7 +8,7 @@ import torch
 from . import _lib
 from ._lib import AffineStage, Chain, ConvOpts, check
 
-__all__ = ["haar1d", "haar2d", "gather", "affine", "channel_affine", "chain_inv", "chain_inv_var", "chain_inv_roi_cov", "chain_inv_samples", "rand_uniform", "rand_trunc_normal", "chain_nll_map", "nll_compose", "chain_fwd", "pack_conv_weight",
+__all__ = ["haar1d", "haar2d", "gather", "affine", "channel_affine", "chain_inv", "chain_inv_var", "chain_inv_roi_cov", "chain_inv_samples", "rand_uniform", "rand_trunc_normal", "rand_poisson", "chain_nll_map", "nll_compose", "chain_fwd", "pack_conv_weight",
            "conv2d", "conv2d_wgrad", "elu_bwd", "set_precision", "gelu_add", "gelu_bwd", "layernorm_bwd", "attention_bwd", "plane_affine", "bn_bwd_stats", "bn_act_bwd", "maxpool2_bwd", "chain_bwd", "chain_inv_bwd", "prelu_bwd", "conv3d_1k1_backward", "pack_1x1_panel", "pack_split_layer_weight", "subnet_layer", "conv3d_1k1", "channel_stats", "bn_fold", "bn_running_update", "maxpool", "sample_stats", "layernorm_apply",
            "convnext_tail", "conv_writes_sample_stats", "attention_combine", "scale_channels", "axpby", "stage", "lion_step", "global_extrema", "wmse_loss"]
 
@@ -394,6 +394,58 @@ def rand_trunc_normal(shape, temperature, seed, stream=0, sample_offset=0, devic
         return out
     check(_lib.lib().cwfa_rand_trunc_normal_f32(_p(out), N, n, n, float(temperature), seed, stream, sample_offset, _stream()),
           "rand_trunc_normal")
+    return out
+
+
+def _poisson_tensor(t, name):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"rand_poisson: {name} must be a contiguous float32 tensor on the HIP device (no CPU path exists), got "
+                         f"{(t.dtype, t.device, 'contiguous' if t.is_contiguous() else 'strided') if torch.is_tensor(t) else type(t)}")
+    return t
+
+
+def _sample_scale(v, N, device, name):
+    """``pre`` / ``post`` of rand_poisson as a float32 device tensor [N] (a Python number is filled in on the device: no read-back)."""
+    if v is None:
+        return None
+    if not torch.is_tensor(v):
+        return torch.full((N,), float(v), dtype=torch.float32, device=device)
+    if _poisson_tensor(v, name).dim() != 1 or v.shape[0] != N or v.device != device:
+        raise ValueError(f"rand_poisson: {name} must be a float32 tensor [{N}] on {device}, got {tuple(v.shape)} on {v.device}")
+    return v
+
+
+def rand_poisson(lam, seed, stream=0, sample_offset=0, n_samples=None, pre=None, post=None, out=None):
+    """Poisson draws of the counter-based generator (cwfa_rand_poisson_f32):
+    ``out[s] = fl32(fl32(k) * post[s])``, ``k ~ Poisson(fl32(lam[s] * pre[s]))``.  ``lam``: contiguous float32 on the HIP device, its
+    leading axis the SAMPLE axis; with ``n_samples`` it is ONE plane shared by all samples and the result is [n_samples, *lam.shape].
+    ``pre`` / ``post``: float32 device tensors [N] or Python numbers (None: 1).  ``out``: a contiguous float32 tensor of the result's
+    shape; ``out=lam`` draws in place (not with ``n_samples``).  Sample s of a call equals sample 0 of a call with
+    ``sample_offset + s``; ``stream`` separates independent uses of one seed.  The counters are NOT those of ``rand_uniform``.
+    Rate 0 gives 0; a rate that is negative, NaN or above 2^30 gives NaN (nothing is read back to validate); rates below 10 are drawn
+    by inversion of a 32-bit uniform, so outcomes of probability below 2^-33 are unreachable; ``fl32(k)`` is exact only below 2^24."""
+    _poisson_tensor(lam, "lam")
+    if n_samples is None:
+        if lam.dim() < 1:
+            raise ValueError("rand_poisson: lam needs a leading sample axis (or pass n_samples)")
+        N, shape = int(lam.shape[0]), tuple(lam.shape)
+        n = lam.numel() // N if N else 0
+        lam_ss = n
+    else:
+        N = int(n_samples)
+        if N < 0:
+            raise ValueError(f"rand_poisson: n_samples = {n_samples}")
+        shape, n, lam_ss = (N,) + tuple(lam.shape), lam.numel(), 0
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=lam.device)
+    else:
+        if tuple(_poisson_tensor(out, "out").shape) != shape or out.device != lam.device:
+            raise ValueError(f"rand_poisson: out must be a float32 tensor {shape} on {lam.device}")
+    pre, post = _sample_scale(pre, N, lam.device, "pre"), _sample_scale(post, N, lam.device, "post")
+    args = _rand_args(seed, stream, sample_offset, "rand_poisson")
+    if out.numel() == 0:
+        return out
+    check(_lib.lib().cwfa_rand_poisson_f32(_p(out), _p(lam), N, n, lam_ss, n, _p(pre), _p(post), *args, _stream()), "rand_poisson")
     return out
 
 

@@ -14,7 +14,7 @@ from .amp import amp_function, amp_region
 
 __all__ = ["psnr", "volume_2_projections", "norm_data", "filter_data", "fast_quantile", "crop_volume_center", "load_process_volume",
            "prepare_XLFM_data", "roll_n", "batch_fftshift2d_real", "fft_conv", "fft_conv_split", "load_PSF", "load_PSF_OTF",
-           "XLFMDeconv"]
+           "XLFMDeconv", "XLFMForward", "simulate_XLFM_image"]
 
 
 def _as_volume(t, name):
@@ -592,3 +592,75 @@ def prior_from_posterior(mean, std, n_depths, obj_size, scale=1.0, offset=0.0):
     prior_mean[:, d0:d1, h0:h1, w0:w1] = mean if neutral else mean * scale + offset
     prior_std[:, d0:d1, h0:h1, w0:w1] = std if neutral else std * scale
     return prior_mean, prior_std
+
+
+def XLFMForward(OTF, vol, ObjSize=None, img_size=None, n_split_fourier=1, out=None):
+    """The forward projection of ``XLFMDeconv``'s loop on its own: the image a volume gives under the transfer function.
+
+    OTF as for ``XLFMDeconv`` (the 5-D form uses ``OTF[..., 0]``); vol float32 [1, D, obj, obj] on the HIP device (``ObjSize``, if
+    given, must name that size).  Returns the estimate [1, 1, F, F], or with ``img_size`` its centred [1, 1, img_size, img_size]
+    window (the bits of that window of the full result: the depth sum reads the window only).  Per chunk of ``n_split_fourier``
+    depths (1: all) the launches are those of the loop: rfft2 of the zero-padded chunk, ``deconv_spectrum_mul``, irfft2,
+    ``deconv_project(pre="relu")`` with the shift and the depth sum.  ``out``: a contiguous float32 tensor of the result's size to
+    write into.  vol and OTF are left unchanged."""
+    if not torch.is_tensor(OTF) or OTF.dim() not in (4, 5) or (OTF.dim() == 5 and OTF.shape[4] != 2) or OTF.shape[0] != 1:
+        raise ValueError("XLFMForward: the OTF must be [1, D, F, F // 2 + 1] or [1, D, F, F // 2 + 1, 2]")
+    nDepths = int(OTF.shape[1])
+    step = nDepths if n_split_fourier == 1 else int(n_split_fourier)
+    if step < 1:
+        raise ValueError(f"XLFMForward: n_split_fourier = {n_split_fourier}")
+    ops._dev(vol, "vol")
+    if vol.dim() != 4 or vol.shape[0] != 1 or vol.shape[1] != nDepths or vol.shape[2] != vol.shape[3]:
+        raise ValueError(f"XLFMForward: expected a volume [1, {nDepths}, obj, obj], got {tuple(vol.shape)}")
+    obj = int(vol.shape[2])
+    if ObjSize is not None and [int(v) for v in ObjSize[:2]] != [obj, obj]:
+        raise ValueError(f"XLFMForward: ObjSize {list(ObjSize)} is not the volume's {obj} x {obj}")
+    F = int(OTF.shape[2])
+    if F % 2 or OTF.shape[3] != F // 2 + 1:
+        raise ValueError(f"XLFMForward: the OTF's planes {tuple(OTF.shape[2:4])} are not [F, F // 2 + 1] of an even full size F")
+    if obj > F or (F - obj) % 2:
+        raise ValueError(f"XLFMForward: the object size {obj} cannot be padded evenly to the full size {F}")
+    size = F if img_size is None else int(img_size[0] if isinstance(img_size, (list, tuple)) else img_size)
+    if isinstance(img_size, (list, tuple)) and int(img_size[-1]) != size:
+        raise ValueError(f"XLFMForward: the image {list(img_size)} is not square")
+    if size < 1 or size > F or (F - size) % 2:
+        raise ValueError(f"XLFMForward: the image size {size} is not a centred window of the full size {F}")
+    po, pi = (F - obj) // 2, (F - size) // 2
+    otf_f = OTF[..., 0] if OTF.dim() == 5 else OTF
+    otf_f = ops._cdev(otf_f if otf_f.is_contiguous() else otf_f.contiguous(), "OTF")
+    dev = vol.device
+    with torch.no_grad():
+        if out is None:
+            out = torch.empty(1, 1, size, size, dtype=torch.float32, device=dev)
+        nz = min(step, nDepths)
+        obj_pad = torch.zeros(1, nz, F, F, dtype=torch.float32, device=dev)
+        spec = torch.empty(1, nz, F, F // 2 + 1, dtype=torch.complex64, device=dev)
+        real = torch.empty(1, nz, F, F, dtype=torch.float32, device=dev)
+        window = None if size == F else (pi, pi, size, size)
+        for jj in range(0, nDepths, step):
+            je = min(jj + step, nDepths)
+            pad, sp, re = obj_pad[:, :je - jj], spec[:, :je - jj], real[:, :je - jj]
+            pad[:, :, po:po + obj, po:po + obj] = vol[:, jj:je]
+            torch.fft.rfft2(pad, out=sp)
+            ops.deconv_spectrum_mul(sp, otf_f[:, jj:je], out=sp)
+            torch.fft.irfft2(sp, s=(F, F), out=re)
+            ops.deconv_project(re, out=out, window=window, pre="relu", accumulate=jj > 0)
+    return out
+
+
+def simulate_XLFM_image(OTF, vol, photons=None, background=0.0, seed=0, sample_offset=0, n_samples=1, **forward_kw):
+    """(clean [1, 1, S, S], noisy [n_samples, 1, S, S]): a measurement of a volume.  clean = ``XLFMForward(OTF, vol, **forward_kw)``;
+    the noisy images are Poisson draws, in photon units, at the fp32 rate  clean * (photons / max(clean)) + background  (``photons`` at
+    the brightest pixel; None: the clean image is in photon units already, rate = clean + background).  The maximum is taken on the
+    device (``ops.volume_extrema``) and nothing is read back; an all-zero clean image with ``photons`` gives NaN rates, hence NaN.
+    Sample s is ``ops.rand_poisson`` sample ``sample_offset + s`` of stream 0 under ``seed``: ``n_samples = 3`` equals three calls
+    with ``sample_offset`` 0, 1 and 2."""
+    clean = XLFMForward(OTF, vol, **forward_kw)
+    with torch.no_grad():
+        rate = clean[0]                                                    # [1, S, S]: one plane shared by all samples
+        if photons is not None:
+            rate = rate * (float(photons) / ops.volume_extrema(clean.reshape(1, 1, 1, -1))[0, 1])
+        if float(background) != 0.0:
+            rate = rate + float(background)
+        noisy = ops.rand_poisson(rate.contiguous(), seed, stream=0, sample_offset=sample_offset, n_samples=int(n_samples))
+    return clean, noisy

@@ -895,6 +895,26 @@ int cwfa_activity_finish_f32(const float* x0, const double* s1, const double* s2
 int cwfa_local_maxima_f32(const float* score, int D, int H, int W, float thr, int dz, int dy, int dx, int mz, int my, int mx,
                           void* workspace, void* out, int64_t capacity, int64_t* count, void* stream);
 
+/* ---- shot noise: a Poisson draw per element, in one launch, nothing read back.
+ *   out[s][e] = fl32(fl32(k) * post[s]),   k ~ Poisson(rate),   rate = fl32(lam[s * lam_ss + e] * pre[s])
+ * for s < N, e < n.  pre / post: nullable DEVICE float [N], NULL means 1.  lam_ss = 0: all N samples draw from one rate plane;
+ * out == lam (in place) is allowed when lam_ss == out_ss: an element reads only its own rate, before it writes.  Strides in
+ * elements, >= n (out_ss > n leaves the gap untouched).  n <= 2^52, CWFA_E_SHAPE beyond.
+ * Counter convention -- part of the interface, and NOT that of cwfa_rand_uniform_f32 above (which packs four elements into a
+ * block): element e of sample s, round t, uses the Philox4x32-10 block with counter
+ *   (e & 0xffffffff, (e >> 32) | (t << 20), sample_offset + s, stream_id)   under the key (seed & 0xffffffff, seed >> 32),
+ * one block per element and round, so a draw depends on nothing but (seed, stream_id, sample_offset + s, e) and its rate: samples
+ * [0, N) equal [0, k) followed by [k, N) under sample_offset + k, bit for bit.  A word r becomes u = (r + 0.5) * 2^-32 in float64
+ * (exact, strictly inside (0, 1)); every comparison of the draw is evaluated in float64:
+ *   rate < 10    inversion by sequential search on word 0 of round 0: k = 0, p = F = exp(-rate); while u > F and k < 80:
+ *                k += 1, p *= rate / k, F += p.  Probabilities below 2^-33 are unreachable.
+ *   rate >= 10   Hoermann's PTRS with b = 0.931 + 2.53 sqrt(rate), a = -0.059 + 0.02483 b, 1/alpha = 1.1239 + 1.1328 / (b - 3.4),
+ *                v_r = 0.9277 - 3.6224 / (b - 2); attempt j takes (U, V) from words (2 (j & 1), 2 (j & 1) + 1) of round j >> 1.
+ *                Bounded: after 32 rounds (64 attempts) k = rint(rate).
+ *   rate = 0 gives 0; a rate that is negative, NaN or above 2^30 gives NaN in out.  fl32(k) is exact only below 2^24. */
+int cwfa_rand_poisson_f32(float* out, const float* lam, int N, int64_t n, int64_t lam_ss, int64_t out_ss, const float* pre,
+                          const float* post, uint64_t seed, uint32_t stream_id, uint32_t sample_offset, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
