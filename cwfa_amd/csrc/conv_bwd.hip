@@ -943,12 +943,16 @@ __global__ __launch_bounds__(256) void conv3d_input_bwd_kernel(const float* __re
     // one descriptor over the K hidden volumes of this sample (< 2 GiB, checked by the host); the channel moves through the
     // scalar offset and the padding marker 0x80000000 is out of range whichever way the offsets are summed
     const auto rm = CWFA_RSRC(m + (int64_t)b * K * vol, (int)((int64_t)K * vol * 4));
+    // a running sum per hidden channel, added to the total once: one chain through all 27 K terms would round 864 times at
+    // K = 32 (1e-6 of the largest dx), this one 27 + K times
     float acc = 0.f;
     for (int k = 0; k < K; ++k) {
         const int so = (int)((int64_t)k * vol * 4);
+        float part = 0.f;
 #pragma unroll
         for (int t = 0; t < 27; ++t)
-            acc = fmaf(w1[k * 27 + t], __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rm, off[t], so, 0)), acc);
+            part = fmaf(w1[k * 27 + t], __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rm, off[t], so, 0)), part);
+        acc += part;
     }
     dx[(int64_t)b * vol + i] = acc;
 }
@@ -982,6 +986,7 @@ __global__ __launch_bounds__(256) void conv3d_input_bwd4_kernel(const float* __r
     for (int k = 0; k < K; ++k) {
         const int so = (int)((int64_t)k * vol * 4);
         const float* wk = w1 + k * 27;
+        float part[4] = {0.f, 0.f, 0.f, 0.f};                 // per hidden channel, as in the scalar kernel
 #pragma unroll
         for (int l = 0; l < 9; ++l) {
             const int ih = l / 3, id = l % 3;
@@ -995,9 +1000,11 @@ __global__ __launch_bounds__(256) void conv3d_input_bwd4_kernel(const float* __r
             for (int iw = 0; iw < 3; ++iw) {
                 const float wv = wk[(ih * 3 + iw) * 3 + id];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = fmaf(wv, v[j + 2 - iw], acc[j]);
+                for (int j = 0; j < 4; ++j) part[j] = fmaf(wv, v[j + 2 - iw], part[j]);
             }
         }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] += part[j];
     }
     *reinterpret_cast<f32x4*>(dx + (int64_t)b * vol + i) = f32x4{acc[0], acc[1], acc[2], acc[3]};
 }
