@@ -3,12 +3,16 @@
 statistics / normalisation of ``ConcatDataset`` (:251-395) on device tensors, and the shot-noise augmentation
 the reference documents (:397-405) but never defines per dataset.  File reading stays the
 reference's.  Not registered by cwfa_amd.install(); a maintainer patches the calls, see INTEGRATION.md."""
+import math
+from collections import namedtuple
+
 import torch
 
 from . import ops
-from .amp import amp_function
+from .amp import amp_function, amp_region
 
-__all__ = ["XLFMDatasetFull", "ConcatDataset", "extract_views", "pad_img_to_min", "center_crop", "prepare_frames", "shot_noise_scales", "add_random_shot_noise_to_datasets"]
+__all__ = ["XLFMDatasetFull", "ConcatDataset", "extract_views", "pad_img_to_min", "center_crop", "prepare_frames", "shot_noise_scales", "add_random_shot_noise_to_datasets",
+           "extract_sparse", "SparseSplit", "quantile_rank"]
 
 
 def extract_views(image, lenslet_coords, subimage_shape, debug=False):
@@ -57,6 +61,56 @@ def prepare_frames(raw, img_shape):
     return ops.prep_frames(raw, img_shape, frame_offsets(raw.shape[-2], raw.shape[-1], img_shape))
 
 
+SparseSplit = namedtuple("SparseSplit", ["sparse", "baseline", "scales", "tau"])
+
+
+def quantile_rank(q, n):
+    """The 0-based rank of the ``q`` quantile of ``n`` samples by the rule of ``numpy.quantile(method="lower")``:
+    floor(q * (n - 1)), formed in float64 on the host."""
+    q, n = float(q), int(n)
+    if not 0.0 <= q <= 1.0 or n < 1:
+        raise ValueError(f"extract_sparse: a quantile in [0, 1] of at least one frame is expected, got q = {q}, N = {n}")
+    return int(math.floor((n - 1) * q))
+
+
+@amp_region
+def extract_sparse(frames, baseline_q=0.5, noise_k=0.0, ths=0.0, scale="ls", pair=False, out=None):
+    """The sparse (activity) component of a contiguous [N,H,W] fp32 / fp16 device stack under a robust rank-1 background
+    L[t,p] = scales[t] * baseline[p] -- the classical form of the stage whose output the reference reads from
+    ``SLNet_preprocessed/``; it is NOT SLNet's output.  Returns ``SparseSplit(sparse, baseline, scales, tau)``; nothing is read back
+    to the host.
+
+    A.  baseline[p]: the ``baseline_q`` quantile of pixel p over time (rank rule of ``numpy.quantile(method="lower")``).
+        scales[t]:   ``scale="ls"``: the least-squares scale <frame t, baseline> / <baseline, baseline> from float64 dot products
+                     (bleaching), 0 where the baseline is all zero; ``scale="none"``: ones.
+    B.  only for ``noise_k != 0``: with m and lo the 0.5 and 0.1587 quantiles of the residual x - scales[t] * baseline[p] over time
+        (its median and the point one sigma below it -- the lower half holds no transients),
+        tau[p] = (m + noise_k * (m - lo)) + ths in fp32; otherwise tau is ``ths`` as a map, or None for ``ths == 0``.
+    C.  sparse = relu(x - scales[t] * baseline[p] - tau[p]), float32 [N,H,W]; ``pair``: the reference's [N,H,W,2] layout with the
+        frames in channel 0 and the sparse component in channel 1.  ``out``: where to write it (an fp32 ``frames`` itself: in place).
+    Three reads of the stack, four with step B."""
+    if not torch.is_tensor(frames) or frames.dim() != 3 or not frames.is_contiguous():
+        raise ValueError("extract_sparse: a contiguous [N,H,W] stack is expected")
+    if scale not in ("ls", "none"):
+        raise ValueError(f"extract_sparse: scale is 'ls' or 'none', got {scale!r}")
+    N = int(frames.shape[0])
+    rank = quantile_rank(baseline_q, N)
+    baseline = ops.temporal_select(frames, [rank])[0]
+    if scale == "ls":
+        sums = ops.frame_dots(frames, baseline)
+        scales = torch.where(sums[N] == 0, torch.zeros_like(sums[:N]), sums[:N] / sums[N]).float()
+    else:
+        scales = torch.ones(N, dtype=torch.float32, device=frames.device)
+    noise_k, ths = float(noise_k), float(ths)
+    if noise_k != 0.0:
+        m, lo = ops.temporal_select(frames, [quantile_rank(0.5, N), quantile_rank(0.1587, N)], a=scales, b=baseline)
+        tau = (m + noise_k * (m - lo)) + ths
+    else:
+        tau = torch.full_like(baseline, ths) if ths != 0.0 else None
+    sparse = ops.sparse_residual(frames, scales, baseline, tau, out=out, pair=pair)
+    return SparseSplit(sparse, baseline, scales, tau)
+
+
 def _scalar(v):
     """A float64 statistic as the 0-dim float32 CPU tensor the reference returns (rounded once)."""
     return torch.tensor(v, dtype=torch.float64).to(torch.float32)
@@ -99,9 +153,17 @@ class XLFMDatasetFull:
         self.gt_cache = []
 
     @classmethod
-    def from_tensors(cls, raw_frames, vols, img_shape, ds_id=""):
-        """From raw fp32 frames [N,h,w] and fp16 volumes [N,D,H0,W0] as read from the files."""
-        return cls(prepare_frames(raw_frames, img_shape), vols, ds_id)
+    def from_tensors(cls, raw_frames, vols, img_shape, ds_id="", sparse=None):
+        """From raw fp32 frames [N,h,w] and fp16 volumes [N,D,H0,W0] as read from the files.  ``sparse``: True, or a dict of
+        ``extract_sparse`` arguments: ``stacked_views`` is then the sparse component of the prepared frames ([N,H,W], or the
+        [N,H,W,2] pair with ``pair=True``) -- what the reference reads from ``SLNet_preprocessed/``."""
+        frames = prepare_frames(raw_frames, img_shape)
+        if sparse is None or sparse is False:
+            return cls(frames, vols, ds_id)
+        kw = {} if sparse is True else dict(sparse)
+        if "out" not in kw and not kw.get("pair", False):
+            kw["out"] = frames                                      # the prepared frames are ours: in place
+        return cls(extract_sparse(frames, **kw).sparse, vols, ds_id)
 
     def __len__(self):
         return int(self.stacked_views.shape[0])

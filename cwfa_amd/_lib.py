@@ -86,6 +86,7 @@ DECONV_UPDATE_UNITS = 256          # CWFA_DECONV_UPDATE_UNITS
 DECONV_NLL_WORKSPACE_BYTES = 8192  # CWFA_DECONV_NLL_WORKSPACE_BYTES
 ACTIVITY_KIND = {"std": 0, "range": 1, "peak": 2, "snr": 3}                     # CWFA_ACTIVITY_*
 NMAX_MAX_DIST = 16                 # CWFA_NMAX_MAX_DIST
+SELECT_FORM = {"auto": 0, "lds": 1, "stream": 2}                                # cwfa_temporal_select's `form`
 
 # name -> (restype, argtypes); must list EVERY function declared in include/cwfa_hip.h (tests/test_boundary.py checks)
 i, i64, f, d, p = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_void_p
@@ -207,6 +208,11 @@ SIGNATURES = {
     "cwfa_activity_finish_f32": (i, [p, p, p, p, p, i64, i, p, p, p, i64, p]),
     "cwfa_local_maxima_f32": (i, [p, i, i, i, f, i, i, i, i, i, i, p, p, i64, p, p]),
     "cwfa_rand_poisson_f32": (i, [p, p, i, i64, i64, i64, p, p, C.c_uint64, C.c_uint32, C.c_uint32, p]),
+    "cwfa_temporal_select": (i, [p, i, i, i64, i64, p, p, C.POINTER(C.c_int), i, p, i, p]),
+    "cwfa_temporal_select_lds_frames": (i, [i, i]),
+    "cwfa_frame_dots_workspace_bytes": (i64, [i, i64]),
+    "cwfa_frame_dots": (i, [p, i, i, i64, i64, p, p, p, i, p]),
+    "cwfa_sparse_residual": (i, [p, i, i, i64, i64, p, p, p, p, i, p]),
 }
 del i, i64, f, d, p
 

@@ -2496,3 +2496,103 @@ def local_maxima(score, thr, dist, margin=(0, 0, 0), n_max=None, capacity=1 << 2
     lin = lin[order]
     zyx = np.stack([lin // (H * W), lin // W % H, lin % W], axis=1).astype(np.int32) if len(lin) else np.zeros((0, 3), dtype=np.int32)
     return zyx, bits[order].view(np.float32).copy(), total
+
+
+# ------------------------------------------------------------------------------------------------ sparse-activity extraction
+_STACK_DTYPE = {torch.float32: 0, torch.float16: 1}
+
+
+def _stack(x, what):
+    """A [T, ...] fp32 / fp16 device stack as (tensor, dtype code, T, P, frame stride): frames contiguous, any stride of at least a
+    frame between them (a band of rows of every frame qualifies without a copy)."""
+    if not torch.is_tensor(x):
+        raise TypeError(f"{what}: expected a torch.Tensor, got {type(x)}")
+    if not x.is_cuda:
+        raise RuntimeError(f"{what}: cwfa_amd runs on MI355X only -- got a {x.device} tensor (no CPU fallback exists)")
+    if x.dtype not in _STACK_DTYPE:
+        raise TypeError(f"{what}: expected a float32 or float16 stack, got {x.dtype}")
+    if x.dim() < 2:
+        raise ValueError(f"{what}: a stack [T, ...] is expected, got {tuple(x.shape)}")
+    T, P = int(x.shape[0]), 1
+    for s in x.shape[1:]:
+        P *= int(s)
+    if T and P and (not x[0].is_contiguous() or (T > 1 and x.stride(0) < P)):
+        x = x.contiguous()
+    return x, _STACK_DTYPE[x.dtype], T, P, (x.stride(0) if T > 1 and P else P)
+
+
+def _vec(t, n, name, what, dtype=torch.float32):
+    """A contiguous device tensor of ``n`` elements of ``dtype`` (any shape)."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError(f"{what}: {name} must be a tensor on the HIP device (no CPU fallback exists)")
+    if t.dtype != dtype or t.numel() != n:
+        raise ValueError(f"{what}: {name} holds {n} {dtype} values, got {tuple(t.shape)} {t.dtype}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def temporal_lds_frames(dtype, transformed=False):
+    """The largest T the one-read form of ``temporal_select`` accepts for a stack of ``dtype`` with (``transformed``) or without a
+    background (a, b).  Host only."""
+    if dtype not in _STACK_DTYPE:
+        raise TypeError(f"temporal_lds_frames: float32 or float16, got {dtype}")
+    return int(_lib.lib().cwfa_temporal_select_lds_frames(_STACK_DTYPE[dtype], int(bool(transformed))))
+
+
+def temporal_select(stack, ranks, a=None, b=None, form="auto"):
+    """Per-pixel temporal order statistics of a [T, ...] fp32 / fp16 device stack: out[k] (float32, the shape of a frame) holds the
+    ``ranks[k]``-th smallest (from 0) of the T values of every pixel, for 1 to 4 ranks; the result is an element of the series, bit
+    for bit (-0 and +0 are one value, returned as +0).  With ``a`` [T] and ``b`` (a frame) the series is x - a[t] * b[p], formed on
+    load in fp32.  ``form``: "lds" (one read of the stack, T up to ``temporal_lds_frames``), "stream" (any T) or "auto"."""
+    L = _lib.lib()
+    stack, dt, T, P, fs = _stack(stack, "temporal_select")
+    if form not in _lib.SELECT_FORM:
+        raise ValueError(f"temporal_select: form is one of {sorted(_lib.SELECT_FORM)}, got {form!r}")
+    ranks = [int(r) for r in ranks]
+    if not 1 <= len(ranks) <= 4:
+        raise ValueError(f"temporal_select: 1 to 4 ranks, got {len(ranks)}")
+    if T < 1 or any(r < 0 or r >= T for r in ranks):
+        raise ValueError(f"temporal_select: ranks {ranks} are not in 0 .. {T - 1}")
+    if (a is None) != (b is None):
+        raise ValueError("temporal_select: a and b are given together or not at all")
+    if a is not None:
+        a, b = _vec(a, T, "a", "temporal_select"), _vec(b, P, "b", "temporal_select")
+    out = torch.empty((len(ranks),) + tuple(stack.shape[1:]), dtype=torch.float32, device=stack.device)
+    check(L.cwfa_temporal_select(_p(stack), dt, T, P, fs, _p(a), _p(b), (C.c_int * len(ranks))(*ranks), len(ranks), _p(out),
+                                 _lib.SELECT_FORM[form], _stream()), "temporal_select")
+    return out
+
+
+def frame_dots(stack, b, sums=None):
+    """float64 [T + 1] on the device: sums[t] = sum_p stack[t, p] * b[p] and sums[T] = sum_p b[p]^2, every product formed in float64,
+    partial sums added in a fixed order (bitwise repeatable).  ``sums``: add to these (bands of rows of one stack add up)."""
+    L = _lib.lib()
+    stack, dt, T, P, fs = _stack(stack, "frame_dots")
+    b = _vec(b, P, "b", "frame_dots")
+    acc = 1
+    if sums is None:
+        acc, sums = 0, torch.empty(T + 1, dtype=torch.float64, device=stack.device)
+    elif not torch.is_tensor(sums) or sums.dtype != torch.float64 or not sums.is_cuda or sums.numel() != T + 1 or not sums.is_contiguous():
+        raise ValueError("frame_dots: sums must be a contiguous float64 [T + 1] device tensor")
+    ws = torch.empty(max(int(L.cwfa_frame_dots_workspace_bytes(T, P)) // 8, 1), dtype=torch.float64, device=stack.device)
+    check(L.cwfa_frame_dots(_p(stack), dt, T, P, fs, _p(b), _p(sums), _p(ws), acc, _stream()), "frame_dots")
+    return sums
+
+
+def sparse_residual(stack, a, b, tau=None, out=None, pair=False):
+    """S = relu(stack - a[t] * b[p] - tau[p]) in separately rounded fp32 operations (``tau`` None: no last subtraction), float32 of
+    the stack's shape; ``pair``: the [T, ..., 2] layout with the widened stack in channel 0 and S in channel 1, written in one pass.
+    ``out``: a contiguous float32 tensor of that shape; an fp32 contiguous ``stack`` itself works in place (``pair`` False)."""
+    L = _lib.lib()
+    given = stack
+    stack, dt, T, P, fs = _stack(stack, "sparse_residual")
+    a, b = _vec(a, T, "a", "sparse_residual"), _vec(b, P, "b", "sparse_residual")
+    tau = None if tau is None else _vec(tau, P, "tau", "sparse_residual")
+    shape = tuple(stack.shape) + ((2,) if pair else ())
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=stack.device)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"sparse_residual: out must be a contiguous float32 {shape} device tensor")
+    elif out is given and stack is not given:
+        raise ValueError("sparse_residual: in place needs a contiguous stack")
+    check(L.cwfa_sparse_residual(_p(stack), dt, T, P, fs, _p(a), _p(b), _p(tau), _p(out), int(bool(pair)), _stream()), "sparse_residual")
+    return out

@@ -915,6 +915,39 @@ int cwfa_local_maxima_f32(const float* score, int D, int H, int W, float thr, in
 int cwfa_rand_poisson_f32(float* out, const float* lam, int N, int64_t n, int64_t lam_ss, int64_t out_ss, const float* pre,
                           const float* post, uint64_t seed, uint32_t stream_id, uint32_t sample_offset, void* stream);
 
+/* ---- sparse-activity extraction: a robust rank-1 background L[t,p] = a[t] * b[p] of a frame stack and the
+ * thresholded positive residual S = relu(x - L - tau).  x: [T, P], `dtype` 0 = fp32, 1 = fp16, frame_stride >= P elements between
+ * frames (a band of rows of every frame is a valid argument).  Inputs are assumed finite.  Arguments are checked before any device
+ * work; nothing is allocated, nothing synchronises.  T == 0 or P == 0: no launch, CWFA_OK (frame_dots: P == 0, and sums that are
+ * overwritten are cleared).
+ *
+ *   temporal_select:  out[k * P + p] (fp32) = the ranks[k]-th smallest (from 0) of the T values v[t] of pixel p; `ranks` is a HOST
+ *                     array of K in 1 .. 4 entries in [0, T), duplicates allowed.  a == b == NULL: v = x (fp16 widened, exactly);
+ *                     both given (device fp32 [T] and [P]): v = fl32(x - fl32(a[t] * b[p])), formed on load.  The result is an
+ *                     element of v, bit for bit, under the order of local_maxima: the unsigned image of the fp32 bits of v + 0.0f
+ *                     (-0 and +0 are one value, returned as +0).  Found by bisection of the key bits from the top, one count of
+ *                     the keys per bit for all K ranks.  form 1, one read of the stack: a workgroup keeps the T keys of a tile of
+ *                     64 pixels in the LDS (32-bit keys; 16-bit keys for fp16 without a background), its waves split the frames;
+ *                     T <= temporal_select_lds_frames, CWFA_E_SHAPE beyond.  form 2, streaming: a thread per pixel counts from
+ *                     memory, one sweep per key bit, any T.  form 0: form 1 where T fits, else form 2.  The forms agree bit for bit.
+ *   temporal_select_lds_frames: host only: the largest T of form 1 for this dtype with (transformed != 0) or without a background.
+ *   frame_dots:       sums[t] = sum_p x[t,p] * b[p] for t < T and sums[T] = sum_p b[p]^2, float64, every product formed in float64
+ *                     (exact for fp32 factors).  Block partials go to `ws` (frame_dots_workspace_bytes(T, P) device bytes, 8-byte
+ *                     aligned, no clearing needed) and are added in a fixed order: no atomics, bitwise repeatable.  accumulate = 1
+ *                     adds to the T + 1 sums (bands of rows add up), 0 overwrites.  sums, ws: 8-byte aligned, CWFA_E_ALIGN otherwise.
+ *   sparse_residual:  r = fl32(fl32(x - fl32(a[t] * b[p])) - tau[p]) (tau == NULL: without the last subtraction), S = r > 0 ? r : 0.
+ *                     pair = 0: out fp32 [T, P]; out == x is allowed for an fp32 stack with frame_stride == P.  pair = 1: out fp32
+ *                     [T, P, 2], channel 0 = x widened, channel 1 = S, written in the same pass.  16-byte accesses (8-byte loads of
+ *                     fp16) where P, the stride and every base allow, element by element otherwise. */
+int cwfa_temporal_select(const void* x, int dtype, int T, int64_t P, int64_t frame_stride, const float* a, const float* b,
+                         const int* ranks, int K, float* out, int form, void* stream);
+int cwfa_temporal_select_lds_frames(int dtype, int transformed);
+int64_t cwfa_frame_dots_workspace_bytes(int T, int64_t P);
+int cwfa_frame_dots(const void* x, int dtype, int T, int64_t P, int64_t frame_stride, const float* b, double* sums, void* ws,
+                    int accumulate, void* stream);
+int cwfa_sparse_residual(const void* x, int dtype, int T, int64_t P, int64_t frame_stride, const float* a, const float* b,
+                         const float* tau, float* out, int pair, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
