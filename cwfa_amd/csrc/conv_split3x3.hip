@@ -21,8 +21,34 @@
 //   and an odd chunk: taps (0,1)(2,3)(4,5)(6,7) of the even one, its tap 8 with tap 0 of the odd one, then (1,2)...(7,8).
 //   The even buffer is free from step 5 and refilled there (loads in steps 2..4), the odd one in steps 0..2 (loads in steps
 //   6..8 of the period before): buffer loads, padding / border / channels >= Cin come back as 0.0 from the range check.
-//   Weights: one slice [piece][k group 4][CT][8] per step through a two-slot ring by LDS-DMA, issued at the start of the
-//   step before, verified at its end; one barrier per step.
+//   Weights: one slice [piece][k group 4][CT][8] per step through a two-slot ring by LDS-DMA, slot(s) = s & 1.
+//   ONE barrier per step, and it sits in the MIDDLE of the step: mid(s), behind n-tile NT/2 - 1 (MIDSTEP; the skip-add forms
+//   keep it at the step boundary, see MIDSTEP in the kernel).  The step boundary then needs no synchronisation: inside the last
+//   n-tile of step s, once the MFMAs that read A[mt] have issued, A[mt] of step s+1 (m-tiles < MA) and the B fragments of its
+//   n-tile 0 are requested, and the MFMA stream of a wave runs from one step into the next without a wait.  (With the barrier at
+//   the boundary all eight waves left it together, asked for their A fragments at once -- 48 KB of LDS reads -- and no matrix
+//   pipe of the CU had an MFMA to issue until they came back, once per step.)  Per step s:
+//     first half    MFMAs of n-tiles 0 .. NT/2-1; A[MA .. MPW) from slot(s) behind the first MFMAs
+//     mid(s)        s_waitcnt vmcnt(0) (this wave's pieces of slice s+1 and its staging loads), the LDS wait that leaves only the
+//                   B look-ahead outstanding, s_barrier
+//     second half   staging stores (steps SB + k / SA + k), staging loads (LA + k / LB + k), dma_w(s + 2, slot(s)), pre-reads
+//   Why that is safe (tests/test_split3x3_schedule_cpu.py replays it with the constants read from this file):
+//     weight ring, write after read: slot(s) is read at the end of step s-1 and the start of step s; every wave has finished
+//       those reads (its LDS wait) when it arrives at mid(s), and dma_w(s + 2, slot(s)) is issued behind mid(s).
+//     weight ring, read after write: slice s+2 is waited for by the wave that requested it (vmcnt(0)) in front of mid(s+1) and
+//       first read at the end of step s+1, behind that barrier; the DMA has one full step in flight.  The prologue lands
+//       slices 0 and 1 in front of its barrier.
+//     input buffers, 3x3: the even buffer is last read in step 4 (tap 8); its stores sit in the second halves of steps SA + k =
+//       5, 6 (, 7), behind mid(5), which a wave reaches after it has finished step 4; they are published by mid(6) .. mid(8) and
+//       first read by the B pre-read at the end of step 8.  The odd buffer is last read in step 8; its stores sit behind mid(0) ..
+//       mid(2) of the next period and its first read is the pre-read at the end of step 3, behind mid(3).
+//       7x7: the even buffer is last read in step 24, stored behind mid(26) .. mid(28), read again at the end of step 48; the
+//       odd one stored behind mid(0) .. mid(2), first read at the end of step 23.  (static_asserts in the loop.)
+//     one staging register set per entry: entry k is stored at SB + k / SA + k and loaded at LA + k / LB + k, different steps
+//       except SA + k = LB + k in the 3x3, where the step's stores come before its loads.
+//     barriers are uniform: NT, the barrier's n-tile and p.nrun are the same for all waves of a block and the barrier sits in
+//       compile-time-unrolled code: one barrier per executed step plus the prologue's (plus one in front of the statistics
+//       epilogue, which overlays the input buffers that slower waves may still be reading in the last step's second half).
 #include "conv_internal.h"
 
 extern int g_cwfa_split_xcd_map;        // conv2d.hip ("split3x3_xcd_map" option)
@@ -246,6 +272,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
     // the A fragments of m-tiles >= MA are requested behind the step's first MFMAs, not in front of them.
     constexpr int NB = MPW == 4 ? 3 : 2, MA = MPW == 4 ? 2 : MPW;
     static_assert(NB - 1 < NT, "B look-ahead");
+    // where the step's one barrier sits: in the MIDDLE of the step (see the header) -- or, for the skip-add forms, at the step
+    // boundary: their staging set is twice as large (input + skip tensor), and with the split in the middle of the step, where
+    // all A fragments and the B look-ahead are live, the allocator spilled 24 of its registers to scratch inside the loop
+    constexpr bool MIDSTEP = !ADD;
     bf16x8 A[MPW][3], Bq[NB][3];
     // staged entries of the chunk after next (+ skip tensor): ONE register set per entry serves the even and the odd chunk in turn
     // (its even-chunk value is stored at SA + k, before the odd-chunk load at LB + k, and that one at SB + k of the next period,
@@ -280,11 +310,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
         cwfa_static_for<NEK>([&](auto kc) { load_entry(kc, x0[decltype(kc)::value], s0[decltype(kc)::value], 0); });
         cwfa_static_for<NEK>([&](auto kc) { load_entry(kc, xs[decltype(kc)::value], sk[decltype(kc)::value], 1); });
         dma_w(0, 0);
+        if constexpr (MIDSTEP) dma_w(1, 1);               // (published with slice 0 right here; mid(0) then frees slot 0 for slice 2)
         cwfa_static_for<NEK>([&](auto kc) { store_entry(kc, x0[decltype(kc)::value], s0[decltype(kc)::value], 0, 0); });
     }
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
 
+    if constexpr (MIDSTEP) read_a(alane, 0, MA);                                    // step 0: slice 0 in slot 0
     read_b(0, blane + (sel ? tap_off<KS, RPW>(0, 1) : tap_off<KS, RPW>(0, 0)), 0);  // step 0: taps 0 | 1 of chunk 0
     // ONE step as the body of a rolled loop (the accumulators are loop-carried values: unrolling the nine steps of a period
     // makes the register allocator split their live ranges and keep copies); P = position in the 9-step period
@@ -296,18 +328,29 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
         const int uA = 2 * P, uB = 2 * P + 1;
         const int bufA = uA >= NTAP, tA = uA - NTAP * bufA, bufB = uB >= NTAP, tB = uB - NTAP * bufB;
         const int offA = bufA * XB + ((tA / KS) * XC + tA % KS) * 16, offB = bufB * XB + ((tB / KS) * XC + tB % KS) * 16;
-        // staging schedule inside a period: the odd buffer is free from step 0 (stores SB + k of the entries loaded in the period
-        // before), the even one right after the step that pairs tap NTAP-1 with the odd chunk's tap 0 (stores SA + k, loads LA + k
-        // a few steps earlier); the odd chunk after next is loaded at LB + k
+        // staging schedule inside a period (MIDSTEP: everything in the SECOND half of its step, behind the step's barrier; otherwise
+        // stores at the start of the step and loads behind its first n-tile): the odd buffer is
+        // free from step 0 (stores SB + k of the entries loaded in the period before), the even one from the step after the one
+        // that pairs tap NTAP-1 with the odd chunk's tap 0 (stores SA + k, loads LA + k a few steps earlier); the odd chunk after
+        // next is loaded at LB + k
         constexpr int SB = 0, SA = KS == 3 ? 5 : 26, LA = KS == 3 ? 2 : 22, LB = KS == 3 ? 6 : 44;       // (+ k < NEK: all below NTAP)
+        constexpr int MID = NT / 2;                       // the step's barrier sits behind n-tile MID - 1
+        constexpr int FO = (NTAP - 1) / 2;                // the step that reads the even buffer last and the odd one first
         static_assert(LB + NEK - 1 < NTAP && LA + NEK - 1 < SA, "staging schedule");
         static_assert(SB < LA && SA <= LB, "staging schedule: one register set per entry (a step's stores come before its loads)");
+        // a store behind mid(t) is published by mid(t + 1); a buffer's first B fragments are requested at the END of the step before
+        static_assert(!MIDSTEP || SB + NEK - 1 <= FO - 2, "staging schedule: the odd buffer is complete one barrier before the end of step FO - 1");
+        static_assert(!MIDSTEP || (SA >= FO + 1 && SA + NEK - 1 <= NTAP - 2), "staging schedule: the even buffer is written behind mid(FO + 1) ... mid(NTAP - 2)");
+        static_assert(MID >= 1 && MID + NB - 2 < NT, "mid-step barrier: the B look-ahead it leaves outstanding lies inside the step");
+        // the n-tiles behind which the staging loads and the weight DMA are issued
+        constexpr int LOAD_NT = MIDSTEP ? MID : 0, DMA_NT = !MIDSTEP ? 1 : NT >= 8 ? MID + 1 : MID;
+        // the staging split + LDS stores of one entry of the chunk after next, into the buffer this step does not read.
         // -- order matters: in this rolled loop the compiler cannot count the vector-memory operations between a staging load
-        // and its use, so it waits for ALL of them (vmcnt(0)) before the split below: that must come BEFORE this step issues
-        // its own DMA and loads, when everything older has long landed (after them it cost 2 - 9 thousand cycles per step).
-        // the vector-heavy part of staging: split + LDS stores of one entry of the chunk after next
+        // and its use, so it waits for ALL of them (vmcnt(0)) before the split: that must come right behind the wait in front of
+        // the step's barrier, when nothing is outstanding, and BEFORE the step issues its own loads and DMA (after them it cost
+        // 2 - 9 thousand cycles per step)
         // (written out per entry: behind a generic lambda the staged-entry arrays stopped being promoted to registers)
-        {
+        auto staging_stores = [&]() {
             const bool odd0 = P == SB, odd1 = P == SB + 1;          // the entry in the set: of the odd chunk (-> buffer 1) or the even one
             if (odd0 || P == SA) store_entry(cwfa_ic<0>{}, xs[0], sk[0], odd0 ? co : ce + 2, odd0);
             if (odd1 || P == SA + 1) store_entry(cwfa_ic<1>{}, xs[1], sk[1], odd1 ? co : ce + 2, odd1);
@@ -315,20 +358,38 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
                 const bool odd2 = P == SB + 2;
                 if (odd2 || P == SA + 2) store_entry(cwfa_ic<NEK - 1>{}, xs[NEK - 1], sk[NEK - 1], odd2 ? co : ce + 2, odd2);
             }
-        }
-        CWFA_FENCE();
-        // first A fragments (the step's first B fragments were requested before the barrier of the step before).  Nothing else is
-        // requested in front of the first MFMA: behind the conditional staging stores the compiler drains the LDS counter there
-        // (lgkmcnt(0)), so every read issued up here would be waited for
-        const int abase = alane + sl * WSL;
+            CWFA_FENCE();
+        };
+        // MIDSTEP: this step's A fragments of m-tiles < MA and the B fragments of n-tile 0 were requested inside the last n-tile of the step
+        // before (the prologue for step 0): the first MFMA issues at once, there is no wait and no barrier at the step boundary
+        const int abase = alane + sl * WSL, anext = alane + (sl ^ 1) * WSL;
         const int bbase = blane + (sel ? offB : offA);
-        read_a(abase, 0, MA);
-        CWFA_FENCE();
+        // first B fragments of the next step (the input tiles it reads were completed at least one barrier ago)
+        auto read_b_next = [&]() {
+            const int nP = P == NTAP - 1 ? 0 : P + 1;
+            const int nA = 2 * nP, nB = 2 * nP + 1;
+            const int nbufA = nA >= NTAP, ntA = nA - NTAP * nbufA, nbufB = nB >= NTAP, ntB = nB - NTAP * nbufB;
+            const int noffA = nbufA * XB + ((ntA / KS) * XC + ntA % KS) * 16, noffB = nbufB * XB + ((ntB / KS) * XC + ntB % KS) * 16;
+            read_b(0, blane + (sel ? noffB : noffA), 0);
+            CWFA_FENCE();
+        };
+        static_assert((NT - 1) % NB != 0 && NT >= 2, "the last n-tile is not multiplied from B set 0 (the next step's first fragments land there)");
+        if constexpr (!MIDSTEP) {
+            // boundary barrier: the stores, then the first A fragments (the step's first B fragments were requested before the
+            // barrier of the step before).  Nothing else is requested in front of the first MFMA: behind the conditional staging
+            // stores the compiler drains the LDS counter there (lgkmcnt(0)), so every read issued up here would be waited for
+            staging_stores();
+            read_a(abase, 0, MA);
+            CWFA_FENCE();
+        }
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             // NB - 1 n-tiles ahead, into the set the n-tile before this one has just been multiplied from (256-channel tiling, n-tile 0:
-            // behind its first MFMAs, see there); from here on the compiler's waits are counted: only the fragment about to be used
+            // behind its first MFMAs, see there); the compiler's waits are counted: only the fragment about to be used
             if ((MA == MPW || nt > 0) && nt + NB - 1 < NT) read_b((nt + NB - 1) % NB, bbase, nt + NB - 1);
+            // MIDSTEP: the look-ahead runs on into the next step -- its n-tile 0 is requested in front of this step's last n-tile
+            // (set 0 is free since n-tile NT - 2 at the latest), so the step boundary exposes no LDS round trip
+            if (MIDSTEP && nt == NT - 1) read_b_next();
             CWFA_FENCE();
 #pragma unroll
             for (int mt = 0; mt < MPW; ++mt) {
@@ -336,19 +397,35 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
                 CWFA_FENCE();                 // keep the six products of a tile back to back (accumulator forwarding)
                 if (MA < MPW && nt == 0 && mt == 0) {
                     // behind the step's first MFMAs, in the order of their use: the remaining A fragments (the MFMAs of m-tile 1
-                    // cover them), then the B fragments of the look-ahead
+                    // cover them; this step's slot, published by the barrier of the step before), then the B fragments of the look-ahead
                     read_a(abase, MA, MPW);
 #pragma unroll
                     for (int n2 = 1; n2 < NB && n2 < NT; ++n2) read_b(n2, bbase, n2);
                     CWFA_FENCE();
                 }
+                if (MIDSTEP && nt == NT - 1 && mt < MA) {
+                    // last n-tile: A[mt] has fed its last MFMAs of this step -> the NEXT step's fragment, from the other slot (its
+                    // slice was waited for in front of this step's barrier); the MFMAs of the m-tiles behind cover the round trip
+                    read_a(anext, mt, mt + 1);
+                    CWFA_FENCE();
+                }
             }
-            // this step's staging loads and the next weight slice are issued from INSIDE the MFMA stream (after the first
-            // n-tiles): issued in a burst right behind the barrier, all eight waves stood in their issue cost (~100 cycles per
-            // DMA instruction) at once with the matrix pipe idle; here the SIMD partner's MFMAs run meanwhile.  Loads BEFORE
-            // the DMA: they overwrite loop-carried registers, so the compiler waits for every older vector-memory
-            // operation first -- which must not include a DMA issued a moment ago.
-            if (nt == 0) {
+            if (MIDSTEP && nt == MID - 1) {
+                // ---- the step's ONE barrier.  In front of it: this wave's pieces of the next slice (requested behind the barrier of
+                // the step before: one full step in flight) and its staging loads have landed; every LDS access of this wave but the
+                // NB - 1 sets of B fragments of the look-ahead is done -- its reads of this step's slot, its staging stores
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"((NB - 1) * NQ) : "memory");
+                __builtin_amdgcn_s_barrier();
+                staging_stores();
+            }
+            // this step's staging loads and the weight slice after next (boundary barrier: the next one) are issued from INSIDE the
+            // MFMA stream, MIDSTEP: of the second half
+            // (in a burst right behind the barrier, all eight waves stood in their issue cost -- ~100 cycles per DMA instruction --
+            // at once with the matrix pipe idle; here the SIMD partner's MFMAs run meanwhile).  Loads BEFORE the DMA: they
+            // overwrite loop-carried registers, so the compiler waits for every older vector-memory operation first -- which must
+            // not include a DMA issued a moment ago.
+            if (nt == LOAD_NT) {
                 if (P == LA || P == LB) load_entry(cwfa_ic<0>{}, xs[0], sk[0], P == LA ? ce + 2 : co + 2);
                 if (P == LA + 1 || P == LB + 1) load_entry(cwfa_ic<1>{}, xs[1], sk[1], P == LA + 1 ? ce + 2 : co + 2);
                 if constexpr (NEK > 2) {
@@ -356,26 +433,20 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
                 }
                 CWFA_FENCE();
             }
-            if (nt == 1) {
-                dma_w(step + 1, sl ^ 1);
+            if (nt == DMA_NT) {
+                if constexpr (MIDSTEP) dma_w(step + 2, sl);     // into THIS step's slot: every wave finished reading it in front of the barrier
+                else dma_w(step + 1, sl ^ 1);
                 CWFA_FENCE();
             }
         }
-        // first B fragments of the next step: the input tiles it reads were completed at least two barriers ago
-        {
-            const int nP = P == NTAP - 1 ? 0 : P + 1;
-            const int nA = 2 * nP, nB = 2 * nP + 1;
-            const int nbufA = nA >= NTAP, ntA = nA - NTAP * nbufA, nbufB = nB >= NTAP, ntB = nB - NTAP * nbufB;
-            const int noffA = nbufA * XB + ((ntA / KS) * XC + ntA % KS) * 16, noffB = nbufB * XB + ((ntB / KS) * XC + ntB % KS) * 16;
-            read_b(0, blane + (sel ? noffB : noffA), 0);
-            CWFA_FENCE();
+        if constexpr (!MIDSTEP) read_b_next();       // (boundary barrier: requested in front of it)
+        if constexpr (!MIDSTEP) {
+            // boundary barrier: the next slice (the youngest vector-memory operation of the step) has landed; LDS: everything but the
+            // B-fragment reads just issued is done, the staging stores of this step included
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(NQ) : "memory");
+            __builtin_amdgcn_s_barrier();
         }
-        // the next slice (the youngest vector-memory operation of the step) has landed
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        // (LDS: everything but the three B-fragment reads just issued is done, the staging stores of this step included)
-        if constexpr (SIX) asm volatile("s_waitcnt lgkmcnt(3)" ::: "memory");
-        else asm volatile("s_waitcnt lgkmcnt(1)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
         sl ^= 1;
         if (++P == NTAP) {
             P = 0;
@@ -439,7 +510,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
         }
         if (cp.logdet) {                                  // block sum -> one float64 atomic per block
             const double ws = cwfa_wave_sum((double)ssum);
-            double* red = reinterpret_cast<double*>(lds);  // the operand buffers are dead (every wave passed the loop's last barrier)
+            double* red = reinterpret_cast<double*>(lds);  // the operand buffers are dead once every wave has passed this barrier
             __builtin_amdgcn_s_barrier();
             if (lane == 0) red[wave] = ws;
             __syncthreads();
@@ -533,6 +604,10 @@ __global__ __launch_bounds__(512, 1) void conv3x3_split_kernel(SParams p) {
         }
         if constexpr (ACT1 != EPI_RUNTIME) {
             if (want_stats) {
+                // MIDSTEP: the loop's last barrier sits in the MIDDLE of the last step, so the other waves may still be reading B
+                // fragments of its second half out of the buffer `red` overlays: one more barrier in front of the first write to it
+                // (uniform: want_stats is a kernel argument, mt a compile-time index)
+                if (MIDSTEP && mt == 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float a1 = cwfa_row16_sum(st1[r]), a2 = cwfa_row16_sum(st2[r]);
