@@ -828,13 +828,23 @@ class ActivityMap:
     or ``XLFMDeconv``), so the series never has to be resident: mean, unbiased std, maximum and minimum over time.  ``finish``'s
     mean and std are bit for bit ``ops.stack_mean_std`` of the whole series, for any chunking (the same float64 additions per voxel in
     the same order).  The state costs 28 bytes per voxel -- the first sample, two float64 sums, maximum, minimum: about 700 MB at
-    96 x 512 x 512."""
+    96 x 512 x 512.
 
-    def __init__(self, shape, device):
+    ``neighbours`` = 6 (faces), 8 (the in-plane ring) or 26 (the cube) also accumulates the pair sums of the local correlation
+    image: ``finish("corr")`` then scores a voxel by the mean correlation of its series with its neighbours',
+    which tells a neuron (its voxels move together) from a voxel that merely fluctuates (a hot pixel, shot noise on a bright
+    structure).  That adds one float64 per forward offset, K = 3, 4 or 13: the state costs 28 + 8 K bytes per voxel, 3.3 GB at
+    96 x 512 x 512 for 26 neighbours.  ``neighbours=0``: no pair sums, the state and the launches above."""
+
+    def __init__(self, shape, device, neighbours=0):
         self.shape = tuple(int(s) for s in shape)
         if len(self.shape) != 3 or min(self.shape) < 0:
             raise ValueError(f"ActivityMap: shape is (D, H, W), got {shape!r}")
+        if neighbours not in (0, 6, 8, 26):
+            raise ValueError(f"ActivityMap: neighbours is 0, 6, 8 or 26, got {neighbours!r}")
+        self.neighbours = neighbours
         self.state = ops.activity_state(self.shape, device)
+        self.cc = ops.correlation_state(self.shape, device, neighbours) if neighbours else None
         self.count = 0
 
     def update(self, volumes):
@@ -845,28 +855,38 @@ class ActivityMap:
         if volumes.dim() != 4 or tuple(volumes.shape[1:]) != self.shape:
             raise ValueError(f"ActivityMap.update: volumes of shape {self.shape} are expected, got {tuple(volumes.shape)}")
         if volumes.shape[0]:
-            ops.activity_update(volumes, self.state, first=self.count == 0)
+            if self.neighbours:
+                ops.activity_update_corr(volumes, self.state, self.cc, self.neighbours, first=self.count == 0)
+            else:
+                ops.activity_update(volumes, self.state, first=self.count == 0)
             self.count += volumes.shape[0]
         return self
 
     def finish(self, kind="std"):
         """(score, mean, std, vmax, vmin), float32 [D,H,W].  ``kind`` chooses the score: "std", "range" = vmax - vmin, "peak" =
-        vmax - mean, "snr" = (vmax - mean) / std with 0 where std == 0.  The state is kept: more volumes may follow (vmax and vmin
-        are the state's own tensors, which a later ``update`` writes)."""
+        vmax - mean, "snr" = (vmax - mean) / std with 0 where std == 0, or "corr", the local correlation image over the object's
+        ``neighbours`` (in [-1, 1], 0 for a pair with a constant or non-finite series; needs ``neighbours != 0``).  The state is kept:
+        more volumes may follow (vmax and vmin are the state's own tensors, which a later ``update`` writes)."""
+        if kind == "corr" and not self.neighbours:
+            raise ValueError("ActivityMap.finish: kind 'corr' needs an ActivityMap(neighbours=6, 8 or 26)")
         if self.count < 1:
             raise ValueError("ActivityMap.finish: no volume has been added")
-        score, mean, std = ops.activity_finish(self.state, self.count, kind)
+        score, mean, std = ops.activity_finish(self.state, self.count, "std" if kind == "corr" else kind)
+        if kind == "corr":
+            score = ops.correlation_finish(self.state, self.cc, self.count, self.neighbours)
         return score, mean, std, self.state[3], self.state[4]
 
 
-def find_neurons(score, r12=5, r3=3, n_max=None, thr=None, rel_thr=0.1, start_plane_offset=-25 // 2, margin=None, dist=None):
+def find_neurons(score, r12=5, r3=3, n_max=None, thr=None, rel_thr=0.1, start_plane_offset=-25 // 2, margin=None, dist=None, kind="std"):
     """Neuron positions as the 3-D local maxima of an activity map: ``(coords, scores)``.
 
-    ``score``: a float32 device map [D,H,W], or an ``ActivityMap`` (finished with ``kind="std"``).  A voxel is kept when it is at
+    ``score``: a float32 device map [D,H,W], or an ``ActivityMap``, which is finished with ``kind`` (used in that case only; "corr"
+    for the local correlation image of an ``ActivityMap(neighbours=...)``).  A voxel is kept when it is at
     least ``thr`` (default ``rel_thr`` times the map's maximum), at least ``margin`` (default ``(r3, r12, r12)``) from every face and
     the maximum of the box of half-widths ``dist`` (default ``(2 r3 - 1, 2 r12 - 1, 2 r12 - 1)``) around it, ties going to the
     lowest linear index (``ops.local_maxima``); the ``n_max`` highest are returned, by descending score.  With the default ``dist`` two
-    detections differ by at least 2 r on one axis, so their ROIs [c - r, c + r) are disjoint.
+    detections differ by at least 2 r on one axis, so their ROIs [c - r, c + r) are disjoint.  On a correlation map ``rel_thr`` is
+    relative to a maximum near 1 whatever the recording, so an absolute ``thr`` (0.5, say) is the natural argument there.
 
     ``coords`` is a list of ``[x, y, z - (D // 2 + start_plane_offset)]`` (x indexes W, y indexes H): the convention of the
     reference's coordinates file, which ``roi_boxes(coords, shape, r12, r3, start_plane_offset)``, ``corr_coeff_3D`` and
@@ -880,7 +900,7 @@ def find_neurons(score, r12=5, r3=3, n_max=None, thr=None, rel_thr=0.1, start_pl
     if thr is None and not 0.0 <= float(rel_thr) <= 1.0:
         raise ValueError(f"find_neurons: rel_thr = {rel_thr} is not in [0, 1]")
     if isinstance(score, ActivityMap):
-        score = score.finish("std")[0]
+        score = score.finish(kind)[0]
     ops._dev(score, "score")
     if score.dim() != 3:
         raise ValueError(f"find_neurons: a [D,H,W] map is expected, got {tuple(score.shape)}")

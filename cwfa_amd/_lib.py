@@ -85,7 +85,8 @@ DECONV_ACCEL_UNITS = 1024          # CWFA_DECONV_ACCEL_UNITS
 DECONV_UPDATE_UNITS = 256          # CWFA_DECONV_UPDATE_UNITS
 DECONV_NLL_WORKSPACE_BYTES = 8192  # CWFA_DECONV_NLL_WORKSPACE_BYTES
 ACTIVITY_KIND = {"std": 0, "range": 1, "peak": 2, "snr": 3}                     # CWFA_ACTIVITY_*
-NMAX_MAX_DIST = 16                 # CWFA_NMAX_MAX_DIST
+CORR_FORWARD = {6: 3, 8: 4, 26: 13}                                            # CWFA_CORR_*: neighbours -> forward offsets K
+NMAX_MAX_DIST = 16                # CWFA_NMAX_MAX_DIST
 SELECT_FORM = {"auto": 0, "lds": 1, "stream": 2}                                # cwfa_temporal_select's `form`
 
 # name -> (restype, argtypes); must list EVERY function declared in include/cwfa_hip.h (tests/test_boundary.py checks)
@@ -207,6 +208,8 @@ SIGNATURES = {
     "cwfa_activity_update_f32": (i, [p, p, p, p, p, p, i, i64, i64, i, p]),
     "cwfa_activity_finish_f32": (i, [p, p, p, p, p, i64, i, p, p, p, i64, p]),
     "cwfa_local_maxima_f32": (i, [p, i, i, i, f, i, i, i, i, i, i, p, p, i64, p, p]),
+    "cwfa_activity_update_corr_f32": (i, [p, p, p, p, p, p, p, i, i, i, i, i64, i, i, p]),
+    "cwfa_activity_corr_finish_f32": (i, [p, p, p, i64, i, i, i, i, p, p]),
     "cwfa_rand_poisson_f32": (i, [p, p, i, i64, i64, i64, p, p, C.c_uint64, C.c_uint32, C.c_uint32, p]),
     "cwfa_temporal_select": (i, [p, i, i, i64, i64, p, p, C.POINTER(C.c_int), i, p, i, p]),
     "cwfa_temporal_select_lds_frames": (i, [i, i]),

@@ -135,6 +135,248 @@ extern "C" int cwfa_activity_finish_f32(const float* x0, const double* s1, const
     return CWFA_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ streaming local correlation
+// DESIGN.md section 25.  Beside the state above, cc[k][i] = sum over the samples after the first of d_i * d_j, j = i + o_k, for the K
+// forward offsets o_k of the neighbourhood: the lexicographically positive half of its (dz, dy, dx), in lexicographic order.  They lie
+// in at most five rows of the volume, numbered 0: the voxel's own, 1: y + 1, 2 .. 4: plane z + 1 at y - 1, y, y + 1.
+template <int NB>
+struct CorrNb {
+    static constexpr int K = NB == CWFA_CORR_6 ? 3 : NB == CWFA_CORR_8 ? 4 : 13;
+    static constexpr int row(int k) { return k == 0 ? 0 : NB == CWFA_CORR_6 ? (k == 1 ? 1 : 3) : 1 + (k - 1) / 3; }
+    static constexpr int dx(int k) { return k == 0 ? 1 : NB == CWFA_CORR_6 ? 0 : (k - 1) % 3 - 1; }
+    static constexpr bool uses(int r) { return r <= 1 || NB == CWFA_CORR_26 || (NB == CWFA_CORR_6 && r == 3); }
+    static constexpr bool left(int r) { return NB != CWFA_CORR_6 && r != 0; }   // the row is read at x - 1 ..
+    static constexpr bool right(int r) { return NB != CWFA_CORR_6 || r == 0; }  // .. and at x + V
+};
+
+// A thread owns V voxels of one row (W % V == 0) and keeps, per row it reads, the window x - 1 .. x + V (columns 0 .. V + 1 of w).
+// A neighbour's d is formed from its x and x0 as its owner forms it.  In the first chunk every x0 comes from x[0]: the x0 array is
+// being written by this launch.  A pair whose neighbour is outside the volume is never added to, so its cc stays the 0.0 of the
+// first chunk; its loads are pointed at the thread's own row instead, so that no load stands behind a branch (hipcc puts a wait
+// for the load into each such branch, which costs a memory round trip per row and time step).  The grid walks the volume in linear
+// order: the rows y + 1 and z + 1 are read by blocks that run at about the same time, so the windows come from L1 / L2 / the
+// Infinity Cache.
+template <int NB, int V>
+__global__ __launch_bounds__(256) void activity_update_corr_kernel(const float* __restrict__ x, float* __restrict__ x0p, double* __restrict__ s1p,
+                                                                   double* __restrict__ s2p, float* __restrict__ vmaxp, float* __restrict__ vminp,
+                                                                   double* __restrict__ ccp, int T, int D, int H, int W, int64_t ss, int first) {
+    typedef float vec __attribute__((ext_vector_type(V)));
+    typedef CorrNb<NB> N;
+    constexpr int K = N::K;
+    const int64_t hw = (int64_t)H * W, m = hw * D, gw = W / V, groups = m / V;
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t line = g / gw;
+        const int xg = (int)(g - line * gw) * V, y = (int)(line % H), z = (int)(line / H);
+        const int64_t e = g * V;
+        const bool below = z + 1 < D;
+        const bool rv[5] = {true, y + 1 < H, below && y > 0, below, below && y + 1 < H};
+        const int64_t ro[5] = {0, rv[1] ? W : 0, rv[2] ? hw - W : 0, rv[3] ? hw : 0, rv[4] ? hw + W : 0};
+        const bool lv = xg > 0, rx = xg + V < W;
+        const int lo = lv ? -1 : 0, hi = rx ? V : V - 1;
+        // the windows of one volume q (at this thread's first voxel): every address is inside the volume
+        auto window = [&](const float* q, float (&w)[5][V + 2]) {
+#pragma unroll
+            for (int r = 0; r < 5; ++r) {
+                if (!N::uses(r)) continue;
+                const vec t = *reinterpret_cast<const vec*>(q + ro[r]);
+#pragma unroll
+                for (int j = 0; j < V; ++j) w[r][1 + j] = t[j];
+                if (N::left(r)) w[r][0] = q[ro[r] + lo];
+                if (N::right(r)) w[r][V + 1] = q[ro[r] + hi];
+            }
+        };
+        const float* p = x + e;
+        float b[5][V + 2] = {};
+        window(first ? p : x0p + e, b);
+        vec mx, mn;
+        double s1[V], s2[V], cc[K][V];
+        if (first) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                mx[j] = mn[j] = b[0][1 + j];
+                s1[j] = s2[j] = 0.0;
+#pragma unroll
+                for (int k = 0; k < K; ++k) cc[k][j] = 0.0;
+            }
+        } else {
+            mx = *reinterpret_cast<const vec*>(vmaxp + e);
+            mn = *reinterpret_cast<const vec*>(vminp + e);
+            if constexpr (V == 1) {
+                s1[0] = s1p[e], s2[0] = s2p[e];
+#pragma unroll
+                for (int k = 0; k < K; ++k) cc[k][0] = ccp[k * m + e];
+            } else {
+#pragma unroll
+                for (int h = 0; h < V / 2; ++h) {
+                    const f64x2 a = *reinterpret_cast<const f64x2*>(s1p + e + 2 * h), c = *reinterpret_cast<const f64x2*>(s2p + e + 2 * h);
+                    s1[2 * h] = a[0], s1[2 * h + 1] = a[1], s2[2 * h] = c[0], s2[2 * h + 1] = c[1];
+#pragma unroll
+                    for (int k = 0; k < K; ++k) {
+                        const f64x2 u = *reinterpret_cast<const f64x2*>(ccp + k * m + e + 2 * h);
+                        cc[k][2 * h] = u[0], cc[k][2 * h + 1] = u[1];
+                    }
+                }
+            }
+        }
+#pragma unroll 1
+        for (int s = first ? 1 : 0; s < T; ++s) {
+            float w[5][V + 2] = {};
+            window(p + s * ss, w);
+            double d[5][V + 2];
+#pragma unroll
+            for (int r = 0; r < 5; ++r)
+#pragma unroll
+                for (int c = 0; c < V + 2; ++c) d[r][c] = (double)w[r][c] - (double)b[r][c];
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const float v = w[0][1 + j];
+                const double di = d[0][1 + j];
+                s1[j] += di;
+                s2[j] += di * di;
+                mx[j] = (v > mx[j] || v != v) ? v : mx[j];
+                mn[j] = (v < mn[j] || v != v) ? v : mn[j];
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const int r = N::row(k), c = 1 + j + N::dx(k);
+                    const bool in = rv[r] && (c == 0 ? lv : c == V + 1 ? rx : true);
+                    const double sum = cc[k][j] + di * d[r][c];
+                    cc[k][j] = in ? sum : cc[k][j];
+                }
+            }
+        }
+        if (first) {
+            vec x0;
+#pragma unroll
+            for (int j = 0; j < V; ++j) x0[j] = b[0][1 + j];
+            *reinterpret_cast<vec*>(x0p + e) = x0;
+        }
+        *reinterpret_cast<vec*>(vmaxp + e) = mx;
+        *reinterpret_cast<vec*>(vminp + e) = mn;
+        if constexpr (V == 1) {
+            s1p[e] = s1[0], s2p[e] = s2[0];
+#pragma unroll
+            for (int k = 0; k < K; ++k) ccp[k * m + e] = cc[k][0];
+        } else {
+#pragma unroll
+            for (int h = 0; h < V / 2; ++h) {
+                *reinterpret_cast<f64x2*>(s1p + e + 2 * h) = f64x2{s1[2 * h], s1[2 * h + 1]};
+                *reinterpret_cast<f64x2*>(s2p + e + 2 * h) = f64x2{s2[2 * h], s2[2 * h + 1]};
+#pragma unroll
+                for (int k = 0; k < K; ++k) *reinterpret_cast<f64x2*>(ccp + k * m + e + 2 * h) = f64x2{cc[k][2 * h], cc[k][2 * h + 1]};
+            }
+        }
+    }
+}
+
+static inline bool corr_known(int neighbours) { return neighbours == CWFA_CORR_6 || neighbours == CWFA_CORR_8 || neighbours == CWFA_CORR_26; }
+
+// D * H * W without overflow (each factor is below 2^31), -1 where it does not fit 2^40 voxels
+static inline int64_t corr_voxels(int D, int H, int W) {
+    const int64_t hw = (int64_t)H * W;
+    if (D == 0 || hw == 0) return 0;
+    return hw > ((int64_t)1 << 40) || D > ((int64_t)1 << 40) / hw ? -1 : hw * D;
+}
+
+template <int NB>
+static void corr_update_launch(bool v4, hipStream_t st, const float* x, float* x0, double* s1, double* s2, float* vmax, float* vmin, double* cc,
+                               int T, int D, int H, int W, int64_t m, int64_t ss, int first) {
+    // voxels per thread on the vector path: the (2 + K) float64 sums per voxel are 10 .. 30 registers
+    constexpr int V = NB == CWFA_CORR_26 ? 2 : 4;
+    if (v4)
+        hipLaunchKernelGGL((activity_update_corr_kernel<NB, V>), dim3(neuron_blocks(m / V, 256, 8192)), dim3(256), 0, st, x, x0, s1, s2, vmax, vmin,
+                           cc, T, D, H, W, ss, first);
+    else
+        hipLaunchKernelGGL((activity_update_corr_kernel<NB, 1>), dim3(neuron_blocks(m, 256, 8192)), dim3(256), 0, st, x, x0, s1, s2, vmax, vmin, cc,
+                           T, D, H, W, ss, first);
+}
+
+extern "C" int cwfa_activity_update_corr_f32(const float* x, float* x0, double* s1, double* s2, float* vmax, float* vmin, double* cc, int T,
+                                             int D, int H, int W, int64_t x_ss, int neighbours, int first, void* stream) {
+    CWFA_REQUIRE(x && x0 && s1 && s2 && vmax && vmin && cc, CWFA_E_INVAL, "cwfa_activity_update_corr_f32: null pointer");
+    CWFA_REQUIRE(T >= 0 && D >= 0 && H >= 0 && W >= 0, CWFA_E_SHAPE, "cwfa_activity_update_corr_f32: negative size");
+    const int64_t m = corr_voxels(D, H, W);
+    CWFA_REQUIRE(m >= 0, CWFA_E_SHAPE, "cwfa_activity_update_corr_f32: %d x %d x %d voxels are more than 2^40", D, H, W);
+    CWFA_REQUIRE(corr_known(neighbours), CWFA_E_INVAL, "cwfa_activity_update_corr_f32: neighbours is 6, 8 or 26, got %d", neighbours);
+    CWFA_REQUIRE(first == 0 || first == 1, CWFA_E_INVAL, "cwfa_activity_update_corr_f32: first is 0 or 1");
+    CWFA_REQUIRE(!first || T >= 1, CWFA_E_SHAPE, "cwfa_activity_update_corr_f32: the first chunk needs at least one volume");
+    CWFA_REQUIRE(T <= 1 || x_ss >= m, CWFA_E_INVAL, "cwfa_activity_update_corr_f32: time stride smaller than a volume");
+    CWFA_REQUIRE(((reinterpret_cast<uintptr_t>(s1) | reinterpret_cast<uintptr_t>(s2) | reinterpret_cast<uintptr_t>(cc)) & 7u) == 0, CWFA_E_ALIGN,
+                 "cwfa_activity_update_corr_f32: the float64 sums must be 8-byte aligned");
+    if (m == 0 || T == 0) return CWFA_OK;
+    hipStream_t st = (hipStream_t)stream;
+    // the vector path of cwfa_activity_update_f32, with whole groups inside a row: W, not only D * H * W, is a multiple of 4
+    const bool v4 = (W & 3) == 0 && (T == 1 || (x_ss & 3) == 0) && cwfa_aligned16(x) && cwfa_aligned16(x0) && cwfa_aligned16(s1) &&
+                    cwfa_aligned16(s2) && cwfa_aligned16(vmax) && cwfa_aligned16(vmin) && cwfa_aligned16(cc);
+    if (neighbours == CWFA_CORR_6)
+        corr_update_launch<CWFA_CORR_6>(v4, st, x, x0, s1, s2, vmax, vmin, cc, T, D, H, W, m, x_ss, first);
+    else if (neighbours == CWFA_CORR_8)
+        corr_update_launch<CWFA_CORR_8>(v4, st, x, x0, s1, s2, vmax, vmin, cc, T, D, H, W, m, x_ss, first);
+    else
+        corr_update_launch<CWFA_CORR_26>(v4, st, x, x0, s1, s2, vmax, vmin, cc, T, D, H, W, m, x_ss, first);
+    CWFA_LAUNCH_CHECK("cwfa_activity_update_corr_f32");
+    return CWFA_OK;
+}
+
+// score_i = (float)(sum of r_ij / n_i) over the in-volume offsets of the whole neighbourhood in lexicographic order: the negatives of
+// the forward offsets from the last to the first (the pair's cc is kept at the lower voxel j = i - o_k), then the forward ones.
+// r = cov / sqrt(v_i v_j) where that is above 0, else 0: a constant voxel, NaN or inf in a series and N = 1 all give 0, never NaN.
+template <int NB>
+__global__ __launch_bounds__(256) void activity_corr_finish_kernel(const double* __restrict__ s1, const double* __restrict__ s2,
+                                                                   const double* __restrict__ cc, double N, int D, int H, int W,
+                                                                   float* __restrict__ score) {
+    typedef CorrNb<NB> C;
+    constexpr int K = C::K;
+    const int64_t hw = (int64_t)H * W, m = hw * D;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t line = i / W;
+        const int xx = (int)(i - line * W), y = (int)(line % H), z = (int)(line / H);
+        const double a = s1[i];
+        double vi = s2[i] - a * a / N;
+        vi = vi < 0.0 ? 0.0 : vi;
+        double sum = 0.0;
+        int n = 0;
+#pragma unroll
+        for (int q = 0; q < 2 * K; ++q) {
+            const int k = q < K ? K - 1 - q : q - K, sg = q < K ? -1 : 1;
+            const int r = C::row(k);
+            const int dz = sg * (r >= 2), dy = sg * (r == 0 ? 0 : r == 1 ? 1 : r - 3), dx = sg * C::dx(k);
+            const int zz = z + dz, yy = y + dy, xj = xx + dx;
+            if (zz < 0 || zz >= D || yy < 0 || yy >= H || xj < 0 || xj >= W) continue;
+            const int64_t j = i + dz * hw + (int64_t)dy * W + dx;
+            const double c = cc[k * m + (sg < 0 ? j : i)], aj = s1[j];
+            double vj = s2[j] - aj * aj / N;
+            vj = vj < 0.0 ? 0.0 : vj;
+            const double cov = c - a * aj / N, den = sqrt(vi * vj);
+            sum += den > 0.0 ? cov / den : 0.0;
+            ++n;
+        }
+        score[i] = n ? (float)(sum / n) : 0.f;
+    }
+}
+
+extern "C" int cwfa_activity_corr_finish_f32(const double* s1, const double* s2, const double* cc, int64_t N, int D, int H, int W,
+                                             int neighbours, float* score, void* stream) {
+    CWFA_REQUIRE(s1 && s2 && cc && score, CWFA_E_INVAL, "cwfa_activity_corr_finish_f32: null pointer");
+    CWFA_REQUIRE(corr_known(neighbours), CWFA_E_INVAL, "cwfa_activity_corr_finish_f32: neighbours is 6, 8 or 26, got %d", neighbours);
+    CWFA_REQUIRE(N >= 1 && N <= 0x7fffffff && D >= 0 && H >= 0 && W >= 0, CWFA_E_SHAPE,
+                 "cwfa_activity_corr_finish_f32: needs at least one sample (fewer than 2^31) and non-negative sizes");
+    const int64_t m = corr_voxels(D, H, W);
+    CWFA_REQUIRE(m >= 0, CWFA_E_SHAPE, "cwfa_activity_corr_finish_f32: %d x %d x %d voxels are more than 2^40", D, H, W);
+    CWFA_REQUIRE(((reinterpret_cast<uintptr_t>(s1) | reinterpret_cast<uintptr_t>(s2) | reinterpret_cast<uintptr_t>(cc)) & 7u) == 0, CWFA_E_ALIGN,
+                 "cwfa_activity_corr_finish_f32: the float64 sums must be 8-byte aligned");
+    if (m == 0) return CWFA_OK;
+    const dim3 grid(neuron_blocks(m, 256, 16384));
+    hipStream_t st = (hipStream_t)stream;
+    if (neighbours == CWFA_CORR_6)
+        hipLaunchKernelGGL(activity_corr_finish_kernel<CWFA_CORR_6>, grid, dim3(256), 0, st, s1, s2, cc, (double)N, D, H, W, score);
+    else if (neighbours == CWFA_CORR_8)
+        hipLaunchKernelGGL(activity_corr_finish_kernel<CWFA_CORR_8>, grid, dim3(256), 0, st, s1, s2, cc, (double)N, D, H, W, score);
+    else
+        hipLaunchKernelGGL(activity_corr_finish_kernel<CWFA_CORR_26>, grid, dim3(256), 0, st, s1, s2, cc, (double)N, D, H, W, score);
+    CWFA_LAUNCH_CHECK("cwfa_activity_corr_finish_f32");
+    return CWFA_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ 3-D local maxima
 // key(v) = ord(S[v]) << 32 | (0xFFFFFFFF - lin(v)): a total order on the voxels, ties on the value going to the lower linear index.
 // ord: the order-preserving unsigned image of the fp32 bits after S + 0.0f (-0 and +0 are one value), NaN -> 0.  Outside the volume

@@ -2428,6 +2428,66 @@ def activity_finish(state, count, kind="std"):
     return score, mean, std
 
 
+def _corr(state, cc, neighbours, what):
+    if neighbours not in _lib.CORR_FORWARD:
+        raise ValueError(f"{what}: neighbours is one of {sorted(_lib.CORR_FORWARD)}, got {neighbours!r}")
+    m = _activity(state, what)
+    if state[0].dim() != 3:
+        raise ValueError(f"{what}: the state of [D,H,W] volumes is expected, got {tuple(state[0].shape)}")
+    if (not torch.is_tensor(cc) or not cc.is_cuda or cc.dtype != torch.float64 or not cc.is_contiguous()
+            or tuple(cc.shape) != (_lib.CORR_FORWARD[neighbours], *state[0].shape)):
+        raise ValueError(f"{what}: cc is a contiguous float64 tensor [{_lib.CORR_FORWARD[neighbours]}, D, H, W] on the HIP device "
+                         f"(ops.correlation_state)")
+    return m
+
+
+def correlation_state(shape, device, neighbours):
+    """The pair sums of a streaming local-correlation map for [D,H,W] volumes of ``shape``: float64 [K,D,H,W], K = 3, 4 or 13 forward
+    offsets for ``neighbours`` = 6 (faces), 8 (the in-plane ring) or 26 (the cube); 8 K bytes per voxel beside the 28 of
+    ``activity_state``, uninitialised -- the first ``activity_update_corr`` (``first=True``) writes all of it."""
+    if neighbours not in _lib.CORR_FORWARD:
+        raise ValueError(f"correlation_state: neighbours is one of {sorted(_lib.CORR_FORWARD)}, got {neighbours!r}")
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 3 or min(shape) < 0:
+        raise ValueError(f"correlation_state: shape is (D, H, W), got {shape!r}")
+    return torch.empty((_lib.CORR_FORWARD[neighbours], *shape), dtype=torch.float64, device=device)
+
+
+def activity_update_corr(x, state, cc, neighbours, first):
+    """``activity_update`` of the chunk ``x`` [T',D,H,W] -- ``state`` comes out bit for bit as that writes it -- which in the same read
+    of the chunk adds, per voxel i and forward offset o_k of ``neighbours``, d_i(t) d_j(t) (j = i + o_k, d = x - x0 in float64) to
+    ``cc`` (``correlation_state``) in time order; 0.0 where j is outside the volume.  Any chunking gives the same bits."""
+    L = _lib.lib()
+    _dev(x, "x")
+    m = _corr(state, cc, neighbours, "activity_update_corr")
+    if x.dim() != 4 or tuple(x.shape[1:]) != tuple(state[0].shape):
+        raise ValueError(f"activity_update_corr: a chunk [T', {', '.join(str(s) for s in state[0].shape)}] is expected, "
+                         f"got {tuple(x.shape)}")
+    T = x.shape[0]
+    if first and T < 1:
+        raise ValueError("activity_update_corr: the first chunk needs at least one volume")
+    if T and m and (not x[0].is_contiguous() or (T > 1 and x.stride(0) < m)):
+        x = x.contiguous()
+    ss = x.stride(0) if T > 1 else m
+    check(L.cwfa_activity_update_corr_f32(_p(x), *(_p(t) for t in state), _p(cc), T, *state[0].shape, ss, int(neighbours), int(bool(first)),
+                                          _stream()), "activity_update_corr")
+    return state, cc
+
+
+def correlation_finish(state, cc, count, neighbours):
+    """The local-correlation map, float32 [D,H,W], after ``count`` samples: per voxel the mean over its in-volume neighbours of the
+    Pearson correlation of the two series, evaluated in float64 from ``state`` and ``cc``; a pair with a constant series, or one
+    holding NaN or inf, counts with 0, so the map holds no NaN and lies in [-1, 1] up to rounding.  The state is only read."""
+    L = _lib.lib()
+    _corr(state, cc, neighbours, "correlation_finish")
+    if int(count) < 1:
+        raise ValueError("correlation_finish: needs at least one sample")
+    score = torch.empty_like(state[0])
+    check(L.cwfa_activity_corr_finish_f32(_p(state[1]), _p(state[2]), _p(cc), int(count), *state[0].shape, int(neighbours), _p(score),
+                                          _stream()), "correlation_finish")
+    return score
+
+
 def _triple(v, name, what):
     try:
         t = tuple(int(a) for a in v)

@@ -895,6 +895,33 @@ int cwfa_activity_finish_f32(const float* x0, const double* s1, const double* s2
 int cwfa_local_maxima_f32(const float* score, int D, int H, int W, float thr, int dz, int dy, int dx, int mz, int my, int mx,
                           void* workspace, void* out, int64_t capacity, int64_t* count, void* stream);
 
+/* ---- streaming local correlation: a neighbour-aware score for the detector above.  A neuron's voxels move
+ * together, noise does not: the score of a voxel is the mean Pearson correlation of its series with its neighbours'.
+ *
+ * `neighbours` selects the offsets (dz, dy, dx): CORR_6 the faces, CORR_8 the in-plane ring (dz = 0), CORR_26 the cube.  The forward
+ * offsets o_0 .. o_{K-1} are the lexicographically positive half in lexicographic order, K = 3, 4, 13: (0,0,1), then the dz = 0,
+ * dy = 1 ones, then the dz = 1 ones.
+ *
+ *   activity_update_corr: everything activity_update does on volumes [D, H, W] (m = D * H * W; x0, s1, s2, vmax, vmin come out bit
+ *                    for bit what that entry point writes), and in the same read of the chunk
+ *                        cc[k][i] += d_i(t) * d_j(t),  j = i + o_k,  d = (double)x - (double)x0,
+ *                    in time order from 0.0, over the samples after the first; cc is float64 [K, D, H, W], 8 K bytes per voxel.
+ *                    The neighbour is taken by coordinates; where it is outside the volume cc[k][i] is 0.0.  d_j is formed from x_j
+ *                    and x0_j exactly as the owner of j forms it (in the first chunk x0 is read from x[0]).  Every thread writes its
+ *                    own voxels' state only: no atomics, any chunking gives the same bits.  16-byte accesses where W % 4 == 0,
+ *                    x_ss % 4 == 0 and every pointer allow, element by element otherwise.  T == 0 (first == 0) or m == 0: no launch.
+ *   activity_corr_finish: score[m] (fp32) from the state of N samples, in float64 per pair (i, j):
+ *                        v_i = max(s2_i - s1_i * s1_i / N, 0),  cov = c - s1_i * s1_j / N,  den = sqrt(v_i * v_j),
+ *                        r = den > 0 ? cov / den : 0            (c: cc[k] at the lower voxel of the pair)
+ *                    score_i = (float)(sum of r / n_i) over the n_i in-volume offsets of the whole neighbourhood in lexicographic
+ *                    order, 0 where n_i == 0.  A constant voxel, NaN or inf in a series and N == 1 give r = 0: never NaN.  The
+ *                    state is only read. */
+enum { CWFA_CORR_6 = 6, CWFA_CORR_8 = 8, CWFA_CORR_26 = 26 };
+int cwfa_activity_update_corr_f32(const float* x, float* x0, double* s1, double* s2, float* vmax, float* vmin, double* cc, int T, int D,
+                                  int H, int W, int64_t x_ss, int neighbours, int first, void* stream);
+int cwfa_activity_corr_finish_f32(const double* s1, const double* s2, const double* cc, int64_t N, int D, int H, int W, int neighbours,
+                                  float* score, void* stream);
+
 /* ---- shot noise: a Poisson draw per element, in one launch, nothing read back.
  *   out[s][e] = fl32(fl32(k) * post[s]),   k ~ Poisson(rate),   rate = fl32(lam[s * lam_ss + e] * pre[s])
  * for s < N, e < n.  pre / post: nullable DEVICE float [N], NULL means 1.  lam_ss = 0: all N samples draw from one rate plane;
