@@ -12,7 +12,7 @@ from . import ops
 from .amp import amp_function, amp_region
 
 __all__ = ["XLFMDatasetFull", "ConcatDataset", "extract_views", "pad_img_to_min", "center_crop", "prepare_frames", "shot_noise_scales", "add_random_shot_noise_to_datasets",
-           "extract_sparse", "SparseSplit", "quantile_rank"]
+           "extract_sparse", "SparseSplit", "quantile_rank", "estimate_shifts", "shift_frames", "register_frames", "valid_window", "Registration"]
 
 
 def extract_views(image, lenslet_coords, subimage_shape, debug=False):
@@ -111,6 +111,143 @@ def extract_sparse(frames, baseline_q=0.5, noise_k=0.0, ths=0.0, scale="ls", pai
     return SparseSplit(sparse, baseline, scales, tau)
 
 
+Registration = namedtuple("Registration", ["frames", "shifts", "peak", "template"])
+
+
+def taper_window(n, taper):
+    """The raised-cosine edge taper of ``n`` samples as a float32 CPU tensor: 0.5 - 0.5 cos(pi (i + 0.5) / taper) on the first and
+    (mirrored) the last ``taper`` samples, 1 between; formed in float64 and rounded once."""
+    w = torch.ones(n, dtype=torch.float64)
+    if taper:
+        edge = 0.5 - 0.5 * torch.cos(math.pi * (torch.arange(taper, dtype=torch.float64) + 0.5) / taper)
+        w[:taper] = edge
+        w[n - taper:] = edge.flip(0)
+    return w.to(torch.float32)
+
+
+def _reg_args(frames, template, max_shift, taper, smooth, eps, chunk, what):
+    """The checks of ``estimate_shifts`` that need no device: (my, mx, taper)."""
+    if not torch.is_tensor(frames) or frames.dim() != 3 or not frames.is_contiguous():
+        raise ValueError(f"{what}: a contiguous [N,H,W] stack is expected")
+    if frames.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"{what}: a float32 or float16 stack is expected, got {frames.dtype}")
+    H, W = int(frames.shape[1]), int(frames.shape[2])
+    if template is not None and (not torch.is_tensor(template) or tuple(template.shape) != (H, W) or template.dtype != torch.float32):
+        raise ValueError(f"{what}: the template is a float32 [{H}, {W}] tensor, the shape of a frame")
+    my, mx = ops._max_shift(max_shift, H, W, what)
+    taper = min(16, min(H, W) // 8) if taper is None else int(taper)
+    if taper < 0 or 2 * taper > min(H, W):
+        raise ValueError(f"{what}: taper = {taper} does not fit a {H} x {W} frame twice")
+    smooth, eps = float(smooth), float(eps)
+    if not 0.0 <= smooth < float("inf") or not 0.0 <= eps < float("inf"):
+        raise ValueError(f"{what}: smooth and eps are finite and not negative, got {smooth}, {eps}")
+    if int(chunk) < 1:
+        raise ValueError(f"{what}: chunk must be at least 1, got {chunk}")
+    return my, mx, taper
+
+
+@amp_region
+def estimate_shifts(frames, template, max_shift=16, taper=None, smooth=0.0, eps=1e-5, subpixel=True, chunk=16):
+    """(shifts float32 [N,2], peak float32 [N]) on the device: the rigid displacement (dy, dx) of every frame of a contiguous [N,H,W]
+    fp32 / fp16 device stack against the float32 ``template`` [H,W] by phase correlation.  A frame that is
+    the template displaced by d (frame[p] = template[p - d]) reports d; ``shift_frames`` undoes it.  ``peak`` is the correlation
+    value at the integer peak (1 for a perfect cyclic copy).  Nothing is read back.
+
+    Both get a raised-cosine edge taper of ``taper`` pixels (None: min(16, side / 8); 0: none); the spectra are whitened
+    separately, F / (|F| + ``eps``), multiplied, optionally low-passed by a Gaussian of ``smooth`` pixels, and transformed back;
+    the peak is searched over |dy| <= my, |dx| <= mx (``max_shift``: an int or (my, mx)) and, with ``subpixel``, refined by a
+    parabola per axis.  The frames go through in chunks of ``chunk`` (their spectra are chunk x H x (W/2+1) x 8 bytes)."""
+    my, mx, taper = _reg_args(frames, template, max_shift, taper, smooth, eps, chunk, "estimate_shifts")
+    if template is None:
+        raise ValueError("estimate_shifts: a template is needed")
+    N, H, W = (int(s) for s in frames.shape)
+    dev = frames.device
+    wy, wx = taper_window(H, taper).to(dev), taper_window(W, taper).to(dev)
+    T = torch.fft.rfft2(ops.reg_window(template.contiguous()[None], wy, wx)[0]).contiguous()
+    U = torch.view_as_real(ops.reg_whiten(T, None, eps, out=T))
+    if smooth > 0.0:
+        ky, kx = torch.fft.fftfreq(H, dtype=torch.float64), torch.fft.rfftfreq(W, dtype=torch.float64)
+        G = torch.exp(-2.0 * math.pi ** 2 * smooth ** 2 * (ky[:, None] ** 2 + kx[None, :] ** 2)).to(torch.float32).to(dev)
+        Wt = torch.stack((U[..., 0] * G, -U[..., 1] * G), dim=-1)
+    else:
+        Wt = torch.stack((U[..., 0], -U[..., 1]), dim=-1)
+    Wt[0, 0] = 0.0
+    Wt = torch.view_as_complex(Wt)
+    shifts = torch.empty((N, 2), dtype=torch.float32, device=dev)
+    ipeak = torch.empty((N, 2), dtype=torch.int32, device=dev)
+    peak = torch.empty((N,), dtype=torch.float32, device=dev)
+    chunk = min(int(chunk), max(N, 1))
+    buf = torch.empty((chunk, H, W), dtype=torch.float32, device=dev)
+    for s in range(0, N, chunk):
+        e = min(s + chunk, N)
+        F = torch.fft.rfft2(ops.reg_window(frames[s:e], wy, wx, out=buf[:e - s])).contiguous()  # (a no-op where rocFFT's layout is dense)
+        corr = torch.fft.irfft2(ops.reg_whiten(F, Wt, eps, out=F), s=(H, W))
+        ops.reg_peak(corr, (my, mx), subpixel, out=(shifts[s:e], ipeak[s:e], peak[s:e]))
+    return shifts, peak
+
+
+@amp_region
+def shift_frames(frames, shifts, mode="bilinear", fill=0.0, out=None):
+    """out[n,y,x] = frames[n, y + dy, x + dx] with (dy, dx) = shifts[n] (float32 [N,2] on the device, as ``estimate_shifts`` returns
+    them): bilinear, or ``mode="nearest"``; pixels from outside the frame are ``fill``.  An integer shift copies bits.  The result
+    has the dtype of ``frames``; ``out`` must not share memory with ``frames``."""
+    if not torch.is_tensor(frames) or frames.dim() != 3 or not frames.is_contiguous():
+        raise ValueError("shift_frames: a contiguous [N,H,W] stack is expected")
+    if mode not in ("bilinear", "nearest"):
+        raise ValueError(f"shift_frames: mode is 'bilinear' or 'nearest', got {mode!r}")
+    if not torch.is_tensor(shifts) or tuple(shifts.shape) != (int(frames.shape[0]), 2) or shifts.dtype != torch.float32:
+        raise ValueError(f"shift_frames: shifts is a float32 [{int(frames.shape[0])}, 2] tensor")
+    if out is not None and (out is frames or (torch.is_tensor(out) and ops._overlap(out, frames))):
+        raise ValueError("shift_frames: out must not alias frames")
+    return ops.reg_shift(frames, shifts, mode=mode, fill=fill, out=out)
+
+
+@amp_region
+def register_frames(frames, template=None, n_iter=1, max_shift=16, subpixel=True, mode="bilinear", taper=None, smooth=0.0, eps=1e-5,
+                    chunk=16, fill=0.0, out=None):
+    """Rigid registration of a contiguous [N,H,W] fp32 / fp16 device stack:
+    ``Registration(frames, shifts, peak, template)`` with frames[n] = the input's frame n moved back by shifts[n].  ``template``
+    None: the per-pixel temporal median of the stack.  ``n_iter`` > 1: the template becomes the median of the registered stack and
+    the shifts are estimated again FROM THE ORIGINAL FRAMES, so interpolation never compounds.  The other arguments are those of
+    ``estimate_shifts`` and ``shift_frames``.  Nothing is read back."""
+    _reg_args(frames, template, max_shift, taper, smooth, eps, chunk, "register_frames")
+    if int(n_iter) < 1:
+        raise ValueError(f"register_frames: n_iter must be at least 1, got {n_iter}")
+    if mode not in ("bilinear", "nearest"):
+        raise ValueError(f"register_frames: mode is 'bilinear' or 'nearest', got {mode!r}")
+    if out is not None and (out is frames or (torch.is_tensor(out) and ops._overlap(out, frames))):
+        raise ValueError("register_frames: out must not alias frames")
+    N = int(frames.shape[0])
+    if N < 1:
+        raise ValueError("register_frames: at least one frame is expected")
+    median = lambda x: ops.temporal_select(x, [quantile_rank(0.5, N)])[0]
+    tmpl = median(frames) if template is None else template
+    for it in range(int(n_iter)):
+        shifts, peak = estimate_shifts(frames, tmpl, max_shift=max_shift, taper=taper, smooth=smooth, eps=eps, subpixel=subpixel, chunk=chunk)
+        out = shift_frames(frames, shifts, mode=mode, fill=fill, out=out)
+        if it + 1 < int(n_iter):
+            tmpl = median(out)
+    return Registration(out, shifts, peak, tmpl)
+
+
+def valid_window(shifts, shape):
+    """(y0, y1, x0, x1): the box of a frame of ``shape`` (H, W) in which every frame registered with ``shifts`` [N,2] holds data
+    and no ``fill`` -- rows y0 .. y1 - 1, columns x0 .. x1 - 1 -- empty (all 0) where a shift is not finite or nothing is left.  A
+    host helper: it reads the shifts back."""
+    H, W = int(shape[0]), int(shape[1])
+    s = torch.as_tensor(shifts).detach().to("cpu", torch.float64).reshape(-1, 2)
+    if s.numel() == 0:
+        return 0, H, 0, W
+    if not bool(torch.isfinite(s).all()):
+        return 0, 0, 0, 0
+    lo, hi = torch.floor(s).amin(0), torch.ceil(s).amax(0)
+    y0, y1 = max(0, int(-lo[0])), min(H, H - int(hi[0]))
+    x0, x1 = max(0, int(-lo[1])), min(W, W - int(hi[1]))
+    if y1 <= y0 or x1 <= x0:
+        return 0, 0, 0, 0
+    return y0, y1, x0, x1
+
+
 def _scalar(v):
     """A float64 statistic as the 0-dim float32 CPU tensor the reference returns (rounded once)."""
     return torch.tensor(v, dtype=torch.float64).to(torch.float32)
@@ -164,6 +301,24 @@ class XLFMDatasetFull:
         if "out" not in kw and not kw.get("pair", False):
             kw["out"] = frames                                      # the prepared frames are ours: in place
         return cls(extract_sparse(frames, **kw).sparse, vols, ds_id)
+
+    @classmethod
+    def from_tensors_registered(cls, raw_frames, vols, img_shape, ds_id="", register=True, sparse=None):
+        """``from_tensors`` with rigid registration of the prepared frames BEFORE ``sparse``: ``register`` is True or a dict of
+        ``register_frames`` arguments (None / False: exactly ``from_tensors``).  The dataset carries the ``Registration`` (without
+        its frames) as ``registration``.  (``from_tensors`` keeps its signature: this is its registering form.)"""
+        if register is None or register is False:
+            return cls.from_tensors(raw_frames, vols, img_shape, ds_id, sparse)
+        reg = register_frames(prepare_frames(raw_frames, img_shape), **({} if register is True else dict(register)))
+        frames = reg.frames
+        if sparse is not None and sparse is not False:
+            kw = {} if sparse is True else dict(sparse)
+            if "out" not in kw and not kw.get("pair", False) and frames.dtype == torch.float32:
+                kw["out"] = frames                                  # the registered frames are ours: in place
+            frames = extract_sparse(frames, **kw).sparse
+        ds = cls(frames, vols, ds_id)
+        ds.registration = reg._replace(frames=None)
+        return ds
 
     def __len__(self):
         return int(self.stacked_views.shape[0])

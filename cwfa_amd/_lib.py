@@ -88,6 +88,7 @@ ACTIVITY_KIND = {"std": 0, "range": 1, "peak": 2, "snr": 3}                     
 CORR_FORWARD = {6: 3, 8: 4, 26: 13}                                            # CWFA_CORR_*: neighbours -> forward offsets K
 NMAX_MAX_DIST = 16                # CWFA_NMAX_MAX_DIST
 SELECT_FORM = {"auto": 0, "lds": 1, "stream": 2}                                # cwfa_temporal_select's `form`
+SHIFT_MODE = {"bilinear": 0, "nearest": 1}                                      # cwfa_reg_shift's `mode`
 
 # name -> (restype, argtypes); must list EVERY function declared in include/cwfa_hip.h (tests/test_boundary.py checks)
 i, i64, f, d, p = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_void_p
@@ -216,6 +217,10 @@ SIGNATURES = {
     "cwfa_frame_dots_workspace_bytes": (i64, [i, i64]),
     "cwfa_frame_dots": (i, [p, i, i, i64, i64, p, p, p, i, p]),
     "cwfa_sparse_residual": (i, [p, i, i, i64, i64, p, p, p, p, i, p]),
+    "cwfa_reg_window": (i, [p, i, i, i, i, i64, p, p, p, p]),
+    "cwfa_reg_whiten_c64": (i, [p, p, i, i64, f, p, p]),
+    "cwfa_reg_peak_f32": (i, [p, i, i, i, i64, i, i, i, p, p, p, p]),
+    "cwfa_reg_shift": (i, [p, i, i, i, i, i64, p, i, f, p, p]),
 }
 del i, i64, f, d, p
 

@@ -1,0 +1,349 @@
+// Rigid frame registration in front of sparse-activity extraction: phase correlation of every frame of a stack
+// against a template, an integer peak in a bounded window with parabolic sub-pixel refinement, and resampling.  rocFFT (through
+// torch.fft) does the transforms; the four passes around them are here: the edge taper (rwin_*), the whitened cross-power
+// (rwht_*), the peak (rpeak_*) and the resampling (rshift_*).  The shifts stay on the device from the peak kernel to the resampling
+// kernel.  Built with -ffp-contract=off; the products, sums and differences the restatement (tests/register_ref.py) counts are
+// spelled with the __f*_rn intrinsics all the same, the square root and the divisions with sqrtf and / (see rwht_one).
+#include <math.h>
+#include <type_traits>
+#include "common.h"
+
+typedef unsigned long long rkey_t;
+
+// ------------------------------------------------------------------------------------------------ the window
+// out[n,y,x] = fl(float(x[n,y,x]) * fl(wy[y] * wx[x])): one read, one fp32 write.  A thread owns V pixels of a row, keeps their
+// window product and walks the frames blockIdx.y, blockIdx.y + gridDim.y, ..
+template <int V, bool HALF>
+__global__ __launch_bounds__(256) void rwin_kernel(const void* __restrict__ x, int N, int H, int W, int64_t fs, const float* __restrict__ wy,
+                                                   const float* __restrict__ wx, float* __restrict__ out) {
+    typedef float fvec __attribute__((ext_vector_type(V)));
+    typedef _Float16 hvec __attribute__((ext_vector_type(V)));
+    const int Wv = W / V;                                             // V > 1: W is a multiple of V
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (int64_t)H * Wv) return;
+    const int y = (int)(q / Wv), x0 = (int)(q - (int64_t)y * Wv) * V;
+    const int64_t p = (int64_t)y * W + x0;
+    float w[V];
+    {
+        const float a = wy[y];
+        const fvec b = *reinterpret_cast<const fvec*>(wx + x0);
+#pragma unroll
+        for (int j = 0; j < V; ++j) w[j] = __fmul_rn(a, b[j]);
+    }
+    for (int n = blockIdx.y; n < N; n += gridDim.y) {
+        fvec r;
+        if constexpr (HALF) {
+            const hvec v = *reinterpret_cast<const hvec*>(reinterpret_cast<const _Float16*>(x) + (int64_t)n * fs + p);
+#pragma unroll
+            for (int j = 0; j < V; ++j) r[j] = __fmul_rn((float)v[j], w[j]);
+        } else {
+            const fvec v = *reinterpret_cast<const fvec*>(reinterpret_cast<const float*>(x) + (int64_t)n * fs + p);
+#pragma unroll
+            for (int j = 0; j < V; ++j) r[j] = __fmul_rn(v[j], w[j]);
+        }
+        *reinterpret_cast<fvec*>(out + (int64_t)n * H * W + p) = r;
+    }
+}
+
+// blocks along y for a kernel whose threads walk the frames: about `target` blocks in all, the per-pixel values reused over N / gy
+// frames.  The window and the resampling keep a few words per thread and take many blocks (an even tail); the whitening keeps a
+// plane of weights and takes one block row where the bins alone fill the chip, so that the plane is read once.
+static inline unsigned reg_grid_y(int64_t gx, int N, int64_t target) {
+    int64_t gy = target / gx < 1 ? 1 : target / gx;
+    gy = gy > 65535 ? 65535 : gy;
+    return (unsigned)(gy > N ? N : gy);
+}
+
+extern "C" int cwfa_reg_window(const void* x, int dtype, int N, int H, int W, int64_t frame_stride, const float* wy, const float* wx,
+                               float* out, void* stream) {
+    CWFA_REQUIRE(x && wy && wx && out, CWFA_E_INVAL, "cwfa_reg_window: null pointer");
+    CWFA_REQUIRE(dtype == 0 || dtype == 1, CWFA_E_INVAL, "cwfa_reg_window: dtype is 0 (fp32) or 1 (fp16), got %d", dtype);
+    CWFA_REQUIRE(N >= 0 && H >= 0 && W >= 0, CWFA_E_SHAPE, "cwfa_reg_window: negative size");
+    CWFA_REQUIRE((int64_t)H * W < ((int64_t)1 << 31), CWFA_E_SHAPE, "cwfa_reg_window: a frame of %d x %d is too large", H, W);
+    if (N == 0 || H == 0 || W == 0) return CWFA_OK;
+    const int64_t P = (int64_t)H * W;
+    CWFA_REQUIRE(frame_stride >= P, CWFA_E_INVAL, "cwfa_reg_window: frame stride smaller than a frame");
+    CWFA_REQUIRE(static_cast<const void*>(out) != x, CWFA_E_INVAL, "cwfa_reg_window: out must not be the stack");
+    const uintptr_t xa = reinterpret_cast<uintptr_t>(x);
+    const bool v4 = (W & 3) == 0 && (frame_stride & 3) == 0 && cwfa_aligned16(wx) && cwfa_aligned16(out) && (xa & (dtype ? 7u : 15u)) == 0;
+    const int64_t gx = ((v4 ? P >> 2 : P) + 255) / 256;
+    const dim3 grid((unsigned)gx, reg_grid_y(gx, N, 65536));
+    hipStream_t st = (hipStream_t)stream;
+#define RWIN_LAUNCH(V, HALF) hipLaunchKernelGGL((rwin_kernel<V, HALF>), grid, dim3(256), 0, st, x, N, H, W, frame_stride, wy, wx, out)
+    if (v4) { if (dtype) RWIN_LAUNCH(4, true); else RWIN_LAUNCH(4, false); }
+    else { if (dtype) RWIN_LAUNCH(1, true); else RWIN_LAUNCH(1, false); }
+#undef RWIN_LAUNCH
+    CWFA_LAUNCH_CHECK("cwfa_reg_window");
+    return CWFA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the whitened cross-power
+// u = z / (|z| + eps), |z| = sqrtf(fl(fl(re re) + fl(im im))), and with a weight plane out = u * w (four products, one difference,
+// one sum, all rounded).  A thread owns a bin, keeps its weight and walks the frames, so the plane is read once per launch (per
+// block row); a bin is 8 bytes, a wave reads 512 consecutive bytes per frame, four frames in flight.  out may be F: an element is
+// read before it is written, by the same thread.
+template <bool WEIGHT>
+__device__ __forceinline__ f32x2 rwht_one(f32x2 z, f32x2 w, float eps) {
+    // sqrtf and / are the correctly rounded forms (hipcc's default); __fsqrt_rn is the native approximation in this tool chain
+    const float m = sqrtf(__fadd_rn(__fmul_rn(z[0], z[0]), __fmul_rn(z[1], z[1])));
+    const float d = __fadd_rn(m, eps);
+    const float ur = z[0] / d, ui = z[1] / d;
+    if constexpr (!WEIGHT) return f32x2{ur, ui};
+    return f32x2{__fsub_rn(__fmul_rn(ur, w[0]), __fmul_rn(ui, w[1])), __fadd_rn(__fmul_rn(ur, w[1]), __fmul_rn(ui, w[0]))};
+}
+
+template <bool WEIGHT>
+__global__ __launch_bounds__(256) void rwht_kernel(const f32x2* F, const f32x2* __restrict__ Wt, int N, int64_t bins, float eps, f32x2* out) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= bins) return;
+    f32x2 w = f32x2{0.f, 0.f};
+    if constexpr (WEIGHT) w = Wt[k];
+    const int step = gridDim.y;
+    int n = blockIdx.y;
+    for (; n + 3 * step < N; n += 4 * step) {
+        f32x2 z[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z[j] = F[(int64_t)(n + j * step) * bins + k];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out[(int64_t)(n + j * step) * bins + k] = rwht_one<WEIGHT>(z[j], w, eps);
+    }
+    for (; n < N; n += step) out[(int64_t)n * bins + k] = rwht_one<WEIGHT>(F[(int64_t)n * bins + k], w, eps);
+}
+
+extern "C" int cwfa_reg_whiten_c64(const void* F, const void* Wt, int N, int64_t bins, float eps, void* out, void* stream) {
+    CWFA_REQUIRE(F && out, CWFA_E_INVAL, "cwfa_reg_whiten_c64: null pointer");
+    CWFA_REQUIRE(eps >= 0.f && eps < INFINITY, CWFA_E_INVAL, "cwfa_reg_whiten_c64: eps must be finite and not negative");
+    CWFA_REQUIRE(N >= 0 && bins >= 0, CWFA_E_SHAPE, "cwfa_reg_whiten_c64: negative size");
+    CWFA_REQUIRE((bins + 255) / 256 < ((int64_t)1 << 31), CWFA_E_SHAPE, "cwfa_reg_whiten_c64: too many bins");
+    CWFA_REQUIRE(((reinterpret_cast<uintptr_t>(F) | reinterpret_cast<uintptr_t>(Wt) | reinterpret_cast<uintptr_t>(out)) & 7u) == 0, CWFA_E_ALIGN,
+                 "cwfa_reg_whiten_c64: complex64 data must be 8-byte aligned");
+    CWFA_REQUIRE(Wt == nullptr || (Wt != F && Wt != out), CWFA_E_INVAL, "cwfa_reg_whiten_c64: the weight plane must not be F or out");
+    if (N == 0 || bins == 0) return CWFA_OK;
+    const int64_t gx = (bins + 255) / 256;
+    const dim3 grid((unsigned)gx, reg_grid_y(gx, N, 8192));
+    hipStream_t st = (hipStream_t)stream;
+    const f32x2* f = static_cast<const f32x2*>(F);
+    const f32x2* w = static_cast<const f32x2*>(Wt);
+    f32x2* o = static_cast<f32x2*>(out);
+    if (Wt) hipLaunchKernelGGL((rwht_kernel<true>), grid, dim3(256), 0, st, f, w, N, bins, eps, o);
+    else hipLaunchKernelGGL((rwht_kernel<false>), grid, dim3(256), 0, st, f, w, N, bins, eps, o);
+    CWFA_LAUNCH_CHECK("cwfa_reg_whiten_c64");
+    return CWFA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the peak
+// One workgroup per frame.  Window index i (row-major from (-my, -mx)) reads c at (sy mod H, sx mod W);
+// key = ord(c + 0.0f) << 32 | (0xFFFFFFFF - i), the order of the detector (neuron_ops.hip): NaN has ord 0, ties go to the lowest
+// index.  The maximum over a thread's indices, over the wave by shuffles, over the waves through the LDS: no atomics, and no trace
+// of the order the threads ran in.  Thread 0 then reads the peak's four neighbours (modulo H / W: they may lie outside the
+// window) and fits the two parabolas in float64.
+#define RPEAK_THREADS 256
+
+__device__ __forceinline__ rkey_t rpeak_key(float v, unsigned i) {
+    unsigned u = __builtin_bit_cast(unsigned, v);
+    u = u == 0x80000000u ? 0u : u;
+    const unsigned o = v != v ? 0u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
+    return ((rkey_t)o << 32) | (rkey_t)(0xFFFFFFFFu - i);
+}
+
+__device__ __forceinline__ double rpeak_delta(float cm, float c0, float cp) {
+    const double a = (double)cm, b = (double)c0, c = (double)cp;
+    const double den = (a - 2.0 * b) + c;
+    double d = (0.5 * (a - c)) / den;
+    if (!(den < 0.0) || !(fabs(d) <= 1.7976931348623157e308)) d = 0.0;
+    return d < -0.5 ? -0.5 : (d > 0.5 ? 0.5 : d);
+}
+
+__global__ __launch_bounds__(RPEAK_THREADS) void rpeak_kernel(const float* __restrict__ c, int H, int W, int64_t fs, int my, int mx, int subpixel,
+                                                              float* __restrict__ shifts, int* __restrict__ ipeak, float* __restrict__ peak) {
+    __shared__ rkey_t best[RPEAK_THREADS / 64];
+    __shared__ int finite[RPEAK_THREADS / 64];
+    const int n = blockIdx.x;
+    const float* cn = c + (int64_t)n * fs;
+    const int wh = 2 * my + 1, ww = 2 * mx + 1;
+    const unsigned nwin = (unsigned)wh * (unsigned)ww;                // <= H * W < 2^31
+    rkey_t k = 0;
+    bool fin = false;
+    for (unsigned i = threadIdx.x; i < nwin; i += RPEAK_THREADS) {
+        const int r = (int)(i / (unsigned)ww), sy = r - my, sx = (int)(i - (unsigned)r * (unsigned)ww) - mx;
+        const int y = sy < 0 ? sy + H : sy, x = sx < 0 ? sx + W : sx;   // |sy| < H and |sx| < W: the window fits the frame
+        const float v = cn[(int64_t)y * W + x];
+        const rkey_t kv = rpeak_key(v, i);
+        k = kv > k ? kv : k;
+        fin = fin || fabsf(v) < INFINITY;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const rkey_t other = __shfl_xor(k, o, 64);
+        k = other > k ? other : k;
+    }
+    const bool wave_fin = __ballot(fin) != 0;
+    if ((threadIdx.x & 63) == 0) best[threadIdx.x >> 6] = k, finite[threadIdx.x >> 6] = wave_fin ? 1 : 0;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    int any = 0;
+#pragma unroll
+    for (int w = 0; w < RPEAK_THREADS / 64; ++w) {
+        k = best[w] > k ? best[w] : k;
+        any |= finite[w];
+    }
+    if (!any) {                                                       // no finite value in the window
+        shifts[2 * n] = 0.f, shifts[2 * n + 1] = 0.f;
+        ipeak[2 * n] = 0, ipeak[2 * n + 1] = 0;
+        peak[n] = __builtin_nanf("");
+        return;
+    }
+    const unsigned i = 0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull);
+    const int r = (int)(i / (unsigned)ww), sy = r - my, sx = (int)(i - (unsigned)r * (unsigned)ww) - mx;
+    const int y = sy < 0 ? sy + H : sy, x = sx < 0 ? sx + W : sx;
+    const float c0 = cn[(int64_t)y * W + x];
+    double dy = 0.0, dx = 0.0;
+    if (subpixel) {
+        const int ym = y == 0 ? H - 1 : y - 1, yp = y + 1 == H ? 0 : y + 1;
+        const int xm = x == 0 ? W - 1 : x - 1, xp = x + 1 == W ? 0 : x + 1;
+        dy = rpeak_delta(cn[(int64_t)ym * W + x], c0, cn[(int64_t)yp * W + x]);
+        dx = rpeak_delta(cn[(int64_t)y * W + xm], c0, cn[(int64_t)y * W + xp]);
+    }
+    shifts[2 * n] = (float)((double)sy + dy), shifts[2 * n + 1] = (float)((double)sx + dx);
+    ipeak[2 * n] = sy, ipeak[2 * n + 1] = sx;
+    peak[n] = c0;
+}
+
+extern "C" int cwfa_reg_peak_f32(const float* c, int N, int H, int W, int64_t frame_stride, int my, int mx, int subpixel, float* shifts,
+                                 int* ipeak, float* peak, void* stream) {
+    CWFA_REQUIRE(c && shifts && ipeak && peak, CWFA_E_INVAL, "cwfa_reg_peak_f32: null pointer");
+    CWFA_REQUIRE(subpixel == 0 || subpixel == 1, CWFA_E_INVAL, "cwfa_reg_peak_f32: subpixel is 0 or 1");
+    CWFA_REQUIRE(N >= 0 && H >= 0 && W >= 0 && my >= 0 && mx >= 0, CWFA_E_SHAPE, "cwfa_reg_peak_f32: negative size");
+    CWFA_REQUIRE((int64_t)H * W < ((int64_t)1 << 31), CWFA_E_SHAPE, "cwfa_reg_peak_f32: a frame of %d x %d is too large", H, W);
+    CWFA_REQUIRE(((reinterpret_cast<uintptr_t>(shifts) | reinterpret_cast<uintptr_t>(ipeak)) & 7u) == 0 && (reinterpret_cast<uintptr_t>(peak) & 3u) == 0 &&
+                     (reinterpret_cast<uintptr_t>(c) & 3u) == 0,
+                 CWFA_E_ALIGN, "cwfa_reg_peak_f32: shifts and ipeak must be 8-byte aligned, c and peak 4-byte aligned");
+    if (N == 0 || H == 0 || W == 0) return CWFA_OK;
+    CWFA_REQUIRE(2 * (int64_t)my + 1 <= H && 2 * (int64_t)mx + 1 <= W, CWFA_E_SHAPE,
+                 "cwfa_reg_peak_f32: the search window (%lld x %lld) is wider than the %d x %d frame", 2 * (long long)my + 1, 2 * (long long)mx + 1, H, W);
+    CWFA_REQUIRE(frame_stride >= (int64_t)H * W, CWFA_E_INVAL, "cwfa_reg_peak_f32: frame stride smaller than a frame");
+    hipLaunchKernelGGL(rpeak_kernel, dim3((unsigned)N), dim3(RPEAK_THREADS), 0, (hipStream_t)stream, c, H, W, frame_stride, my, mx, subpixel,
+                       shifts, ipeak, peak);
+    CWFA_LAUNCH_CHECK("cwfa_reg_peak_f32");
+    return CWFA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the resampling
+// out[n,y,x] = sum over the taps (0,0), (0,1), (1,0), (1,1) of w * in[n, y + iy + r, x + ix + c], iy = floorf(dy), fy = dy - iy,
+// w = fl(wy_r * wx_c) with wy = (fl(1 - fy), fy): every weight and product rounded, the terms added in that order, a tap of
+// weight exactly 0 neither read nor added (an integer shift copies bits), a tap outside the frame reads `fill`, a non-finite shift
+// fills the frame.  The shift of frame n is read from device memory.  A thread writes V consecutive pixels of a row (a 16-byte
+// store: 4 of fp32, 8 of fp16) from the V + 1 source pixels of either row.  The source rows start anywhere: inside the frame the
+// span is one load of element alignment (the compiler makes it a vector load plus one element), at the borders element by element.
+template <class T, int K>
+struct rshift_span {
+    T v[K];
+};
+
+template <int V, bool HALF>
+__global__ __launch_bounds__(256) void rshift_kernel(const void* __restrict__ in, int N, int H, int W, int64_t fs, const f32x2* __restrict__ shifts,
+                                                     int nearest, float fill, void* __restrict__ out) {
+    using elem = std::conditional_t<HALF, _Float16, float>;
+    typedef elem evec __attribute__((ext_vector_type(V)));
+    const int Wv = W / V;                                             // V > 1: W is a multiple of V
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (int64_t)H * Wv) return;
+    const int y = (int)(q / Wv), x0 = (int)(q - (int64_t)y * Wv) * V;
+    for (int n = blockIdx.y; n < N; n += gridDim.y) {
+        const f32x2 s = shifts[n];
+        float dy = s[0], dx = s[1];
+        elem* o = reinterpret_cast<elem*>(out) + (int64_t)n * H * W + (int64_t)y * W + x0;
+        float acc[V];
+        if (!(fabsf(dy) < INFINITY) || !(fabsf(dx) < INFINITY)) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) acc[j] = fill;
+        } else {
+            if (nearest) dy = rintf(dy), dx = rintf(dx);
+            const float iyf = floorf(dy), ixf = floorf(dx);
+            const float fy = __fsub_rn(dy, iyf), fx = __fsub_rn(dx, ixf);
+            // beyond +-(size + 1) every tap is outside whatever the value: clamp before the conversion to int
+            const int iy = (int)fminf(fmaxf(iyf, -(float)(H + 1)), (float)(H + 1));
+            const int ix = (int)fminf(fmaxf(ixf, -(float)(W + 1)), (float)(W + 1));
+            const float wy[2] = {__fsub_rn(1.f, fy), fy}, wx[2] = {__fsub_rn(1.f, fx), fx};
+            const elem* src = reinterpret_cast<const elem*>(in) + (int64_t)n * fs;
+            bool have = false;
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const float w0 = __fmul_rn(wy[r], wx[0]), w1 = __fmul_rn(wy[r], wx[1]);
+                if (w0 == 0.f && w1 == 0.f) continue;                 // the whole row of taps has weight 0: not read
+                const int yy = y + iy + r;
+                const bool row_in = yy >= 0 && yy < H;
+                const elem* row = src + (int64_t)(row_in ? yy : 0) * W;
+                float v[V + 1];
+                const int xs = x0 + ix;
+                if (V > 1 && row_in && xs >= 0 && xs + V < W) {       // the span lies inside the row: one unaligned vector load
+                    rshift_span<elem, V + 1> sp;
+                    __builtin_memcpy(&sp, row + xs, sizeof(sp));
+#pragma unroll
+                    for (int j = 0; j <= V; ++j) v[j] = (float)sp.v[j];
+                } else {
+#pragma unroll
+                    for (int j = 0; j <= V; ++j) {
+                        const int xx = xs + j;
+                        const bool need = j < V ? (w0 != 0.f || (j > 0 && w1 != 0.f)) : w1 != 0.f;
+                        v[j] = need && row_in && xx >= 0 && xx < W ? (float)row[xx] : fill;
+                    }
+                }
+                if (w0 != 0.f) {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) {
+                        const float t = __fmul_rn(w0, v[j]);
+                        acc[j] = have ? __fadd_rn(acc[j], t) : t;
+                    }
+                    have = true;
+                }
+                if (w1 != 0.f) {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) {
+                        const float t = __fmul_rn(w1, v[j + 1]);
+                        acc[j] = have ? __fadd_rn(acc[j], t) : t;
+                    }
+                    have = true;
+                }
+            }
+            if (!have) {                                              // all four weights underflowed to 0
+#pragma unroll
+                for (int j = 0; j < V; ++j) acc[j] = 0.f;
+            }
+        }
+        evec r;
+#pragma unroll
+        for (int j = 0; j < V; ++j) r[j] = (elem)acc[j];
+        *reinterpret_cast<evec*>(o) = r;
+    }
+}
+
+extern "C" int cwfa_reg_shift(const void* in, int dtype, int N, int H, int W, int64_t frame_stride, const float* shifts, int mode, float fill,
+                              void* out, void* stream) {
+    CWFA_REQUIRE(in && shifts && out, CWFA_E_INVAL, "cwfa_reg_shift: null pointer");
+    CWFA_REQUIRE(dtype == 0 || dtype == 1, CWFA_E_INVAL, "cwfa_reg_shift: dtype is 0 (fp32) or 1 (fp16), got %d", dtype);
+    CWFA_REQUIRE(mode == 0 || mode == 1, CWFA_E_INVAL, "cwfa_reg_shift: mode is 0 (bilinear) or 1 (nearest), got %d", mode);
+    CWFA_REQUIRE(N >= 0 && H >= 0 && W >= 0, CWFA_E_SHAPE, "cwfa_reg_shift: negative size");
+    CWFA_REQUIRE((int64_t)H * W < ((int64_t)1 << 31) && H < (1 << 30) && W < (1 << 30), CWFA_E_SHAPE,
+                 "cwfa_reg_shift: a frame of %d x %d is too large", H, W);      // y + iy + 1 with |iy| <= H + 1 stays an int
+    CWFA_REQUIRE((reinterpret_cast<uintptr_t>(shifts) & 7u) == 0, CWFA_E_ALIGN, "cwfa_reg_shift: shifts must be 8-byte aligned");
+    CWFA_REQUIRE(out != in, CWFA_E_INVAL, "cwfa_reg_shift: out must not alias the stack");
+    if (N == 0 || H == 0 || W == 0) return CWFA_OK;
+    const int64_t P = (int64_t)H * W;
+    CWFA_REQUIRE(frame_stride >= P, CWFA_E_INVAL, "cwfa_reg_shift: frame stride smaller than a frame");
+    // 16-byte stores where W and out's base allow: four fp32 or eight fp16 pixels per thread; four fp16 pixels (8 bytes) next
+    const bool v8 = dtype == 1 && (W & 7) == 0 && cwfa_aligned16(out);
+    const bool v4 = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & (dtype ? 7u : 15u)) == 0;
+    const int64_t gx = ((v8 ? P >> 3 : v4 ? P >> 2 : P) + 255) / 256;
+    const dim3 grid((unsigned)gx, reg_grid_y(gx, N, 65536));
+    hipStream_t st = (hipStream_t)stream;
+    const f32x2* sh = reinterpret_cast<const f32x2*>(shifts);
+#define RSHIFT_LAUNCH(V, HALF) \
+    hipLaunchKernelGGL((rshift_kernel<V, HALF>), grid, dim3(256), 0, st, in, N, H, W, frame_stride, sh, mode, fill, out)
+    if (v8) RSHIFT_LAUNCH(8, true);
+    else if (v4) { if (dtype) RSHIFT_LAUNCH(4, true); else RSHIFT_LAUNCH(4, false); }
+    else { if (dtype) RSHIFT_LAUNCH(1, true); else RSHIFT_LAUNCH(1, false); }
+#undef RSHIFT_LAUNCH
+    CWFA_LAUNCH_CHECK("cwfa_reg_shift");
+    return CWFA_OK;
+}

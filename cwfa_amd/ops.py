@@ -2656,3 +2656,122 @@ def sparse_residual(stack, a, b, tau=None, out=None, pair=False):
         raise ValueError("sparse_residual: in place needs a contiguous stack")
     check(L.cwfa_sparse_residual(_p(stack), dt, T, P, fs, _p(a), _p(b), _p(tau), _p(out), int(bool(pair)), _stream()), "sparse_residual")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ rigid frame registration
+def _frames(x, what):
+    """A [N, H, W] stack as ``_stack`` returns it, with H and W."""
+    x, dt, N, P, fs = _stack(x, what)
+    if x.dim() != 3:
+        raise ValueError(f"{what}: a stack [N, H, W] is expected, got {tuple(x.shape)}")
+    H, W = int(x.shape[1]), int(x.shape[2])
+    if H * W >= 1 << 31:
+        raise ValueError(f"{what}: a frame of {H} x {W} is too large")
+    return x, dt, N, H, W, fs
+
+
+def _overlap(a, b):
+    """Whether two tensors share bytes of one storage (bounds of the views, conservative)."""
+    if a.numel() == 0 or b.numel() == 0 or a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr():
+        return False
+    span = lambda t: (t.data_ptr(), t.data_ptr() + (sum((s - 1) * st for s, st in zip(t.shape, t.stride())) + 1) * t.element_size())
+    (a0, a1), (b0, b1) = span(a), span(b)
+    return a0 < b1 and b0 < a1
+
+
+def reg_window(stack, wy, wx, out=None):
+    """float32 [N,H,W]: fl(float(stack) * fl(wy[y] * wx[x])) for a [N,H,W] fp32 / fp16 device stack and fp32 device vectors ``wy``
+    [H], ``wx`` [W] -- the edge taper in front of the forward transform, with the widening of an fp16 stack, in one read and one
+    write.  ``out``: a contiguous float32 tensor of the stack's shape that shares no memory with it."""
+    L = _lib.lib()
+    stack, dt, N, H, W, fs = _frames(stack, "reg_window")
+    wy, wx = _vec(wy, H, "wy", "reg_window"), _vec(wx, W, "wx", "reg_window")
+    if out is None:
+        out = torch.empty((N, H, W), dtype=torch.float32, device=stack.device)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (N, H, W) or not out.is_contiguous():
+        raise ValueError(f"reg_window: out must be a contiguous float32 {(N, H, W)} device tensor")
+    elif _overlap(out, stack):
+        raise ValueError("reg_window: out must not alias the stack")
+    check(L.cwfa_reg_window(_p(stack), dt, N, H, W, fs, _p(wy), _p(wx), _p(out), _stream()), "reg_window")
+    return out
+
+
+def reg_whiten(F, W=None, eps=1e-5, out=None):
+    """F / (|F| + eps) for a contiguous complex64 device tensor, times the complex64 weight plane ``W`` where one is given: ``W``
+    has the shape of F's trailing axes and is shared by everything in front of them.  Each factor is whitened on its own: the
+    modulus of a product of two spectra overflows fp32 where the factors' do not.  ``out``: F itself (in place) or a contiguous
+    complex64 tensor of its shape."""
+    L = _lib.lib()
+    _cdev(F, "reg_whiten")
+    eps = float(eps)
+    if not 0.0 <= eps < float("inf"):
+        raise ValueError(f"reg_whiten: eps must be finite and not negative, got {eps}")
+    if W is None:
+        N, bins = 1, F.numel()
+    else:
+        _cdev(W, "reg_whiten: W")
+        if W.dim() > F.dim() or tuple(F.shape[F.dim() - W.dim():]) != tuple(W.shape):
+            raise ValueError(f"reg_whiten: W {tuple(W.shape)} is not the trailing shape of F {tuple(F.shape)}")
+        bins = W.numel()
+        N = F.numel() // bins if bins else 0
+        if _overlap(W, F) or (out is not None and torch.is_tensor(out) and _overlap(W, out)):
+            raise ValueError("reg_whiten: W must not alias F or out")
+    if out is None:
+        out = torch.empty_like(F)
+    elif out is not F:
+        _cdev(out, "reg_whiten: out")
+        if tuple(out.shape) != tuple(F.shape):
+            raise ValueError(f"reg_whiten: out must have F's shape {tuple(F.shape)}")
+        if _overlap(out, F) and out.data_ptr() != F.data_ptr():
+            raise ValueError("reg_whiten: out is F itself or shares no memory with it")
+    check(L.cwfa_reg_whiten_c64(_p(F), _p(W), N, bins, eps, _p(out), _stream()), "reg_whiten")
+    return out
+
+
+def _max_shift(max_shift, H, W, what):
+    my, mx = (max_shift, max_shift) if isinstance(max_shift, int) else tuple(max_shift)
+    my, mx = int(my), int(mx)
+    if my < 0 or mx < 0 or (H and W and (2 * my + 1 > H or 2 * mx + 1 > W)):
+        raise ValueError(f"{what}: max_shift ({my}, {mx}) needs 0 <= 2 m + 1 <= the frame's {H} x {W}")
+    return my, mx
+
+
+def reg_peak(corr, max_shift, subpixel=True, out=None):
+    """(shifts float32 [N,2], ipeak int32 [N,2], peak float32 [N]) on the device from float32 correlation maps [N,H,W]: the maximum
+    over the signed window |sy| <= my, |sx| <= mx (read modulo the frame) under the total order of ``local_maxima`` -- ties to the
+    lowest window index, NaN below everything -- and, with ``subpixel``, a parabola per axis through the peak and its two
+    neighbours in float64.  A window without a finite value gives shift (0, 0) and peak NaN.  ``out``: the three tensors."""
+    L = _lib.lib()
+    corr, dt, N, H, W, fs = _frames(corr, "reg_peak")
+    if dt != 0:
+        raise TypeError("reg_peak: float32 correlation maps are expected")
+    my, mx = _max_shift(max_shift, H, W, "reg_peak")
+    if out is None:
+        out = (torch.empty((N, 2), dtype=torch.float32, device=corr.device), torch.empty((N, 2), dtype=torch.int32, device=corr.device),
+               torch.empty((N,), dtype=torch.float32, device=corr.device))
+    shifts, ipeak, peak = out
+    for t, dtype, shape, name in ((shifts, torch.float32, (N, 2), "shifts"), (ipeak, torch.int32, (N, 2), "ipeak"), (peak, torch.float32, (N,), "peak")):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"reg_peak: {name} must be a contiguous {dtype} {shape} device tensor")
+    check(L.cwfa_reg_peak_f32(_p(corr), N, H, W, fs, my, mx, int(bool(subpixel)), _p(shifts), _p(ipeak), _p(peak), _stream()), "reg_peak")
+    return shifts, ipeak, peak
+
+
+def reg_shift(stack, shifts, mode="bilinear", fill=0.0, out=None):
+    """out[n,y,x] = stack[n, y + dy, x + dx] with (dy, dx) = shifts[n] read on the device (float32 [N,2]): bilinear with separately
+    rounded fp32 weights and products, or ``mode="nearest"`` (rintf of the shift).  A tap of weight exactly 0 is neither read nor
+    added, so an integer shift copies bits; a tap outside the frame reads ``fill``; a non-finite shift fills the frame.  The result
+    has the stack's dtype.  ``out``: a contiguous tensor of the stack's shape and dtype that shares no memory with it."""
+    L = _lib.lib()
+    stack, dt, N, H, W, fs = _frames(stack, "reg_shift")
+    if mode not in _lib.SHIFT_MODE:
+        raise ValueError(f"reg_shift: mode is one of {sorted(_lib.SHIFT_MODE)}, got {mode!r}")
+    shifts = _vec(shifts, 2 * N, "shifts", "reg_shift")
+    if out is None:
+        out = torch.empty((N, H, W), dtype=stack.dtype, device=stack.device)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != stack.dtype or tuple(out.shape) != (N, H, W) or not out.is_contiguous():
+        raise ValueError(f"reg_shift: out must be a contiguous {stack.dtype} {(N, H, W)} device tensor")
+    elif _overlap(out, stack):
+        raise ValueError("reg_shift: out must not alias the stack")
+    check(L.cwfa_reg_shift(_p(stack), dt, N, H, W, fs, _p(shifts), _lib.SHIFT_MODE[mode], float(fill), _p(out), _stream()), "reg_shift")
+    return out

@@ -975,6 +975,43 @@ int cwfa_frame_dots(const void* x, int dtype, int T, int64_t P, int64_t frame_st
 int cwfa_sparse_residual(const void* x, int dtype, int T, int64_t P, int64_t frame_stride, const float* a, const float* b,
                          const float* tau, float* out, int pair, void* stream);
 
+/* ---- rigid frame registration: phase correlation of the frames of a stack against a template, an integer
+ * peak in a bounded window with parabolic sub-pixel refinement, resampling.  The transforms between these passes are rocFFT's.
+ * Real stacks: [N, H, W], `dtype` 0 = fp32, 1 = fp16, frame_stride >= H * W elements between frames; H * W < 2^31.  Arguments are
+ * checked before any device work; nothing is allocated, nothing synchronises, nothing is read back.  An empty problem: no launch,
+ * CWFA_OK.
+ *
+ *   reg_window:     out[n,y,x] (fp32, contiguous) = fl32(float(x[n,y,x]) * fl32(wy[y] * wx[x])), wy [H] and wx [W] device fp32.
+ *                   One read and one write; 16-byte accesses (8-byte loads of fp16) where W, the stride and the bases allow.
+ *   reg_whiten_c64: F [N, bins] and out [N, bins] interleaved complex64, out == F allowed.  u = z / (|z| + eps) with
+ *                   |z| = sqrtf(fl32(fl32(re re) + fl32(im im))) and two divisions; Wt == NULL: out = u; else Wt [bins] complex64 and
+ *                   out = u * Wt (four products, a difference, a sum, each rounded).  A thread owns a bin and walks the frames.
+ *                   eps >= 0, finite.  All three 8-byte aligned, CWFA_E_ALIGN otherwise.
+ *   reg_peak_f32:   one workgroup per frame of the correlation maps c [N, H, W] fp32.  Window index i, row-major over
+ *                   sy in [-my, my], sx in [-mx, mx], reads c at (sy mod H, sx mod W); the maximum of
+ *                   key = ord(c + 0.0f) << 32 | (0xFFFFFFFF - i) under the order of local_maxima (NaN: ord 0; ties go to the lowest
+ *                   index) is found without atomics.  2 my + 1 <= H and 2 mx + 1 <= W, CWFA_E_SHAPE otherwise.  subpixel = 1: per
+ *                   axis, from the peak and its two neighbours modulo H / W, in float64: den = (c- - 2 c0) + c+,
+ *                   d = (0.5 (c- - c+)) / den where den < 0 and d is finite, else 0, clamped to [-0.5, 0.5];
+ *                   shifts[n] = (float)((double)peak + d).  Writes shifts fp32 [N, 2] (dy, dx), ipeak int32 [N, 2], peak fp32 [N] (the
+ *                   map's value at the integer peak).  A window without a finite value: shift (0, 0), ipeak (0, 0), peak NaN.
+ *                   shifts and ipeak 8-byte aligned, CWFA_E_ALIGN otherwise.
+ *   reg_shift:      out[n,y,x] = sum of w * in[n, y + iy + r, x + ix + c] over the taps (r, c) = (0,0), (0,1), (1,0), (1,1) in that
+ *                   order, (dy, dx) = shifts[n] read on the device, iy = floorf(dy), fy = fl32(dy - iy),
+ *                   w = fl32((fl32(1 - fy), fy)[r] * (fl32(1 - fx), fx)[c]), every product and sum rounded to fp32.  A tap of weight
+ *                   exactly 0 is neither read nor added: an integer shift copies the source bits.  A tap outside the frame reads
+ *                   `fill`; a non-finite shift fills the frame.  mode 0 bilinear, 1 nearest (rintf of the shift first).  out
+ *                   [N, H, W] contiguous of the input's dtype (fp16: round to nearest even of the fp32 sum), out != in.  A thread
+ *                   writes four consecutive fp32 pixels (eight of fp16: 16 bytes; four of fp16 next) where W and out's base allow, one
+ *                   otherwise.  shifts 8-byte aligned, CWFA_E_ALIGN otherwise. */
+int cwfa_reg_window(const void* x, int dtype, int N, int H, int W, int64_t frame_stride, const float* wy, const float* wx,
+                    float* out, void* stream);
+int cwfa_reg_whiten_c64(const void* F, const void* Wt, int N, int64_t bins, float eps, void* out, void* stream);
+int cwfa_reg_peak_f32(const float* c, int N, int H, int W, int64_t frame_stride, int my, int mx, int subpixel, float* shifts,
+                      int* ipeak, float* peak, void* stream);
+int cwfa_reg_shift(const void* in, int dtype, int N, int H, int W, int64_t frame_stride, const float* shifts, int mode, float fill,
+                   void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
