@@ -89,6 +89,7 @@ CORR_FORWARD = {6: 3, 8: 4, 26: 13}                                            #
 NMAX_MAX_DIST = 16                # CWFA_NMAX_MAX_DIST
 SELECT_FORM = {"auto": 0, "lds": 1, "stream": 2}                                # cwfa_temporal_select's `form`
 SHIFT_MODE = {"bilinear": 0, "nearest": 1}                                      # cwfa_reg_shift's `mode`
+FOOTPRINT_SELECT_MAX = 1 << 15    # CWFA_FOOTPRINT_SELECT_MAX
 
 # name -> (restype, argtypes); must list EVERY function declared in include/cwfa_hip.h (tests/test_boundary.py checks)
 i, i64, f, d, p = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_void_p
@@ -221,6 +222,12 @@ SIGNATURES = {
     "cwfa_reg_whiten_c64": (i, [p, p, i, i64, f, p, p]),
     "cwfa_reg_peak_f32": (i, [p, i, i, i, i64, i, i, i, p, p, p, p]),
     "cwfa_reg_shift": (i, [p, i, i, i, i, i64, p, i, f, p, p]),
+    "cwfa_roi_mark_u8": (i, [p, i, p, i, i, i, p]),
+    "cwfa_roi_weighted_sums_f32": (i, [p, p, p, p, p, i, i, i, i, i, i64, p]),
+    "cwfa_roi_shell_sums_f32": (i, [p, p, p, p, p, p, i, i, i, i, i, i64, p]),
+    "cwfa_footprint_update_f32": (i, [p, p, p, p, p, p, p, p, i, i, i, i, i, i64, i, p]),
+    "cwfa_footprint_corr_f32": (i, [p, p, p, i, i64, i, p, p]),
+    "cwfa_footprint_select_f32": (i, [p, p, p, p, i, f, p, p, p, p]),
 }
 del i, i64, f, d, p
 

@@ -2775,3 +2775,239 @@ def reg_shift(stack, shifts, mode="bilinear", fill=0.0, out=None):
         raise ValueError("reg_shift: out must not alias the stack")
     check(L.cwfa_reg_shift(_p(stack), dt, N, H, W, fs, _p(shifts), _lib.SHIFT_MODE[mode], float(fill), _p(out), _stream()), "reg_shift")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ neuron footprints
+def _nonneg_triple(v, name, what):
+    t = _triple(v, name, what)
+    if any(a < 0 for a in t):
+        raise ValueError(f"{what}: {name} = {t} is negative")
+    return t
+
+
+def _box_table(boxes, name, what, shape=None):
+    import numpy as np
+    try:
+        b = np.asarray(boxes)
+        ok = b.size == 0 or (np.issubdtype(b.dtype, np.integer) and b.ndim == 2 and b.shape[1] == 6)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: {name} is an integer [N,6] table (z0, z1, y0, y1, x0, x1)")
+    b = np.ascontiguousarray(b.reshape(-1, 6).astype(np.int32))
+    if shape is not None:
+        lim = np.asarray(shape, dtype=np.int64)
+        lo, hi = b[:, 0::2].astype(np.int64), b[:, 1::2].astype(np.int64)
+        if ((lo < 0) | (lo > hi) | (hi > lim)).any():
+            raise ValueError(f"{what}: every row of {name} is a half-open range inside the volume {tuple(shape)}")
+    return b
+
+
+class FootprintGeometry:
+    """The host tables of the footprint passes for ``boxes`` (``roi_boxes``' int32 [N,6]) in volumes of ``shape`` (D, H, W):
+
+    ``cores`` [N,6]: the seed region of every neuron, inside its box; ``shell_outer`` / ``shell_inner`` [N,6]: the box grown by
+    ``gap + annulus`` and by ``gap`` per axis and clipped by the volume -- the neuropil shell of neuron n is outer minus inner minus
+    every voxel of ``occupancy`` (an empty box has an empty shell); ``offsets`` int64 [N+1]: box n's voxels lie at ``offsets[n]`` of
+    the ragged state in the box's own (z, y, x) linear order, ``V = offsets[N]``.  ``occupancy``: uint8 [D,H,W] on ``device``, 1 inside
+    any box, marked once on first use.  The tables themselves travel in the kernels' arguments: nothing else is uploaded."""
+
+    def __init__(self, boxes, cores, shape, gap=(1, 2, 2), annulus=(2, 4, 4), device="cuda"):
+        import numpy as np
+        what = "footprint_geometry"
+        shape = tuple(int(s) for s in shape)
+        if len(shape) != 3 or min(shape) < 0:
+            raise ValueError(f"{what}: shape is (D, H, W), got {shape!r}")
+        gap, annulus = _nonneg_triple(gap, "gap", what), _nonneg_triple(annulus, "annulus", what)
+        self.shape, self.gap, self.annulus, self.device = shape, gap, annulus, device
+        self.boxes = _box_table(boxes, "boxes", what, shape)
+        self.cores = _box_table(cores, "cores", what, shape)
+        if len(self.cores) != len(self.boxes):
+            raise ValueError(f"{what}: one core per box, got {len(self.cores)} for {len(self.boxes)}")
+        b, c = self.boxes, self.cores
+        if ((c[:, 0::2] < b[:, 0::2]) | (c[:, 1::2] > b[:, 1::2])).any():
+            raise ValueError(f"{what}: every core lies inside its box")
+        size = (b[:, 1::2] - b[:, 0::2]).astype(np.int64)
+        count = size.prod(axis=1)
+        if (count >= 1 << 31).any():
+            raise ValueError(f"{what}: a box of 2^31 voxels or more")
+        self.N = len(b)
+        self.offsets = np.zeros(self.N + 1, dtype=np.int64)
+        np.cumsum(count, out=self.offsets[1:])
+        self.V = int(self.offsets[-1])
+        self.shell_outer, self.shell_inner = np.zeros_like(b), np.zeros_like(b)
+        live = count > 0
+        for k in range(3):
+            for table, grow in ((self.shell_outer, gap[k] + annulus[k]), (self.shell_inner, gap[k])):
+                table[live, 2 * k] = np.maximum(b[live, 2 * k] - grow, 0)
+                table[live, 2 * k + 1] = np.minimum(b[live, 2 * k + 1] + grow, shape[k])
+        self._occupancy = None
+
+    @property
+    def occupancy(self):
+        if self._occupancy is None:
+            self._occupancy = roi_mark(self.boxes, self.shape, self.device)
+        return self._occupancy
+
+
+def footprint_geometry(boxes, cores, shape, gap=(1, 2, 2), annulus=(2, 4, 4), device="cuda"):
+    """``FootprintGeometry(boxes, cores, shape, gap, annulus, device)``: the tables are checked here, on the host, once."""
+    return FootprintGeometry(boxes, cores, shape, gap, annulus, device)
+
+
+def _host(a):
+    return C.c_void_p(a.ctypes.data)
+
+
+def _volumes(x, shape, what):
+    """(x, T, time stride) of a float32 device stack [T, D, H, W] with contiguous volumes of ``shape``."""
+    _dev(x, "volumes")
+    if x.dim() != 4 or (shape is not None and tuple(x.shape[1:]) != tuple(shape)):
+        want = "D, H, W" if shape is None else ", ".join(str(s) for s in shape)
+        raise ValueError(f"{what}: volumes [T', {want}] are expected, got {tuple(x.shape)}")
+    T, m = x.shape[0], x[0].numel() if x.shape[0] else 0
+    if T and m and (not x[0].is_contiguous() or (T > 1 and x.stride(0) < m)):
+        x = x.contiguous()
+    return x, T, (x.stride(0) if T > 1 else m)
+
+
+def roi_mark(boxes, shape, device="cuda"):
+    """uint8 [D,H,W] on ``device``: 1 inside any box of the integer [N,6] host table, 0 elsewhere."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 3 or min(shape) < 0:
+        raise ValueError(f"roi_mark: shape is (D, H, W), got {shape!r}")
+    bx = _box_table(boxes, "boxes", "roi_mark", shape)
+    if torch.device(device).type != "cuda":
+        raise RuntimeError(f"roi_mark: cwfa_amd runs on MI355X only -- got device {device!r} (no CPU fallback exists)")
+    L = _lib.lib()
+    occ = torch.empty(shape, dtype=torch.uint8, device=device)
+    check(L.cwfa_roi_mark_u8(_host(bx), len(bx), _p(occ), *shape, _stream()), "roi_mark")
+    return occ
+
+
+def roi_weighted_sums(stack, boxes, weights=None, offsets=None):
+    """float64 [N, T]: sum over box n of weights[offsets[n] + i] * stack[t, voxel i] (box-linear i), or the plain box sum for
+    ``weights=None``.  ``boxes``: integer [N,6] host table inside the volume; ``weights``: float32 device [V]; ``offsets``: the int64
+    [N+1] host table of ``FootprintGeometry``.  Each product is exact in float64; a fixed tree adds them."""
+    import numpy as np
+    stack, T, ss = _volumes(stack, None, "roi_weighted_sums")
+    D, H, W = stack.shape[1:]
+    bx = _box_table(boxes, "boxes", "roi_weighted_sums", (D, H, W))
+    off = None
+    if weights is not None:
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1)) if offsets is not None else None
+        if off is None or len(off) != len(bx) + 1:
+            raise ValueError("roi_weighted_sums: weights need the int64 [N+1] offsets of the boxes")
+        _dev(weights, "weights")
+        if weights.dim() != 1 or weights.numel() != int(off[-1]) or not weights.is_contiguous():
+            raise ValueError(f"roi_weighted_sums: weights is a contiguous [V] tensor, V = offsets[N] = {int(off[-1])}")
+    L = _lib.lib()
+    out = torch.empty(len(bx), T, dtype=torch.float64, device=stack.device)
+    check(L.cwfa_roi_weighted_sums_f32(_p(stack), _host(bx), None if off is None else _host(off), _p(weights), _p(out), T, D, H, W, len(bx),
+                                       ss, _stream()), "roi_weighted_sums")
+    return out
+
+
+def roi_shell_sums(stack, geometry):
+    """(sums float64 [N,T], counts int32 [N]) of the neuropil shells of ``geometry``: outer box minus inner box minus every occupied
+    voxel.  A shell without voxels has count 0 and sum 0."""
+    if not isinstance(geometry, FootprintGeometry):
+        raise ValueError("roi_shell_sums: geometry is a FootprintGeometry (ops.footprint_geometry)")
+    stack, T, ss = _volumes(stack, geometry.shape, "roi_shell_sums")
+    L = _lib.lib()
+    g = geometry
+    sums = torch.empty(g.N, T, dtype=torch.float64, device=stack.device)
+    counts = torch.zeros(g.N, dtype=torch.int32, device=stack.device)
+    check(L.cwfa_roi_shell_sums_f32(_p(stack), _host(g.shell_outer), _host(g.shell_inner), _p(g.occupancy), _p(sums), _p(counts), T,
+                                    *g.shape, g.N, ss, _stream()), "roi_shell_sums")
+    return sums, counts
+
+
+def footprint_state(geometry, device="cuda"):
+    """The state of the footprint pass for ``geometry``: (x0 float32 [V], acc float64 [4,V] = s1, s2, sc, su, ref float64 [N,7] = c0,
+    u0, e1, e2, g1, g2, eg), 36 bytes per box voxel, uninitialised -- the first ``footprint_update`` (``first=True``) writes all of it."""
+    if not isinstance(geometry, FootprintGeometry):
+        raise ValueError("footprint_state: geometry is a FootprintGeometry (ops.footprint_geometry)")
+    return (torch.empty(geometry.V, dtype=torch.float32, device=device), torch.empty(4, geometry.V, dtype=torch.float64, device=device),
+            torch.empty(geometry.N, 7, dtype=torch.float64, device=device))
+
+
+def _footprint(state, geometry, what):
+    if not isinstance(geometry, FootprintGeometry):
+        raise ValueError(f"{what}: geometry is a FootprintGeometry (ops.footprint_geometry)")
+    shapes = ((geometry.V,), (4, geometry.V), (geometry.N, 7))
+    if len(state) != 3 or any(not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != s
+                              for t, dt, s in zip(state, (torch.float32, torch.float64, torch.float64), shapes)):
+        raise ValueError(f"{what}: the state is (x0 float32 {shapes[0]}, acc float64 {shapes[1]}, ref float64 {shapes[2]}), contiguous, on "
+                         f"the HIP device (ops.footprint_state)")
+
+
+def _ref_trace(t, N, T, name, what):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float64 or tuple(t.shape) != (N, T):
+        raise ValueError(f"{what}: {name} is a float64 [{N}, {T}] tensor on the HIP device")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def footprint_update(x, geometry, c, u, state, first):
+    """Add the chunk ``x`` [T',D,H,W] to ``state`` (``footprint_state``).  ``c``: float64 device [N,T'], the seed traces of the chunk;
+    ``u``: the neuropil traces, or None (su, g1, g2, eg stay 0.0).  Per box voxel, d = x - x0 (x0 its first sample ever seen), e = c - c0,
+    g = u - u0: s1 += d, s2 += d d, sc += d e, su += d g, and per neuron e1, e2, g1, g2, eg likewise, in float64, in time order; the
+    first chunk skips its own first volume.  Any chunking gives the same bits."""
+    what = "footprint_update"
+    _dev(x, "x")
+    _footprint(state, geometry, what)
+    x, T, ss = _volumes(x, geometry.shape, what)
+    if first and T < 1:
+        raise ValueError(f"{what}: the first chunk needs at least one volume")
+    g = geometry
+    c = _ref_trace(c, g.N, T, "c", what)
+    u = None if u is None else _ref_trace(u, g.N, T, "u", what)
+    L = _lib.lib()
+    check(L.cwfa_footprint_update_f32(_p(x), _host(g.boxes), _host(g.offsets), _p(c), _p(u), *(_p(t) for t in state), T, *g.shape, g.N, ss,
+                                      int(bool(first)), _stream()), what)
+    return state
+
+
+def footprint_corr(state, geometry, count, neuropil=True):
+    """float32 [V]: per box voxel the correlation of its series with its neuron's seed trace after ``count`` samples -- the partial
+    correlation given the neuropil trace for ``neuropil=True`` -- in float64 from ``state``.  A constant series, NaN, inf and
+    ``count`` = 1 give 0, never NaN.  The state is only read."""
+    what = "footprint_corr"
+    _footprint(state, geometry, what)
+    if int(count) < 1:
+        raise ValueError(f"{what}: needs at least one sample")
+    L = _lib.lib()
+    corr = torch.empty(geometry.V, dtype=torch.float32, device=state[0].device)
+    check(L.cwfa_footprint_corr_f32(_p(state[1]), _p(state[2]), _host(geometry.offsets), geometry.N, int(count), int(bool(neuropil)),
+                                    _p(corr), _stream()), what)
+    return corr
+
+
+def footprint_threshold(thr, what):
+    thr = float(thr)
+    if not 0.0 < thr <= 1.0:
+        raise ValueError(f"{what}: thr = {thr} is not in (0, 1]")
+    return thr
+
+
+def footprint_select(corr, geometry, thr):
+    """(weights float32 [V], wsum float64 [N], sizes int32 [N]): per neuron the voxels with ``corr >= thr`` (0 < thr <= 1) that are
+    connected through faces, inside the box, to such a voxel of the neuron's core; weights = corr there, 0 elsewhere; wsum: their
+    float64 sum in box-linear order.  Boxes hold at most 2^15 voxels."""
+    what = "footprint_select"
+    thr = footprint_threshold(thr, what)
+    if not isinstance(geometry, FootprintGeometry):
+        raise ValueError(f"{what}: geometry is a FootprintGeometry (ops.footprint_geometry)")
+    g = geometry
+    if g.N and int((g.offsets[1:] - g.offsets[:-1]).max()) > _lib.FOOTPRINT_SELECT_MAX:
+        raise ValueError(f"{what}: a box of more than {_lib.FOOTPRINT_SELECT_MAX} voxels")
+    _dev(corr, "corr")
+    if corr.dim() != 1 or corr.numel() != g.V or not corr.is_contiguous():
+        raise ValueError(f"{what}: corr is a contiguous [V] tensor, V = {g.V}")
+    L = _lib.lib()
+    w = torch.empty_like(corr)
+    wsum = torch.empty(g.N, dtype=torch.float64, device=corr.device)
+    sizes = torch.empty(g.N, dtype=torch.int32, device=corr.device)
+    check(L.cwfa_footprint_select_f32(_p(corr), _host(g.boxes), _host(g.cores), _host(g.offsets), g.N, _f32(thr), _p(w), _p(wsum),
+                                      _p(sizes), _stream()), what)
+    return w, wsum, sizes

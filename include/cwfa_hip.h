@@ -1012,6 +1012,50 @@ int cwfa_reg_peak_f32(const float* c, int N, int H, int W, int64_t frame_stride,
 int cwfa_reg_shift(const void* in, int dtype, int N, int H, int W, int64_t frame_stride, const float* shifts, int mode, float fill,
                    void* out, void* stream);
 
+/* ---- neuron footprints: behind the detector, which voxels of a neuron's ROI box move with its centre once the
+ * signal shared with the surroundings is taken out, and the traces weighted by that.  x: volumes [T, D, H, W] fp32, contiguous
+ * volumes, t_stride >= D * H * W elements between them.  Box tables are HOST int32 [N][6] = {z0,z1,y0,y1,x0,x1}, half-open, inside the
+ * volume and below 2^31 voxels each (as cwfa_roi_means_f32); they are checked and travel in the kernel arguments, any N.  The state is
+ * ragged: offsets is HOST int64 [N + 1], offsets[0] = 0, offsets[n + 1] - offsets[n] = the volume of box n, V = offsets[N]; box n's
+ * voxels lie at offsets[n] in the box's own (z, y, x) linear order, so overlapping boxes share nothing.  Arguments are checked before
+ * any device work; nothing is allocated, nothing synchronises, no atomics.  N == 0 or T == 0: no launch, CWFA_OK.  Float64 arrays are
+ * 8-byte aligned, CWFA_E_ALIGN otherwise.  Every floating-point operation is rounded separately.
+ *
+ *   roi_mark:          occ [D, H, W] (device bytes) = 1 inside any box, 0 elsewhere (the call clears the map; every writer stores 1).
+ *   roi_weighted_sums: out[n][t] (double) = sum over box n of w[offsets[n] + i] * x[t, voxel i], each product exact in float64, added
+ *                      by one wave in a fixed tree.  w == NULL: the plain sum (offsets is then not read).  An empty box gives 0.
+ *   roi_shell_sums:    sums[n][t] (double) = the sum of x[t] over the voxels of outer[n] that are outside inner[n] and have occ == 0,
+ *                      by one workgroup in a fixed tree; counts[n] (int32) = their number (written when T >= 1).
+ *   footprint_update:  adds the chunk to the state x0 [V] (fp32), acc [4][V] (double: s1, s2, sc, su), ref [N][7] (double: c0, u0, e1,
+ *                      e2, g1, g2, eg).  c, u: DEVICE double [N][T], the seed and neuropil traces of the chunk (u == NULL: without
+ *                      neuropil; su, u0, g1, g2, eg are then written as 0.0 by the first chunk and kept).  With x0 the voxel's first
+ *                      sample ever seen, c0 / u0 the traces' first values, d = (double)x - (double)x0, e = c - c0, g = u - u0:
+ *                          s1 += d, s2 += d d, sc += d e, su += d g          e1 += e, e2 += e e, g1 += g, g2 += g g, eg += e g
+ *                      in time order from 0.0, the first chunk (first != 0, T >= 1) skipping its own first volume: the state after
+ *                      any chunking is bit for bit that of the whole series.  A thread owns a state voxel and walks the time axis.
+ *   footprint_corr:    corr[V] (fp32) from the state of T samples, a thread per state voxel, in float64:
+ *                          v_a = max(s2_a - s1_a s1_a / T, 0),  r_ab = den > 0 ? (s_ab - s1_a s1_b / T) / den : 0,  den = sqrt(v_a v_b)
+ *                      for the pairs voxel-seed (ie), voxel-neuropil (ig), seed-neuropil (eg); neuropil != 0:
+ *                          q = (1 - r_ig r_ig)(1 - r_eg r_eg),  r = q > 0 ? (r_ie - r_ig r_eg) / sqrt(q) : 0;     else r = r_ie.
+ *                      NaN, inf, a constant series and T = 1 give 0, never NaN.  Only offsets' monotony is checked (no boxes).
+ *   footprint_select:  above_i = corr_i >= thr (0 < thr <= 1); the footprint of box n is the set of above voxels connected through
+ *                      faces, inside the box, to an above voxel of cores[n] (HOST [N][6], inside its box).  w[V] = corr on the
+ *                      footprint, 0 elsewhere; size[n] (int32) its voxel count; wsum[n] (double) the sum of box n's w in the box's
+ *                      linear order from 0.0.  One workgroup per neuron with a byte per box voxel in the LDS, swept to the fixpoint:
+ *                      a box above CWFA_FOOTPRINT_SELECT_MAX voxels is refused with CWFA_E_SHAPE. */
+#define CWFA_FOOTPRINT_SELECT_MAX (1 << 15)
+int cwfa_roi_mark_u8(const int32_t* boxes, int N, uint8_t* occ, int D, int H, int W, void* stream);
+int cwfa_roi_weighted_sums_f32(const float* x, const int32_t* boxes, const int64_t* offsets, const float* w, double* out, int T, int D,
+                               int H, int W, int N, int64_t t_stride, void* stream);
+int cwfa_roi_shell_sums_f32(const float* x, const int32_t* outer, const int32_t* inner, const uint8_t* occ, double* sums, int32_t* counts,
+                            int T, int D, int H, int W, int N, int64_t t_stride, void* stream);
+int cwfa_footprint_update_f32(const float* x, const int32_t* boxes, const int64_t* offsets, const double* c, const double* u, float* x0,
+                              double* acc, double* ref, int T, int D, int H, int W, int N, int64_t t_stride, int first, void* stream);
+int cwfa_footprint_corr_f32(const double* acc, const double* ref, const int64_t* offsets, int N, int64_t T, int neuropil, float* corr,
+                            void* stream);
+int cwfa_footprint_select_f32(const float* corr, const int32_t* boxes, const int32_t* cores, const int64_t* offsets, int N, float thr,
+                              float* w, double* wsum, int32_t* size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
