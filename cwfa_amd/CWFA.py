@@ -21,7 +21,7 @@ __all__ = ["sample_z_truncated", "check_empty_depths", "evaluate_INN_forward", "
            "denormalise_prediction", "denormalise_ground_truth", "compute_INN_step_performance", "evaluate_step", "roi_boxes",
            "corr_coeff_3D", "truncated_normal_variance", "posterior_moments", "posterior_samples", "posterior_roi_means",
            "ActivityMap", "find_neurons", "read_neural_coordinates_from_file", "write_neural_coordinates_to_file",
-           "NeuronFootprints", "Footprints", "extract_traces"]
+           "NeuronFootprints", "Footprints", "extract_traces", "trace_baseline", "delta_f_over_f", "trace_noise", "infer_spikes"]
 
 
 def _no_grad_trunc_normal_(tensor, mean=0., std=1., a=-1., b=1.):
@@ -1013,6 +1013,93 @@ def extract_traces(volumes, footprints, geometry=None, alpha=0.7):
     sums, counts = ops.roi_shell_sums(volumes, geometry)
     Fnp = sums / counts.to(torch.float64)[:, None]
     return F, Fnp, torch.where(torch.isnan(Fnp), F, F - float(alpha) * Fnp)
+
+
+# ---- what a user reads from the traces: dF/F against a running-percentile baseline, a robust noise level
+# and spikes by exact AR(1) deconvolution.  float64 [N,T] on the device throughout; nothing is read back.
+def _window(half_window, percentile, what):
+    import operator
+    try:                                                                          # any integer type (numpy's too), no float, no bool
+        h = None if isinstance(half_window, bool) else operator.index(half_window)
+    except TypeError:
+        h = None
+    if h is None or h < 0:
+        raise ValueError(f"{what}: half_window is a non-negative integer number of samples, got {half_window!r}")
+    try:
+        p = None if isinstance(percentile, bool) else operator.index(percentile)
+    except TypeError:
+        p = None
+    if p is None or not 0 <= p <= 100:
+        raise ValueError(f"{what}: percentile is an integer in 0 .. 100, got {percentile!r}")
+    return h, p
+
+
+def trace_baseline(traces, half_window, percentile=8):
+    """The running-percentile baseline of ``traces`` (float64 device [N,T], or a view with a row stride): per sample the
+    ``(percentile * (m - 1)) // 100``-th smallest of the m samples within ``half_window`` of it, an element of the trace bit for bit
+    (no interpolation; NaN sorts last).  ``half_window >= T - 1`` gives the row's global quantile everywhere."""
+    h, p = _window(half_window, percentile, "trace_baseline")
+    return ops.sliding_quantile(ops._rows(traces, "trace_baseline")[0], h, p)
+
+
+def delta_f_over_f(F, Fnp=None, alpha=0.7, half_window=300, percentile=8, floor=0.0):
+    """``(dff, B, D)`` of the raw traces ``F`` and neuropil traces ``Fnp`` of ``extract_traces``: Fc = F - alpha Fnp (F where Fnp is
+    NaN or None), B and D the ``trace_baseline`` of Fc and of F, dff = (Fc - B) / max(D, floor) where that denominator is positive,
+    NaN elsewhere.  The denominator is the raw trace's baseline: the corrected one's can be zero or negative.  ``half_window`` is in
+    samples; the default suits 10 Hz recordings (a minute), set it from the frame rate."""
+    what = "delta_f_over_f"
+    h, p = _window(half_window, percentile, what)
+    floor = float(floor)
+    if not floor >= 0.0:
+        raise ValueError(f"{what}: floor = {floor} is negative")
+    F = ops._rows(F, what, "F")[0]
+    if Fnp is None:
+        Fc = F
+    else:
+        Fnp = ops._rows(Fnp, what, "Fnp")[0]
+        if Fnp.shape != F.shape:
+            raise ValueError(f"{what}: Fnp {tuple(Fnp.shape)} does not match F {tuple(F.shape)}")
+        Fc = torch.where(torch.isnan(Fnp), F, F - float(alpha) * Fnp)
+    B = ops.sliding_quantile(Fc, h, p)
+    D = B if Fnp is None else ops.sliding_quantile(F, h, p)
+    den = torch.clamp_min(D, floor)
+    return torch.where(den > 0, (Fc - B) / den, torch.full_like(den, float("nan"))), B, D
+
+
+def trace_noise(traces):
+    """float64 [N]: the noise level of every trace from its first differences d, sigma = 1.0483580825075305 * mad with
+    mad = lmed(|d - lmed(d)|) and lmed the element of rank (len - 1) // 2 -- 1 / (0.6744897501960817 sqrt 2) turns the median
+    absolute deviation of the difference of two samples into the standard deviation of one.  T < 2 gives NaN."""
+    x, N, T, _ = ops._rows(traces, "trace_noise")
+    if T < 2:
+        return torch.full((N,), float("nan"), dtype=torch.float64, device=x.device)
+    d = x[:, 1:] - x[:, :-1]
+    r = [(T - 2) // 2]
+    med = ops.trace_select(d, r)[0]
+    mad = ops.trace_select((d - med[:, None]).abs(), r)[0]
+    return mad * 1.0483580825075305
+
+
+def infer_spikes(traces, gamma, lam=None, lam_sigma=None):
+    """``(c, s, pools)``: the denoised calcium c and the spikes s >= 0 (float64 [N,T]) of every trace by exact non-negative AR(1)
+    deconvolution -- the minimiser of 1/2 sum (y - c)^2 + lam sum s with s_0 = c_0, s_t = c_t - gamma c_{t-1} (OASIS) -- and the
+    number of pools (int32 [N]).  ``gamma`` in [0, 1): the decay per sample, one for all rows.  Exactly one of ``lam`` (a float or a
+    float64 device [N] tensor) and ``lam_sigma`` (lam = lam_sigma * ``trace_noise(traces)``, which stays on the device) is given."""
+    what = "infer_spikes"
+    if (lam is None) == (lam_sigma is None):
+        raise ValueError(f"{what}: exactly one of lam and lam_sigma is given")
+    gamma = float(gamma)
+    if not 0.0 <= gamma < 1.0:
+        raise ValueError(f"{what}: gamma = {gamma} is not in [0, 1)")
+    x, N, T, _ = ops._rows(traces, what)
+    if lam_sigma is not None:
+        lam = float(lam_sigma) * trace_noise(x)
+    elif torch.is_tensor(lam):
+        if not lam.is_cuda or lam.dtype != torch.float64 or tuple(lam.shape) != (N,):
+            raise ValueError(f"{what}: lam is a float or a float64 [{N}] tensor on the HIP device, got {tuple(lam.shape)} {lam.dtype} on {lam.device}")
+    else:
+        lam = torch.full((N,), float(lam), dtype=torch.float64, device=x.device)
+    return ops.ar1_deconv(x, gamma, lam)
 
 
 def read_neural_coordinates_from_file(filename):

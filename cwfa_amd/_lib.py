@@ -228,6 +228,11 @@ SIGNATURES = {
     "cwfa_footprint_update_f32": (i, [p, p, p, p, p, p, p, p, i, i, i, i, i, i64, i, p]),
     "cwfa_footprint_corr_f32": (i, [p, p, p, i, i64, i, p, p]),
     "cwfa_footprint_select_f32": (i, [p, p, p, p, i, f, p, p, p, p]),
+    "cwfa_sliding_quantile_limits": (i, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "cwfa_sliding_quantile_f64": (i, [p, i, i, i64, i, i, p, i, p]),
+    "cwfa_trace_select_f64": (i, [p, i, i, i64, C.POINTER(C.c_int), i, p, p]),
+    "cwfa_ar1_deconv_workspace_bytes": (i64, [i, i]),
+    "cwfa_ar1_deconv_f64": (i, [p, i, i, i64, d, p, p, p, p, p, p, p]),
 }
 del i, i64, f, d, p
 

@@ -3011,3 +3011,89 @@ def footprint_select(corr, geometry, thr):
     check(L.cwfa_footprint_select_f32(_p(corr), _host(g.boxes), _host(g.cores), _host(g.offsets), g.N, _f32(thr), _p(w), _p(wsum),
                                       _p(sizes), _stream()), what)
     return w, wsum, sizes
+
+
+# ------------------------------------------------------------------------------------------------ trace post-processing
+def _rows(x, what, name="traces"):
+    """A float64 device [N, T] tensor with contiguous rows (T >= 1) as (tensor, N, T, row stride in elements): a view with a row
+    stride of at least T qualifies without a copy.  Anything else is refused, before any device work."""
+    if not torch.is_tensor(x):
+        raise TypeError(f"{what}: {name}: expected a torch.Tensor, got {type(x)}")
+    if x.dtype != torch.float64:
+        raise TypeError(f"{what}: {name}: expected float64, got {x.dtype}")
+    if x.dim() != 2 or x.shape[1] < 1:
+        raise ValueError(f"{what}: {name} is [N, T] with T >= 1, got {tuple(x.shape)}")
+    if not x.is_cuda:
+        raise RuntimeError(f"{what}: cwfa_amd runs on MI355X only -- got a {x.device} tensor (no CPU fallback exists)")
+    N, T = int(x.shape[0]), int(x.shape[1])
+    if N and ((T > 1 and x.stride(1) != 1) or (N > 1 and x.stride(0) < T)):
+        x = x.contiguous()
+    return x, N, T, (int(x.stride(0)) if N > 1 else T)
+
+
+def sliding_quantile_limits():
+    """(tile, max_half_lds): the outputs a workgroup of the LDS form of ``sliding_quantile`` owns, and the largest half window that
+    form takes.  Host only."""
+    tile, most = C.c_int(0), C.c_int(0)
+    check(_lib.lib().cwfa_sliding_quantile_limits(C.byref(tile), C.byref(most)), "sliding_quantile_limits")
+    return tile.value, most.value
+
+
+def sliding_quantile(x, half_window, percentile, form="auto"):
+    """float64 [N, T]: out[n, t] = the k-th smallest (from 0) of x[n, lo..hi], lo = max(0, t - h), hi = min(T - 1, t + h),
+    k = (p * (hi - lo)) // 100 -- an element of the series, bit for bit, without interpolation; -0 and +0 are one value (returned as
+    +0) and NaN sorts last.  ``x``: float64 device [N, T], rows contiguous, any row stride.  ``form``: "lds" (half windows up to
+    ``sliding_quantile_limits()[1]``), "stream" (any) or "auto"."""
+    what = "sliding_quantile"
+    if form not in _lib.SELECT_FORM:
+        raise ValueError(f"{what}: form is one of {sorted(_lib.SELECT_FORM)}, got {form!r}")
+    h, p = int(half_window), int(percentile)
+    if h != half_window or h < 0:
+        raise ValueError(f"{what}: the half window is a non-negative integer, got {half_window!r}")
+    if p != percentile or not 0 <= p <= 100:
+        raise ValueError(f"{what}: the percentile is an integer in 0 .. 100, got {percentile!r}")
+    x, N, T, stride = _rows(x, what, "x")
+    L = _lib.lib()
+    out = torch.empty(N, T, dtype=torch.float64, device=x.device)
+    check(L.cwfa_sliding_quantile_f64(_p(x), N, T, stride, min(h, 0x7fffffff), p, _p(out), _lib.SELECT_FORM[form], _stream()), what)
+    return out
+
+
+def trace_select(x, ranks):
+    """float64 [K, N]: out[k, n] = the ``ranks[k]``-th smallest (from 0) of row n of the float64 device [N, T] tensor ``x``, 1 to 4
+    ranks in 0 .. T - 1, in the order of ``sliding_quantile``: the row-major float64 twin of ``temporal_select``."""
+    what = "trace_select"
+    ranks = [int(r) for r in ranks]
+    if not 1 <= len(ranks) <= 4:
+        raise ValueError(f"{what}: 1 to 4 ranks, got {len(ranks)}")
+    x, N, T, stride = _rows(x, what, "x")
+    if any(r < 0 or r >= T for r in ranks):
+        raise ValueError(f"{what}: ranks {ranks} are not in 0 .. {T - 1}")
+    L = _lib.lib()
+    out = torch.empty(len(ranks), N, dtype=torch.float64, device=x.device)
+    check(L.cwfa_trace_select_f64(_p(x), N, T, stride, (C.c_int * len(ranks))(*ranks), len(ranks), _p(out), _stream()), what)
+    return out
+
+
+def ar1_deconv(y, gamma, lam):
+    """(c, s, pools): per row of the float64 device [N, T] tensor ``y`` the minimiser of 1/2 sum (y - c)^2 + lam sum s under
+    s_0 = c_0 >= 0, s_t = c_t - gamma c_{t-1} >= 0, by the pool algorithm (exact).  ``gamma``: a float in [0, 1); ``lam``: float64
+    device [N].  c, s: float64 [N, T]; pools: int32 [N].  A row with a non-finite sample, or a lam that is NaN, infinite or
+    negative, gets NaN in c and s and 0 pools."""
+    import numpy as np
+    what = "ar1_deconv"
+    gamma = float(gamma)
+    if not 0.0 <= gamma < 1.0:
+        raise ValueError(f"{what}: gamma = {gamma} is not in [0, 1)")
+    y, N, T, stride = _rows(y, what, "y")
+    lam = _vec(lam, N, "lam", what, torch.float64)
+    L = _lib.lib()
+    table = np.full(T + 1, gamma)
+    table[0] = 1.0
+    pw = torch.from_numpy(np.multiply.accumulate(table)).to(y.device)             # pw[k] = pw[k - 1] * gamma, rounded one by one
+    c = torch.empty(N, T, dtype=torch.float64, device=y.device)
+    s = torch.empty_like(c)
+    pools = torch.empty(N, dtype=torch.int32, device=y.device)
+    ws = torch.empty(max((int(L.cwfa_ar1_deconv_workspace_bytes(N, T)) + 7) // 8, 1), dtype=torch.float64, device=y.device)
+    check(L.cwfa_ar1_deconv_f64(_p(y), N, T, stride, gamma, _p(lam), _p(pw), _p(c), _p(s), _p(pools), _p(ws), _stream()), what)
+    return c, s, pools

@@ -1056,6 +1056,34 @@ int cwfa_footprint_corr_f32(const double* acc, const double* ref, const int64_t*
 int cwfa_footprint_select_f32(const float* corr, const int32_t* boxes, const int32_t* cores, const int64_t* offsets, int N, float thr,
                               float* w, double* wsum, int32_t* size, void* stream);
 
+/* ---- trace post-processing: behind extract_traces, on float64 rows x [N][T] with `stride` >= T elements between
+ * rows (DEVICE, 8-byte aligned, CWFA_E_ALIGN otherwise).  N >= 0, T >= 1 (CWFA_E_SHAPE otherwise); arguments are checked before any
+ * device work, nothing is allocated, nothing synchronises, no atomics; N == 0: no launch, CWFA_OK.  Every float64 operation is rounded
+ * separately.  The order is that of cwfa_temporal_select widened to 64 bits: the unsigned image of the float64 bits of v + 0.0 (-0
+ * and +0 are one value, returned as +0); every NaN sorts last and is returned as 0x7ff8000000000000.  A result of the two selections
+ * is an element of the series, bit for bit.
+ *
+ *   sliding_quantile:  out[n][t] (contiguous [N][T]) = the k-th smallest (from 0) of x[n][lo .. hi], lo = max(0, t - h),
+ *                      hi = min(T - 1, t + h), k = (p * (hi - lo)) / 100 in integers; h >= 0, 0 <= p <= 100 (CWFA_E_INVAL otherwise).
+ *                      form 0: chosen here; 1: a workgroup stages a segment of `tile` outputs and its halo in the LDS, ranks the
+ *                      staged keys and bisects on 16-bit ranks, h <= max_half_lds (CWFA_E_SHAPE beyond); 2: a thread per output
+ *                      counts its window from memory, any h.  sliding_quantile_limits (host only) reports tile and max_half_lds.
+ *   trace_select:      out[k][n] (double [K][N]) = the ranks[k]-th smallest of row n; ranks: HOST int [K], 1 <= K <= 4, each in
+ *                      0 .. T - 1 (CWFA_E_INVAL otherwise).  One workgroup per row.
+ *   ar1_deconv:        per row the minimiser of 1/2 sum (y_t - c_t)^2 + lam sum s_t under s_0 = c_0 >= 0, s_t = c_t - gamma c_{t-1} >= 0,
+ *                      by the pool algorithm in the operation order of DESIGN.md section 28.1.  0 <= gamma < 1 (CWFA_E_INVAL
+ *                      otherwise, NaN included); lam: DEVICE double [N]; pw: DEVICE double [T + 1], pw[0] = 1, pw[k] = pw[k-1] * gamma
+ *                      (the caller's table); c, s: double [N][T] contiguous; pools: int32 [N], the number of pools of the row.  A row
+ *                      with a non-finite sample, or a lam that is NaN, infinite or negative, gets NaN in c and s and pools = 0.  A
+ *                      thread owns a row; ws: ar1_deconv_workspace_bytes(N, T) DEVICE bytes, 8-byte aligned: the pool stacks, transposed
+ *                      (20 N T bytes rounded up to a multiple of 8; the kernel writes nothing behind them). */
+int cwfa_sliding_quantile_limits(int* tile, int* max_half_lds);
+int cwfa_sliding_quantile_f64(const double* x, int N, int T, int64_t stride, int h, int p, double* out, int form, void* stream);
+int cwfa_trace_select_f64(const double* x, int N, int T, int64_t stride, const int* ranks, int K, double* out, void* stream);
+int64_t cwfa_ar1_deconv_workspace_bytes(int N, int T);
+int cwfa_ar1_deconv_f64(const double* y, int N, int T, int64_t stride, double gamma, const double* lam, const double* pw, double* c,
+                        double* s, int32_t* pools, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
