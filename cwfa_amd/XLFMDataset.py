@@ -146,8 +146,17 @@ def _reg_args(frames, template, max_shift, taper, smooth, eps, chunk, what):
     return my, mx, taper
 
 
+def _subpixel_arg(subpixel, upsample, what):
+    """(dft, upsample): ``subpixel`` is True / False (the parabola through the integer peak, or nothing) or "dft"."""
+    if isinstance(subpixel, str):
+        if subpixel != "dft":
+            raise ValueError(f"{what}: subpixel is True, False or 'dft', got {subpixel!r}")
+        return True, ops._count(upsample, "upsample", what)
+    return False, None
+
+
 @amp_region
-def estimate_shifts(frames, template, max_shift=16, taper=None, smooth=0.0, eps=1e-5, subpixel=True, chunk=16):
+def estimate_shifts(frames, template, max_shift=16, taper=None, smooth=0.0, eps=1e-5, subpixel=True, chunk=16, upsample=16):
     """(shifts float32 [N,2], peak float32 [N]) on the device: the rigid displacement (dy, dx) of every frame of a contiguous [N,H,W]
     fp32 / fp16 device stack against the float32 ``template`` [H,W] by phase correlation.  A frame that is
     the template displaced by d (frame[p] = template[p - d]) reports d; ``shift_frames`` undoes it.  ``peak`` is the correlation
@@ -156,8 +165,12 @@ def estimate_shifts(frames, template, max_shift=16, taper=None, smooth=0.0, eps=
     Both get a raised-cosine edge taper of ``taper`` pixels (None: min(16, side / 8); 0: none); the spectra are whitened
     separately, F / (|F| + ``eps``), multiplied, optionally low-passed by a Gaussian of ``smooth`` pixels, and transformed back;
     the peak is searched over |dy| <= my, |dx| <= mx (``max_shift``: an int or (my, mx)) and, with ``subpixel``, refined by a
-    parabola per axis.  The frames go through in chunks of ``chunk`` (their spectra are chunk x H x (W/2+1) x 8 bytes)."""
+    parabola per axis.  ``subpixel="dft"``: the correlation is instead evaluated from the whitened spectra on a grid of
+    1 / ``upsample`` px over +-1 px around the integer peak (an up-sampled DFT in float64, section 26.5) and the parabola is fitted
+    on that grid; ``peak`` is then the fine maximum.  The frames go through in chunks of ``chunk`` (their spectra are
+    chunk x H x (W/2+1) x 8 bytes)."""
     my, mx, taper = _reg_args(frames, template, max_shift, taper, smooth, eps, chunk, "estimate_shifts")
+    dft, upsample = _subpixel_arg(subpixel, upsample, "estimate_shifts")
     if template is None:
         raise ValueError("estimate_shifts: a template is needed")
     N, H, W = (int(s) for s in frames.shape)
@@ -182,7 +195,9 @@ def estimate_shifts(frames, template, max_shift=16, taper=None, smooth=0.0, eps=
         e = min(s + chunk, N)
         F = torch.fft.rfft2(ops.reg_window(frames[s:e], wy, wx, out=buf[:e - s])).contiguous()  # (a no-op where rocFFT's layout is dense)
         corr = torch.fft.irfft2(ops.reg_whiten(F, Wt, eps, out=F), s=(H, W))
-        ops.reg_peak(corr, (my, mx), subpixel, out=(shifts[s:e], ipeak[s:e], peak[s:e]))
+        ops.reg_peak(corr, (my, mx), subpixel and not dft, out=(shifts[s:e], ipeak[s:e], peak[s:e]))
+        if dft:                                                       # F is read again: irfft2 leaves its input alone (section 26.5)
+            ops.reg_fine_peak(ops.reg_upsample(F, ipeak[s:e], (H, W), upsample), ipeak[s:e], upsample, out=(shifts[s:e], peak[s:e]))
     return shifts, peak
 
 
@@ -204,13 +219,14 @@ def shift_frames(frames, shifts, mode="bilinear", fill=0.0, out=None):
 
 @amp_region
 def register_frames(frames, template=None, n_iter=1, max_shift=16, subpixel=True, mode="bilinear", taper=None, smooth=0.0, eps=1e-5,
-                    chunk=16, fill=0.0, out=None):
+                    chunk=16, fill=0.0, out=None, upsample=16):
     """Rigid registration of a contiguous [N,H,W] fp32 / fp16 device stack:
     ``Registration(frames, shifts, peak, template)`` with frames[n] = the input's frame n moved back by shifts[n].  ``template``
     None: the per-pixel temporal median of the stack.  ``n_iter`` > 1: the template becomes the median of the registered stack and
     the shifts are estimated again FROM THE ORIGINAL FRAMES, so interpolation never compounds.  The other arguments are those of
     ``estimate_shifts`` and ``shift_frames``.  Nothing is read back."""
     _reg_args(frames, template, max_shift, taper, smooth, eps, chunk, "register_frames")
+    _subpixel_arg(subpixel, upsample, "register_frames")
     if int(n_iter) < 1:
         raise ValueError(f"register_frames: n_iter must be at least 1, got {n_iter}")
     if mode not in ("bilinear", "nearest"):
@@ -223,7 +239,8 @@ def register_frames(frames, template=None, n_iter=1, max_shift=16, subpixel=True
     median = lambda x: ops.temporal_select(x, [quantile_rank(0.5, N)])[0]
     tmpl = median(frames) if template is None else template
     for it in range(int(n_iter)):
-        shifts, peak = estimate_shifts(frames, tmpl, max_shift=max_shift, taper=taper, smooth=smooth, eps=eps, subpixel=subpixel, chunk=chunk)
+        shifts, peak = estimate_shifts(frames, tmpl, max_shift=max_shift, taper=taper, smooth=smooth, eps=eps, subpixel=subpixel, chunk=chunk,
+                                      upsample=upsample)
         out = shift_frames(frames, shifts, mode=mode, fill=fill, out=out)
         if it + 1 < int(n_iter):
             tmpl = median(out)

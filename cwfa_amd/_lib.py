@@ -222,6 +222,9 @@ SIGNATURES = {
     "cwfa_reg_whiten_c64": (i, [p, p, i, i64, f, p, p]),
     "cwfa_reg_peak_f32": (i, [p, i, i, i, i64, i, i, i, p, p, p, p]),
     "cwfa_reg_shift": (i, [p, i, i, i, i, i64, p, i, f, p, p]),
+    "cwfa_reg_upsample_workspace_bytes": (i64, [i, i, i, i]),
+    "cwfa_reg_upsample_c64": (i, [p, i, i, i, i64, p, i, i, p, p, p, p, p]),
+    "cwfa_reg_fine_peak_f64": (i, [p, p, i, i, i, i, p, p, p]),
     "cwfa_roi_mark_u8": (i, [p, i, p, i, i, i, p]),
     "cwfa_roi_weighted_sums_f32": (i, [p, p, p, p, p, i, i, i, i, i, i64, p]),
     "cwfa_roi_shell_sums_f32": (i, [p, p, p, p, p, p, i, i, i, i, i, i64, p]),

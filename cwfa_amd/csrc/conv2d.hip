@@ -658,6 +658,7 @@ int launch(const ConvParams& p, int epi, hipStream_t st) {
 int g_cwfa_split_xcd_map = 1;
 int g_cwfa_split_rows16 = 1;
 extern int g_cwfa_mip3_ablate;          // eval_ops.hip ("mip3_ablate" option)
+extern int g_cwfa_reg_upsample_stages;  // register_ops.hip ("reg_upsample_stages" option)
 namespace {
 
 int fill_params(ConvParams& p, const char* name, const float* x, const float* w_packed, float* y, int B, int Cin, int H,
@@ -1019,6 +1020,11 @@ extern "C" int cwfa_set_option(const char* name, int value) {
     if (strcmp(name, "mip3_ablate") == 0) {         // (measurement only) bits 0..2: drop the over-depth / over-H / over-W reduction of cwfa_mip3_f32
         CWFA_REQUIRE(value >= 0 && value <= 7, CWFA_E_INVAL, "cwfa_set_option: mip3_ablate is a mask of bits 0..2");
         g_cwfa_mip3_ablate = value;
+        return CWFA_OK;
+    }
+    if (strcmp(name, "reg_upsample_stages") == 0) { // (measurement only) bits 0..2: launch the twiddle / row / column kernel of cwfa_reg_upsample_c64
+        CWFA_REQUIRE(value >= 0 && value <= 7, CWFA_E_INVAL, "cwfa_set_option: reg_upsample_stages is a mask of bits 0..2");
+        g_cwfa_reg_upsample_stages = value;
         return CWFA_OK;
     }
     if (strcmp(name, "split3x3_rows16") == 0) {     // (ablation) 0: the 64-channel tiling of the split 3x3 kernel always on 8-row tiles

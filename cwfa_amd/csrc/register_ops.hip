@@ -2,7 +2,8 @@
 // against a template, an integer peak in a bounded window with parabolic sub-pixel refinement, and resampling.  rocFFT (through
 // torch.fft) does the transforms; the four passes around them are here: the edge taper (rwin_*), the whitened cross-power
 // (rwht_*), the peak (rpeak_*) and the resampling (rshift_*).  The shifts stay on the device from the peak kernel to the resampling
-// kernel.  Built with -ffp-contract=off; the products, sums and differences the restatement (tests/register_ref.py) counts are
+// kernel.  Behind them the up-sampled DFT that refines the peak from the whitened spectra (rups_*, rfp_*; section 26.5).  Built with
+// -ffp-contract=off; the products, sums and differences the restatement (tests/register_ref.py) counts are
 // spelled with the __f*_rn intrinsics all the same, the square root and the divisions with sqrtf and / (see rwht_one).
 #include <math.h>
 #include <type_traits>
@@ -345,5 +346,285 @@ extern "C" int cwfa_reg_shift(const void* in, int dtype, int N, int H, int W, in
     else { if (dtype) RSHIFT_LAUNCH(1, true); else RSHIFT_LAUNCH(1, false); }
 #undef RSHIFT_LAUNCH
     CWFA_LAUNCH_CHECK("cwfa_reg_shift");
+    return CWFA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the up-sampled DFT (section 26.5)
+// The trigonometric interpolant of the correlation on the fine grid y = py + j / u, x = px + j / u, j = -r .. r (U = 2 r + 1), from
+// the whitened cross-power R that irfft2 also reads.  Three kernels, all float64, every product and sum rounded on its own:
+//   rups_twiddle  Tx[n, kx, j] = w[kx] root_x[(kx m_j) mod (W u)],  Ty[n, ky, j] = root_y[(s(ky) m_j) mod (H u)], m_j = p u + j - r
+//                 reduced in integers; the Nyquist column / row keep the real part only; w = 1, 2, .., 2, (1) is exact
+//   rups_rows     E[n, ky, j] = sum over kx = 0 .. K - 1, in that order, of R[n, ky, kx] * Tx[n, kx, j]            (the hot pass)
+//   rups_cols     C[n, jy, jx] = (sum over ky of Re(Ty[n, ky, jy] * E[n, ky, jx])) * (1 / (H W)), the ky axis in RUPS_SEG segments of
+//                 ceil(H / RUPS_SEG) rows, each summed in order from 0.0, the segments then added in order
+// The root tables are the caller's (ops.reg_roots): root[k] = exp(2 pi i k / M), k = 0 .. M - 1, interleaved doubles.
+// rups_rows: a workgroup owns G * RUPS_RT rows of one frame and a tile of fine columns; a thread owns one fine column and RUPS_RT
+// rows: RUPS_RT complex accumulators in registers, one 16-byte twiddle load (coalesced along j) and RUPS_RT broadcast LDS reads per
+// kx.  The rows are staged through the LDS RUPS_KC bins at a time, widened to float64 once, read from memory once, coalesced.
+#define RUPS_RT 8
+#define RUPS_KC 32
+#define RUPS_GMAX 8
+#define RUPS_SEG 8
+#define RUPS_JT 32
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+__global__ __launch_bounds__(256) void rups_twiddle_kernel(const int* __restrict__ ipeak, int H, int W, int u, int r, const f64x2* __restrict__ rootx,
+                                                           const f64x2* __restrict__ rooty, f64x2* __restrict__ Tx, f64x2* __restrict__ Ty) {
+    const int K = W / 2 + 1, U = 2 * r + 1;
+    const int n = blockIdx.y;
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t nx = (int64_t)K * U, ny = (int64_t)H * U;
+    if (q >= nx + ny) return;
+    const bool isx = q < nx;
+    const int64_t e = isx ? q : q - nx;
+    const int k = (int)(e / U), j = (int)(e - (int64_t)k * U);
+    const int64_t M = (int64_t)(isx ? W : H) * u;                     // < 2^31
+    int64_t m = ((int64_t)ipeak[2 * n + (isx ? 1 : 0)] * u + (j - r)) % M;
+    m = m < 0 ? m + M : m;
+    const int size = isx ? W : H;
+    const int64_t s = isx || 2 * (int64_t)k < H ? k : (int64_t)k - H;
+    int64_t idx = (s * m) % M;                                        // |s| < 2^31, m < 2^31
+    idx = idx < 0 ? idx + M : idx;
+    f64x2 t = (isx ? rootx : rooty)[idx];
+    const bool nyq = (size & 1) == 0 && k == size / 2;
+    if (nyq) t[1] = 0.0;
+    if (isx && k != 0 && !nyq) t = f64x2{2.0 * t[0], 2.0 * t[1]};
+    if (isx) Tx[(int64_t)n * nx + e] = t;
+    else Ty[(int64_t)n * ny + e] = t;
+}
+
+__global__ __launch_bounds__(256) void rups_rows_kernel(const f32x2* __restrict__ R, int H, int K, int64_t fs, int U, int UT, int G,
+                                                        const f64x2* __restrict__ Tx, f64x2* __restrict__ E) {
+    __shared__ f64x2 z[RUPS_GMAX * RUPS_RT * RUPS_KC];                // 32 KiB
+    const int n = blockIdx.z;
+    const int rows = G * RUPS_RT;
+    const int row0 = blockIdx.x * rows;
+    const int g = threadIdx.x / UT, jl = threadIdx.x - g * UT;
+    const int j = blockIdx.y * UT + jl;
+    const bool active = g < G && j < U;
+    const f32x2* Rn = R + (int64_t)n * fs;
+    const f64x2* Tn = Tx + (int64_t)n * K * U;
+    double ar[RUPS_RT], ai[RUPS_RT];
+#pragma unroll
+    for (int i = 0; i < RUPS_RT; ++i) ar[i] = 0.0, ai[i] = 0.0;
+    // both streams run one step ahead in registers: the next tile of R while this one is summed, the next four twiddles while these
+    // four are used (a wave has few neighbours to hide a load behind: the grid is a few workgroups per CU)
+    const int sk = threadIdx.x & (RUPS_KC - 1), sr = threadIdx.x / RUPS_KC;
+    constexpr int SN = RUPS_GMAX * RUPS_RT * RUPS_KC / 256;
+    f32x2 stage[SN];
+    auto stage_load = [&](int k0) {
+#pragma unroll
+        for (int s = 0; s < SN; ++s) {
+            const int rr = sr + s * (256 / RUPS_KC), y = row0 + rr, k = k0 + sk;
+            stage[s] = rr < rows && y < H && k < K ? Rn[(int64_t)y * K + k] : f32x2{0.f, 0.f};
+        }
+    };
+    auto twiddle = [&](int k) { return Tn[(int64_t)(k < K ? k : K - 1) * U + j]; };     // past the end: the last row again, not used
+    stage_load(0);
+    f64x2 tn[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) tn[q] = active ? twiddle(q) : f64x2{0.0, 0.0};
+    for (int k0 = 0; k0 < K; k0 += RUPS_KC) {
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < SN; ++s) {
+            const int rr = sr + s * (256 / RUPS_KC);
+            if (rr < rows) z[rr * RUPS_KC + sk] = f64x2{(double)stage[s][0], (double)stage[s][1]};
+        }
+        __syncthreads();
+        if (k0 + RUPS_KC < K) stage_load(k0 + RUPS_KC);
+        if (active) {
+            const int kn = K - k0 < RUPS_KC ? K - k0 : RUPS_KC;
+            const f64x2* zr = z + g * RUPS_RT * RUPS_KC;
+            for (int kk = 0; kk < kn; kk += 4) {                      // RUPS_KC is a multiple of 4: the groups run on across tiles
+                f64x2 t[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) t[q] = tn[q];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) tn[q] = twiddle(k0 + kk + 4 + q);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if (kk + q >= kn) break;
+#pragma unroll
+                    for (int i = 0; i < RUPS_RT; ++i) {
+                        const f64x2 v = zr[i * RUPS_KC + kk + q];
+                        ar[i] = ar[i] + (v[0] * t[q][0] - v[1] * t[q][1]);
+                        ai[i] = ai[i] + (v[0] * t[q][1] + v[1] * t[q][0]);
+                    }
+                }
+            }
+        }
+    }
+    if (!active) return;
+    f64x2* En = E + (int64_t)n * H * U;
+#pragma unroll
+    for (int i = 0; i < RUPS_RT; ++i) {
+        const int y = row0 + g * RUPS_RT + i;
+        if (y < H) En[(int64_t)y * U + j] = f64x2{ar[i], ai[i]};
+    }
+}
+
+__global__ __launch_bounds__(RUPS_JT* RUPS_SEG) void rups_cols_kernel(const f64x2* __restrict__ E, const f64x2* __restrict__ Ty, int H, int U, double inv,
+                                                                       double* __restrict__ C) {
+    __shared__ double part[RUPS_SEG][RUPS_JT];
+    const int n = blockIdx.z, jy = blockIdx.y;
+    const int jl = threadIdx.x & (RUPS_JT - 1), s = threadIdx.x / RUPS_JT;
+    const int jx = blockIdx.x * RUPS_JT + jl;
+    const int L = (H + RUPS_SEG - 1) / RUPS_SEG;
+    const int y0 = s * L < H ? s * L : H, y1 = H - y0 < L ? H : y0 + L;   // H < 2^30
+    const f64x2* En = E + (int64_t)n * H * U;
+    const f64x2* Tn = Ty + (int64_t)n * H * U;
+    double a = 0.0;
+    if (jx < U)
+#pragma unroll 4
+        for (int y = y0; y < y1; ++y) {
+            const f64x2 t = Tn[(int64_t)y * U + jy], v = En[(int64_t)y * U + jx];
+            a = a + (t[0] * v[0] - t[1] * v[1]);
+        }
+    part[s][jl] = a;
+    __syncthreads();
+    if (s != 0 || jx >= U) return;
+    double c = 0.0;
+#pragma unroll
+    for (int i = 0; i < RUPS_SEG; ++i) c = c + part[i][jl];
+    C[((int64_t)n * U + jy) * U + jx] = c * inv;
+}
+
+// "reg_upsample_stages" option (measurement only: with a bit cleared the map is not computed): bit 0 launches the twiddle kernel, bit 1
+// the row kernel, bit 2 the column kernel
+int g_cwfa_reg_upsample_stages = 7;
+
+// the fine grid must stay an int index space and the tables' indices ints
+static inline bool rups_sizes_ok(int H, int W, int u, int r) {
+    return H >= 1 && W >= 1 && u >= 1 && r >= 1 && H < (1 << 30) && W < (1 << 30) && (int64_t)H * W < ((int64_t)1 << 31) &&
+           (int64_t)H * u < ((int64_t)1 << 31) && (int64_t)W * u < ((int64_t)1 << 31) && r < (1 << 14);        // U * U < 2^31
+}
+
+extern "C" int64_t cwfa_reg_upsample_workspace_bytes(int N, int H, int W, int r) {
+    if (N < 0 || !rups_sizes_ok(H, W, 1, r)) return -1;
+    const int64_t U = 2 * (int64_t)r + 1, K = W / 2 + 1;
+    return (int64_t)N * (K * U + 2 * (int64_t)H * U) * 16;            // Tx, Ty, E
+}
+
+extern "C" int cwfa_reg_upsample_c64(const void* R, int N, int H, int W, int64_t frame_stride, const int* ipeak, int u, int r, const double* rootx,
+                                     const double* rooty, double* C, void* ws, void* stream) {
+    CWFA_REQUIRE(R && ipeak && rootx && rooty && C && ws, CWFA_E_INVAL, "cwfa_reg_upsample_c64: null pointer");
+    CWFA_REQUIRE(N >= 0, CWFA_E_SHAPE, "cwfa_reg_upsample_c64: negative size");
+    CWFA_REQUIRE(H >= 1 && W >= 1, CWFA_E_SHAPE, "cwfa_reg_upsample_c64: a frame of %d x %d", H, W);
+    CWFA_REQUIRE(u >= 1 && r >= 1, CWFA_E_INVAL, "cwfa_reg_upsample_c64: the factor and the radius are at least 1, got %d and %d", u, r);
+    CWFA_REQUIRE(rups_sizes_ok(H, W, u, r), CWFA_E_SHAPE, "cwfa_reg_upsample_c64: %d x %d at factor %d, radius %d is too large", H, W, u, r);
+    const int K = W / 2 + 1, U = 2 * r + 1;
+    CWFA_REQUIRE(frame_stride >= (int64_t)H * K, CWFA_E_INVAL, "cwfa_reg_upsample_c64: frame stride smaller than a frame's spectrum");
+    CWFA_REQUIRE(((reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(ipeak) | reinterpret_cast<uintptr_t>(C)) & 7u) == 0 &&
+                     ((reinterpret_cast<uintptr_t>(rootx) | reinterpret_cast<uintptr_t>(rooty) | reinterpret_cast<uintptr_t>(ws)) & 15u) == 0,
+                 CWFA_E_ALIGN, "cwfa_reg_upsample_c64: R, ipeak and C must be 8-byte aligned, the root tables and the workspace 16-byte aligned");
+    if (N == 0) return CWFA_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const f64x2 *rx = reinterpret_cast<const f64x2*>(rootx), *ry = reinterpret_cast<const f64x2*>(rooty);
+    const int UT = U < 256 ? U : 256, G = 256 / UT < RUPS_GMAX ? 256 / UT : RUPS_GMAX;
+    const double inv = 1.0 / (double)((int64_t)H * W);
+    const int64_t per = ((int64_t)K + H) * U;
+    for (int n0 = 0; n0 < N; n0 += 65535) {                           // a grid axis holds 65535 frames
+        const int nb = N - n0 < 65535 ? N - n0 : 65535;
+        f64x2* Tx = static_cast<f64x2*>(ws) + (int64_t)n0 * K * U;     // the three arrays in turn, each [N, ..]
+        f64x2* Ty = static_cast<f64x2*>(ws) + (int64_t)N * K * U + (int64_t)n0 * H * U;
+        f64x2* E = static_cast<f64x2*>(ws) + (int64_t)N * ((int64_t)K + H) * U + (int64_t)n0 * H * U;
+        const f32x2* Rb = static_cast<const f32x2*>(R) + (int64_t)n0 * frame_stride;
+        if (g_cwfa_reg_upsample_stages & 1)
+            hipLaunchKernelGGL(rups_twiddle_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)nb), dim3(256), 0, st, ipeak + 2 * (int64_t)n0, H, W, u, r,
+                               rx, ry, Tx, Ty);
+        if (g_cwfa_reg_upsample_stages & 2)
+            hipLaunchKernelGGL(rups_rows_kernel, dim3((unsigned)((H + G * RUPS_RT - 1) / (G * RUPS_RT)), (unsigned)((U + UT - 1) / UT), (unsigned)nb), dim3(256),
+                               0, st, Rb, H, K, frame_stride, U, UT, G, Tx, E);
+        if (g_cwfa_reg_upsample_stages & 4)
+            hipLaunchKernelGGL(rups_cols_kernel, dim3((unsigned)((U + RUPS_JT - 1) / RUPS_JT), (unsigned)U, (unsigned)nb), dim3(RUPS_JT * RUPS_SEG), 0, st, E,
+                           Ty, H, U, inv, C + (int64_t)n0 * U * U);
+    }
+    CWFA_LAUNCH_CHECK("cwfa_reg_upsample_c64");
+    return CWFA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the fine peak
+// One workgroup per frame over the fine map C [U, U] (float64): the maximum under the order of the integer peak widened to 64 bits
+// (the unsigned image of the bits of c + 0.0, NaN 0, ties to the lowest row-major index), reduced like rpeak_kernel; thread 0 fits
+// the float64 parabola per axis where the maximum is not on the grid's border along it.
+struct rfp_best {
+    uint64_t o;
+    unsigned i;
+};
+__device__ __forceinline__ uint64_t rfp_ord(double v) {
+    uint64_t b = __builtin_bit_cast(uint64_t, v);
+    b = b == 0x8000000000000000ull ? 0ull : b;
+    return v != v ? 0ull : ((b >> 63) ? ~b : (b | 0x8000000000000000ull));
+}
+__device__ __forceinline__ rfp_best rfp_max(rfp_best a, rfp_best b) { return (b.o > a.o || (b.o == a.o && b.i < a.i)) ? b : a; }
+
+__device__ __forceinline__ double rfp_delta(double a, double b, double c) {
+    const double den = (a - 2.0 * b) + c;
+    double d = (0.5 * (a - c)) / den;
+    if (!(den < 0.0) || !(fabs(d) <= 1.7976931348623157e308)) d = 0.0;
+    return d < -0.5 ? -0.5 : (d > 0.5 ? 0.5 : d);
+}
+
+__global__ __launch_bounds__(RPEAK_THREADS) void rfp_kernel(const double* __restrict__ C, const int* __restrict__ ipeak, int U, int u, int keep,
+                                                            float* __restrict__ shifts, float* __restrict__ peak) {
+    __shared__ uint64_t bo[RPEAK_THREADS / 64];
+    __shared__ unsigned bi[RPEAK_THREADS / 64];
+    __shared__ int finite[RPEAK_THREADS / 64];
+    const int n = blockIdx.x;
+    if (keep) {                                                       // uniform over the workgroup
+        const float p = peak[n];
+        if (p != p) return;
+    }
+    const double* cn = C + (int64_t)n * U * U;
+    const unsigned cells = (unsigned)U * (unsigned)U;
+    rfp_best k = {0ull, 0xFFFFFFFFu};
+    bool fin = false;
+    for (unsigned i = threadIdx.x; i < cells; i += RPEAK_THREADS) {
+        const double v = cn[i];
+        k = rfp_max(k, rfp_best{rfp_ord(v), i});
+        fin = fin || fabs(v) < (double)INFINITY;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) k = rfp_max(k, rfp_best{__shfl_xor(k.o, o, 64), (unsigned)__shfl_xor((int)k.i, o, 64)});
+    const bool wave_fin = __ballot(fin) != 0;
+    if ((threadIdx.x & 63) == 0) bo[threadIdx.x >> 6] = k.o, bi[threadIdx.x >> 6] = k.i, finite[threadIdx.x >> 6] = wave_fin ? 1 : 0;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    int any = 0;
+#pragma unroll
+    for (int w = 0; w < RPEAK_THREADS / 64; ++w) {
+        k = rfp_max(k, rfp_best{bo[w], bi[w]});
+        any |= finite[w];
+    }
+    const int py = ipeak[2 * n], px = ipeak[2 * n + 1];
+    if (!any) {                                                       // no finite value on the fine grid: the integer peak
+        shifts[2 * n] = (float)(double)py, shifts[2 * n + 1] = (float)(double)px;
+        peak[n] = __builtin_nanf("");
+        return;
+    }
+    const int r = U / 2;
+    const int jy = (int)(k.i / (unsigned)U), jx = (int)(k.i - (unsigned)jy * (unsigned)U);
+    const double c0 = cn[k.i];
+    double dy = 0.0, dx = 0.0;
+    if (jy > 0 && jy < U - 1) dy = rfp_delta(cn[k.i - U], c0, cn[k.i + U]);
+    if (jx > 0 && jx < U - 1) dx = rfp_delta(cn[k.i - 1], c0, cn[k.i + 1]);
+    shifts[2 * n] = (float)((double)py + ((double)(jy - r) + dy) / (double)u);
+    shifts[2 * n + 1] = (float)((double)px + ((double)(jx - r) + dx) / (double)u);
+    peak[n] = (float)c0;
+}
+
+extern "C" int cwfa_reg_fine_peak_f64(const double* C, const int* ipeak, int N, int U, int u, int keep, float* shifts, float* peak, void* stream) {
+    CWFA_REQUIRE(C && ipeak && shifts && peak, CWFA_E_INVAL, "cwfa_reg_fine_peak_f64: null pointer");
+    CWFA_REQUIRE(keep == 0 || keep == 1, CWFA_E_INVAL, "cwfa_reg_fine_peak_f64: keep is 0 or 1");
+    CWFA_REQUIRE(N >= 0, CWFA_E_SHAPE, "cwfa_reg_fine_peak_f64: negative size");
+    CWFA_REQUIRE(u >= 1, CWFA_E_INVAL, "cwfa_reg_fine_peak_f64: the factor is at least 1, got %d", u);
+    CWFA_REQUIRE(U >= 3 && (U & 1) == 1 && U < (1 << 15), CWFA_E_SHAPE, "cwfa_reg_fine_peak_f64: the fine grid has 2 r + 1 points a side, 1 <= r < 2^14, got %d", U);
+    CWFA_REQUIRE(((reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(shifts) | reinterpret_cast<uintptr_t>(ipeak)) & 7u) == 0 &&
+                     (reinterpret_cast<uintptr_t>(peak) & 3u) == 0,
+                 CWFA_E_ALIGN, "cwfa_reg_fine_peak_f64: C, shifts and ipeak must be 8-byte aligned, peak 4-byte aligned");
+    if (N == 0) return CWFA_OK;
+    hipLaunchKernelGGL(rfp_kernel, dim3((unsigned)N), dim3(RPEAK_THREADS), 0, (hipStream_t)stream, C, ipeak, U, u, keep, shifts, peak);
+    CWFA_LAUNCH_CHECK("cwfa_reg_fine_peak_f64");
     return CWFA_OK;
 }

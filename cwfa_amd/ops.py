@@ -2757,6 +2757,147 @@ def reg_peak(corr, max_shift, subpixel=True, out=None):
     return shifts, ipeak, peak
 
 
+def reg_roots(M):
+    """float64 [M, 2] on the CPU: (cos, sin)(2 pi k / M), k = 0 .. M - 1, the root table of ``reg_upsample``.  The angle is reduced
+    to the first octant in integers -- pi p / q with p = 2 k, q = M, mirrored at pi, pi / 2 and pi / 4 -- and only then formed in
+    float64 as fl(fl(pi * p) / q); ``math.cos`` and ``math.sin`` of that, swapped and signed by the mirrors."""
+    import math
+    M = int(M)
+    rows = []
+    for k in range(M):
+        p, q, sc, ss = 2 * k, M, 1.0, 1.0
+        if p > q:
+            p, ss = 2 * q - p, -1.0
+        if 2 * p > q:
+            p, sc = q - p, -1.0
+        swap = 4 * p > q
+        if swap:
+            p, q = q - 2 * p, 2 * q
+        t = math.pi * p / q
+        c, s = (math.sin(t), math.cos(t)) if swap else (math.cos(t), math.sin(t))
+        rows.append((sc * c, ss * s))
+    return torch.tensor(rows, dtype=torch.float64).reshape(M, 2)
+
+
+_REG_ROOTS = {}
+
+
+def _reg_roots_dev(M, device):
+    key = (int(M), str(device))
+    if key not in _REG_ROOTS:
+        if len(_REG_ROOTS) >= 8:
+            _REG_ROOTS.clear()
+        _REG_ROOTS[key] = reg_roots(M).to(device)
+    return _REG_ROOTS[key]
+
+
+def _count(v, name, what):
+    """An integer of at least 1 (bool and float refused)."""
+    import operator
+    try:
+        if isinstance(v, bool):
+            raise TypeError
+        n = operator.index(v)
+    except TypeError:
+        raise ValueError(f"{what}: {name} must be an integer, got {v!r}") from None
+    if n < 1:
+        raise ValueError(f"{what}: {name} must be at least 1, got {n}")
+    return n
+
+
+def _fine_grid(upsample, radius, what):
+    u = _count(upsample, "upsample", what)
+    r = u if radius is None else _count(radius, "radius", what)
+    if r >= 1 << 14:
+        raise ValueError(f"{what}: radius = {r} is too large")
+    return u, r
+
+
+def _ipeak(ipeak, N, what):
+    if not torch.is_tensor(ipeak) or ipeak.dtype != torch.int32 or tuple(ipeak.shape) != (N, 2) or not ipeak.is_contiguous():
+        raise ValueError(f"{what}: ipeak must be a contiguous int32 {(N, 2)} tensor")
+    if not ipeak.is_cuda:
+        raise RuntimeError(f"{what}: cwfa_amd runs on MI355X only -- ipeak is a {ipeak.device} tensor (no CPU fallback exists)")
+    return ipeak
+
+
+def reg_upsample(R, ipeak, shape, upsample, radius=None, out=None, workspace=None):
+    """float64 [N, U, U], U = 2 ``radius`` + 1: the correlation irfft2(R, s=shape) interpolated trigonometrically on the fine grid
+    y = py + j / ``upsample``, x = px + j / ``upsample``, j = -radius .. radius, around the integer peaks ``ipeak`` (int32 [N,2], as
+    ``reg_peak`` writes them), straight from the spectra R (complex64 [N, H, W/2+1], frames contiguous, any stride between them): an
+    up-sampled DFT in float64 with a fixed summation order.  ``radius`` None: ``upsample``, i.e. +-1 px.
+    ``out``: a contiguous float64 [N,U,U] device tensor.  ``workspace``: a device tensor of at least
+    ``cwfa_reg_upsample_workspace_bytes`` bytes, 16-byte aligned."""
+    what = "reg_upsample"
+    u, r = _fine_grid(upsample, radius, what)
+    if not isinstance(shape, (tuple, list, torch.Size)) or len(shape) != 2:
+        raise ValueError(f"{what}: shape is (H, W), got {shape!r}")
+    H, W = (_count(s, "shape", what) for s in shape)
+    if not torch.is_tensor(R):
+        raise TypeError(f"{what}: expected a torch.Tensor, got {type(R)}")
+    if R.dtype != torch.complex64:
+        raise TypeError(f"{what}: expected complex64 spectra, got {R.dtype}")
+    if R.dim() != 3 or tuple(R.shape[1:]) != (H, W // 2 + 1):
+        raise ValueError(f"{what}: R {tuple(R.shape)} is not [N, {H}, {W // 2 + 1}], the spectra of {H} x {W} frames")
+    if H * W >= 1 << 31 or H * u >= 1 << 31 or W * u >= 1 << 31:
+        raise ValueError(f"{what}: {H} x {W} at factor {u} is too large")
+    N, K, U = int(R.shape[0]), W // 2 + 1, 2 * r + 1
+    ipeak = _ipeak(ipeak, N, what)
+    if not R.is_cuda:
+        raise RuntimeError(f"{what}: cwfa_amd runs on MI355X only -- got a {R.device} tensor (no CPU fallback exists)")
+    if N and (not R[0].is_contiguous() or (N > 1 and R.stride(0) < H * K)):
+        R = R.contiguous()
+    fs = R.stride(0) if N > 1 else H * K
+    if out is None:
+        out = torch.empty((N, U, U), dtype=torch.float64, device=R.device)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float64 or tuple(out.shape) != (N, U, U) or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous float64 {(N, U, U)} device tensor")
+    if N == 0:
+        return out
+    L = _lib.lib()
+    nbytes = int(L.cwfa_reg_upsample_workspace_bytes(N, H, W, r))
+    if nbytes < 0:
+        raise ValueError(f"{what}: {H} x {W} at radius {r} is too large")
+    if workspace is None:
+        workspace = torch.empty(max(nbytes // 8, 2), dtype=torch.float64, device=R.device)
+    elif not torch.is_tensor(workspace) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < nbytes:
+        raise ValueError(f"{what}: workspace must be a contiguous device tensor of at least {nbytes} bytes")
+    check(L.cwfa_reg_upsample_c64(_p(R), N, H, W, fs, _p(ipeak), u, r, _p(_reg_roots_dev(W * u, R.device)), _p(_reg_roots_dev(H * u, R.device)),
+                                  _p(out), _p(workspace), _stream()), what)
+    return out
+
+
+def reg_fine_peak(C, ipeak, upsample, out=None):
+    """(shifts float32 [N,2], peak float32 [N]) on the device from the fine maps ``C`` (float64 [N,U,U] of ``reg_upsample``) and the
+    integer peaks: the maximum of every map under the order of ``reg_peak`` widened to 64 bits, a float64 parabola per axis through
+    it and its two fine neighbours where it is not on the grid's border, shift = ipeak + (j + delta) / ``upsample``.  A map without
+    a finite value gives the integer peak and peak NaN.  ``out``: the two tensors as ``reg_peak`` filled them -- a frame whose peak
+    is NaN there is left as it is."""
+    what = "reg_fine_peak"
+    u = _count(upsample, "upsample", what)
+    if not torch.is_tensor(C):
+        raise TypeError(f"{what}: expected a torch.Tensor, got {type(C)}")
+    if C.dtype != torch.float64:
+        raise TypeError(f"{what}: expected float64 maps, got {C.dtype}")
+    if C.dim() != 3 or C.shape[1] != C.shape[2] or C.shape[1] < 3 or C.shape[1] % 2 == 0 or C.shape[1] >= 1 << 15 or not C.is_contiguous():
+        raise ValueError(f"{what}: C {tuple(C.shape)} is not a contiguous [N, U, U] with U = 2 r + 1, r >= 1")
+    N, U = int(C.shape[0]), int(C.shape[1])
+    ipeak = _ipeak(ipeak, N, what)
+    if not C.is_cuda:
+        raise RuntimeError(f"{what}: cwfa_amd runs on MI355X only -- got a {C.device} tensor (no CPU fallback exists)")
+    keep = out is not None
+    if out is None:
+        out = (torch.empty((N, 2), dtype=torch.float32, device=C.device), torch.empty((N,), dtype=torch.float32, device=C.device))
+    shifts, peak = out
+    for t, shape, name in ((shifts, (N, 2), "shifts"), (peak, (N,), "peak")):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous float32 {shape} device tensor")
+    if N == 0:
+        return shifts, peak
+    check(_lib.lib().cwfa_reg_fine_peak_f64(_p(C), _p(ipeak), N, U, u, int(keep), _p(shifts), _p(peak), _stream()), what)
+    return shifts, peak
+
+
 def reg_shift(stack, shifts, mode="bilinear", fill=0.0, out=None):
     """out[n,y,x] = stack[n, y + dy, x + dx] with (dy, dx) = shifts[n] read on the device (float32 [N,2]): bilinear with separately
     rounded fp32 weights and products, or ``mode="nearest"`` (rintf of the shift).  A tap of weight exactly 0 is neither read nor

@@ -70,6 +70,8 @@ const char* cwfa_last_error(void);
  *   "mip3_ablate"       : measurement only (results are then WRONG): mask, bit 0 / 1 / 2 drops the over-depth / over-H / over-W
  *                         reduction of cwfa_mip3_f32 (which of the three bounds the kernel); default 0.
  *   "split3x3_rows16"   : 0: (ablation) the 64-channel tiling of the split 3x3 kernel always on 8-row tiles.
+ *   "reg_upsample_stages": measurement only (with a bit cleared the map is NOT computed): mask, bit 0 / 1 / 2 launches the twiddle /
+ *                         row / column kernel of cwfa_reg_upsample_c64 (what each of them costs); default 7.
  * returns 0, or CWFA_E_INVAL for an unknown name or an invalid value. */
 int cwfa_set_option(const char* name, int value);
 
@@ -1011,6 +1013,36 @@ int cwfa_reg_peak_f32(const float* c, int N, int H, int W, int64_t frame_stride,
                       int* ipeak, float* peak, void* stream);
 int cwfa_reg_shift(const void* in, int dtype, int N, int H, int W, int64_t frame_stride, const float* shifts, int mode, float fill,
                    void* out, void* stream);
+
+/* ---- up-sampled-DFT refinement of the registration peak.  R: the whitened cross-power spectra, interleaved
+ * complex64 [N, H, K], K = W / 2 + 1, frame_stride >= H K elements between frames; ipeak int32 [N, 2] as reg_peak_f32 writes it.
+ * Everything is float64, every product and sum rounded separately; no atomics, nothing allocated, nothing synchronises; arguments are
+ * checked before any device work; N == 0: no launch, CWFA_OK.  H, W >= 1 below 2^30 with H W, H u, W u < 2^31, u >= 1, 1 <= r < 2^14.
+ *
+ *   reg_upsample_c64:  C [N, U, U] (double), U = 2 r + 1: the trigonometric interpolant of irfft2(R) at y = py + (jy - r) / u,
+ *                      x = px + (jx - r) / u.  With m_j = (p u + j - r) reduced modulo M = (W or H) u in integers:
+ *                        Tx[kx, j] = w[kx] rootx[(kx m_j) mod (W u)],       w = 1 at kx = 0 and at kx = W / 2 (W even), else 2 (exact)
+ *                        Ty[ky, j] = rooty[(s(ky) m_j) mod (H u)],          s(ky) = ky where 2 ky < H, else ky - H
+ *                      the Nyquist column (kx = W / 2, W even) and row (ky = H / 2, H even) with imaginary part 0;
+ *                        E[ky, jx] = sum over kx = 0 .. K - 1 in that order from (0, 0) of R[ky, kx] * Tx[kx, jx]
+ *                                    (re = fl(fl(a c) - fl(b d)), im = fl(fl(a d) + fl(b c)), each added to its sum)
+ *                        C[jy, jx] = fl(S * fl(1 / (H W))),  S = the sum over 8 segments of ceil(H / 8) rows, in order from 0.0, of
+ *                                    the segment's sum over ky, in order from 0.0, of fl(fl(Ty.re E.re) - fl(Ty.im E.im)).
+ *                      rootx [W u], rooty [H u]: DEVICE interleaved doubles, root[k] = exp(2 pi i k / M), the caller's tables,
+ *                      16-byte aligned.  ws: reg_upsample_workspace_bytes(N, H, W, r) DEVICE bytes, 16-byte aligned (Tx, Ty and E,
+ *                      16 N U (K + 2 H) bytes; nothing is written behind them).  R, ipeak, C 8-byte aligned, CWFA_E_ALIGN otherwise.
+ *                      reg_upsample_workspace_bytes (host only) returns -1 for sizes the entry point refuses.
+ *   reg_fine_peak_f64: one workgroup per frame of C [N, U, U], U odd >= 3: the maximum under the order of reg_peak_f32 widened to
+ *                      64 bits (the image of the bits of c + 0.0, NaN below everything, ties to the lowest row-major index), found
+ *                      without atomics; per axis, where the maximum is not on the border of the grid along it, the parabola of
+ *                      reg_peak_f32 through it and its two fine neighbours (d in fine steps), else d = 0;
+ *                      shifts[n] = (float)((double)p + ((double)(j - r) + d) / (double)u), peak[n] = (float)C at the maximum.  A map
+ *                      without a finite value: shifts = the integer peak, peak NaN.  keep = 1: shifts and peak hold reg_peak_f32's
+ *                      results and a frame whose peak is NaN there is left as it is (its map is not read); keep = 0: never read. */
+int64_t cwfa_reg_upsample_workspace_bytes(int N, int H, int W, int r);
+int cwfa_reg_upsample_c64(const void* R, int N, int H, int W, int64_t frame_stride, const int* ipeak, int u, int r, const double* rootx,
+                          const double* rooty, double* C, void* ws, void* stream);
+int cwfa_reg_fine_peak_f64(const double* C, const int* ipeak, int N, int U, int u, int keep, float* shifts, float* peak, void* stream);
 
 /* ---- neuron footprints: behind the detector, which voxels of a neuron's ROI box move with its centre once the
  * signal shared with the surroundings is taken out, and the traces weighted by that.  x: volumes [T, D, H, W] fp32, contiguous
