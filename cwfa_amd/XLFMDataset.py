@@ -12,7 +12,8 @@ from . import ops
 from .amp import amp_function, amp_region
 
 __all__ = ["XLFMDatasetFull", "ConcatDataset", "extract_views", "pad_img_to_min", "center_crop", "prepare_frames", "shot_noise_scales", "add_random_shot_noise_to_datasets",
-           "extract_sparse", "SparseSplit", "quantile_rank", "estimate_shifts", "shift_frames", "register_frames", "valid_window", "Registration"]
+           "extract_sparse", "SparseSplit", "quantile_rank", "estimate_shifts", "shift_frames", "register_frames", "valid_window", "Registration",
+           "view_labels", "estimate_view_shifts", "fit_view_shifts", "shift_views", "register_views", "valid_view_windows", "ViewFit", "ViewRegistration"]
 
 
 def extract_views(image, lenslet_coords, subimage_shape, debug=False):
@@ -263,6 +264,207 @@ def valid_window(shifts, shape):
     if y1 <= y0 or x1 <= x0:
         return 0, 0, 0, 0
     return y0, y1, x0, x1
+
+
+# ------------------------------------------------------------------------------------------------ per-lenslet registration
+ViewFit = namedtuple("ViewFit", ["table", "params", "inlier"])
+ViewRegistration = namedtuple("ViewRegistration", ["frames", "table", "params", "shifts", "peak", "inlier", "template"])
+VIEW_CHUNK_BYTES = 256 << 20          # the default chunk keeps the tapered views of a chunk at or below this
+
+
+def view_labels(shape, centers, view_shape, device="cuda"):
+    """uint8 [H,W] on the device: which lenslet view a pixel of a frame of ``shape`` belongs to.  View i is
+    the box of ``view_shape`` (ph, pw) whose first row is centers[i][0] - ph // 2 (columns alike): for even sizes the box of
+    ``extract_views``, for odd sizes not -- ``extract_views`` returns 2 (s // 2) pixels.  Where boxes overlap the pixel goes to the
+    nearest centre (integer squared distance, ties to the lowest index); a pixel in no box gets L, the rest of the frame.  Computed
+    once per geometry."""
+    return ops.reg_label_map(shape, centers, view_shape, device)
+
+
+def _view_args(frames, template, centers, view_shape, max_shift, taper, smooth, eps, chunk, what):
+    """The checks of ``estimate_view_shifts`` that need no device: (centers int32 [L,2], ph, pw, my, mx, taper, chunk)."""
+    if not torch.is_tensor(frames) or frames.dim() != 3 or not frames.is_contiguous():
+        raise ValueError(f"{what}: a contiguous [N,H,W] stack is expected")
+    if frames.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"{what}: a float32 or float16 stack is expected, got {frames.dtype}")
+    H, W = int(frames.shape[1]), int(frames.shape[2])
+    if template is not None and (not torch.is_tensor(template) or tuple(template.shape) != (H, W) or template.dtype != torch.float32):
+        raise ValueError(f"{what}: the template is a float32 [{H}, {W}] tensor, the shape of a frame")
+    c, ph, pw = ops._view_centers(centers, view_shape, what)
+    my, mx = ops._max_shift(max_shift, ph, pw, what)
+    taper = min(16, min(ph, pw) // 8) if taper is None else int(taper)
+    if taper < 0 or 2 * taper > min(ph, pw):
+        raise ValueError(f"{what}: taper = {taper} does not fit a {ph} x {pw} view twice")
+    smooth, eps = float(smooth), float(eps)
+    if not 0.0 <= smooth < float("inf") or not 0.0 <= eps < float("inf"):
+        raise ValueError(f"{what}: smooth and eps are finite and not negative, got {smooth}, {eps}")
+    if chunk is None:
+        chunk = max(1, VIEW_CHUNK_BYTES // (len(c) * ph * pw * 4))
+    if int(chunk) < 1:
+        raise ValueError(f"{what}: chunk must be at least 1, got {chunk}")
+    return c, ph, pw, my, mx, taper, int(chunk)
+
+
+@amp_region
+def estimate_view_shifts(frames, template, centers, view_shape, max_shift=8, taper=None, smooth=0.0, eps=1e-5, subpixel=True, chunk=None,
+                         upsample=16):
+    """(shifts float32 [N,L,2], peak float32 [N,L]) on the device: ``estimate_shifts`` for every lenslet view of every frame against
+    the same view of the float32 ``template`` [H,W].  ``centers``: an integer [L,2] host table of (row,
+    column); ``view_shape`` (ph, pw): the boxes of ``view_labels``, read as 0 outside the frame.  The views are cut, widened and
+    tapered in one read of the stack (``taper`` None: min(16, side / 8) of a view); whitening, the peak (|dy| <= my, |dx| <= mx of
+    ``max_shift``), the parabola and the up-sampled DFT are the kernels of ``estimate_shifts`` on the batch of views.  ``chunk`` is in
+    FRAMES: a chunk holds chunk x L x ph x pw x 4 bytes of tapered views plus their spectra, chunk x L x ph x (pw/2+1) x 8 bytes, and
+    the correlation maps; None keeps the views at or below 256 MiB.  Nothing is read back."""
+    what = "estimate_view_shifts"
+    c, ph, pw, my, mx, taper, chunk = _view_args(frames, template, centers, view_shape, max_shift, taper, smooth, eps, chunk, what)
+    dft, upsample = _subpixel_arg(subpixel, upsample, what)
+    if template is None:
+        raise ValueError(f"{what}: a template is needed")
+    N, L = int(frames.shape[0]), len(c)
+    dev = frames.device
+    wy, wx = taper_window(ph, taper).to(dev), taper_window(pw, taper).to(dev)
+    T = torch.fft.rfft2(ops.reg_window_views(template.contiguous()[None], c, (ph, pw), wy, wx)[0]).contiguous()      # [L, ph, pw/2+1]
+    U = torch.view_as_real(ops.reg_whiten(T, None, eps, out=T))
+    if smooth > 0.0:
+        ky, kx = torch.fft.fftfreq(ph, dtype=torch.float64), torch.fft.rfftfreq(pw, dtype=torch.float64)
+        G = torch.exp(-2.0 * math.pi ** 2 * smooth ** 2 * (ky[:, None] ** 2 + kx[None, :] ** 2)).to(torch.float32).to(dev)
+        Wt = torch.stack((U[..., 0] * G, -U[..., 1] * G), dim=-1)
+    else:
+        Wt = torch.stack((U[..., 0], -U[..., 1]), dim=-1)
+    Wt[:, 0, 0] = 0.0
+    Wt = torch.view_as_complex(Wt)
+    shifts = torch.empty((N * L, 2), dtype=torch.float32, device=dev)
+    ipeak = torch.empty((N * L, 2), dtype=torch.int32, device=dev)
+    peak = torch.empty((N * L,), dtype=torch.float32, device=dev)
+    chunk = min(chunk, max(N, 1))
+    buf = torch.empty((chunk, L, ph, pw), dtype=torch.float32, device=dev)
+    for s in range(0, N, chunk):
+        e = min(s + chunk, N)
+        a, b = s * L, e * L
+        F = torch.fft.rfft2(ops.reg_window_views(frames[s:e], c, (ph, pw), wy, wx, out=buf[:e - s])).contiguous()
+        corr = torch.fft.irfft2(ops.reg_whiten(F, Wt, eps, out=F), s=(ph, pw)).reshape(b - a, ph, pw)
+        ops.reg_peak(corr, (my, mx), subpixel and not dft, out=(shifts[a:b], ipeak[a:b], peak[a:b]))
+        if dft:
+            ops.reg_fine_peak(ops.reg_upsample(F.reshape(b - a, ph, pw // 2 + 1), ipeak[a:b], (ph, pw), upsample), ipeak[a:b], upsample,
+                              out=(shifts[a:b], peak[a:b]))
+    return shifts.reshape(N, L, 2), peak.reshape(N, L)
+
+
+def _directions(directions, c, device, what):
+    """float64 [L,2] on the device: the given directions, or centers - mean(centers)."""
+    if directions is None:
+        g = torch.from_numpy(c).to(torch.float64)
+        return (g - g.mean(dim=0, keepdim=True)).to(device)
+    g = torch.as_tensor(directions)
+    if tuple(g.shape) != (len(c), 2) or not (g.is_floating_point() or g.dtype in (torch.int32, torch.int64)):
+        raise ValueError(f"{what}: directions is a [{len(c)}, 2] table, one (row, column) vector per view")
+    return g.to(device=device, dtype=torch.float64).contiguous()
+
+
+def fit_view_shifts(shifts, peak, directions, min_peak=0.0, reject=1.0, model="axial"):
+    """``ViewFit(table, params, inlier)`` from the per-view shifts of ``estimate_view_shifts``: per frame the lateral displacement d
+    and the axial coefficient a of s_i = d + a g_i (``directions`` g: [L,2], converted to float64), fitted in float64 over the views
+    whose peak is finite and >= ``min_peak``, with one rejection pass at ``reject`` pixels.  ``params``
+    float64 [N,3] = (d_y, d_x, a) -- a is a z-drift monitor in its own right; ``inlier`` uint8 [N,L]; ``table`` float32 [N,L+1,2]:
+    the shift of every view (``model="axial"``: the model's; ``"free"``: the measured one where it is an inlier) and, in row L, of
+    the rest of the frame (d).  Everything stays on the device."""
+    if not torch.is_tensor(shifts) or not shifts.is_cuda:
+        raise RuntimeError("fit_view_shifts: cwfa_amd runs on MI355X only -- shifts must be a device tensor (no CPU fallback exists)")
+    if shifts.dim() != 3:
+        raise ValueError("fit_view_shifts: shifts is a float32 [N,L,2] tensor")
+    g = torch.as_tensor(directions)
+    if tuple(g.shape) != (int(shifts.shape[1]), 2):
+        raise ValueError(f"fit_view_shifts: directions is a [{int(shifts.shape[1])}, 2] table, one (row, column) vector per view")
+    g = g.to(device=shifts.device, dtype=torch.float64).contiguous()
+    return ViewFit(*ops.reg_fit_views(shifts, peak, g, min_peak, reject, model))
+
+
+@amp_region
+def shift_views(frames, table, labels, mode="bilinear", fill=0.0, out=None):
+    """out[n,y,x] = frames[n, y + dy, x + dx] with (dy, dx) = table[n, min(labels[y,x], L)]: ``shift_frames`` with a shift per lenslet
+    view (``table`` float32 [N,L+1,2] of ``fit_view_shifts``, ``labels`` uint8 [H,W] of ``view_labels``).  The source is the whole
+    frame: a tap that leaves its view's box reads what lies there (``valid_view_windows`` gives the part of every view where none
+    does).  An integer shift copies bits; ``out`` must not share memory with ``frames``."""
+    if not torch.is_tensor(frames) or frames.dim() != 3 or not frames.is_contiguous():
+        raise ValueError("shift_views: a contiguous [N,H,W] stack is expected")
+    if mode not in ("bilinear", "nearest"):
+        raise ValueError(f"shift_views: mode is 'bilinear' or 'nearest', got {mode!r}")
+    N, H, W = (int(s) for s in frames.shape)
+    if not torch.is_tensor(table) or table.dim() != 3 or int(table.shape[0]) != N or table.shape[2] != 2 or table.dtype != torch.float32:
+        raise ValueError(f"shift_views: table is a float32 [{N}, L + 1, 2] tensor")
+    if not torch.is_tensor(labels) or tuple(labels.shape) != (H, W) or labels.dtype != torch.uint8:
+        raise ValueError(f"shift_views: labels is a uint8 [{H}, {W}] map")
+    if out is not None and (out is frames or (torch.is_tensor(out) and ops._overlap(out, frames))):
+        raise ValueError("shift_views: out must not alias frames")
+    return ops.reg_shift_labeled(frames, table, labels, mode=mode, fill=fill, out=out)
+
+
+@amp_region
+def register_views(frames, centers, view_shape, template=None, directions=None, model="axial", n_iter=1, max_shift=8, subpixel=True,
+                   mode="bilinear", taper=None, smooth=0.0, eps=1e-5, chunk=None, fill=0.0, out=None, upsample=16, min_peak=0.0, reject=1.0,
+                   labels=None):
+    """Per-lenslet registration of a contiguous [N,H,W] fp32 / fp16 device stack:
+    ``ViewRegistration(frames, table, params, shifts, peak, inlier, template)``.  Every view of every frame is registered against the
+    same view of the template, the L shifts of a frame are fitted by a lateral displacement plus an axial fan a g_i
+    (``directions`` g; None: centers - mean(centers)), and every pixel is moved back by its view's vector (the rest of the frame by
+    d).  ``template`` None: the per-pixel temporal median; ``n_iter`` > 1: the template becomes the median of the registered stack
+    and the shifts are estimated again FROM THE ORIGINAL FRAMES.  ``labels``: the map of ``view_labels`` where it is at hand.  The
+    other arguments are those of ``estimate_view_shifts``, ``fit_view_shifts`` and ``shift_views``.  Nothing is read back."""
+    what = "register_views"
+    c = _view_args(frames, template, centers, view_shape, max_shift, taper, smooth, eps, chunk, what)[0]
+    _subpixel_arg(subpixel, upsample, what)
+    if int(n_iter) < 1:
+        raise ValueError(f"{what}: n_iter must be at least 1, got {n_iter}")
+    if mode not in ("bilinear", "nearest"):
+        raise ValueError(f"{what}: mode is 'bilinear' or 'nearest', got {mode!r}")
+    if model not in ("axial", "free"):
+        raise ValueError(f"{what}: model is 'axial' or 'free', got {model!r}")
+    if out is not None and (out is frames or (torch.is_tensor(out) and ops._overlap(out, frames))):
+        raise ValueError(f"{what}: out must not alias frames")
+    N, H, W = (int(s) for s in frames.shape)
+    if N < 1:
+        raise ValueError(f"{what}: at least one frame is expected")
+    g = _directions(directions, c, frames.device, what)
+    if labels is None:
+        labels = view_labels((H, W), c, view_shape, frames.device)
+    median = lambda x: ops.temporal_select(x, [quantile_rank(0.5, N)])[0]
+    tmpl = median(frames) if template is None else template
+    for it in range(int(n_iter)):
+        shifts, peak = estimate_view_shifts(frames, tmpl, c, view_shape, max_shift=max_shift, taper=taper, smooth=smooth, eps=eps,
+                                            subpixel=subpixel, chunk=chunk, upsample=upsample)
+        fit = fit_view_shifts(shifts, peak, g, min_peak=min_peak, reject=reject, model=model)
+        out = shift_views(frames, fit.table, labels, mode=mode, fill=fill, out=out)
+        if it + 1 < int(n_iter):
+            tmpl = median(out)
+    return ViewRegistration(out, fit.table, fit.params, shifts, peak, fit.inlier, tmpl)
+
+
+def valid_view_windows(table, centers, view_shape, shape):
+    """int [L,4] rows (y0, y1, x0, x1) in FRAME coordinates: per view, the box in which every frame's taps under ``table`` [N,L+1,2]
+    stay inside that view's box and inside the frame -- rows y0 .. y1 - 1, columns x0 .. x1 - 1; all 0 where a shift of the view is
+    not finite or nothing is left.  (Where boxes overlap, a pixel of that window may carry another view's label.)  A host helper: it
+    reads the table back, like ``valid_window``."""
+    import numpy as np
+    c, ph, pw = ops._view_centers(centers, view_shape, "valid_view_windows")
+    H, W = int(shape[0]), int(shape[1])
+    t = torch.as_tensor(table).detach().to("cpu", torch.float64)
+    if t.dim() != 3 or t.shape[1] != len(c) + 1 or t.shape[2] != 2:
+        raise ValueError(f"valid_view_windows: table is a [N, {len(c) + 1}, 2] tensor")
+    t = t.numpy()
+    out = np.zeros((len(c), 4), dtype=np.int64)
+    for i in range(len(c)):
+        by0, bx0 = int(c[i, 0]) - ph // 2, int(c[i, 1]) - pw // 2
+        lo, hi = (max(by0, 0), max(bx0, 0)), (min(by0 + ph, H), min(bx0 + pw, W))
+        s = t[:, i]
+        if s.size:
+            if not np.isfinite(s).all():
+                continue
+            fl, ce = np.floor(s).min(0), np.ceil(s).max(0)
+            lo = (max(lo[0], lo[0] - int(fl[0])), max(lo[1], lo[1] - int(fl[1])))
+            hi = (min(hi[0], hi[0] - int(ce[0])), min(hi[1], hi[1] - int(ce[1])))
+        if hi[0] > lo[0] and hi[1] > lo[1]:
+            out[i] = lo[0], hi[0], lo[1], hi[1]
+    return out
 
 
 def _scalar(v):

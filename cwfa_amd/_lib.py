@@ -89,7 +89,9 @@ CORR_FORWARD = {6: 3, 8: 4, 26: 13}                                            #
 NMAX_MAX_DIST = 16                # CWFA_NMAX_MAX_DIST
 SELECT_FORM = {"auto": 0, "lds": 1, "stream": 2}                                # cwfa_temporal_select's `form`
 SHIFT_MODE = {"bilinear": 0, "nearest": 1}                                      # cwfa_reg_shift's `mode`
-FOOTPRINT_SELECT_MAX = 1 << 15    # CWFA_FOOTPRINT_SELECT_MAX
+VIEW_MODEL = {"axial": 0, "free": 1}                                            # cwfa_reg_fit_views_f64's `model`
+REG_MAX_VIEWS = 254               # a label is a byte; label L is the rest of the frame
+FOOTPRINT_SELECT_MAX = 1 << 15   # CWFA_FOOTPRINT_SELECT_MAX
 
 # name -> (restype, argtypes); must list EVERY function declared in include/cwfa_hip.h (tests/test_boundary.py checks)
 i, i64, f, d, p = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_void_p
@@ -225,6 +227,10 @@ SIGNATURES = {
     "cwfa_reg_upsample_workspace_bytes": (i64, [i, i, i, i]),
     "cwfa_reg_upsample_c64": (i, [p, i, i, i, i64, p, i, i, p, p, p, p, p]),
     "cwfa_reg_fine_peak_f64": (i, [p, p, i, i, i, i, p, p, p]),
+    "cwfa_reg_window_views": (i, [p, i, i, i, i, i64, p, i, i, i, p, p, p, p]),
+    "cwfa_reg_label_map": (i, [p, i, i, i, i, i, p, p]),
+    "cwfa_reg_fit_views_f64": (i, [p, p, p, i, i, d, d, i, p, p, p, p]),
+    "cwfa_reg_shift_labeled": (i, [p, i, i, i, i, i64, p, p, i, i, f, p, p]),
     "cwfa_roi_mark_u8": (i, [p, i, p, i, i, i, p]),
     "cwfa_roi_weighted_sums_f32": (i, [p, p, p, p, p, i, i, i, i, i, i64, p]),
     "cwfa_roi_shell_sums_f32": (i, [p, p, p, p, p, p, i, i, i, i, i, i64, p]),

@@ -8,6 +8,7 @@
 #include <math.h>
 #include <type_traits>
 #include "common.h"
+#include "register_internal.h"
 
 typedef unsigned long long rkey_t;
 
@@ -44,15 +45,6 @@ __global__ __launch_bounds__(256) void rwin_kernel(const void* __restrict__ x, i
         }
         *reinterpret_cast<fvec*>(out + (int64_t)n * H * W + p) = r;
     }
-}
-
-// blocks along y for a kernel whose threads walk the frames: about `target` blocks in all, the per-pixel values reused over N / gy
-// frames.  The window and the resampling keep a few words per thread and take many blocks (an even tail); the whitening keeps a
-// plane of weights and takes one block row where the bins alone fill the chip, so that the plane is read once.
-static inline unsigned reg_grid_y(int64_t gx, int N, int64_t target) {
-    int64_t gy = target / gx < 1 ? 1 : target / gx;
-    gy = gy > 65535 ? 65535 : gy;
-    return (unsigned)(gy > N ? N : gy);
 }
 
 extern "C" int cwfa_reg_window(const void* x, int dtype, int N, int H, int W, int64_t frame_stride, const float* wy, const float* wx,
@@ -236,11 +228,7 @@ extern "C" int cwfa_reg_peak_f32(const float* c, int N, int H, int W, int64_t fr
 // fills the frame.  The shift of frame n is read from device memory.  A thread writes V consecutive pixels of a row (a 16-byte
 // store: 4 of fp32, 8 of fp16) from the V + 1 source pixels of either row.  The source rows start anywhere: inside the frame the
 // span is one load of element alignment (the compiler makes it a vector load plus one element), at the borders element by element.
-template <class T, int K>
-struct rshift_span {
-    T v[K];
-};
-
+// The arithmetic is rshift_pixels (register_internal.h), which the labelled resampling of section 29 shares.
 template <int V, bool HALF>
 __global__ __launch_bounds__(256) void rshift_kernel(const void* __restrict__ in, int N, int H, int W, int64_t fs, const f32x2* __restrict__ shifts,
                                                      int nearest, float fill, void* __restrict__ out) {
@@ -252,66 +240,9 @@ __global__ __launch_bounds__(256) void rshift_kernel(const void* __restrict__ in
     const int y = (int)(q / Wv), x0 = (int)(q - (int64_t)y * Wv) * V;
     for (int n = blockIdx.y; n < N; n += gridDim.y) {
         const f32x2 s = shifts[n];
-        float dy = s[0], dx = s[1];
         elem* o = reinterpret_cast<elem*>(out) + (int64_t)n * H * W + (int64_t)y * W + x0;
         float acc[V];
-        if (!(fabsf(dy) < INFINITY) || !(fabsf(dx) < INFINITY)) {
-#pragma unroll
-            for (int j = 0; j < V; ++j) acc[j] = fill;
-        } else {
-            if (nearest) dy = rintf(dy), dx = rintf(dx);
-            const float iyf = floorf(dy), ixf = floorf(dx);
-            const float fy = __fsub_rn(dy, iyf), fx = __fsub_rn(dx, ixf);
-            // beyond +-(size + 1) every tap is outside whatever the value: clamp before the conversion to int
-            const int iy = (int)fminf(fmaxf(iyf, -(float)(H + 1)), (float)(H + 1));
-            const int ix = (int)fminf(fmaxf(ixf, -(float)(W + 1)), (float)(W + 1));
-            const float wy[2] = {__fsub_rn(1.f, fy), fy}, wx[2] = {__fsub_rn(1.f, fx), fx};
-            const elem* src = reinterpret_cast<const elem*>(in) + (int64_t)n * fs;
-            bool have = false;
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const float w0 = __fmul_rn(wy[r], wx[0]), w1 = __fmul_rn(wy[r], wx[1]);
-                if (w0 == 0.f && w1 == 0.f) continue;                 // the whole row of taps has weight 0: not read
-                const int yy = y + iy + r;
-                const bool row_in = yy >= 0 && yy < H;
-                const elem* row = src + (int64_t)(row_in ? yy : 0) * W;
-                float v[V + 1];
-                const int xs = x0 + ix;
-                if (V > 1 && row_in && xs >= 0 && xs + V < W) {       // the span lies inside the row: one unaligned vector load
-                    rshift_span<elem, V + 1> sp;
-                    __builtin_memcpy(&sp, row + xs, sizeof(sp));
-#pragma unroll
-                    for (int j = 0; j <= V; ++j) v[j] = (float)sp.v[j];
-                } else {
-#pragma unroll
-                    for (int j = 0; j <= V; ++j) {
-                        const int xx = xs + j;
-                        const bool need = j < V ? (w0 != 0.f || (j > 0 && w1 != 0.f)) : w1 != 0.f;
-                        v[j] = need && row_in && xx >= 0 && xx < W ? (float)row[xx] : fill;
-                    }
-                }
-                if (w0 != 0.f) {
-#pragma unroll
-                    for (int j = 0; j < V; ++j) {
-                        const float t = __fmul_rn(w0, v[j]);
-                        acc[j] = have ? __fadd_rn(acc[j], t) : t;
-                    }
-                    have = true;
-                }
-                if (w1 != 0.f) {
-#pragma unroll
-                    for (int j = 0; j < V; ++j) {
-                        const float t = __fmul_rn(w1, v[j + 1]);
-                        acc[j] = have ? __fadd_rn(acc[j], t) : t;
-                    }
-                    have = true;
-                }
-            }
-            if (!have) {                                              // all four weights underflowed to 0
-#pragma unroll
-                for (int j = 0; j < V; ++j) acc[j] = 0.f;
-            }
-        }
+        rshift_pixels<V, elem>(reinterpret_cast<const elem*>(in) + (int64_t)n * fs, H, W, y, x0, s[0], s[1], nearest, fill, acc);
         evec r;
 #pragma unroll
         for (int j = 0; j < V; ++j) r[j] = (elem)acc[j];

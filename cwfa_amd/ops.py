@@ -2918,6 +2918,133 @@ def reg_shift(stack, shifts, mode="bilinear", fill=0.0, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ per-lenslet registration
+def _view_centers(centers, view_shape, what):
+    """(int32 [L,2] host table, ph, pw): the lenslet centres (row, column) as the entry points take them, 1 <= L <= 254."""
+    import numpy as np
+    if torch.is_tensor(centers):
+        centers = centers.detach().cpu().numpy()
+    try:
+        c = np.asarray(centers)
+        ok = np.issubdtype(c.dtype, np.integer) and c.ndim == 2 and c.shape[1] == 2
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: centers is an integer [L,2] table of (row, column)")
+    if not 1 <= len(c) <= _lib.REG_MAX_VIEWS:
+        raise ValueError(f"{what}: 1 to {_lib.REG_MAX_VIEWS} views are expected, got {len(c)}")
+    if (np.abs(c.astype(np.int64)) >= 1 << 29).any():
+        raise ValueError(f"{what}: a centre is out of range")
+    if not isinstance(view_shape, (tuple, list, torch.Size)) or len(view_shape) != 2:
+        raise ValueError(f"{what}: view_shape is (ph, pw), got {view_shape!r}")
+    ph, pw = (_count(s, "view_shape", what) for s in view_shape)
+    if ph * pw >= 1 << 31:
+        raise ValueError(f"{what}: a view of {ph} x {pw} is too large")
+    return np.ascontiguousarray(c.astype(np.int32)), ph, pw
+
+
+def reg_window_views(stack, centers, view_shape, wy, wx, out=None):
+    """float32 [N,L,ph,pw]: the L views of every frame of a [N,H,W] fp32 / fp16 device stack, cut, widened and tapered in one read:
+    fl(float(stack[n, cy - ph//2 + y, cx - pw//2 + x]) * fl(wy[y] * wx[x])), a pixel outside the frame read as 0.  ``centers``: an
+    integer [L,2] HOST table of (row, column), 1 <= L <= 254; ``wy`` [ph], ``wx`` [pw] fp32 device vectors.  For even sizes the box is
+    that of ``extract_views``; odd sizes differ (``extract_views`` returns 2 (s // 2)).  ``out``: a contiguous float32 tensor of that
+    shape that shares no memory with the stack."""
+    what = "reg_window_views"
+    c, ph, pw = _view_centers(centers, view_shape, what)
+    stack, dt, N, H, W, fs = _frames(stack, what)
+    if H < 1 or W < 1:
+        raise ValueError(f"{what}: a frame of {H} x {W}")
+    wy, wx = _vec(wy, ph, "wy", what), _vec(wx, pw, "wx", what)
+    shape = (N, len(c), ph, pw)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=stack.device)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous float32 {shape} device tensor")
+    elif _overlap(out, stack):
+        raise ValueError(f"{what}: out must not alias the stack")
+    if N == 0:
+        return out
+    check(_lib.lib().cwfa_reg_window_views(_p(stack), dt, N, H, W, fs, _host(c), len(c), ph, pw, _p(wy), _p(wx), _p(out), _stream()), what)
+    return out
+
+
+def reg_label_map(shape, centers, view_shape, device="cuda"):
+    """uint8 [H,W] on ``device``: the index of the view whose box holds the pixel -- among several boxes the one whose centre is
+    nearest in integer squared distance, ties to the lowest index -- and L, "the rest of the frame", where none does."""
+    what = "reg_label_map"
+    c, ph, pw = _view_centers(centers, view_shape, what)
+    if not isinstance(shape, (tuple, list, torch.Size)) or len(shape) != 2:
+        raise ValueError(f"{what}: shape is (H, W), got {shape!r}")
+    H, W = (_count(s, "shape", what) for s in shape)
+    if H * W >= 1 << 31:
+        raise ValueError(f"{what}: a frame of {H} x {W} is too large")
+    if torch.device(device).type != "cuda":
+        raise RuntimeError(f"{what}: cwfa_amd runs on MI355X only -- got device {device!r} (no CPU fallback exists)")
+    L = _lib.lib()
+    labels = torch.empty((H, W), dtype=torch.uint8, device=device)
+    check(L.cwfa_reg_label_map(_host(c), len(c), ph, pw, H, W, _p(labels), _stream()), what)
+    return labels
+
+
+def reg_fit_views(shifts, peak, directions, min_peak=0.0, reject=1.0, model="axial"):
+    """(table float32 [N,L+1,2], params float64 [N,3], inlier uint8 [N,L]) on the device from the per-view shifts (float32 [N,L,2]),
+    their peaks (float32 [N,L]) and the directions g (float64 [L,2]): per frame the least-squares fit s_i = d + a g_i over the views
+    whose peak is finite and >= ``min_peak``, one rejection pass at ``reject`` pixels (inf: none) and a second fit, in float64 with a
+    fixed summation order.  ``params`` = (d_y, d_x, a).  Row L of ``table`` is d; row i is d + a g_i
+    (``model="axial"``) or the measured s_i where ``inlier`` and the model value where not (``"free"``)."""
+    what = "reg_fit_views"
+    if model not in _lib.VIEW_MODEL:
+        raise ValueError(f"{what}: model is one of {sorted(_lib.VIEW_MODEL)}, got {model!r}")
+    min_peak, reject = float(min_peak), float(reject)
+    if not min_peak >= 0.0 or not reject >= 0.0:
+        raise ValueError(f"{what}: min_peak and reject are not negative and not NaN, got {min_peak}, {reject}")
+    if not torch.is_tensor(shifts) or shifts.dim() != 3 or shifts.shape[2] != 2:
+        raise ValueError(f"{what}: shifts is a float32 [N,L,2] tensor")
+    N, Lv = int(shifts.shape[0]), int(shifts.shape[1])
+    if not 1 <= Lv <= _lib.REG_MAX_VIEWS:
+        raise ValueError(f"{what}: 1 to {_lib.REG_MAX_VIEWS} views are expected, got {Lv}")
+    shifts, peak = _vec(shifts, 2 * N * Lv, "shifts", what), _vec(peak, N * Lv, "peak", what)
+    directions = _vec(directions, 2 * Lv, "directions", what, torch.float64)
+    dev = shifts.device
+    table = torch.empty((N, Lv + 1, 2), dtype=torch.float32, device=dev)
+    params = torch.empty((N, 3), dtype=torch.float64, device=dev)
+    inlier = torch.empty((N, Lv), dtype=torch.uint8, device=dev)
+    if N == 0:
+        return table, params, inlier
+    check(_lib.lib().cwfa_reg_fit_views_f64(_p(shifts), _p(peak), _p(directions), N, Lv, min_peak, reject, _lib.VIEW_MODEL[model], _p(params),
+                                            _p(inlier), _p(table), _stream()), what)
+    return table, params, inlier
+
+
+def reg_shift_labeled(stack, table, labels, mode="bilinear", fill=0.0, out=None):
+    """``reg_shift`` with a shift per pixel label: out[n,y,x] = stack[n, y + dy, x + dx], (dy, dx) = table[n, min(labels[y,x], L)]
+    read on the device (``table`` float32 [N,L+1,2], ``labels`` uint8 [H,W]).  Taps, weights, order, ``fill`` and dtype are those of
+    ``reg_shift``, bit for bit; the source is the whole frame, so a tap that leaves its view's box reads what lies there.  ``out``: a
+    contiguous tensor of the stack's shape and dtype that shares no memory with it."""
+    what = "reg_shift_labeled"
+    stack, dt, N, H, W, fs = _frames(stack, what)
+    if mode not in _lib.SHIFT_MODE:
+        raise ValueError(f"{what}: mode is one of {sorted(_lib.SHIFT_MODE)}, got {mode!r}")
+    if not torch.is_tensor(table) or table.dim() != 3 or int(table.shape[0]) != N or table.shape[2] != 2 or not 2 <= table.shape[1] <= _lib.REG_MAX_VIEWS + 1:
+        raise ValueError(f"{what}: table is a float32 [{N}, L + 1, 2] tensor, 1 <= L <= {_lib.REG_MAX_VIEWS}")
+    Lv = int(table.shape[1]) - 1
+    table = _vec(table, 2 * N * (Lv + 1), "table", what)
+    labels = _vec(labels, H * W, "labels", what, torch.uint8)
+    if H < 1 or W < 1:
+        raise ValueError(f"{what}: a frame of {H} x {W}")
+    if out is None:
+        out = torch.empty((N, H, W), dtype=stack.dtype, device=stack.device)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != stack.dtype or tuple(out.shape) != (N, H, W) or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous {stack.dtype} {(N, H, W)} device tensor")
+    elif _overlap(out, stack):
+        raise ValueError(f"{what}: out must not alias the stack")
+    if N == 0:
+        return out
+    check(_lib.lib().cwfa_reg_shift_labeled(_p(stack), dt, N, H, W, fs, _p(table), _p(labels), Lv, _lib.SHIFT_MODE[mode], float(fill), _p(out),
+                                            _stream()), what)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ neuron footprints
 def _nonneg_triple(v, name, what):
     t = _triple(v, name, what)

@@ -1044,6 +1044,42 @@ int cwfa_reg_upsample_c64(const void* R, int N, int H, int W, int64_t frame_stri
                           const double* rooty, double* C, void* ws, void* stream);
 int cwfa_reg_fine_peak_f64(const double* C, const int* ipeak, int N, int U, int u, int keep, float* shifts, float* peak, void* stream);
 
+/* ---- per-lenslet registration with an axial-motion fit.  A frame [H, W] holds L views, 1 <= L <= 254; centers is
+ * a HOST int32 [L][2] table of (row, column), every entry inside +-2^29; it is checked and travels in the kernel arguments.  View i is
+ * the box of rows cy_i - ph / 2 .. cy_i - ph / 2 + ph - 1 and the matching columns, ph, pw >= 1, ph pw < 2^31; it may leave the
+ * frame.  Stacks as above (dtype 0 = fp32, 1 = fp16, frame_stride >= H W, H, W >= 1).  Arguments are checked before any device work;
+ * nothing is allocated, nothing synchronises, no atomics; N == 0: no launch, CWFA_OK.  Every floating-point operation is rounded
+ * separately.
+ *
+ *   reg_window_views:  out [N, L, ph, pw] fp32 contiguous = fl32(float(x[n, cy - ph/2 + y, cx - pw/2 + x]) * fl32(wy[y] * wx[x])), a
+ *                      pixel outside the frame read as 0.0f; wy [ph], wx [pw] device fp32.  One read of the views' pixels, one write;
+ *                      a thread owns four pixels of a view's row (16-byte stores) where pw % 4 == 0 and out is 16-byte aligned, one
+ *                      otherwise, and reads them in one load of element alignment inside the frame.
+ *   reg_label_map:     labels [H, W] device bytes: the index of the view whose box holds the pixel; among several the smallest integer
+ *                      squared distance to the centre, ties to the lowest index; L where none does.
+ *   reg_fit_views_f64: per frame n from shifts [N, L, 2] fp32, peak [N, L] fp32 and directions g [L, 2] float64 (all device), one
+ *                      thread per frame, float64, sums over i = 0 .. L - 1 in order from 0.0 skipping views of weight 0:
+ *                      w_i = 1 where peak is finite and >= min_peak, else 0; m = sum w; for m >= 1: gm = (sum w g) / m,
+ *                      sm = (sum w s) / m, q = sum w (ey ey + ex ex) with e = g_i - gm, a = q > 0 ? (sum w (ey ty + ex tx)) / q : 0
+ *                      with t = s_i - sm, d = sm - a gm.  Then r_i = max(|s_iy - (d_y + a g_iy)|, |s_ix - (d_x + a g_ix)|) and
+ *                      w_i = 0 where r_i > reject; if a weight is left the fit is repeated, if none is the first fit and weights
+ *                      stand.  m == 0: d = 0, a = 0.  params [N, 3] float64 = (d_y, d_x, a); inlier [N, L] bytes = the final w;
+ *                      table [N, L + 1, 2] fp32: row L = (float)d; model 0 (axial): row i = (float)(d + a g_i); model 1 (free): row i
+ *                      = s_i where inlier, the axial value where not.  min_peak, reject >= 0 (reject may be +inf), CWFA_E_INVAL
+ *                      otherwise (NaN included).  directions, params, table 8-byte aligned, CWFA_E_ALIGN otherwise.
+ *   reg_shift_labeled: reg_shift with (dy, dx) = table[n, min(labels[y,x], L)] (table [N, L + 1, 2] fp32, labels [H, W] bytes, both
+ *                      device): the same taps, weights, order, fill and store forms, bit for bit; the source is the whole frame.
+ *                      A thread resamples its group of pixels once per label in the group (once where the labels agree) and keeps, of
+ *                      each pass, the pixels that carry the label: every pixel comes from its own taps by the same code.
+ *                      out != in; table 8-byte aligned, CWFA_E_ALIGN otherwise. */
+int cwfa_reg_window_views(const void* x, int dtype, int N, int H, int W, int64_t frame_stride, const int32_t* centers, int L, int ph,
+                          int pw, const float* wy, const float* wx, float* out, void* stream);
+int cwfa_reg_label_map(const int32_t* centers, int L, int ph, int pw, int H, int W, uint8_t* labels, void* stream);
+int cwfa_reg_fit_views_f64(const float* shifts, const float* peak, const double* directions, int N, int L, double min_peak, double reject,
+                           int model, double* params, uint8_t* inlier, float* table, void* stream);
+int cwfa_reg_shift_labeled(const void* in, int dtype, int N, int H, int W, int64_t frame_stride, const float* table, const uint8_t* labels,
+                           int L, int mode, float fill, void* out, void* stream);
+
 /* ---- neuron footprints: behind the detector, which voxels of a neuron's ROI box move with its centre once the
  * signal shared with the surroundings is taken out, and the traces weighted by that.  x: volumes [T, D, H, W] fp32, contiguous
  * volumes, t_stride >= D * H * W elements between them.  Box tables are HOST int32 [N][6] = {z0,z1,y0,y1,x0,x1}, half-open, inside the
