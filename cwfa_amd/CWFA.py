@@ -9,11 +9,13 @@ Out of scope: experiment management of ``run_CWFA``
 TensorBoard, figures, TIFF export.
 """
 import math
+from collections import namedtuple
 
 import torch
 
 from . import ops
-from .amp import amp_function
+from .amp import amp_function, amp_region
+from .XLFMDataset import quantile_rank, taper_window
 
 __all__ = ["sample_z_truncated", "check_empty_depths", "evaluate_INN_forward", "inverse_pass", "nll_step",
            "nll_terms", "allreduce_nll", "build_networks", "step_log_likelihoods", "allgather_scores", "detect_ood",
@@ -21,7 +23,8 @@ __all__ = ["sample_z_truncated", "check_empty_depths", "evaluate_INN_forward", "
            "denormalise_prediction", "denormalise_ground_truth", "compute_INN_step_performance", "evaluate_step", "roi_boxes",
            "corr_coeff_3D", "truncated_normal_variance", "posterior_moments", "posterior_samples", "posterior_roi_means",
            "ActivityMap", "find_neurons", "read_neural_coordinates_from_file", "write_neural_coordinates_to_file",
-           "NeuronFootprints", "Footprints", "extract_traces", "trace_baseline", "delta_f_over_f", "trace_noise", "infer_spikes"]
+           "NeuronFootprints", "Footprints", "extract_traces", "trace_baseline", "delta_f_over_f", "trace_noise", "infer_spikes",
+           "estimate_volume_shifts", "shift_volumes", "register_volumes", "VolumeRegistration", "VolumeRegistrar", "valid_box"]
 
 
 def _no_grad_trunc_normal_(tensor, mean=0., std=1., a=-1., b=1.):
@@ -910,6 +913,210 @@ def find_neurons(score, r12=5, r3=3, n_max=None, thr=None, rel_thr=0.1, start_pl
     zyx, scores, _ = ops.local_maxima(score, thr, dist, margin, n_max)
     shift = score.shape[0] // 2 + int(start_plane_offset)
     return [[int(x), int(y), int(z) - shift] for z, y, x in zyx], scores
+
+
+# ---------------------------------------------------------------------------------------------------- registration of volumes
+# In front of everything that works per voxel over time: the rigid registration of section 26 carried to
+# [N,D,H,W] stacks -- for volumes whose frames are gone, for comparing two reconstructions of one frame, and for motion the fan model
+# of section 29 does not hold.
+VolumeRegistration = namedtuple("VolumeRegistration", ["volumes", "shifts", "peak", "template"])
+
+
+def _vol_reg_args(volumes, template, max_shift, taper, smooth, eps, chunk, subpixel, what):
+    """The checks of ``estimate_volume_shifts`` that need no device: ((mz, my, mx), (tz, ty, tx))."""
+    if not torch.is_tensor(volumes) or volumes.dim() != 4 or not volumes.is_contiguous():
+        raise ValueError(f"{what}: a contiguous [N,D,H,W] stack is expected")
+    if volumes.dtype != torch.float32:
+        raise ValueError(f"{what}: a float32 stack is expected, got {volumes.dtype}")
+    shape = tuple(int(s) for s in volumes.shape[1:])
+    if template is not None and (not torch.is_tensor(template) or tuple(template.shape) != shape or template.dtype != torch.float32):
+        raise ValueError(f"{what}: the template is a float32 {list(shape)} tensor, the shape of a volume")
+    if isinstance(subpixel, str):
+        if subpixel == "dft":
+            raise ValueError(f"{what}: subpixel='dft' (the up-sampled DFT of section 26.5) is not built for volumes; True fits a parabola per axis")
+        raise ValueError(f"{what}: subpixel is True or False, got {subpixel!r}")
+    m = ops._max_shift3(max_shift, *shape, what)
+    if taper is None:
+        taper = tuple(min(16, s // 8) for s in shape)
+    elif isinstance(taper, int):
+        taper = (taper,) * 3
+    else:
+        taper = tuple(int(t) for t in taper)
+        if len(taper) != 3:
+            raise ValueError(f"{what}: taper is an int or (tz, ty, tx), got {taper!r}")
+    if any(t < 0 or 2 * t > s for t, s in zip(taper, shape)):
+        raise ValueError(f"{what}: taper = {taper} does not fit a {shape} volume twice")
+    smooth, eps = float(smooth), float(eps)
+    if not 0.0 <= smooth < float("inf") or not 0.0 <= eps < float("inf"):
+        raise ValueError(f"{what}: smooth and eps are finite and not negative, got {smooth}, {eps}")
+    if int(chunk) < 1:
+        raise ValueError(f"{what}: chunk must be at least 1, got {chunk}")
+    return m, taper
+
+
+@amp_region
+def estimate_volume_shifts(volumes, template, max_shift=(2, 8, 8), taper=None, smooth=0.0, eps=1e-5, subpixel=True, chunk=1):
+    """(shifts float32 [N,3] as (dz, dy, dx), peak float32 [N]) on the device: the rigid displacement of every volume of a contiguous
+    [N,D,H,W] float32 device stack against the float32 ``template`` [D,H,W] by phase correlation, the steps of
+    ``XLFMDataset.estimate_shifts`` over three axes.  A volume that is the template displaced by d (volume[p] = template[p - d])
+    reports d; ``shift_volumes`` undoes it.  ``peak`` is the correlation value at the integer peak.  Nothing is read back.
+
+    Both get a raised-cosine edge taper (``taper``: None for min(16, side / 8) per axis, an int, or (tz, ty, tx); 0: none); the
+    spectra (``rfftn`` over the last three axes) are whitened separately, F / (|F| + ``eps``), multiplied, optionally low-passed by a
+    Gaussian of ``smooth`` voxels, and transformed back; the peak is searched over |d| <= ``max_shift`` (an int or (mz, my, mx)) and,
+    with ``subpixel``, refined by a parabola per axis.  ``subpixel="dft"`` is refused: it is not built for volumes.  The volumes go
+    through in chunks of ``chunk`` (a chunk's spectra are chunk x D x H x (W/2+1) x 8 bytes: 101 MB per 96 x 512 x 512 volume)."""
+    what = "estimate_volume_shifts"
+    (mz, my, mx), (tz, ty, tx) = _vol_reg_args(volumes, template, max_shift, taper, smooth, eps, chunk, subpixel, what)
+    if template is None:
+        raise ValueError(f"{what}: a template is needed")
+    N, D, H, W = (int(s) for s in volumes.shape)
+    dev = volumes.device
+    wz, wy, wx = taper_window(D, tz).to(dev), taper_window(H, ty).to(dev), taper_window(W, tx).to(dev)
+    T = torch.fft.rfftn(ops.reg_window3d(template.contiguous()[None], wz, wy, wx)[0], dim=(-3, -2, -1)).contiguous()
+    U = torch.view_as_real(ops.reg_whiten(T, None, eps, out=T))
+    if smooth > 0.0:
+        kz, ky, kx = (torch.fft.fftfreq(D, dtype=torch.float64), torch.fft.fftfreq(H, dtype=torch.float64), torch.fft.rfftfreq(W, dtype=torch.float64))
+        k2 = kz[:, None, None] ** 2 + ky[None, :, None] ** 2 + kx[None, None, :] ** 2
+        G = torch.exp(-2.0 * math.pi ** 2 * smooth ** 2 * k2).to(torch.float32).to(dev)
+        Wt = torch.stack((U[..., 0] * G, -U[..., 1] * G), dim=-1)
+    else:
+        Wt = torch.stack((U[..., 0], -U[..., 1]), dim=-1)
+    Wt[0, 0, 0] = 0.0
+    Wt = torch.view_as_complex(Wt)
+    shifts = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    ipeak = torch.empty((N, 3), dtype=torch.int32, device=dev)
+    peak = torch.empty((N,), dtype=torch.float32, device=dev)
+    chunk = min(int(chunk), max(N, 1))
+    buf = torch.empty((chunk, D, H, W), dtype=torch.float32, device=dev)
+    for s in range(0, N, chunk):
+        e = min(s + chunk, N)
+        F = torch.fft.rfftn(ops.reg_window3d(volumes[s:e], wz, wy, wx, out=buf[:e - s]), dim=(-3, -2, -1)).contiguous()
+        corr = torch.fft.irfftn(ops.reg_whiten(F, Wt, eps, out=F), s=(D, H, W), dim=(-3, -2, -1))
+        ops.reg_peak3d(corr, (mz, my, mx), bool(subpixel), out=(shifts[s:e], ipeak[s:e], peak[s:e]))
+    return shifts, peak
+
+
+def _shift_volume_args(volumes, shifts, mode, out, what):
+    if not torch.is_tensor(volumes) or volumes.dim() != 4 or not volumes.is_contiguous():
+        raise ValueError(f"{what}: a contiguous [N,D,H,W] stack is expected")
+    if volumes.dtype != torch.float32:
+        raise ValueError(f"{what}: a float32 stack is expected, got {volumes.dtype}")
+    if mode not in ("bilinear", "nearest"):
+        raise ValueError(f"{what}: mode is 'bilinear' or 'nearest', got {mode!r}")
+    if shifts is not None and (not torch.is_tensor(shifts) or tuple(shifts.shape) != (int(volumes.shape[0]), 3) or shifts.dtype != torch.float32):
+        raise ValueError(f"{what}: shifts is a float32 [{int(volumes.shape[0])}, 3] tensor")
+    if out is not None and (out is volumes or (torch.is_tensor(out) and ops._overlap(out, volumes))):
+        raise ValueError(f"{what}: out must not alias volumes")
+
+
+@amp_region
+def shift_volumes(volumes, shifts, mode="bilinear", fill=0.0, out=None):
+    """out[n,z,y,x] = volumes[n, z + dz, y + dy, x + dx] with (dz, dy, dx) = shifts[n] (float32 [N,3] on the device, as
+    ``estimate_volume_shifts`` returns them): trilinear ("bilinear" in every plane, blended along z), or ``mode="nearest"``; voxels
+    from outside the volume are ``fill``.  An integer shift copies bits.  ``out`` must not share memory with ``volumes``."""
+    _shift_volume_args(volumes, shifts, mode, out, "shift_volumes")
+    return ops.reg_shift3d(volumes, shifts, mode=mode, fill=fill, out=out)
+
+
+def _volume_median(volumes):
+    """The per-voxel lower temporal median of a contiguous [N,D,H,W] stack."""
+    N = int(volumes.shape[0])
+    return ops.temporal_select(volumes.view(N, -1), [quantile_rank(0.5, N)])[0].view(volumes.shape[1:])
+
+
+@amp_region
+def register_volumes(volumes, template=None, n_iter=1, max_shift=(2, 8, 8), subpixel=True, mode="bilinear", taper=None, smooth=0.0, eps=1e-5,
+                     chunk=1, fill=0.0, out=None):
+    """Rigid registration of a contiguous [N,D,H,W] float32 device stack:
+    ``VolumeRegistration(volumes, shifts, peak, template)`` with volumes[n] = the input's volume n moved back by shifts[n].
+    ``template`` None: the per-voxel lower temporal median of the stack (usable where most volumes rest: section 26.4).
+    ``n_iter`` > 1: the template becomes the median of the registered stack and the shifts are estimated again FROM THE ORIGINAL
+    VOLUMES, so interpolation never compounds.  The other arguments are those of ``estimate_volume_shifts`` and ``shift_volumes``.
+    Nothing is read back."""
+    what = "register_volumes"
+    _vol_reg_args(volumes, template, max_shift, taper, smooth, eps, chunk, subpixel, what)
+    _shift_volume_args(volumes, None, mode, out, what)
+    if int(n_iter) < 1:
+        raise ValueError(f"{what}: n_iter must be at least 1, got {n_iter}")
+    if int(volumes.shape[0]) < 1:
+        raise ValueError(f"{what}: at least one volume is expected")
+    tmpl = _volume_median(volumes) if template is None else template
+    for it in range(int(n_iter)):
+        shifts, peak = estimate_volume_shifts(volumes, tmpl, max_shift=max_shift, taper=taper, smooth=smooth, eps=eps, subpixel=subpixel, chunk=chunk)
+        out = shift_volumes(volumes, shifts, mode=mode, fill=fill, out=out)
+        if it + 1 < int(n_iter):
+            tmpl = _volume_median(out)
+    return VolumeRegistration(out, shifts, peak, tmpl)
+
+
+class VolumeRegistrar:
+    """Registration of a series that is never resident, against a fixed float32 ``template`` [D,H,W]: ``reg(chunk)`` returns the
+    registered [T',D,H,W] chunk (or volume, for one [D,H,W] volume) and appends the chunk's shifts and peaks to the device lists
+    ``reg.shifts`` and ``reg.peak``; nothing is read back inside the call.  ``all_shifts()`` / ``all_peaks()`` concatenate them
+    ([N,3], [N]); pass the former to ``valid_box``.  ``estimate_args``: those of ``estimate_volume_shifts``; ``mode`` and ``fill``:
+    those of ``shift_volumes``.  This is how ``ActivityMap`` and ``NeuronFootprints`` are fed::
+
+        reg = VolumeRegistrar(template, max_shift=(2, 8, 8))
+        for cond in batches:
+            fp.update(reg(inverse_pass(conv_inn, cond_nets, cond, mean_vols_cache)[:, 0]))
+        box = valid_box(reg.all_shifts(), template.shape)      # the one read-back, after the loop
+    """
+
+    def __init__(self, template, mode="bilinear", fill=0.0, **estimate_args):
+        ops._dev(template, "template")
+        if template.dim() != 3:
+            raise ValueError(f"VolumeRegistrar: the template is a float32 [D,H,W] tensor, got {tuple(template.shape)}")
+        if mode not in ("bilinear", "nearest"):
+            raise ValueError(f"VolumeRegistrar: mode is 'bilinear' or 'nearest', got {mode!r}")
+        self.template, self.mode, self.fill, self.estimate_args = template.contiguous(), mode, float(fill), dict(estimate_args)
+        probe = torch.empty((0,) + tuple(template.shape), dtype=torch.float32, device=template.device)
+        _vol_reg_args(probe, self.template, self.estimate_args.get("max_shift", (2, 8, 8)), self.estimate_args.get("taper"),
+                      self.estimate_args.get("smooth", 0.0), self.estimate_args.get("eps", 1e-5), self.estimate_args.get("chunk", 1),
+                      self.estimate_args.get("subpixel", True), "VolumeRegistrar")
+        self.shifts, self.peak = [], []
+
+    def __call__(self, volumes, out=None):
+        single = torch.is_tensor(volumes) and volumes.dim() == 3
+        if single:
+            volumes = volumes.unsqueeze(0)
+        shifts, peak = estimate_volume_shifts(volumes, self.template, **self.estimate_args)
+        moved = shift_volumes(volumes, shifts, mode=self.mode, fill=self.fill, out=out)
+        self.shifts.append(shifts)
+        self.peak.append(peak)
+        return moved[0] if single else moved
+
+    def all_shifts(self):
+        """float32 [N,3] on the device: the shifts of every volume seen so far."""
+        return torch.cat(self.shifts) if self.shifts else torch.empty((0, 3), dtype=torch.float32, device=self.template.device)
+
+    def all_peaks(self):
+        """float32 [N] on the device: the correlation peaks of every volume seen so far."""
+        return torch.cat(self.peak) if self.peak else torch.empty((0,), dtype=torch.float32, device=self.template.device)
+
+
+def valid_box(shifts, shape):
+    """(z0, z1, y0, y1, x0, x1): the box of a volume of ``shape`` (D, H, W) in which every volume registered with ``shifts`` [N,3]
+    holds data and no ``fill`` -- planes z0 .. z1 - 1, rows y0 .. y1 - 1, columns x0 .. x1 - 1 -- all 0 where a shift is not finite
+    or nothing is left.  A host helper: it reads the shifts back.  A detection whose ROI leaves the box saw ``fill`` in some
+    volume; ``find_neurons(score, r12, r3, margin=(max(r3, z0, D - z1), max(r12, y0, H - y1), max(r12, x0, W - x1)))`` keeps every
+    ROI inside it."""
+    dims = tuple(int(v) for v in shape)
+    if len(dims) != 3:
+        raise ValueError(f"valid_box: shape is (D, H, W), got {shape!r}")
+    s = torch.as_tensor(shifts).detach().to("cpu", torch.float64).reshape(-1, 3)
+    if s.numel() == 0:
+        return 0, dims[0], 0, dims[1], 0, dims[2]
+    if not bool(torch.isfinite(s).all()):
+        return (0,) * 6
+    lo, hi = torch.floor(s).amin(0), torch.ceil(s).amax(0)
+    box = []
+    for a, side in enumerate(dims):
+        b0, b1 = max(0, int(-lo[a])), min(side, side - int(hi[a]))
+        if b1 <= b0:
+            return (0,) * 6
+        box += [b0, b1]
+    return tuple(box)
 
 
 # ---------------------------------------------------------------------------------------------------- neuron footprints

@@ -231,6 +231,9 @@ SIGNATURES = {
     "cwfa_reg_label_map": (i, [p, i, i, i, i, i, p, p]),
     "cwfa_reg_fit_views_f64": (i, [p, p, p, i, i, d, d, i, p, p, p, p]),
     "cwfa_reg_shift_labeled": (i, [p, i, i, i, i, i64, p, p, i, i, f, p, p]),
+    "cwfa_reg_window3d_f32": (i, [p, i, i, i, i, i64, p, p, p, p, p]),
+    "cwfa_reg_peak3d_f32": (i, [p, i, i, i, i, i64, i, i, i, i, p, p, p, p]),
+    "cwfa_reg_shift3d_f32": (i, [p, i, i, i, i, i64, p, i, f, p, p]),
     "cwfa_roi_mark_u8": (i, [p, i, p, i, i, i, p]),
     "cwfa_roi_weighted_sums_f32": (i, [p, p, p, p, p, i, i, i, i, i, i64, p]),
     "cwfa_roi_shell_sums_f32": (i, [p, p, p, p, p, p, i, i, i, i, i, i64, p]),

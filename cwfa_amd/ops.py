@@ -3045,6 +3045,91 @@ def reg_shift_labeled(stack, table, labels, mode="bilinear", fill=0.0, out=None)
     return out
 
 
+# ------------------------------------------------------------------------------------------------ registration of volumes
+def _volume_stack(x, what):
+    """A [N, D, H, W] float32 stack as ``_stack`` returns it, with D, H and W."""
+    x, dt, N, P, vs = _stack(x, what)
+    if dt != 0:
+        raise TypeError(f"{what}: float32 volumes are expected, got {x.dtype}")
+    if x.dim() != 4:
+        raise ValueError(f"{what}: a stack [N, D, H, W] is expected, got {tuple(x.shape)}")
+    D, H, W = (int(s) for s in x.shape[1:])
+    if D * H * W >= 1 << 31:
+        raise ValueError(f"{what}: a volume of {D} x {H} x {W} is too large")
+    return x, N, D, H, W, vs
+
+
+def _max_shift3(max_shift, D, H, W, what):
+    """``_max_shift`` for volumes: an int or a (mz, my, mx) triple."""
+    try:
+        m = (max_shift,) * 3 if isinstance(max_shift, int) else tuple(max_shift)
+        if len(m) != 3:
+            raise TypeError
+        mz, my, mx = (int(v) for v in m)
+    except TypeError:
+        raise ValueError(f"{what}: max_shift is an int or (mz, my, mx), got {max_shift!r}") from None
+    if min(mz, my, mx) < 0 or (D and H and W and (2 * mz + 1 > D or 2 * my + 1 > H or 2 * mx + 1 > W)):
+        raise ValueError(f"{what}: max_shift ({mz}, {my}, {mx}) needs 0 <= 2 m + 1 <= the volume's {D} x {H} x {W}")
+    return mz, my, mx
+
+
+def reg_window3d(stack, wz, wy, wx, out=None):
+    """float32 [N,D,H,W]: fl(stack * fl(fl(wz[z] * wy[y]) * wx[x])) for a [N,D,H,W] float32 device stack and float32 device vectors
+    ``wz`` [D], ``wy`` [H], ``wx`` [W] -- the edge taper in front of the forward transform, in one read and one write.  ``out``: a
+    contiguous float32 tensor of the stack's shape that shares no memory with it."""
+    L = _lib.lib()
+    stack, N, D, H, W, vs = _volume_stack(stack, "reg_window3d")
+    wz, wy, wx = _vec(wz, D, "wz", "reg_window3d"), _vec(wy, H, "wy", "reg_window3d"), _vec(wx, W, "wx", "reg_window3d")
+    if out is None:
+        out = torch.empty((N, D, H, W), dtype=torch.float32, device=stack.device)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (N, D, H, W) or not out.is_contiguous():
+        raise ValueError(f"reg_window3d: out must be a contiguous float32 {(N, D, H, W)} device tensor")
+    elif _overlap(out, stack):
+        raise ValueError("reg_window3d: out must not alias the stack")
+    check(L.cwfa_reg_window3d_f32(_p(stack), N, D, H, W, vs, _p(wz), _p(wy), _p(wx), _p(out), _stream()), "reg_window3d")
+    return out
+
+
+def reg_peak3d(corr, max_shift, subpixel=True, out=None):
+    """(shifts float32 [N,3] as (dz, dy, dx), ipeak int32 [N,3], peak float32 [N]) on the device from float32 correlation maps
+    [N,D,H,W]: ``reg_peak`` with one more axis -- the maximum over the signed window |sz| <= mz, |sy| <= my, |sx| <= mx (read modulo
+    the volume; ``max_shift``: an int or (mz, my, mx)), ties to the lowest window index, NaN below everything, and with ``subpixel``
+    a float64 parabola per axis.  A window without a finite value gives shift 0 and peak NaN.  ``out``: the three tensors."""
+    L = _lib.lib()
+    corr, N, D, H, W, vs = _volume_stack(corr, "reg_peak3d")
+    mz, my, mx = _max_shift3(max_shift, D, H, W, "reg_peak3d")
+    if out is None:
+        out = (torch.empty((N, 3), dtype=torch.float32, device=corr.device), torch.empty((N, 3), dtype=torch.int32, device=corr.device),
+               torch.empty((N,), dtype=torch.float32, device=corr.device))
+    shifts, ipeak, peak = out
+    for t, dtype, shape, name in ((shifts, torch.float32, (N, 3), "shifts"), (ipeak, torch.int32, (N, 3), "ipeak"), (peak, torch.float32, (N,), "peak")):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f"reg_peak3d: {name} must be a contiguous {dtype} {shape} device tensor")
+    check(L.cwfa_reg_peak3d_f32(_p(corr), N, D, H, W, vs, mz, my, mx, int(bool(subpixel)), _p(shifts), _p(ipeak), _p(peak), _stream()), "reg_peak3d")
+    return shifts, ipeak, peak
+
+
+def reg_shift3d(stack, shifts, mode="bilinear", fill=0.0, out=None):
+    """out[n,z,y,x] = stack[n, z + dz, y + dy, x + dx] with (dz, dy, dx) = shifts[n] read on the device (float32 [N,3]): ``reg_shift``
+    of the planes z + floor(dz) and the next one under (dy, dx), blended along z with separately rounded fp32 weights and products;
+    ``mode="nearest"``: rintf of the shift.  A plane or tap of weight exactly 0 is neither read nor added, so an integer shift
+    copies bits; whatever lies outside the volume reads ``fill``; a non-finite shift fills the volume.  ``out``: a contiguous
+    float32 tensor of the stack's shape that shares no memory with it."""
+    L = _lib.lib()
+    stack, N, D, H, W, vs = _volume_stack(stack, "reg_shift3d")
+    if mode not in _lib.SHIFT_MODE:
+        raise ValueError(f"reg_shift3d: mode is one of {sorted(_lib.SHIFT_MODE)}, got {mode!r}")
+    shifts = _vec(shifts, 3 * N, "shifts", "reg_shift3d")
+    if out is None:
+        out = torch.empty((N, D, H, W), dtype=torch.float32, device=stack.device)
+    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (N, D, H, W) or not out.is_contiguous():
+        raise ValueError(f"reg_shift3d: out must be a contiguous float32 {(N, D, H, W)} device tensor")
+    elif _overlap(out, stack):
+        raise ValueError("reg_shift3d: out must not alias the stack")
+    check(L.cwfa_reg_shift3d_f32(_p(stack), N, D, H, W, vs, _p(shifts), _lib.SHIFT_MODE[mode], float(fill), _p(out), _stream()), "reg_shift3d")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ neuron footprints
 def _nonneg_triple(v, name, what):
     t = _triple(v, name, what)

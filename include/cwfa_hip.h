@@ -1080,6 +1080,39 @@ int cwfa_reg_fit_views_f64(const float* shifts, const float* peak, const double*
 int cwfa_reg_shift_labeled(const void* in, int dtype, int N, int H, int W, int64_t frame_stride, const float* table, const uint8_t* labels,
                            int L, int mode, float fill, void* out, void* stream);
 
+/* ---- rigid registration of reconstructed volumes: the passes of section 26 for stacks of volumes.  Volumes are
+ * fp32 [N, D, H, W], every volume contiguous, vol_stride >= D * H * W elements between volumes; D, H, W < 2^30, D * H * W < 2^31; all
+ * offsets are 64-bit (a stack may exceed 2^31 elements).  The spectra between the passes are whitened by reg_whiten_c64 with
+ * bins = D * H * (W / 2 + 1).  Arguments are checked before any device work; nothing is allocated, nothing synchronises, no atomics,
+ * nothing is read back; N == 0 (or an empty volume): no launch, CWFA_OK.  The grids stay inside the hardware limits for any N: the
+ * kernels walk the volumes.  Every pointer 4-byte aligned, CWFA_E_ALIGN otherwise.
+ *
+ *   reg_window3d_f32: out[n,z,y,x] (contiguous) = fl32(x[n,z,y,x] * fl32(fl32(wz[z] * wy[y]) * wx[x])), wz [D], wy [H], wx [W] device
+ *                     fp32.  One read and one write; 16-byte accesses where W, the stride and the bases allow, element by element
+ *                     otherwise.  D = 1 with wz = {1}: the bits of reg_window.  out != x.
+ *   reg_peak3d_f32:   one workgroup per volume of the correlation maps c.  Window index i, row-major over sz in [-mz, mz],
+ *                     sy in [-my, my], sx in [-mx, mx], reads c at the shifts modulo (D, H, W); the maximum of
+ *                     key = ord(c + 0.0f) << 32 | (0xFFFFFFFF - i) under the order of reg_peak_f32, by wave shuffles and through the
+ *                     LDS.  2 m + 1 <= the side on every axis, CWFA_E_SHAPE otherwise.  subpixel = 1: the float64 parabola of
+ *                     reg_peak_f32 per axis (its guards, its clamp to +-0.5), from the peak's neighbours modulo the side.  Writes
+ *                     shifts fp32 [N, 3] (dz, dy, dx), ipeak int32 [N, 3], peak fp32 [N].  A window without a finite value: shift 0,
+ *                     ipeak 0, peak NaN.  D = 1, mz = 0: columns 1 and 2 and peak are the bits of reg_peak_f32.
+ *   reg_shift3d_f32:  (dz, dy, dx) = shifts[n] (fp32 [N, 3]) read on the device; a non-finite component fills the volume with `fill`;
+ *                     mode 1 (nearest) applies rintf to all three first.  iz = floorf(dz), fz = fl32(dz - iz),
+ *                     wz = (fl32(1 - fz), fz); for r = 0, 1 with wz[r] != 0, p_r[y,x] is what reg_shift's rule gives for plane
+ *                     z + iz + r under (dy, dx), a plane outside the volume holding `fill` everywhere;
+ *                     out = fl32(wz[0] p_0), then + fl32(wz[1] p_1), each rounded; a plane of weight exactly 0 is neither read nor
+ *                     added.  So an integer shift copies source bits, an integer dz gives reg_shift's bits on plane z + dz, and
+ *                     D = 1, dz = 0 gives reg_shift's bits.  out [N, D, H, W] contiguous, out != in.  A thread writes four
+ *                     consecutive voxels of a row in one 16-byte store where W and out's base allow, one voxel otherwise, and walks
+ *                     up to 16 planes keeping p_1 as the next plane's p_0: a source plane is read once per 16 output planes. */
+int cwfa_reg_window3d_f32(const float* x, int N, int D, int H, int W, int64_t vol_stride, const float* wz, const float* wy, const float* wx,
+                          float* out, void* stream);
+int cwfa_reg_peak3d_f32(const float* c, int N, int D, int H, int W, int64_t vol_stride, int mz, int my, int mx, int subpixel, float* shifts,
+                        int* ipeak, float* peak, void* stream);
+int cwfa_reg_shift3d_f32(const float* in, int N, int D, int H, int W, int64_t vol_stride, const float* shifts, int mode, float fill,
+                         float* out, void* stream);
+
 /* ---- neuron footprints: behind the detector, which voxels of a neuron's ROI box move with its centre once the
  * signal shared with the surroundings is taken out, and the traces weighted by that.  x: volumes [T, D, H, W] fp32, contiguous
  * volumes, t_stride >= D * H * W elements between them.  Box tables are HOST int32 [N][6] = {z0,z1,y0,y1,x0,x1}, half-open, inside the
