@@ -23,7 +23,7 @@ __all__ = ["sample_z_truncated", "check_empty_depths", "evaluate_INN_forward", "
            "denormalise_prediction", "denormalise_ground_truth", "compute_INN_step_performance", "evaluate_step", "roi_boxes",
            "corr_coeff_3D", "truncated_normal_variance", "posterior_moments", "posterior_samples", "posterior_roi_means",
            "ActivityMap", "find_neurons", "read_neural_coordinates_from_file", "write_neural_coordinates_to_file",
-           "NeuronFootprints", "Footprints", "extract_traces", "trace_baseline", "delta_f_over_f", "trace_noise", "infer_spikes",
+           "NeuronFootprints", "Footprints", "extract_traces", "demix_plan", "demix_traces", "trace_baseline", "delta_f_over_f", "trace_noise", "infer_spikes",
            "estimate_volume_shifts", "shift_volumes", "register_volumes", "VolumeRegistration", "VolumeRegistrar", "valid_box"]
 
 
@@ -1220,6 +1220,59 @@ def extract_traces(volumes, footprints, geometry=None, alpha=0.7):
     sums, counts = ops.roi_shell_sums(volumes, geometry)
     Fnp = sums / counts.to(torch.float64)[:, None]
     return F, Fnp, torch.where(torch.isnan(Fnp), F, F - float(alpha) * Fnp)
+
+
+# ---- demixing of overlapping footprints: F_n carries a share M_nm of every neighbour m whose light falls on
+# voxels of footprint n; the shares follow from the footprints alone, and the traces are solved for per time step.
+@amp_region
+def demix_plan(footprints):
+    """The ``ops.DemixPlan`` of ``footprints`` (what ``NeuronFootprints.finish`` returns): the pairs of boxes that intersect, the
+    overlap sums G_nm = sum w_n w_m over the intersections and the mixing coefficients M_nm = (G_nm wsum_m) / (G_mm wsum_n).
+    Computed once per recording; it allocates and waits for its tables to reach the device."""
+    if not isinstance(footprints, Footprints):
+        raise ValueError("demix_plan: footprints is what NeuronFootprints.finish returns")
+    return ops.DemixPlan(footprints)
+
+
+@amp_region
+def demix_traces(F, footprints_or_plan, n_sweeps=64, tol=0.0, nonneg=True):
+    """``(Fd, sweeps)``: the raw traces ``F`` of ``extract_traces`` (float64 [N,T'] on the device, any chunking of time, a row stride
+    allowed) with the neighbours' shares taken out, and the sweeps every time step ran (int32 [T']).  The model is that the voxels of
+    the footprints hold sum_m w_m(v) f_m(t), so F_n = f_n + sum_{m != n} M_nm f_m; it is solved per time step by projected
+    Gauss-Seidel from f = F (``nonneg``: f >= 0), ending after the first sweep that changes nothing by more than ``tol`` or after
+    ``n_sweeps``.  A neuron whose box meets no other footprint returns the bits of its F; an empty footprint's row is NaN and
+    reaches nobody.  ``footprints_or_plan``: a ``DemixPlan`` (``demix_plan``, once per recording) or the ``Footprints``, for which
+    the plan is made here, every call.
+
+    Intended use: ``delta_f_over_f(Fd, Fnp)`` -- demix the raw trace, then correct for neuropil; the shells exclude every box, so
+    ``Fnp`` needs no demixing.  Limits: light of a neighbour that falls on footprint n outside the neighbour's own thresholded
+    footprint is not removed; under a strong common background (0.4 of a blob's amplitude in the tests' scene) the result is not
+    reliably better and some neurons get worse; two identical footprints make the system singular."""
+    what = "demix_traces"
+    plan = footprints_or_plan
+    if isinstance(plan, Footprints):
+        plan = ops.DemixPlan(plan)
+    if not isinstance(plan, ops.DemixPlan):
+        raise ValueError(f"{what}: footprints_or_plan is a DemixPlan (demix_plan) or what NeuronFootprints.finish returns")
+    try:
+        sweeps_ok = int(n_sweeps) >= 1 and int(n_sweeps) == n_sweeps
+    except (TypeError, ValueError):
+        sweeps_ok = False
+    try:
+        tol_ok = float(tol) >= 0.0
+    except (TypeError, ValueError):
+        tol_ok = False
+    if not sweeps_ok:
+        raise ValueError(f"{what}: n_sweeps is a positive integer, got {n_sweeps!r}")
+    if not tol_ok:
+        raise ValueError(f"{what}: tol is a non-negative number, got {tol!r}")
+    if not torch.is_tensor(F) or F.dtype != torch.float64 or F.dim() != 2 or F.shape[1] < 1:
+        raise ValueError(f"{what}: F is a float64 [N, T] tensor on the HIP device with T >= 1 (extract_traces)")
+    if F.shape[0] != plan.N:
+        raise ValueError(f"{what}: F has {F.shape[0]} rows, the footprints {plan.N} neurons")
+    if not F.is_cuda:
+        raise ValueError(f"{what}: F is a float64 [N, T] tensor on the HIP device, got one on {F.device}")
+    return ops.demix_solve(F, plan, int(n_sweeps), float(tol), bool(nonneg))
 
 
 # ---- what a user reads from the traces (DESIGN.md section 28): dF/F against a running-percentile baseline, a robust noise level

@@ -92,6 +92,7 @@ SHIFT_MODE = {"bilinear": 0, "nearest": 1}                                      
 VIEW_MODEL = {"axial": 0, "free": 1}                                            # cwfa_reg_fit_views_f64's `model`
 REG_MAX_VIEWS = 254               # a label is a byte; label L is the rest of the frame
 FOOTPRINT_SELECT_MAX = 1 << 15   # CWFA_FOOTPRINT_SELECT_MAX
+DEMIX_PAIR_BYTES = 48             # CWFA_DEMIX_PAIR_BYTES
 
 # name -> (restype, argtypes); must list EVERY function declared in include/cwfa_hip.h (tests/test_boundary.py checks)
 i, i64, f, d, p = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_void_p
@@ -245,6 +246,11 @@ SIGNATURES = {
     "cwfa_trace_select_f64": (i, [p, i, i, i64, C.POINTER(C.c_int), i, p, p]),
     "cwfa_ar1_deconv_workspace_bytes": (i64, [i, i]),
     "cwfa_ar1_deconv_f64": (i, [p, i, i, i64, d, p, p, p, p, p, p, p]),
+    "cwfa_footprint_overlaps_f32": (i, [p, p, p, i, p, i64, p, p, p]),
+    "cwfa_demix_plan_create": (i, [p, p, i, p, i64, C.POINTER(C.c_void_p)]),
+    "cwfa_demix_plan_destroy": (i, [p]),
+    "cwfa_demix_coeffs_f64": (i, [p, p, i64, p, p, i, p, p]),
+    "cwfa_demix_solve_f64": (i, [p, i64, p, i, i, p, i, d, i, p, p]),
 }
 del i, i64, f, d, p
 

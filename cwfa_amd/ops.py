@@ -3366,6 +3366,155 @@ def footprint_select(corr, geometry, thr):
     return w, wsum, sizes
 
 
+# ------------------------------------------------------------------------------------------------ demixing of overlapping footprints
+def footprint_pairs(boxes):
+    """int32 [P,2] on the host: every (n, m), n <= m, whose boxes (an integer [N,6] table) share a voxel, ascending in (n, m); the
+    diagonal (n, n) of every box is included, empty or not.  Blocks of rows against all later boxes in numpy: no Python loop over
+    pairs."""
+    import numpy as np
+    b = _box_table(boxes, "boxes", "footprint_pairs")
+    N = len(b)
+    lo, hi = b[:, 0::2], b[:, 1::2]
+    if ((lo < 0) | (lo > hi)).any():
+        raise ValueError("footprint_pairs: every row of boxes is a half-open range (z0, z1, y0, y1, x0, x1)")
+    live = (hi > lo).all(axis=1)
+    out = []
+    for r0 in range(0, N, 256):
+        r1 = min(N, r0 + 256)
+        hit = live[r0:r1, None] & live[None, r0:]
+        for k in range(3):
+            hit &= (lo[r0:r1, None, k] < hi[None, r0:, k]) & (lo[None, r0:, k] < hi[r0:r1, None, k])
+        rows = np.arange(r1 - r0)
+        hit[rows, rows] = True                                                    # the diagonal, also of an empty box
+        hit &= rows[:, None] <= np.arange(N - r0)[None, :]
+        n, m = np.nonzero(hit)
+        out.append(np.stack([n + r0, m + r0], axis=1))
+    pairs = np.concatenate(out) if out else np.zeros((0, 2))
+    return np.ascontiguousarray(pairs.astype(np.int32))
+
+
+def _pair_table(pairs, N, what):
+    import numpy as np
+    try:
+        q = np.asarray(pairs)
+        ok = q.size == 0 or (np.issubdtype(q.dtype, np.integer) and q.ndim == 2 and q.shape[1] == 2)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{what}: pairs is an integer [P,2] table (ops.footprint_pairs)")
+    q = np.ascontiguousarray(q.reshape(-1, 2).astype(np.int32))
+    key = q[:, 0].astype(np.int64) * max(N, 1) + q[:, 1]
+    if len(q) and ((q[:, 0] < 0) | (q[:, 0] > q[:, 1]) | (q[:, 1] >= N) | (np.diff(key, prepend=-1) <= 0)).any():
+        raise ValueError(f"{what}: every row of pairs is 0 <= n <= m < {N}, ascending in (n, m)")
+    return q
+
+
+def footprint_overlaps(footprints, pairs):
+    """float64 [P] on the device: G[p] = sum over the intersection of boxes n and m of w_n(v) w_m(v) for ``pairs[p]`` = (n, m).
+    ``footprints``: what ``NeuronFootprints.finish`` returns (``boxes``, ``offsets`` on the host, ``weights`` float32 [V] on the
+    device); ``pairs``: ``footprint_pairs``' table.  Each product is exact in float64; one wave adds a pair's in a fixed tree."""
+    import numpy as np
+    what = "footprint_overlaps"
+    try:
+        boxes, offsets, w = footprints.boxes, footprints.offsets, footprints.weights
+    except AttributeError:
+        raise ValueError(f"{what}: footprints is what NeuronFootprints.finish returns") from None
+    bx = _box_table(boxes, "boxes", what)
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+    if len(off) != len(bx) + 1:
+        raise ValueError(f"{what}: offsets is the int64 [N+1] table of the boxes")
+    q = _pair_table(pairs, len(bx), what)
+    _dev(w, "weights")
+    if w.dim() != 1 or w.numel() != int(off[-1]) or not w.is_contiguous():
+        raise ValueError(f"{what}: weights is a contiguous [V] tensor, V = offsets[N] = {int(off[-1])}")
+    L = _lib.lib()
+    G = torch.empty(len(q), dtype=torch.float64, device=w.device)
+    ws = torch.empty(len(q) * _lib.DEMIX_PAIR_BYTES // 8, dtype=torch.int64, device=w.device)
+    check(L.cwfa_footprint_overlaps_f32(_p(w), _host(bx), _host(off), len(bx), _host(q), len(q), _p(ws), _p(G), _stream()), what)
+    return G
+
+
+def demix_structure(pairs, N):
+    """(rowptr int32 [N+1], col int32 [E]) on the host: the directed CSR pattern of ``pairs``' off-diagonal entries, (n, m) and
+    (m, n) for every pair n < m, columns ascending within a row."""
+    import numpy as np
+    q = _pair_table(pairs, N, "demix_structure")
+    off = q[q[:, 0] != q[:, 1]]
+    rows, cols = np.concatenate([off[:, 0], off[:, 1]]), np.concatenate([off[:, 1], off[:, 0]])
+    order = np.lexsort((cols, rows))
+    rowptr = np.zeros(N + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=N), out=rowptr[1:])
+    if rowptr[-1] >= 1 << 31:
+        raise ValueError("demix_structure: 2^31 entries or more")
+    return rowptr.astype(np.int32), np.ascontiguousarray(cols[order].astype(np.int32))
+
+
+class DemixPlan:
+    """What demixing needs of a recording's footprints, computed once: on the host ``pairs`` int32 [P,2] (``footprint_pairs``) and the
+    directed CSR pattern ``rowptr`` int32 [N+1], ``col`` int32 [E]; on the device ``G`` float64 [P] (``footprint_overlaps``) and ``val``
+    float64 [E], the mixing coefficients M_nm = (G_nm wsum_m) / (G_mm wsum_n) of the entries (0.0 where G_nm == 0, a denominator is
+    not > 0 or a footprint is empty).  The index arrays the kernels read are the library's own checked copy, behind ``handle``."""
+
+    def __init__(self, footprints, pairs=None):
+        import numpy as np
+        what = "DemixPlan"
+        try:
+            wsum, sizes = footprints.wsum, footprints.sizes
+            N = len(footprints.boxes)
+        except (AttributeError, TypeError):
+            raise ValueError(f"{what}: footprints is what NeuronFootprints.finish returns") from None
+        self.N = N
+        self.pairs = footprint_pairs(footprints.boxes) if pairs is None else _pair_table(pairs, N, what)
+        for t, dt, name in ((wsum, torch.float64, "wsum"), (sizes, torch.int32, "sizes")):
+            if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != (N,) or not t.is_contiguous():
+                raise ValueError(f"{what}: {name} is a contiguous {dt} [{N}] tensor on the HIP device")
+        self.rowptr, self.col = demix_structure(self.pairs, N)
+        self.E = len(self.col)
+        self.G = footprint_overlaps(footprints, self.pairs)
+        self.device = self.G.device
+        L = _lib.lib()
+        handle = C.c_void_p()
+        self.handle = None
+        check(L.cwfa_demix_plan_create(_host(self.rowptr), _host(self.col), N, _host(self.pairs), len(self.pairs), C.byref(handle)), what)
+        self.handle = handle
+        self.val = torch.empty(self.E, dtype=torch.float64, device=self.device)
+        check(L.cwfa_demix_coeffs_f64(self.handle, _p(self.G), len(self.pairs), _p(wsum), _p(sizes), N, _p(self.val), _stream()), what)
+
+    def __del__(self):
+        handle, self.handle = getattr(self, "handle", None), None
+        if handle is not None:
+            try:
+                _lib.lib().cwfa_demix_plan_destroy(handle)
+            except Exception:                                                     # interpreter shutdown
+                pass
+
+
+def demix_solve(F, plan, n_sweeps=64, tol=0.0, nonneg=True):
+    """(Fd float64 [N,T], sweeps int32 [T]): projected Gauss-Seidel on F_n = f_n + sum_m M_nm f_m, independently per time step, from
+    f = F, n = 0 .. N-1 per sweep, a row's entries by ascending m; with ``nonneg`` a negative value becomes 0.  A time step ends
+    after the first sweep in which every change is <= ``tol``, or after ``n_sweeps``.  ``F``: float64 device [N,T], rows contiguous,
+    any row stride; rows of empty footprints come back NaN and feed nobody."""
+    what = "demix_solve"
+    if not isinstance(plan, DemixPlan):
+        raise ValueError(f"{what}: plan is a DemixPlan")
+    n_sweeps, tol = int(n_sweeps), float(tol)
+    if n_sweeps < 1:
+        raise ValueError(f"{what}: n_sweeps = {n_sweeps} is not positive")
+    if not tol >= 0.0:
+        raise ValueError(f"{what}: tol = {tol} is negative or NaN")
+    F, N, T, stride = _rows(F, what, "F")
+    if N != plan.N:
+        raise ValueError(f"{what}: F has {N} rows, the plan {plan.N} neurons")
+    if F.device != plan.device:
+        raise ValueError(f"{what}: F is on {F.device}, the plan on {plan.device}")
+    L = _lib.lib()
+    out = torch.empty(N, T, dtype=torch.float64, device=F.device)
+    sweeps = torch.empty(T, dtype=torch.int32, device=F.device)
+    check(L.cwfa_demix_solve_f64(_p(F), stride, _p(out), N, T, plan.handle, min(n_sweeps, 0x7fffffff), tol, int(bool(nonneg)), _p(sweeps),
+                                 _stream()), what)
+    return out, sweeps
+
+
 # ------------------------------------------------------------------------------------------------ trace post-processing
 def _rows(x, what, name="traces"):
     """A float64 device [N, T] tensor with contiguous rows (T >= 1) as (tensor, N, T, row stride in elements): a view with a row

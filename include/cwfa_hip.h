@@ -1185,6 +1185,45 @@ int64_t cwfa_ar1_deconv_workspace_bytes(int N, int T);
 int cwfa_ar1_deconv_f64(const double* y, int N, int T, int64_t stride, double gamma, const double* lam, const double* pw, double* c,
                         double* s, int32_t* pools, void* ws, void* stream);
 
+/* ---- demixing of overlapping footprints: between the footprints and the traces' post-processing.  With w_n a
+ * footprint's weights (the ragged fp32 array of cwfa_footprint_select_f32), wsum_n their sum and F the traces sum w x / wsum, the
+ * voxels are modelled as sum_m w_m(v) c_m(t), so that F_n = f_n + sum_{m != n} M_nm f_m.  Every float64 operation is rounded
+ * separately; no atomics; two runs are bitwise equal.
+ *
+ *   footprint_overlaps: G[p] (DEVICE double [P]) = sum over the intersection of boxes n and m of w_n(v) w_m(v) for pairs[p] = (n, m),
+ *                      each product exact in float64, added by one wave in a fixed tree; an empty intersection gives 0.0.  boxes,
+ *                      offsets: the HOST tables of the footprints (boxes well-formed and below 2^31 voxels each, offsets their
+ *                      running volume); pairs: HOST int32 [P][2], 0 <= n <= m < N, strictly ascending in (n, m), P < 2^31.  ws: DEVICE,
+ *                      P * CWFA_DEMIX_PAIR_BYTES bytes, 8-byte aligned: the entry point writes one record per pair (the intersection
+ *                      and where it starts in either box) from the checked tables and copies them there on the stream, waiting
+ *                      for the copy; the kernel indexes with nothing else.
+ *   demix_plan_create: checks the directed CSR structure of the coupled neurons (HOST rowptr int32 [N+1] from 0 and monotone, col
+ *                      int32 [rowptr[N]] in 0 .. N-1, ascending within a row, never the row itself) against the pair table (every
+ *                      entry (n, m) has its pair (min, max) and the diagonal pair (m, m)), and keeps a DEVICE copy of its own:
+ *                      the only index arrays the two kernels below read.  Allocates and synchronises: once per recording.
+ *                      demix_plan_destroy frees it; a pointer that is not a live plan is refused by every entry point.
+ *   demix_coeffs:      the CSR values, a thread per entry: M_nm = (G_nm wsum_m) / (G_mm wsum_n) for the entry (n, m), 0.0 where
+ *                      G_nm == 0, where G_mm, wsum_n or their product is not > 0 and where sizes[n] or sizes[m] is 0.  G: DEVICE
+ *                      double [P] in the order of the plan's pair table; wsum double [N], sizes int32 [N]: DEVICE.  The values stay
+ *                      in the plan; val_out (nullable, DEVICE double [E]) receives a copy.
+ *   demix_solve:       projected Gauss-Seidel, one thread per time step.  F: DEVICE double [N][T], f_stride >= T elements between rows;
+ *                      out: double [N][T] contiguous, not F; sweeps: int32 [T].  out = F (NaN in the rows with sizes == 0), then per
+ *                      sweep and n = 0 .. N-1: acc = 0.0; over the row's entries by ascending m, acc = acc + M_nm out_m where M_nm
+ *                      != 0.0 (selected: a NaN behind a zero coefficient reaches nobody); new = F_n - acc, with nonneg new < 0
+ *                      becomes 0.0 (NaN stays; every NaN is stored as 0x7ff8000000000000); out_n = new.  A time step ends after the
+ *                      first sweep in which every |new - old| <= tol (a NaN difference is not; the rows with sizes == 0 do not
+ *                      count) or after n_sweeps >= 1; sweeps[t] is the number it ran.  tol >= 0. */
+#define CWFA_DEMIX_PAIR_BYTES 48
+typedef struct cwfa_demix_plan cwfa_demix_plan;
+int cwfa_footprint_overlaps_f32(const float* w, const int32_t* boxes, const int64_t* offsets, int N, const int32_t* pairs, int64_t P,
+                                void* ws, double* G, void* stream);
+int cwfa_demix_plan_create(const int32_t* rowptr, const int32_t* col, int N, const int32_t* pairs, int64_t P, cwfa_demix_plan** plan);
+int cwfa_demix_plan_destroy(cwfa_demix_plan* plan);
+int cwfa_demix_coeffs_f64(cwfa_demix_plan* plan, const double* G, int64_t P, const double* wsum, const int32_t* sizes, int N,
+                          double* val_out, void* stream);
+int cwfa_demix_solve_f64(const double* F, int64_t f_stride, double* out, int N, int T, const cwfa_demix_plan* plan, int n_sweeps,
+                         double tol, int nonneg, int32_t* sweeps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
