@@ -15,7 +15,7 @@ import torch
 
 from . import ops
 from .amp import amp_function, amp_region
-from .XLFMDataset import quantile_rank, taper_window
+from .XLFMDataset import _estimate, _reg_args, _register, _register_args, quantile_rank, taper_window
 
 __all__ = ["sample_z_truncated", "check_empty_depths", "evaluate_INN_forward", "inverse_pass", "nll_step",
            "nll_terms", "allreduce_nll", "build_networks", "step_log_likelihoods", "allgather_scores", "detect_ood",
@@ -923,35 +923,14 @@ VolumeRegistration = namedtuple("VolumeRegistration", ["volumes", "shifts", "pea
 
 
 def _vol_reg_args(volumes, template, max_shift, taper, smooth, eps, chunk, subpixel, what):
-    """The checks of ``estimate_volume_shifts`` that need no device: ((mz, my, mx), (tz, ty, tx))."""
-    if not torch.is_tensor(volumes) or volumes.dim() != 4 or not volumes.is_contiguous():
-        raise ValueError(f"{what}: a contiguous [N,D,H,W] stack is expected")
-    if volumes.dtype != torch.float32:
-        raise ValueError(f"{what}: a float32 stack is expected, got {volumes.dtype}")
-    shape = tuple(int(s) for s in volumes.shape[1:])
-    if template is not None and (not torch.is_tensor(template) or tuple(template.shape) != shape or template.dtype != torch.float32):
-        raise ValueError(f"{what}: the template is a float32 {list(shape)} tensor, the shape of a volume")
+    """The checks of ``estimate_volume_shifts`` that need no device, those of ``XLFMDataset._reg_args`` and the refusal of the
+    up-sampled DFT: ((mz, my, mx), (tz, ty, tx), chunk)."""
+    args = _reg_args(volumes, template, max_shift, taper, smooth, eps, chunk, what, "volume")[:3]
     if isinstance(subpixel, str):
         if subpixel == "dft":
             raise ValueError(f"{what}: subpixel='dft' (the up-sampled DFT of section 26.5) is not built for volumes; True fits a parabola per axis")
         raise ValueError(f"{what}: subpixel is True or False, got {subpixel!r}")
-    m = ops._max_shift3(max_shift, *shape, what)
-    if taper is None:
-        taper = tuple(min(16, s // 8) for s in shape)
-    elif isinstance(taper, int):
-        taper = (taper,) * 3
-    else:
-        taper = tuple(int(t) for t in taper)
-        if len(taper) != 3:
-            raise ValueError(f"{what}: taper is an int or (tz, ty, tx), got {taper!r}")
-    if any(t < 0 or 2 * t > s for t, s in zip(taper, shape)):
-        raise ValueError(f"{what}: taper = {taper} does not fit a {shape} volume twice")
-    smooth, eps = float(smooth), float(eps)
-    if not 0.0 <= smooth < float("inf") or not 0.0 <= eps < float("inf"):
-        raise ValueError(f"{what}: smooth and eps are finite and not negative, got {smooth}, {eps}")
-    if int(chunk) < 1:
-        raise ValueError(f"{what}: chunk must be at least 1, got {chunk}")
-    return m, taper
+    return args
 
 
 @amp_region
@@ -967,34 +946,12 @@ def estimate_volume_shifts(volumes, template, max_shift=(2, 8, 8), taper=None, s
     with ``subpixel``, refined by a parabola per axis.  ``subpixel="dft"`` is refused: it is not built for volumes.  The volumes go
     through in chunks of ``chunk`` (a chunk's spectra are chunk x D x H x (W/2+1) x 8 bytes: 101 MB per 96 x 512 x 512 volume)."""
     what = "estimate_volume_shifts"
-    (mz, my, mx), (tz, ty, tx) = _vol_reg_args(volumes, template, max_shift, taper, smooth, eps, chunk, subpixel, what)
+    m, taper, chunk = _vol_reg_args(volumes, template, max_shift, taper, smooth, eps, chunk, subpixel, what)
     if template is None:
         raise ValueError(f"{what}: a template is needed")
-    N, D, H, W = (int(s) for s in volumes.shape)
-    dev = volumes.device
-    wz, wy, wx = taper_window(D, tz).to(dev), taper_window(H, ty).to(dev), taper_window(W, tx).to(dev)
-    T = torch.fft.rfftn(ops.reg_window3d(template.contiguous()[None], wz, wy, wx)[0], dim=(-3, -2, -1)).contiguous()
-    U = torch.view_as_real(ops.reg_whiten(T, None, eps, out=T))
-    if smooth > 0.0:
-        kz, ky, kx = (torch.fft.fftfreq(D, dtype=torch.float64), torch.fft.fftfreq(H, dtype=torch.float64), torch.fft.rfftfreq(W, dtype=torch.float64))
-        k2 = kz[:, None, None] ** 2 + ky[None, :, None] ** 2 + kx[None, None, :] ** 2
-        G = torch.exp(-2.0 * math.pi ** 2 * smooth ** 2 * k2).to(torch.float32).to(dev)
-        Wt = torch.stack((U[..., 0] * G, -U[..., 1] * G), dim=-1)
-    else:
-        Wt = torch.stack((U[..., 0], -U[..., 1]), dim=-1)
-    Wt[0, 0, 0] = 0.0
-    Wt = torch.view_as_complex(Wt)
-    shifts = torch.empty((N, 3), dtype=torch.float32, device=dev)
-    ipeak = torch.empty((N, 3), dtype=torch.int32, device=dev)
-    peak = torch.empty((N,), dtype=torch.float32, device=dev)
-    chunk = min(int(chunk), max(N, 1))
-    buf = torch.empty((chunk, D, H, W), dtype=torch.float32, device=dev)
-    for s in range(0, N, chunk):
-        e = min(s + chunk, N)
-        F = torch.fft.rfftn(ops.reg_window3d(volumes[s:e], wz, wy, wx, out=buf[:e - s]), dim=(-3, -2, -1)).contiguous()
-        corr = torch.fft.irfftn(ops.reg_whiten(F, Wt, eps, out=F), s=(D, H, W), dim=(-3, -2, -1))
-        ops.reg_peak3d(corr, (mz, my, mx), bool(subpixel), out=(shifts[s:e], ipeak[s:e], peak[s:e]))
-    return shifts, peak
+    w = [taper_window(n, t).to(volumes.device) for n, t in zip(volumes.shape[1:], taper)]
+    return _estimate(lambda s, e, out: ops.reg_window3d(volumes[s:e], *w, out=out), ops.reg_window3d(template.contiguous()[None], *w)[0],
+                     int(volumes.shape[0]), tuple(int(n) for n in volumes.shape[1:]), m, smooth, eps, bool(subpixel), False, None, chunk)
 
 
 def _shift_volume_args(volumes, shifts, mode, out, what):
@@ -1036,17 +993,10 @@ def register_volumes(volumes, template=None, n_iter=1, max_shift=(2, 8, 8), subp
     Nothing is read back."""
     what = "register_volumes"
     _vol_reg_args(volumes, template, max_shift, taper, smooth, eps, chunk, subpixel, what)
-    _shift_volume_args(volumes, None, mode, out, what)
-    if int(n_iter) < 1:
-        raise ValueError(f"{what}: n_iter must be at least 1, got {n_iter}")
-    if int(volumes.shape[0]) < 1:
-        raise ValueError(f"{what}: at least one volume is expected")
-    tmpl = _volume_median(volumes) if template is None else template
-    for it in range(int(n_iter)):
-        shifts, peak = estimate_volume_shifts(volumes, tmpl, max_shift=max_shift, taper=taper, smooth=smooth, eps=eps, subpixel=subpixel, chunk=chunk)
-        out = shift_volumes(volumes, shifts, mode=mode, fill=fill, out=out)
-        if it + 1 < int(n_iter):
-            tmpl = _volume_median(out)
+    _register_args(volumes, n_iter, mode, out, what, "volume")
+    estimate = lambda tmpl: estimate_volume_shifts(volumes, tmpl, max_shift=max_shift, taper=taper, smooth=smooth, eps=eps, subpixel=subpixel, chunk=chunk)
+    out, (shifts, peak), tmpl = _register(volumes, template, n_iter, _volume_median, estimate,
+                                          lambda est, out: shift_volumes(volumes, est[0], mode=mode, fill=fill, out=out), out)
     return VolumeRegistration(out, shifts, peak, tmpl)
 
 

@@ -126,25 +126,46 @@ def taper_window(n, taper):
     return w.to(torch.float32)
 
 
-def _reg_args(frames, template, max_shift, taper, smooth, eps, chunk, what):
-    """The checks of ``estimate_shifts`` that need no device: (my, mx, taper)."""
-    if not torch.is_tensor(frames) or frames.dim() != 3 or not frames.is_contiguous():
-        raise ValueError(f"{what}: a contiguous [N,H,W] stack is expected")
-    if frames.dtype not in (torch.float32, torch.float16):
-        raise ValueError(f"{what}: a float32 or float16 stack is expected, got {frames.dtype}")
-    H, W = int(frames.shape[1]), int(frames.shape[2])
-    if template is not None and (not torch.is_tensor(template) or tuple(template.shape) != (H, W) or template.dtype != torch.float32):
-        raise ValueError(f"{what}: the template is a float32 [{H}, {W}] tensor, the shape of a frame")
-    my, mx = ops._max_shift(max_shift, H, W, what)
-    taper = min(16, min(H, W) // 8) if taper is None else int(taper)
-    if taper < 0 or 2 * taper > min(H, W):
-        raise ValueError(f"{what}: taper = {taper} does not fit a {H} x {W} frame twice")
+def _reg_args(stack, template, max_shift, taper, smooth, eps, chunk, what, item="frame", views=None):
+    """The checks of the three estimators that need no device, for a stack of frames (``item`` "frame", or "view" with ``views`` =
+    (centers, view_shape): window and taper are then a view's) or of volumes ("volume"): (max_shift and taper per axis, chunk,
+    centers int32 [L,2] or None)."""
+    rank = 3 if item == "volume" else 2
+    layout, dtypes, word = ("[N,D,H,W]", (torch.float32,), "float32") if rank == 3 else ("[N,H,W]", (torch.float32, torch.float16), "float32 or float16")
+    if not torch.is_tensor(stack) or stack.dim() != rank + 1 or not stack.is_contiguous():
+        raise ValueError(f"{what}: a contiguous {layout} stack is expected")
+    if stack.dtype not in dtypes:
+        raise ValueError(f"{what}: a {word} stack is expected, got {stack.dtype}")
+    sides = tuple(int(n) for n in stack.shape[1:])
+    if template is not None and (not torch.is_tensor(template) or tuple(template.shape) != sides or template.dtype != torch.float32):
+        raise ValueError(f"{what}: the template is a float32 {list(sides)} tensor, the shape of a {'volume' if rank == 3 else 'frame'}")
+    c = None
+    if views is not None:
+        c, *sides = ops._view_centers(*views, what)
+    m = ops._max_shift(max_shift, *sides, what)
+    if rank == 2:                                                     # one width for both axes
+        taper = (min(16, min(sides) // 8) if taper is None else int(taper),) * 2
+        shown, size = taper[0], f"{sides[0]} x {sides[1]}"
+    else:
+        if taper is None:
+            taper = tuple(min(16, n // 8) for n in sides)
+        elif isinstance(taper, int):
+            taper = (taper,) * 3
+        else:
+            taper = tuple(int(t) for t in taper)
+            if len(taper) != 3:
+                raise ValueError(f"{what}: taper is an int or (tz, ty, tx), got {taper!r}")
+        shown, size = taper, tuple(sides)
+    if any(t < 0 or 2 * t > n for t, n in zip(taper, sides)):
+        raise ValueError(f"{what}: taper = {shown} does not fit a {size} {item} twice")
     smooth, eps = float(smooth), float(eps)
     if not 0.0 <= smooth < float("inf") or not 0.0 <= eps < float("inf"):
         raise ValueError(f"{what}: smooth and eps are finite and not negative, got {smooth}, {eps}")
+    if chunk is None and views is not None:
+        chunk = max(1, VIEW_CHUNK_BYTES // (len(c) * sides[0] * sides[1] * 4))
     if int(chunk) < 1:
         raise ValueError(f"{what}: chunk must be at least 1, got {chunk}")
-    return my, mx, taper
+    return m, taper, int(chunk), c
 
 
 def _subpixel_arg(subpixel, upsample, what):
@@ -154,6 +175,46 @@ def _subpixel_arg(subpixel, upsample, what):
             raise ValueError(f"{what}: subpixel is True, False or 'dft', got {subpixel!r}")
         return True, ops._count(upsample, "upsample", what)
     return False, None
+
+
+def _estimate(window, tapered, N, shape, max_shift, smooth, eps, subpixel, dft, upsample, chunk):
+    """(shifts float32 [n, rank], peak float32 [n]), n = N x the items of a stack element: the phase correlation the three estimators
+    share.  ``tapered``: the tapered float32 template, [*items, *shape] with ``shape`` the 2 or 3 transformed axes (items: nothing, or
+    L views); ``window(s, e, out)`` writes the tapered float32 elements s .. e - 1 of the stack into ``out`` [e - s, *items, *shape] and
+    returns it.  The template is transformed, whitened and conjugated, low-passed where ``smooth`` > 0, its DC bin zeroed; a chunk
+    is windowed, transformed, whitened against that plane, transformed back, and searched for its peak."""
+    rank, dev = len(shape), tapered.device
+    axes = tuple(range(-rank, 0))
+    per = math.prod(tapered.shape[:-rank])
+    T = torch.fft.rfftn(tapered, dim=axes).contiguous()
+    U = torch.view_as_real(ops.reg_whiten(T, None, eps, out=T))
+    if smooth > 0.0:
+        k2 = None                                                     # the axes' squared frequencies, summed in axis order, float64
+        for a, n in enumerate(shape):
+            k = (torch.fft.rfftfreq if a == rank - 1 else torch.fft.fftfreq)(n, dtype=torch.float64)
+            k = k.reshape([-1 if b == a else 1 for b in range(rank)]) ** 2
+            k2 = k if k2 is None else k2 + k
+        G = torch.exp(-2.0 * math.pi ** 2 * smooth ** 2 * k2).to(torch.float32).to(dev)
+        Wt = torch.stack((U[..., 0] * G, -U[..., 1] * G), dim=-1)
+    else:
+        Wt = torch.stack((U[..., 0], -U[..., 1]), dim=-1)
+    Wt[(..., *(0,) * rank, slice(None))] = 0.0                        # DC, per item
+    Wt = torch.view_as_complex(Wt)
+    shifts = torch.empty((N * per, rank), dtype=torch.float32, device=dev)
+    ipeak = torch.empty((N * per, rank), dtype=torch.int32, device=dev)
+    peak = torch.empty((N * per,), dtype=torch.float32, device=dev)
+    chunk = min(chunk, max(N, 1))
+    buf = torch.empty((chunk, *tapered.shape), dtype=torch.float32, device=dev)
+    for s in range(0, N, chunk):
+        e = min(s + chunk, N)
+        a, b = s * per, e * per
+        F = torch.fft.rfftn(window(s, e, buf[:e - s]), dim=axes).contiguous()  # (a no-op where rocFFT's layout is dense)
+        corr = torch.fft.irfftn(ops.reg_whiten(F, Wt, eps, out=F), s=shape, dim=axes).reshape(b - a, *shape)
+        (ops.reg_peak if rank == 2 else ops.reg_peak3d)(corr, max_shift, subpixel and not dft, out=(shifts[a:b], ipeak[a:b], peak[a:b]))
+        if dft:                                                       # F is read again: irfft2 leaves its input alone (section 26.5)
+            ops.reg_fine_peak(ops.reg_upsample(F.reshape(b - a, shape[0], shape[1] // 2 + 1), ipeak[a:b], shape, upsample), ipeak[a:b], upsample,
+                              out=(shifts[a:b], peak[a:b]))
+    return shifts, peak
 
 
 @amp_region
@@ -170,36 +231,15 @@ def estimate_shifts(frames, template, max_shift=16, taper=None, smooth=0.0, eps=
     1 / ``upsample`` px over +-1 px around the integer peak (an up-sampled DFT in float64, section 26.5) and the parabola is fitted
     on that grid; ``peak`` is then the fine maximum.  The frames go through in chunks of ``chunk`` (their spectra are
     chunk x H x (W/2+1) x 8 bytes)."""
-    my, mx, taper = _reg_args(frames, template, max_shift, taper, smooth, eps, chunk, "estimate_shifts")
-    dft, upsample = _subpixel_arg(subpixel, upsample, "estimate_shifts")
+    what = "estimate_shifts"
+    m, (ty, tx), chunk, _ = _reg_args(frames, template, max_shift, taper, smooth, eps, chunk, what)
+    dft, upsample = _subpixel_arg(subpixel, upsample, what)
     if template is None:
-        raise ValueError("estimate_shifts: a template is needed")
+        raise ValueError(f"{what}: a template is needed")
     N, H, W = (int(s) for s in frames.shape)
-    dev = frames.device
-    wy, wx = taper_window(H, taper).to(dev), taper_window(W, taper).to(dev)
-    T = torch.fft.rfft2(ops.reg_window(template.contiguous()[None], wy, wx)[0]).contiguous()
-    U = torch.view_as_real(ops.reg_whiten(T, None, eps, out=T))
-    if smooth > 0.0:
-        ky, kx = torch.fft.fftfreq(H, dtype=torch.float64), torch.fft.rfftfreq(W, dtype=torch.float64)
-        G = torch.exp(-2.0 * math.pi ** 2 * smooth ** 2 * (ky[:, None] ** 2 + kx[None, :] ** 2)).to(torch.float32).to(dev)
-        Wt = torch.stack((U[..., 0] * G, -U[..., 1] * G), dim=-1)
-    else:
-        Wt = torch.stack((U[..., 0], -U[..., 1]), dim=-1)
-    Wt[0, 0] = 0.0
-    Wt = torch.view_as_complex(Wt)
-    shifts = torch.empty((N, 2), dtype=torch.float32, device=dev)
-    ipeak = torch.empty((N, 2), dtype=torch.int32, device=dev)
-    peak = torch.empty((N,), dtype=torch.float32, device=dev)
-    chunk = min(int(chunk), max(N, 1))
-    buf = torch.empty((chunk, H, W), dtype=torch.float32, device=dev)
-    for s in range(0, N, chunk):
-        e = min(s + chunk, N)
-        F = torch.fft.rfft2(ops.reg_window(frames[s:e], wy, wx, out=buf[:e - s])).contiguous()  # (a no-op where rocFFT's layout is dense)
-        corr = torch.fft.irfft2(ops.reg_whiten(F, Wt, eps, out=F), s=(H, W))
-        ops.reg_peak(corr, (my, mx), subpixel and not dft, out=(shifts[s:e], ipeak[s:e], peak[s:e]))
-        if dft:                                                       # F is read again: irfft2 leaves its input alone (section 26.5)
-            ops.reg_fine_peak(ops.reg_upsample(F, ipeak[s:e], (H, W), upsample), ipeak[s:e], upsample, out=(shifts[s:e], peak[s:e]))
-    return shifts, peak
+    wy, wx = taper_window(H, ty).to(frames.device), taper_window(W, tx).to(frames.device)
+    return _estimate(lambda s, e, out: ops.reg_window(frames[s:e], wy, wx, out=out), ops.reg_window(template.contiguous()[None], wy, wx)[0], N, (H, W),
+                     m, smooth, eps, subpixel, dft, upsample, chunk)
 
 
 @amp_region
@@ -218,6 +258,36 @@ def shift_frames(frames, shifts, mode="bilinear", fill=0.0, out=None):
     return ops.reg_shift(frames, shifts, mode=mode, fill=fill, out=out)
 
 
+def _register_args(stack, n_iter, mode, out, what, item="frame"):
+    """The checks the three ``register_*`` add to their estimator's."""
+    if int(n_iter) < 1:
+        raise ValueError(f"{what}: n_iter must be at least 1, got {n_iter}")
+    if mode not in ("bilinear", "nearest"):
+        raise ValueError(f"{what}: mode is 'bilinear' or 'nearest', got {mode!r}")
+    if out is not None and (out is stack or (torch.is_tensor(out) and ops._overlap(out, stack))):
+        raise ValueError(f"{what}: out must not alias {item}s")
+    if int(stack.shape[0]) < 1:
+        raise ValueError(f"{what}: at least one {item} is expected")
+
+
+def _register(stack, template, n_iter, median, estimate, move, out):
+    """(moved stack, the last estimate, the last template): ``estimate(template)`` measures the stack against a template --
+    ``median(stack)`` where none is given -- and ``move(estimate, out)`` resamples THE ORIGINAL stack under it; with ``n_iter`` > 1
+    the template becomes the median of the moved stack and both are done again, so interpolation never compounds."""
+    tmpl = median(stack) if template is None else template
+    for it in range(int(n_iter)):
+        est = estimate(tmpl)
+        out = move(est, out)
+        if it + 1 < int(n_iter):
+            tmpl = median(out)
+    return out, est, tmpl
+
+
+def _frame_median(frames):
+    """The per-pixel lower temporal median of a [N,H,W] stack."""
+    return ops.temporal_select(frames, [quantile_rank(0.5, int(frames.shape[0]))])[0]
+
+
 @amp_region
 def register_frames(frames, template=None, n_iter=1, max_shift=16, subpixel=True, mode="bilinear", taper=None, smooth=0.0, eps=1e-5,
                     chunk=16, fill=0.0, out=None, upsample=16):
@@ -228,23 +298,11 @@ def register_frames(frames, template=None, n_iter=1, max_shift=16, subpixel=True
     ``estimate_shifts`` and ``shift_frames``.  Nothing is read back."""
     _reg_args(frames, template, max_shift, taper, smooth, eps, chunk, "register_frames")
     _subpixel_arg(subpixel, upsample, "register_frames")
-    if int(n_iter) < 1:
-        raise ValueError(f"register_frames: n_iter must be at least 1, got {n_iter}")
-    if mode not in ("bilinear", "nearest"):
-        raise ValueError(f"register_frames: mode is 'bilinear' or 'nearest', got {mode!r}")
-    if out is not None and (out is frames or (torch.is_tensor(out) and ops._overlap(out, frames))):
-        raise ValueError("register_frames: out must not alias frames")
-    N = int(frames.shape[0])
-    if N < 1:
-        raise ValueError("register_frames: at least one frame is expected")
-    median = lambda x: ops.temporal_select(x, [quantile_rank(0.5, N)])[0]
-    tmpl = median(frames) if template is None else template
-    for it in range(int(n_iter)):
-        shifts, peak = estimate_shifts(frames, tmpl, max_shift=max_shift, taper=taper, smooth=smooth, eps=eps, subpixel=subpixel, chunk=chunk,
-                                      upsample=upsample)
-        out = shift_frames(frames, shifts, mode=mode, fill=fill, out=out)
-        if it + 1 < int(n_iter):
-            tmpl = median(out)
+    _register_args(frames, n_iter, mode, out, "register_frames")
+    estimate = lambda tmpl: estimate_shifts(frames, tmpl, max_shift=max_shift, taper=taper, smooth=smooth, eps=eps, subpixel=subpixel, chunk=chunk,
+                                            upsample=upsample)
+    out, (shifts, peak), tmpl = _register(frames, template, n_iter, _frame_median, estimate,
+                                          lambda est, out: shift_frames(frames, est[0], mode=mode, fill=fill, out=out), out)
     return Registration(out, shifts, peak, tmpl)
 
 
@@ -281,30 +339,6 @@ def view_labels(shape, centers, view_shape, device="cuda"):
     return ops.reg_label_map(shape, centers, view_shape, device)
 
 
-def _view_args(frames, template, centers, view_shape, max_shift, taper, smooth, eps, chunk, what):
-    """The checks of ``estimate_view_shifts`` that need no device: (centers int32 [L,2], ph, pw, my, mx, taper, chunk)."""
-    if not torch.is_tensor(frames) or frames.dim() != 3 or not frames.is_contiguous():
-        raise ValueError(f"{what}: a contiguous [N,H,W] stack is expected")
-    if frames.dtype not in (torch.float32, torch.float16):
-        raise ValueError(f"{what}: a float32 or float16 stack is expected, got {frames.dtype}")
-    H, W = int(frames.shape[1]), int(frames.shape[2])
-    if template is not None and (not torch.is_tensor(template) or tuple(template.shape) != (H, W) or template.dtype != torch.float32):
-        raise ValueError(f"{what}: the template is a float32 [{H}, {W}] tensor, the shape of a frame")
-    c, ph, pw = ops._view_centers(centers, view_shape, what)
-    my, mx = ops._max_shift(max_shift, ph, pw, what)
-    taper = min(16, min(ph, pw) // 8) if taper is None else int(taper)
-    if taper < 0 or 2 * taper > min(ph, pw):
-        raise ValueError(f"{what}: taper = {taper} does not fit a {ph} x {pw} view twice")
-    smooth, eps = float(smooth), float(eps)
-    if not 0.0 <= smooth < float("inf") or not 0.0 <= eps < float("inf"):
-        raise ValueError(f"{what}: smooth and eps are finite and not negative, got {smooth}, {eps}")
-    if chunk is None:
-        chunk = max(1, VIEW_CHUNK_BYTES // (len(c) * ph * pw * 4))
-    if int(chunk) < 1:
-        raise ValueError(f"{what}: chunk must be at least 1, got {chunk}")
-    return c, ph, pw, my, mx, taper, int(chunk)
-
-
 @amp_region
 def estimate_view_shifts(frames, template, centers, view_shape, max_shift=8, taper=None, smooth=0.0, eps=1e-5, subpixel=True, chunk=None,
                          upsample=16):
@@ -316,37 +350,15 @@ def estimate_view_shifts(frames, template, centers, view_shape, max_shift=8, tap
     FRAMES: a chunk holds chunk x L x ph x pw x 4 bytes of tapered views plus their spectra, chunk x L x ph x (pw/2+1) x 8 bytes, and
     the correlation maps; None keeps the views at or below 256 MiB.  Nothing is read back."""
     what = "estimate_view_shifts"
-    c, ph, pw, my, mx, taper, chunk = _view_args(frames, template, centers, view_shape, max_shift, taper, smooth, eps, chunk, what)
+    m, (ty, tx), chunk, c = _reg_args(frames, template, max_shift, taper, smooth, eps, chunk, what, "view", (centers, view_shape))
     dft, upsample = _subpixel_arg(subpixel, upsample, what)
     if template is None:
         raise ValueError(f"{what}: a template is needed")
-    N, L = int(frames.shape[0]), len(c)
-    dev = frames.device
-    wy, wx = taper_window(ph, taper).to(dev), taper_window(pw, taper).to(dev)
-    T = torch.fft.rfft2(ops.reg_window_views(template.contiguous()[None], c, (ph, pw), wy, wx)[0]).contiguous()      # [L, ph, pw/2+1]
-    U = torch.view_as_real(ops.reg_whiten(T, None, eps, out=T))
-    if smooth > 0.0:
-        ky, kx = torch.fft.fftfreq(ph, dtype=torch.float64), torch.fft.rfftfreq(pw, dtype=torch.float64)
-        G = torch.exp(-2.0 * math.pi ** 2 * smooth ** 2 * (ky[:, None] ** 2 + kx[None, :] ** 2)).to(torch.float32).to(dev)
-        Wt = torch.stack((U[..., 0] * G, -U[..., 1] * G), dim=-1)
-    else:
-        Wt = torch.stack((U[..., 0], -U[..., 1]), dim=-1)
-    Wt[:, 0, 0] = 0.0
-    Wt = torch.view_as_complex(Wt)
-    shifts = torch.empty((N * L, 2), dtype=torch.float32, device=dev)
-    ipeak = torch.empty((N * L, 2), dtype=torch.int32, device=dev)
-    peak = torch.empty((N * L,), dtype=torch.float32, device=dev)
-    chunk = min(chunk, max(N, 1))
-    buf = torch.empty((chunk, L, ph, pw), dtype=torch.float32, device=dev)
-    for s in range(0, N, chunk):
-        e = min(s + chunk, N)
-        a, b = s * L, e * L
-        F = torch.fft.rfft2(ops.reg_window_views(frames[s:e], c, (ph, pw), wy, wx, out=buf[:e - s])).contiguous()
-        corr = torch.fft.irfft2(ops.reg_whiten(F, Wt, eps, out=F), s=(ph, pw)).reshape(b - a, ph, pw)
-        ops.reg_peak(corr, (my, mx), subpixel and not dft, out=(shifts[a:b], ipeak[a:b], peak[a:b]))
-        if dft:
-            ops.reg_fine_peak(ops.reg_upsample(F.reshape(b - a, ph, pw // 2 + 1), ipeak[a:b], (ph, pw), upsample), ipeak[a:b], upsample,
-                              out=(shifts[a:b], peak[a:b]))
+    N, L, (ph, pw) = int(frames.shape[0]), len(c), (int(v) for v in view_shape)
+    wy, wx = taper_window(ph, ty).to(frames.device), taper_window(pw, tx).to(frames.device)
+    shifts, peak = _estimate(lambda s, e, out: ops.reg_window_views(frames[s:e], c, (ph, pw), wy, wx, out=out),
+                             ops.reg_window_views(template.contiguous()[None], c, (ph, pw), wy, wx)[0], N, (ph, pw), m, smooth, eps, subpixel, dft,
+                             upsample, chunk)
     return shifts.reshape(N, L, 2), peak.reshape(N, L)
 
 
@@ -411,31 +423,22 @@ def register_views(frames, centers, view_shape, template=None, directions=None, 
     and the shifts are estimated again FROM THE ORIGINAL FRAMES.  ``labels``: the map of ``view_labels`` where it is at hand.  The
     other arguments are those of ``estimate_view_shifts``, ``fit_view_shifts`` and ``shift_views``.  Nothing is read back."""
     what = "register_views"
-    c = _view_args(frames, template, centers, view_shape, max_shift, taper, smooth, eps, chunk, what)[0]
+    c = _reg_args(frames, template, max_shift, taper, smooth, eps, chunk, what, "view", (centers, view_shape))[3]
     _subpixel_arg(subpixel, upsample, what)
-    if int(n_iter) < 1:
-        raise ValueError(f"{what}: n_iter must be at least 1, got {n_iter}")
-    if mode not in ("bilinear", "nearest"):
-        raise ValueError(f"{what}: mode is 'bilinear' or 'nearest', got {mode!r}")
+    _register_args(frames, n_iter, mode, out, what)
     if model not in ("axial", "free"):
         raise ValueError(f"{what}: model is 'axial' or 'free', got {model!r}")
-    if out is not None and (out is frames or (torch.is_tensor(out) and ops._overlap(out, frames))):
-        raise ValueError(f"{what}: out must not alias frames")
-    N, H, W = (int(s) for s in frames.shape)
-    if N < 1:
-        raise ValueError(f"{what}: at least one frame is expected")
     g = _directions(directions, c, frames.device, what)
     if labels is None:
-        labels = view_labels((H, W), c, view_shape, frames.device)
-    median = lambda x: ops.temporal_select(x, [quantile_rank(0.5, N)])[0]
-    tmpl = median(frames) if template is None else template
-    for it in range(int(n_iter)):
-        shifts, peak = estimate_view_shifts(frames, tmpl, c, view_shape, max_shift=max_shift, taper=taper, smooth=smooth, eps=eps,
-                                            subpixel=subpixel, chunk=chunk, upsample=upsample)
-        fit = fit_view_shifts(shifts, peak, g, min_peak=min_peak, reject=reject, model=model)
-        out = shift_views(frames, fit.table, labels, mode=mode, fill=fill, out=out)
-        if it + 1 < int(n_iter):
-            tmpl = median(out)
+        labels = view_labels(frames.shape[1:], c, view_shape, frames.device)
+
+    def estimate(tmpl):
+        shifts, peak = estimate_view_shifts(frames, tmpl, c, view_shape, max_shift=max_shift, taper=taper, smooth=smooth, eps=eps, subpixel=subpixel,
+                                            chunk=chunk, upsample=upsample)
+        return shifts, peak, fit_view_shifts(shifts, peak, g, min_peak=min_peak, reject=reject, model=model)
+
+    out, (shifts, peak, fit), tmpl = _register(frames, template, n_iter, _frame_median, estimate,
+                                               lambda est, out: shift_views(frames, est[2].table, labels, mode=mode, fill=fill, out=out), out)
     return ViewRegistration(out, fit.table, fit.params, shifts, peak, fit.inlier, tmpl)
 
 

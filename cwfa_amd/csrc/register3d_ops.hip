@@ -1,51 +1,20 @@
 // Rigid registration of reconstructed volumes: the passes of section 26 carried to [N, D, H, W] stacks.  rocFFT
 // (through torch.fft.rfftn) does the transforms and cwfa_reg_whiten_c64 the whitened cross-power (a bin is a bin in any dimension);
-// here are the edge taper (rwin3_*), the peak (rpeak3_*) and the trilinear resampling (rshift3_*).  Each is the 2-D arithmetic of
-// register_ops.hip plus one axis, spelled so that D = 1 gives the 2-D bits.  All offsets into a stack are 64-bit: 32 volumes of
-// 96 x 512 x 512 are 3 * 2^28 elements.  Built with -ffp-contract=off; the counted operations use the __f*_rn intrinsics all the same.
+// the edge taper is the kernel of register_internal.h that the frames run at D = 1; here are its entry point for volumes, the peak
+// (rpeak3_*, over the key and the parabola of register_internal.h) and the trilinear resampling (rshift3_*), the 2-D arithmetic plus
+// one axis, spelled so that D = 1 gives the 2-D bits.  All offsets into a stack are 64-bit: 32 volumes of 96 x 512 x 512 are
+// 3 * 2^28 elements.  Built with -ffp-contract=off; the counted operations use the __f*_rn intrinsics all the same.
 #include <math.h>
 #include "common.h"
 #include "register_internal.h"
-
-typedef unsigned long long rkey_t;
-
-// ------------------------------------------------------------------------------------------------ the window
-// out[n,z,y,x] = fl(x[n,z,y,x] * fl(fl(wz[z] * wy[y]) * wx[x])): one read, one write.  A thread owns V voxels of a row, keeps their
-// window product and walks the volumes blockIdx.y, blockIdx.y + gridDim.y, ..
-template <int V>
-__global__ __launch_bounds__(256) void rwin3_kernel(const float* __restrict__ x, int N, int D, int H, int W, int64_t vs, const float* __restrict__ wz,
-                                                    const float* __restrict__ wy, const float* __restrict__ wx, float* __restrict__ out) {
-    typedef float fvec __attribute__((ext_vector_type(V)));
-    const int Wv = W / V;                                             // V > 1: W is a multiple of V
-    const int64_t rows = (int64_t)D * H;
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= rows * Wv) return;
-    const int64_t row = q / Wv;                                       // z * H + y
-    const int x0 = (int)(q - row * Wv) * V;
-    const int z = (int)(row / H), y = (int)(row - (int64_t)z * H);
-    const int64_t p = row * W + x0;
-    const int64_t P = rows * W;
-    float w[V];
-    {
-        const float a = __fmul_rn(wz[z], wy[y]);
-        const fvec b = *reinterpret_cast<const fvec*>(wx + x0);
-#pragma unroll
-        for (int j = 0; j < V; ++j) w[j] = __fmul_rn(a, b[j]);
-    }
-    for (int n = blockIdx.y; n < N; n += gridDim.y) {
-        const fvec v = *reinterpret_cast<const fvec*>(x + (int64_t)n * vs + p);
-        fvec r;
-#pragma unroll
-        for (int j = 0; j < V; ++j) r[j] = __fmul_rn(v[j], w[j]);
-        *reinterpret_cast<fvec*>(out + (int64_t)n * P + p) = r;
-    }
-}
 
 // what the three entry points ask of a volume: sides that stay ints with a margin, fewer than 2^31 voxels
 static inline bool r3_sizes_ok(int D, int H, int W) {
     return D < (1 << 30) && H < (1 << 30) && W < (1 << 30) && (int64_t)D * H < ((int64_t)1 << 31) && (int64_t)D * H * W < ((int64_t)1 << 31);
 }
 
+// ------------------------------------------------------------------------------------------------ the window
+// out[n,z,y,x] = fl(x[n,z,y,x] * fl(fl(wz[z] * wy[y]) * wx[x])): reg_window_kernel (register_internal.h), fp32 only.
 extern "C" int cwfa_reg_window3d_f32(const float* x, int N, int D, int H, int W, int64_t vol_stride, const float* wz, const float* wy,
                                      const float* wx, float* out, void* stream) {
     CWFA_REQUIRE(x && wz && wy && wx && out, CWFA_E_INVAL, "cwfa_reg_window3d_f32: null pointer");
@@ -59,37 +28,16 @@ extern "C" int cwfa_reg_window3d_f32(const float* x, int N, int D, int H, int W,
     CWFA_REQUIRE(vol_stride >= P, CWFA_E_INVAL, "cwfa_reg_window3d_f32: volume stride smaller than a volume");
     CWFA_REQUIRE(out != x, CWFA_E_INVAL, "cwfa_reg_window3d_f32: out must not be the stack");
     const bool v4 = (W & 3) == 0 && (vol_stride & 3) == 0 && cwfa_aligned16(wx) && cwfa_aligned16(out) && cwfa_aligned16(x);
-    const int64_t gx = ((v4 ? P >> 2 : P) + 255) / 256;               // < 2^23
-    const dim3 grid((unsigned)gx, reg_grid_y(gx, N, 65536));
-    hipStream_t st = (hipStream_t)stream;
-    if (v4) hipLaunchKernelGGL((rwin3_kernel<4>), grid, dim3(256), 0, st, x, N, D, H, W, vol_stride, wz, wy, wx, out);
-    else hipLaunchKernelGGL((rwin3_kernel<1>), grid, dim3(256), 0, st, x, N, D, H, W, vol_stride, wz, wy, wx, out);
+    reg_window_launch(x, false, N, D, H, W, vol_stride, wz, wy, wx, out, v4, (hipStream_t)stream);
     CWFA_LAUNCH_CHECK("cwfa_reg_window3d_f32");
     return CWFA_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ the peak
-// One workgroup per volume.  Window index i (row-major from (-mz, -my, -mx)) reads c at the shifts modulo (D, H, W); the key, its
-// order and the reduction are rpeak_kernel's (register_ops.hip): the maximum over a thread's indices, over the wave by shuffles,
-// over the waves through the LDS, no atomics.  Thread 0 then reads the peak's six neighbours (modulo the sides: they may lie
-// outside the window) and fits the three parabolas in float64.
-#define RPEAK3_THREADS 256
-
-__device__ __forceinline__ rkey_t rpeak3_key(float v, unsigned i) {
-    unsigned u = __builtin_bit_cast(unsigned, v);
-    u = u == 0x80000000u ? 0u : u;                                    // v + 0.0f
-    const unsigned o = v != v ? 0u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
-    return ((rkey_t)o << 32) | (rkey_t)(0xFFFFFFFFu - i);
-}
-
-__device__ __forceinline__ double rpeak3_delta(float cm, float c0, float cp) {
-    const double a = (double)cm, b = (double)c0, c = (double)cp;
-    const double den = (a - 2.0 * b) + c;
-    double d = (0.5 * (a - c)) / den;
-    if (!(den < 0.0) || !(fabs(d) <= 1.7976931348623157e308)) d = 0.0;
-    return d < -0.5 ? -0.5 : (d > 0.5 ? 0.5 : d);
-}
-
+// One workgroup per volume.  Window index i (row-major from (-mz, -my, -mx)) reads c at the shifts modulo (D, H, W); the key and its
+// order are reg_peak_key's (register_internal.h), the reduction is rpeak_kernel's (register_ops.hip): the maximum over a thread's
+// indices, over the wave by shuffles, over the waves through the LDS, no atomics.  Thread 0 then reads the peak's six neighbours
+// (modulo the sides: they may lie outside the window) and fits the three parabolas in float64.
 struct rpeak3_pos {
     int sz, sy, sx, z, y, x;
 };
@@ -103,20 +51,20 @@ __device__ __forceinline__ rpeak3_pos rpeak3_at(unsigned i, int D, int H, int W,
     return p;
 }
 
-__global__ __launch_bounds__(RPEAK3_THREADS) void rpeak3_kernel(const float* __restrict__ c, int N, int D, int H, int W, int64_t vs, int mz, int my,
+__global__ __launch_bounds__(REG_PEAK_THREADS) void rpeak3_kernel(const float* __restrict__ c, int N, int D, int H, int W, int64_t vs, int mz, int my,
                                                                 int mx, int subpixel, float* __restrict__ shifts, int* __restrict__ ipeak,
                                                                 float* __restrict__ peak) {
-    __shared__ rkey_t best[RPEAK3_THREADS / 64];
-    __shared__ int finite[RPEAK3_THREADS / 64];
+    __shared__ rkey_t best[REG_PEAK_THREADS / 64];
+    __shared__ int finite[REG_PEAK_THREADS / 64];
     const unsigned nwin = (2u * (unsigned)mz + 1u) * (2u * (unsigned)my + 1u) * (2u * (unsigned)mx + 1u);   // <= D * H * W < 2^31
     for (int n = blockIdx.x; n < N; n += gridDim.x) {                 // uniform over the workgroup
         const float* cn = c + (int64_t)n * vs;
         rkey_t k = 0;
         bool fin = false;
-        for (unsigned i = threadIdx.x; i < nwin; i += RPEAK3_THREADS) {
+        for (unsigned i = threadIdx.x; i < nwin; i += REG_PEAK_THREADS) {
             const rpeak3_pos p = rpeak3_at(i, D, H, W, mz, my, mx);
             const float v = cn[((int64_t)p.z * H + p.y) * W + p.x];
-            const rkey_t kv = rpeak3_key(v, i);
+            const rkey_t kv = reg_peak_key(v, i);
             k = kv > k ? kv : k;
             fin = fin || fabsf(v) < INFINITY;
         }
@@ -132,7 +80,7 @@ __global__ __launch_bounds__(RPEAK3_THREADS) void rpeak3_kernel(const float* __r
         if (threadIdx.x != 0) continue;
         int any = 0;
 #pragma unroll
-        for (int w = 0; w < RPEAK3_THREADS / 64; ++w) {
+        for (int w = 0; w < REG_PEAK_THREADS / 64; ++w) {
             k = best[w] > k ? best[w] : k;
             any |= finite[w];
         }
@@ -153,9 +101,9 @@ __global__ __launch_bounds__(RPEAK3_THREADS) void rpeak3_kernel(const float* __r
             const int zm = p.z == 0 ? D - 1 : p.z - 1, zp = p.z + 1 == D ? 0 : p.z + 1;
             const int ym = p.y == 0 ? H - 1 : p.y - 1, yp = p.y + 1 == H ? 0 : p.y + 1;
             const int xm = p.x == 0 ? W - 1 : p.x - 1, xp = p.x + 1 == W ? 0 : p.x + 1;
-            dz = rpeak3_delta(at(zm, p.y, p.x), c0, at(zp, p.y, p.x));
-            dy = rpeak3_delta(at(p.z, ym, p.x), c0, at(p.z, yp, p.x));
-            dx = rpeak3_delta(at(p.z, p.y, xm), c0, at(p.z, p.y, xp));
+            dz = reg_parabola((double)at(zm, p.y, p.x), (double)c0, (double)at(zp, p.y, p.x));
+            dy = reg_parabola((double)at(p.z, ym, p.x), (double)c0, (double)at(p.z, yp, p.x));
+            dx = reg_parabola((double)at(p.z, p.y, xm), (double)c0, (double)at(p.z, p.y, xp));
         }
         s[0] = (float)((double)p.sz + dz), s[1] = (float)((double)p.sy + dy), s[2] = (float)((double)p.sx + dx);
         ip[0] = p.sz, ip[1] = p.sy, ip[2] = p.sx;
@@ -179,7 +127,7 @@ extern "C" int cwfa_reg_peak3d_f32(const float* c, int N, int D, int H, int W, i
                  2 * (long long)my + 1, 2 * (long long)mx + 1, D, H, W);
     CWFA_REQUIRE(vol_stride >= (int64_t)D * H * W, CWFA_E_INVAL, "cwfa_reg_peak3d_f32: volume stride smaller than a volume");
     const unsigned gx = N < 65536 ? (unsigned)N : 65536u;             // a workgroup walks the volumes gridDim.x apart
-    hipLaunchKernelGGL(rpeak3_kernel, dim3(gx), dim3(RPEAK3_THREADS), 0, (hipStream_t)stream, c, N, D, H, W, vol_stride, mz, my, mx, subpixel, shifts,
+    hipLaunchKernelGGL(rpeak3_kernel, dim3(gx), dim3(REG_PEAK_THREADS), 0, (hipStream_t)stream, c, N, D, H, W, vol_stride, mz, my, mx, subpixel, shifts,
                        ipeak, peak);
     CWFA_LAUNCH_CHECK("cwfa_reg_peak3d_f32");
     return CWFA_OK;

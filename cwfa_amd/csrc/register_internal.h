@@ -1,10 +1,16 @@
-// What the resampling kernels of the registration share (register_ops.hip: one shift per frame; register_views_ops.hip: one shift
-// per pixel label): the arithmetic of step 7 of DESIGN.md section 26.1 for V consecutive pixels of a row, and the grid rule of the
-// kernels whose threads walk the frames.  One definition, so that the labelled form is the rigid form's bits by construction.
+// What the registration kernels share (register_ops.hip: frames; register_views_ops.hip: lenslet views; register3d_ops.hip: volumes).
+// One definition of each, so that a frame is a volume of one plane by construction and not by a copy kept in step:
+//   the grid rule of the kernels whose threads walk the items                                         reg_grid_y
+//   the edge taper over [N, D, H, W], D = 1 and no wz for frames                                      reg_window_kernel
+//   the order of the integer peak's keys and the float64 parabola                                     reg_peak_key, reg_parabola
+//   the arithmetic of step 7 of DESIGN.md section 26.1 for V consecutive pixels of a row              rshift_pixels
+//   the store form of the two 2-D resampling entry points                                             reg_store_width
 #pragma once
 #include <math.h>
 #include <type_traits>
 #include "common.h"
+
+typedef unsigned long long rkey_t;
 
 // blocks along y for a kernel whose threads walk the frames: about `target` blocks in all, the per-pixel values reused over N / gy
 // frames.  The window and the resampling keep a few words per thread and take many blocks (an even tail); the whitening keeps a
@@ -13,6 +19,79 @@ static inline unsigned reg_grid_y(int64_t gx, int N, int64_t target) {
     int64_t gy = target / gx < 1 ? 1 : target / gx;
     gy = gy > 65535 ? 65535 : gy;
     return (unsigned)(gy > N ? N : gy);
+}
+
+// ------------------------------------------------------------------------------------------------ the window
+// out[n,z,y,x] = fl(float(x[n,z,y,x]) * fl(a * wx[x])) with a = fl(wz[z] * wy[y]), or, PLANAR (frames: D = 1, wz null), wy[y] itself:
+// no product by 1 is formed and no z is split off.  One read, one fp32 write.  A thread owns V elements of a row, keeps their
+// window product and walks the items blockIdx.y, blockIdx.y + gridDim.y, ..  `stride` is the distance between items, in elements.
+// (PLANAR is a compile-time flag because it measured: with `wz ? .. : ..` decided in the kernel the fp16 chunk of DESIGN.md
+// section 26.3 took 0.095 ms beside 0.090 ms.)
+template <int V, bool HALF, bool PLANAR>
+__global__ __launch_bounds__(256) void reg_window_kernel(const void* __restrict__ x, int N, int D, int H, int W, int64_t stride,
+                                                         const float* __restrict__ wz, const float* __restrict__ wy, const float* __restrict__ wx,
+                                                         float* __restrict__ out) {
+    using elem = std::conditional_t<HALF, _Float16, float>;
+    typedef float fvec __attribute__((ext_vector_type(V)));
+    typedef elem evec __attribute__((ext_vector_type(V)));
+    const int Wv = W / V;                                             // V > 1: W is a multiple of V
+    const int64_t rows = (int64_t)D * H;
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= rows * Wv) return;
+    const int64_t row = q / Wv;                                       // z * H + y < 2^31
+    const int x0 = (int)(q - row * Wv) * V;
+    const int z = PLANAR ? 0 : (int)((unsigned)row / (unsigned)H), y = (int)row - z * H;
+    const int64_t p = row * W + x0;
+    const int64_t P = rows * W;
+    float w[V];
+    {
+        const float a = PLANAR ? wy[y] : __fmul_rn(wz[z], wy[y]);
+        const fvec b = *reinterpret_cast<const fvec*>(wx + x0);
+#pragma unroll
+        for (int j = 0; j < V; ++j) w[j] = __fmul_rn(a, b[j]);
+    }
+    for (int n = blockIdx.y; n < N; n += gridDim.y) {
+        const evec v = *reinterpret_cast<const evec*>(reinterpret_cast<const elem*>(x) + (int64_t)n * stride + p);
+        fvec r;
+#pragma unroll
+        for (int j = 0; j < V; ++j) r[j] = __fmul_rn((float)v[j], w[j]);
+        *reinterpret_cast<fvec*>(out + (int64_t)n * P + p) = r;
+    }
+}
+
+// the launch of both entry points, whose checks have been made: D * H * W < 2^31, `v4` where 16-byte (fp16: 8-byte) accesses are
+// allowed; a null wz is the frames' form (D = 1), fp16 is theirs alone
+static inline void reg_window_launch(const void* x, bool half, int N, int D, int H, int W, int64_t stride, const float* wz, const float* wy,
+                                     const float* wx, float* out, bool v4, hipStream_t st) {
+    const int64_t P = (int64_t)D * H * W;
+    const int64_t gx = ((v4 ? P >> 2 : P) + 255) / 256;               // < 2^23
+    const dim3 grid((unsigned)gx, reg_grid_y(gx, N, 65536));
+#define REG_WINDOW_LAUNCH(V, HALF, PLANAR) \
+    hipLaunchKernelGGL((reg_window_kernel<V, HALF, PLANAR>), grid, dim3(256), 0, st, x, N, D, H, W, stride, wz, wy, wx, out)
+    if (wz) { if (v4) REG_WINDOW_LAUNCH(4, false, false); else REG_WINDOW_LAUNCH(1, false, false); }
+    else if (v4) { if (half) REG_WINDOW_LAUNCH(4, true, true); else REG_WINDOW_LAUNCH(4, false, true); }
+    else { if (half) REG_WINDOW_LAUNCH(1, true, true); else REG_WINDOW_LAUNCH(1, false, true); }
+#undef REG_WINDOW_LAUNCH
+}
+
+// ------------------------------------------------------------------------------------------------ the peak's order and parabola
+// key = ord(c + 0.0f) << 32 | (0xFFFFFFFF - i), the order of the detector (neuron_ops.hip): NaN has ord 0, ties go to the lowest
+// window index i.  The peak kernels (rpeak_kernel, rpeak3_kernel) take the maximum key; they and the fine peak fit reg_parabola.
+#define REG_PEAK_THREADS 256
+
+__device__ __forceinline__ rkey_t reg_peak_key(float v, unsigned i) {
+    unsigned u = __builtin_bit_cast(unsigned, v);
+    u = u == 0x80000000u ? 0u : u;                                    // v + 0.0f
+    const unsigned o = v != v ? 0u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
+    return ((rkey_t)o << 32) | (rkey_t)(0xFFFFFFFFu - i);
+}
+
+// the offset of the vertex of the parabola through (-1, a), (0, b), (1, c), clamped to half a sample; 0 where b is no strict maximum
+__device__ __forceinline__ double reg_parabola(double a, double b, double c) {
+    const double den = (a - 2.0 * b) + c;
+    double d = (0.5 * (a - c)) / den;
+    if (!(den < 0.0) || !(fabs(d) <= 1.7976931348623157e308)) d = 0.0;
+    return d < -0.5 ? -0.5 : (d > 0.5 ? 0.5 : d);
 }
 
 template <class T, int K>
@@ -86,3 +165,25 @@ __device__ __forceinline__ void rshift_pixels(const elem* __restrict__ src, int 
         }
     }
 }
+
+// ------------------------------------------------------------------------------------------------ the store form of the 2-D resampling
+// Pixels per thread of rshift_kernel and rshiftl_kernel: 16-byte stores where W and out's base allow (eight fp16 or four fp32 pixels),
+// four fp16 pixels (8 bytes) next, else one.  Every row of every frame then starts on that alignment; the loads take any.
+static inline int reg_store_width(int dtype, int W, const void* out) {
+    if (dtype == 1 && (W & 7) == 0 && cwfa_aligned16(out)) return 8;
+    if ((W & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & (dtype ? 7u : 15u)) == 0) return 4;
+    return 1;
+}
+
+// launches KERNEL<V, HALF> for the width `v` of reg_store_width on a grid of ceil(P / v / 256) x reg_grid_y blocks, P pixels a frame
+#define REG_SHIFT_LAUNCH(KERNEL, v, dtype, P, N, st, ...)                                                                  \
+    do {                                                                                                                   \
+        const int v_ = (v);                                                                                                \
+        const int64_t gx_ = ((P) / v_ + 255) / 256;                                                                        \
+        const dim3 grid_((unsigned)gx_, reg_grid_y(gx_, N, 65536));                                                        \
+        if (v_ == 8) hipLaunchKernelGGL((KERNEL<8, true>), grid_, dim3(256), 0, st, __VA_ARGS__);                          \
+        else if (v_ == 4 && (dtype)) hipLaunchKernelGGL((KERNEL<4, true>), grid_, dim3(256), 0, st, __VA_ARGS__);          \
+        else if (v_ == 4) hipLaunchKernelGGL((KERNEL<4, false>), grid_, dim3(256), 0, st, __VA_ARGS__);                    \
+        else if (dtype) hipLaunchKernelGGL((KERNEL<1, true>), grid_, dim3(256), 0, st, __VA_ARGS__);                       \
+        else hipLaunchKernelGGL((KERNEL<1, false>), grid_, dim3(256), 0, st, __VA_ARGS__);                                 \
+    } while (0)

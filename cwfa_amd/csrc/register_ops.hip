@@ -1,52 +1,18 @@
 // Rigid frame registration in front of sparse-activity extraction: phase correlation of every frame of a stack
 // against a template, an integer peak in a bounded window with parabolic sub-pixel refinement, and resampling.  rocFFT (through
-// torch.fft) does the transforms; the four passes around them are here: the edge taper (rwin_*), the whitened cross-power
-// (rwht_*), the peak (rpeak_*) and the resampling (rshift_*).  The shifts stay on the device from the peak kernel to the resampling
-// kernel.  Behind them the up-sampled DFT that refines the peak from the whitened spectra (rups_*, rfp_*; section 26.5).  Built with
-// -ffp-contract=off; the products, sums and differences the restatement (tests/register_ref.py) counts are
-// spelled with the __f*_rn intrinsics all the same, the square root and the divisions with sqrtf and / (see rwht_one).
+// torch.fft) does the transforms; the four passes around them are here: the edge taper (the kernel of register_internal.h, which
+// the volumes of section 30 share), the whitened cross-power (rwht_*), the peak (rpeak_*) and the resampling (rshift_*).
+// The shifts stay on the device from the peak kernel to the resampling kernel.  Behind them the up-sampled DFT that refines the
+// peak from the whitened spectra (rups_*, rfp_*; section 26.5).  Built with -ffp-contract=off; the products, sums and differences
+// the restatement (tests/register_ref.py) counts are spelled with the __f*_rn intrinsics all the same, the square root and the
+// divisions with sqrtf and / (see rwht_one).
 #include <math.h>
 #include <type_traits>
 #include "common.h"
 #include "register_internal.h"
 
-typedef unsigned long long rkey_t;
-
 // ------------------------------------------------------------------------------------------------ the window
-// out[n,y,x] = fl(float(x[n,y,x]) * fl(wy[y] * wx[x])): one read, one fp32 write.  A thread owns V pixels of a row, keeps their
-// window product and walks the frames blockIdx.y, blockIdx.y + gridDim.y, ..
-template <int V, bool HALF>
-__global__ __launch_bounds__(256) void rwin_kernel(const void* __restrict__ x, int N, int H, int W, int64_t fs, const float* __restrict__ wy,
-                                                   const float* __restrict__ wx, float* __restrict__ out) {
-    typedef float fvec __attribute__((ext_vector_type(V)));
-    typedef _Float16 hvec __attribute__((ext_vector_type(V)));
-    const int Wv = W / V;                                             // V > 1: W is a multiple of V
-    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= (int64_t)H * Wv) return;
-    const int y = (int)(q / Wv), x0 = (int)(q - (int64_t)y * Wv) * V;
-    const int64_t p = (int64_t)y * W + x0;
-    float w[V];
-    {
-        const float a = wy[y];
-        const fvec b = *reinterpret_cast<const fvec*>(wx + x0);
-#pragma unroll
-        for (int j = 0; j < V; ++j) w[j] = __fmul_rn(a, b[j]);
-    }
-    for (int n = blockIdx.y; n < N; n += gridDim.y) {
-        fvec r;
-        if constexpr (HALF) {
-            const hvec v = *reinterpret_cast<const hvec*>(reinterpret_cast<const _Float16*>(x) + (int64_t)n * fs + p);
-#pragma unroll
-            for (int j = 0; j < V; ++j) r[j] = __fmul_rn((float)v[j], w[j]);
-        } else {
-            const fvec v = *reinterpret_cast<const fvec*>(reinterpret_cast<const float*>(x) + (int64_t)n * fs + p);
-#pragma unroll
-            for (int j = 0; j < V; ++j) r[j] = __fmul_rn(v[j], w[j]);
-        }
-        *reinterpret_cast<fvec*>(out + (int64_t)n * H * W + p) = r;
-    }
-}
-
+// out[n,y,x] = fl(float(x[n,y,x]) * fl(wy[y] * wx[x])): reg_window_kernel (register_internal.h) over [N, 1, H, W] without a z factor.
 extern "C" int cwfa_reg_window(const void* x, int dtype, int N, int H, int W, int64_t frame_stride, const float* wy, const float* wx,
                                float* out, void* stream) {
     CWFA_REQUIRE(x && wy && wx && out, CWFA_E_INVAL, "cwfa_reg_window: null pointer");
@@ -59,13 +25,7 @@ extern "C" int cwfa_reg_window(const void* x, int dtype, int N, int H, int W, in
     CWFA_REQUIRE(static_cast<const void*>(out) != x, CWFA_E_INVAL, "cwfa_reg_window: out must not be the stack");
     const uintptr_t xa = reinterpret_cast<uintptr_t>(x);
     const bool v4 = (W & 3) == 0 && (frame_stride & 3) == 0 && cwfa_aligned16(wx) && cwfa_aligned16(out) && (xa & (dtype ? 7u : 15u)) == 0;
-    const int64_t gx = ((v4 ? P >> 2 : P) + 255) / 256;
-    const dim3 grid((unsigned)gx, reg_grid_y(gx, N, 65536));
-    hipStream_t st = (hipStream_t)stream;
-#define RWIN_LAUNCH(V, HALF) hipLaunchKernelGGL((rwin_kernel<V, HALF>), grid, dim3(256), 0, st, x, N, H, W, frame_stride, wy, wx, out)
-    if (v4) { if (dtype) RWIN_LAUNCH(4, true); else RWIN_LAUNCH(4, false); }
-    else { if (dtype) RWIN_LAUNCH(1, true); else RWIN_LAUNCH(1, false); }
-#undef RWIN_LAUNCH
+    reg_window_launch(x, dtype == 1, N, 1, H, W, frame_stride, nullptr, wy, wx, out, v4, (hipStream_t)stream);
     CWFA_LAUNCH_CHECK("cwfa_reg_window");
     return CWFA_OK;
 }
@@ -125,43 +85,25 @@ extern "C" int cwfa_reg_whiten_c64(const void* F, const void* Wt, int N, int64_t
 }
 
 // ------------------------------------------------------------------------------------------------ the peak
-// One workgroup per frame.  Window index i (row-major from (-my, -mx)) reads c at (sy mod H, sx mod W);
-// key = ord(c + 0.0f) << 32 | (0xFFFFFFFF - i), the order of the detector (neuron_ops.hip): NaN has ord 0, ties go to the lowest
-// index.  The maximum over a thread's indices, over the wave by shuffles, over the waves through the LDS: no atomics, and no trace
-// of the order the threads ran in.  Thread 0 then reads the peak's four neighbours (modulo H / W: they may lie outside the
-// window) and fits the two parabolas in float64.
-#define RPEAK_THREADS 256
-
-__device__ __forceinline__ rkey_t rpeak_key(float v, unsigned i) {
-    unsigned u = __builtin_bit_cast(unsigned, v);
-    u = u == 0x80000000u ? 0u : u;
-    const unsigned o = v != v ? 0u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));
-    return ((rkey_t)o << 32) | (rkey_t)(0xFFFFFFFFu - i);
-}
-
-__device__ __forceinline__ double rpeak_delta(float cm, float c0, float cp) {
-    const double a = (double)cm, b = (double)c0, c = (double)cp;
-    const double den = (a - 2.0 * b) + c;
-    double d = (0.5 * (a - c)) / den;
-    if (!(den < 0.0) || !(fabs(d) <= 1.7976931348623157e308)) d = 0.0;
-    return d < -0.5 ? -0.5 : (d > 0.5 ? 0.5 : d);
-}
-
-__global__ __launch_bounds__(RPEAK_THREADS) void rpeak_kernel(const float* __restrict__ c, int H, int W, int64_t fs, int my, int mx, int subpixel,
-                                                              float* __restrict__ shifts, int* __restrict__ ipeak, float* __restrict__ peak) {
-    __shared__ rkey_t best[RPEAK_THREADS / 64];
-    __shared__ int finite[RPEAK_THREADS / 64];
+// One workgroup per frame.  Window index i (row-major from (-my, -mx)) reads c at (sy mod H, sx mod W); the key is reg_peak_key
+// (register_internal.h): NaN below everything, ties to the lowest index.  The maximum over a thread's indices, over the wave by
+// shuffles, over the waves through the LDS: no atomics, and no trace of the order the threads ran in.  Thread 0 then reads the
+// peak's four neighbours (modulo H / W: they may lie outside the window) and fits the two parabolas in float64.
+__global__ __launch_bounds__(REG_PEAK_THREADS) void rpeak_kernel(const float* __restrict__ c, int H, int W, int64_t fs, int my, int mx, int subpixel,
+                                                                 float* __restrict__ shifts, int* __restrict__ ipeak, float* __restrict__ peak) {
+    __shared__ rkey_t best[REG_PEAK_THREADS / 64];
+    __shared__ int finite[REG_PEAK_THREADS / 64];
     const int n = blockIdx.x;
     const float* cn = c + (int64_t)n * fs;
     const int wh = 2 * my + 1, ww = 2 * mx + 1;
     const unsigned nwin = (unsigned)wh * (unsigned)ww;                // <= H * W < 2^31
     rkey_t k = 0;
     bool fin = false;
-    for (unsigned i = threadIdx.x; i < nwin; i += RPEAK_THREADS) {
+    for (unsigned i = threadIdx.x; i < nwin; i += REG_PEAK_THREADS) {
         const int r = (int)(i / (unsigned)ww), sy = r - my, sx = (int)(i - (unsigned)r * (unsigned)ww) - mx;
         const int y = sy < 0 ? sy + H : sy, x = sx < 0 ? sx + W : sx;   // |sy| < H and |sx| < W: the window fits the frame
         const float v = cn[(int64_t)y * W + x];
-        const rkey_t kv = rpeak_key(v, i);
+        const rkey_t kv = reg_peak_key(v, i);
         k = kv > k ? kv : k;
         fin = fin || fabsf(v) < INFINITY;
     }
@@ -176,7 +118,7 @@ __global__ __launch_bounds__(RPEAK_THREADS) void rpeak_kernel(const float* __res
     if (threadIdx.x != 0) return;
     int any = 0;
 #pragma unroll
-    for (int w = 0; w < RPEAK_THREADS / 64; ++w) {
+    for (int w = 0; w < REG_PEAK_THREADS / 64; ++w) {
         k = best[w] > k ? best[w] : k;
         any |= finite[w];
     }
@@ -194,8 +136,8 @@ __global__ __launch_bounds__(RPEAK_THREADS) void rpeak_kernel(const float* __res
     if (subpixel) {
         const int ym = y == 0 ? H - 1 : y - 1, yp = y + 1 == H ? 0 : y + 1;
         const int xm = x == 0 ? W - 1 : x - 1, xp = x + 1 == W ? 0 : x + 1;
-        dy = rpeak_delta(cn[(int64_t)ym * W + x], c0, cn[(int64_t)yp * W + x]);
-        dx = rpeak_delta(cn[(int64_t)y * W + xm], c0, cn[(int64_t)y * W + xp]);
+        dy = reg_parabola((double)cn[(int64_t)ym * W + x], (double)c0, (double)cn[(int64_t)yp * W + x]);
+        dx = reg_parabola((double)cn[(int64_t)y * W + xm], (double)c0, (double)cn[(int64_t)y * W + xp]);
     }
     shifts[2 * n] = (float)((double)sy + dy), shifts[2 * n + 1] = (float)((double)sx + dx);
     ipeak[2 * n] = sy, ipeak[2 * n + 1] = sx;
@@ -215,7 +157,7 @@ extern "C" int cwfa_reg_peak_f32(const float* c, int N, int H, int W, int64_t fr
     CWFA_REQUIRE(2 * (int64_t)my + 1 <= H && 2 * (int64_t)mx + 1 <= W, CWFA_E_SHAPE,
                  "cwfa_reg_peak_f32: the search window (%lld x %lld) is wider than the %d x %d frame", 2 * (long long)my + 1, 2 * (long long)mx + 1, H, W);
     CWFA_REQUIRE(frame_stride >= (int64_t)H * W, CWFA_E_INVAL, "cwfa_reg_peak_f32: frame stride smaller than a frame");
-    hipLaunchKernelGGL(rpeak_kernel, dim3((unsigned)N), dim3(RPEAK_THREADS), 0, (hipStream_t)stream, c, H, W, frame_stride, my, mx, subpixel,
+    hipLaunchKernelGGL(rpeak_kernel, dim3((unsigned)N), dim3(REG_PEAK_THREADS), 0, (hipStream_t)stream, c, H, W, frame_stride, my, mx, subpixel,
                        shifts, ipeak, peak);
     CWFA_LAUNCH_CHECK("cwfa_reg_peak_f32");
     return CWFA_OK;
@@ -263,19 +205,8 @@ extern "C" int cwfa_reg_shift(const void* in, int dtype, int N, int H, int W, in
     if (N == 0 || H == 0 || W == 0) return CWFA_OK;
     const int64_t P = (int64_t)H * W;
     CWFA_REQUIRE(frame_stride >= P, CWFA_E_INVAL, "cwfa_reg_shift: frame stride smaller than a frame");
-    // 16-byte stores where W and out's base allow: four fp32 or eight fp16 pixels per thread; four fp16 pixels (8 bytes) next
-    const bool v8 = dtype == 1 && (W & 7) == 0 && cwfa_aligned16(out);
-    const bool v4 = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & (dtype ? 7u : 15u)) == 0;
-    const int64_t gx = ((v8 ? P >> 3 : v4 ? P >> 2 : P) + 255) / 256;
-    const dim3 grid((unsigned)gx, reg_grid_y(gx, N, 65536));
-    hipStream_t st = (hipStream_t)stream;
     const f32x2* sh = reinterpret_cast<const f32x2*>(shifts);
-#define RSHIFT_LAUNCH(V, HALF) \
-    hipLaunchKernelGGL((rshift_kernel<V, HALF>), grid, dim3(256), 0, st, in, N, H, W, frame_stride, sh, mode, fill, out)
-    if (v8) RSHIFT_LAUNCH(8, true);
-    else if (v4) { if (dtype) RSHIFT_LAUNCH(4, true); else RSHIFT_LAUNCH(4, false); }
-    else { if (dtype) RSHIFT_LAUNCH(1, true); else RSHIFT_LAUNCH(1, false); }
-#undef RSHIFT_LAUNCH
+    REG_SHIFT_LAUNCH(rshift_kernel, reg_store_width(dtype, W, out), dtype, P, N, (hipStream_t)stream, in, N, H, W, frame_stride, sh, mode, fill, out);
     CWFA_LAUNCH_CHECK("cwfa_reg_shift");
     return CWFA_OK;
 }
@@ -490,18 +421,11 @@ __device__ __forceinline__ uint64_t rfp_ord(double v) {
 }
 __device__ __forceinline__ rfp_best rfp_max(rfp_best a, rfp_best b) { return (b.o > a.o || (b.o == a.o && b.i < a.i)) ? b : a; }
 
-__device__ __forceinline__ double rfp_delta(double a, double b, double c) {
-    const double den = (a - 2.0 * b) + c;
-    double d = (0.5 * (a - c)) / den;
-    if (!(den < 0.0) || !(fabs(d) <= 1.7976931348623157e308)) d = 0.0;
-    return d < -0.5 ? -0.5 : (d > 0.5 ? 0.5 : d);
-}
-
-__global__ __launch_bounds__(RPEAK_THREADS) void rfp_kernel(const double* __restrict__ C, const int* __restrict__ ipeak, int U, int u, int keep,
-                                                            float* __restrict__ shifts, float* __restrict__ peak) {
-    __shared__ uint64_t bo[RPEAK_THREADS / 64];
-    __shared__ unsigned bi[RPEAK_THREADS / 64];
-    __shared__ int finite[RPEAK_THREADS / 64];
+__global__ __launch_bounds__(REG_PEAK_THREADS) void rfp_kernel(const double* __restrict__ C, const int* __restrict__ ipeak, int U, int u, int keep,
+                                                               float* __restrict__ shifts, float* __restrict__ peak) {
+    __shared__ uint64_t bo[REG_PEAK_THREADS / 64];
+    __shared__ unsigned bi[REG_PEAK_THREADS / 64];
+    __shared__ int finite[REG_PEAK_THREADS / 64];
     const int n = blockIdx.x;
     if (keep) {                                                       // uniform over the workgroup
         const float p = peak[n];
@@ -511,7 +435,7 @@ __global__ __launch_bounds__(RPEAK_THREADS) void rfp_kernel(const double* __rest
     const unsigned cells = (unsigned)U * (unsigned)U;
     rfp_best k = {0ull, 0xFFFFFFFFu};
     bool fin = false;
-    for (unsigned i = threadIdx.x; i < cells; i += RPEAK_THREADS) {
+    for (unsigned i = threadIdx.x; i < cells; i += REG_PEAK_THREADS) {
         const double v = cn[i];
         k = rfp_max(k, rfp_best{rfp_ord(v), i});
         fin = fin || fabs(v) < (double)INFINITY;
@@ -524,7 +448,7 @@ __global__ __launch_bounds__(RPEAK_THREADS) void rfp_kernel(const double* __rest
     if (threadIdx.x != 0) return;
     int any = 0;
 #pragma unroll
-    for (int w = 0; w < RPEAK_THREADS / 64; ++w) {
+    for (int w = 0; w < REG_PEAK_THREADS / 64; ++w) {
         k = rfp_max(k, rfp_best{bo[w], bi[w]});
         any |= finite[w];
     }
@@ -538,8 +462,8 @@ __global__ __launch_bounds__(RPEAK_THREADS) void rfp_kernel(const double* __rest
     const int jy = (int)(k.i / (unsigned)U), jx = (int)(k.i - (unsigned)jy * (unsigned)U);
     const double c0 = cn[k.i];
     double dy = 0.0, dx = 0.0;
-    if (jy > 0 && jy < U - 1) dy = rfp_delta(cn[k.i - U], c0, cn[k.i + U]);
-    if (jx > 0 && jx < U - 1) dx = rfp_delta(cn[k.i - 1], c0, cn[k.i + 1]);
+    if (jy > 0 && jy < U - 1) dy = reg_parabola(cn[k.i - U], c0, cn[k.i + U]);
+    if (jx > 0 && jx < U - 1) dx = reg_parabola(cn[k.i - 1], c0, cn[k.i + 1]);
     shifts[2 * n] = (float)((double)py + ((double)(jy - r) + dy) / (double)u);
     shifts[2 * n + 1] = (float)((double)px + ((double)(jx - r) + dx) / (double)u);
     peak[n] = (float)c0;
@@ -555,7 +479,7 @@ extern "C" int cwfa_reg_fine_peak_f64(const double* C, const int* ipeak, int N, 
                      (reinterpret_cast<uintptr_t>(peak) & 3u) == 0,
                  CWFA_E_ALIGN, "cwfa_reg_fine_peak_f64: C, shifts and ipeak must be 8-byte aligned, peak 4-byte aligned");
     if (N == 0) return CWFA_OK;
-    hipLaunchKernelGGL(rfp_kernel, dim3((unsigned)N), dim3(RPEAK_THREADS), 0, (hipStream_t)stream, C, ipeak, U, u, keep, shifts, peak);
+    hipLaunchKernelGGL(rfp_kernel, dim3((unsigned)N), dim3(REG_PEAK_THREADS), 0, (hipStream_t)stream, C, ipeak, U, u, keep, shifts, peak);
     CWFA_LAUNCH_CHECK("cwfa_reg_fine_peak_f64");
     return CWFA_OK;
 }

@@ -297,19 +297,9 @@ extern "C" int cwfa_reg_shift_labeled(const void* in, int dtype, int N, int H, i
     CWFA_REQUIRE(out != in, CWFA_E_INVAL, "%s: out must not alias the stack", fn);
     if (N == 0) return CWFA_OK;
     const int64_t P = (int64_t)H * W;
-    // the store forms of cwfa_reg_shift: 16 bytes where W and out's base allow (four fp32 or eight fp16 pixels), four fp16 pixels next
-    const bool v8 = dtype == 1 && (W & 7) == 0 && cwfa_aligned16(out);
-    const bool v4 = (W & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & (dtype ? 7u : 15u)) == 0;
-    const int64_t gx = ((v8 ? P >> 3 : v4 ? P >> 2 : P) + 255) / 256;
-    const dim3 grid((unsigned)gx, reg_grid_y(gx, N, 65536));
-    hipStream_t st = (hipStream_t)stream;
     const f32x2* tb = reinterpret_cast<const f32x2*>(table);
-#define RSHIFTL_LAUNCH(V, HALF) \
-    hipLaunchKernelGGL((rshiftl_kernel<V, HALF>), grid, dim3(256), 0, st, in, N, H, W, frame_stride, tb, labels, L, mode, fill, out)
-    if (v8) RSHIFTL_LAUNCH(8, true);
-    else if (v4) { if (dtype) RSHIFTL_LAUNCH(4, true); else RSHIFTL_LAUNCH(4, false); }
-    else { if (dtype) RSHIFTL_LAUNCH(1, true); else RSHIFTL_LAUNCH(1, false); }
-#undef RSHIFTL_LAUNCH
+    REG_SHIFT_LAUNCH(rshiftl_kernel, reg_store_width(dtype, W, out), dtype, P, N, (hipStream_t)stream, in, N, H, W, frame_stride, tb, labels, L, mode,
+                     fill, out);
     CWFA_LAUNCH_CHECK("cwfa_reg_shift_labeled");
     return CWFA_OK;
 }

@@ -2659,15 +2659,25 @@ def sparse_residual(stack, a, b, tau=None, out=None, pair=False):
 
 
 # ------------------------------------------------------------------------------------------------ rigid frame registration
-def _frames(x, what):
-    """A [N, H, W] stack as ``_stack`` returns it, with H and W."""
+_REG_AXES = {2: ("[N, H, W]", "frame", "(my, mx)"), 3: ("[N, D, H, W]", "volume", "(mz, my, mx)")}
+
+
+def _by(sides):
+    return " x ".join(str(s) for s in sides)
+
+
+def _reg_stack(x, rank, what):
+    """A stack of frames [N, H, W] (``rank`` 2, fp32 / fp16) or of volumes [N, D, H, W] (``rank`` 3, fp32) as ``_stack`` returns it:
+    (tensor, dtype code, N, (H, W) or (D, H, W), item stride)."""
     x, dt, N, P, fs = _stack(x, what)
-    if x.dim() != 3:
-        raise ValueError(f"{what}: a stack [N, H, W] is expected, got {tuple(x.shape)}")
-    H, W = int(x.shape[1]), int(x.shape[2])
-    if H * W >= 1 << 31:
-        raise ValueError(f"{what}: a frame of {H} x {W} is too large")
-    return x, dt, N, H, W, fs
+    if rank == 3 and dt != 0:
+        raise TypeError(f"{what}: float32 volumes are expected, got {x.dtype}")
+    if x.dim() != rank + 1:
+        raise ValueError(f"{what}: a stack {_REG_AXES[rank][0]} is expected, got {tuple(x.shape)}")
+    shape = tuple(x.shape[1:])
+    if P >= 1 << 31:
+        raise ValueError(f"{what}: a {_REG_AXES[rank][1]} of {_by(shape)} is too large")
+    return x, dt, N, shape, fs
 
 
 def _overlap(a, b):
@@ -2679,21 +2689,36 @@ def _overlap(a, b):
     return a0 < b1 and b0 < a1
 
 
+def _reg_out(out, shape, dtype, word, what, like, alias=True):
+    """``out`` of a registration pass: a new tensor of ``shape`` and ``dtype`` on the device of ``like``, or the given one, which
+    must be that, contiguous, and (``alias``) share no memory with ``like``, the stack.  ``word``: the dtype as the message names it."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    if not torch.is_tensor(out) or not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be a contiguous {word} {shape} device tensor")
+    if alias and _overlap(out, like):
+        raise ValueError(f"{what}: out must not alias the stack")
+    return out
+
+
+def _reg_window(stack, w, out, what):
+    """``reg_window`` (two vectors) and ``reg_window3d`` (three): one kernel, a frame being a volume of one plane."""
+    L = _lib.lib()
+    stack, dt, N, shape, fs = _reg_stack(stack, len(w), what)
+    w = [_vec(v, n, name, what) for v, n, name in zip(w, shape, ("wz", "wy", "wx")[3 - len(w):])]
+    out = _reg_out(out, (N, *shape), torch.float32, "float32", what, stack)
+    if len(w) == 2:
+        check(L.cwfa_reg_window(_p(stack), dt, N, *shape, fs, _p(w[0]), _p(w[1]), _p(out), _stream()), what)
+    else:
+        check(L.cwfa_reg_window3d_f32(_p(stack), N, *shape, fs, _p(w[0]), _p(w[1]), _p(w[2]), _p(out), _stream()), what)
+    return out
+
+
 def reg_window(stack, wy, wx, out=None):
     """float32 [N,H,W]: fl(float(stack) * fl(wy[y] * wx[x])) for a [N,H,W] fp32 / fp16 device stack and fp32 device vectors ``wy``
     [H], ``wx`` [W] -- the edge taper in front of the forward transform, with the widening of an fp16 stack, in one read and one
     write.  ``out``: a contiguous float32 tensor of the stack's shape that shares no memory with it."""
-    L = _lib.lib()
-    stack, dt, N, H, W, fs = _frames(stack, "reg_window")
-    wy, wx = _vec(wy, H, "wy", "reg_window"), _vec(wx, W, "wx", "reg_window")
-    if out is None:
-        out = torch.empty((N, H, W), dtype=torch.float32, device=stack.device)
-    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (N, H, W) or not out.is_contiguous():
-        raise ValueError(f"reg_window: out must be a contiguous float32 {(N, H, W)} device tensor")
-    elif _overlap(out, stack):
-        raise ValueError("reg_window: out must not alias the stack")
-    check(L.cwfa_reg_window(_p(stack), dt, N, H, W, fs, _p(wy), _p(wx), _p(out), _stream()), "reg_window")
-    return out
+    return _reg_window(stack, (wy, wx), out, "reg_window")
 
 
 def reg_whiten(F, W=None, eps=1e-5, out=None):
@@ -2728,12 +2753,43 @@ def reg_whiten(F, W=None, eps=1e-5, out=None):
     return out
 
 
-def _max_shift(max_shift, H, W, what):
-    my, mx = (max_shift, max_shift) if isinstance(max_shift, int) else tuple(max_shift)
-    my, mx = int(my), int(mx)
-    if my < 0 or mx < 0 or (H and W and (2 * my + 1 > H or 2 * mx + 1 > W)):
-        raise ValueError(f"{what}: max_shift ({my}, {mx}) needs 0 <= 2 m + 1 <= the frame's {H} x {W}")
-    return my, mx
+def _max_shift(max_shift, *sides_and_what):
+    """``_max_shift(max_shift, H, W, what)`` or ``(max_shift, D, H, W, what)``: an int or one bound per axis, as a tuple."""
+    shape, what = sides_and_what[:-1], sides_and_what[-1]
+    try:
+        m = (max_shift,) * len(shape) if isinstance(max_shift, int) else tuple(max_shift)
+        if len(m) != len(shape):
+            raise TypeError
+        m = tuple(map(int, m))
+    except TypeError:
+        raise ValueError(f"{what}: max_shift is an int or {_REG_AXES[len(shape)][2]}, got {max_shift!r}") from None
+    fits = 0 not in shape
+    for v, n in zip(m, shape):
+        if v < 0 or (fits and 2 * v + 1 > n):
+            raise ValueError(f"{what}: max_shift ({', '.join(map(str, m))}) needs 0 <= 2 m + 1 <= the {_REG_AXES[len(shape)][1]}'s {_by(shape)}")
+    return m
+
+
+_max_shift3 = _max_shift          # the name the volume side grew up with
+
+
+def _reg_peak(corr, max_shift, subpixel, out, rank, what):
+    """``reg_peak`` (``rank`` 2) and ``reg_peak3d`` (3): the checks and the call; the kernels are two over one key order."""
+    L = _lib.lib()
+    corr, dt, N, shape, fs = _reg_stack(corr, rank, what)
+    if dt != 0:
+        raise TypeError(f"{what}: float32 correlation maps are expected")
+    m = _max_shift(max_shift, *shape, what)
+    if out is None:
+        out = (torch.empty((N, rank), dtype=torch.float32, device=corr.device), torch.empty((N, rank), dtype=torch.int32, device=corr.device),
+               torch.empty((N,), dtype=torch.float32, device=corr.device))
+    shifts, ipeak, peak = out
+    for t, dtype, tshape, name in ((shifts, torch.float32, (N, rank), "shifts"), (ipeak, torch.int32, (N, rank), "ipeak"), (peak, torch.float32, (N,), "peak")):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != tshape or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous {dtype} {tshape} device tensor")
+    fn = L.cwfa_reg_peak_f32 if rank == 2 else L.cwfa_reg_peak3d_f32
+    check(fn(_p(corr), N, *shape, fs, *m, int(bool(subpixel)), _p(shifts), _p(ipeak), _p(peak), _stream()), what)
+    return shifts, ipeak, peak
 
 
 def reg_peak(corr, max_shift, subpixel=True, out=None):
@@ -2741,20 +2797,7 @@ def reg_peak(corr, max_shift, subpixel=True, out=None):
     over the signed window |sy| <= my, |sx| <= mx (read modulo the frame) under the total order of ``local_maxima`` -- ties to the
     lowest window index, NaN below everything -- and, with ``subpixel``, a parabola per axis through the peak and its two
     neighbours in float64.  A window without a finite value gives shift (0, 0) and peak NaN.  ``out``: the three tensors."""
-    L = _lib.lib()
-    corr, dt, N, H, W, fs = _frames(corr, "reg_peak")
-    if dt != 0:
-        raise TypeError("reg_peak: float32 correlation maps are expected")
-    my, mx = _max_shift(max_shift, H, W, "reg_peak")
-    if out is None:
-        out = (torch.empty((N, 2), dtype=torch.float32, device=corr.device), torch.empty((N, 2), dtype=torch.int32, device=corr.device),
-               torch.empty((N,), dtype=torch.float32, device=corr.device))
-    shifts, ipeak, peak = out
-    for t, dtype, shape, name in ((shifts, torch.float32, (N, 2), "shifts"), (ipeak, torch.int32, (N, 2), "ipeak"), (peak, torch.float32, (N,), "peak")):
-        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f"reg_peak: {name} must be a contiguous {dtype} {shape} device tensor")
-    check(L.cwfa_reg_peak_f32(_p(corr), N, H, W, fs, my, mx, int(bool(subpixel)), _p(shifts), _p(ipeak), _p(peak), _stream()), "reg_peak")
-    return shifts, ipeak, peak
+    return _reg_peak(corr, max_shift, subpixel, out, 2, "reg_peak")
 
 
 def reg_roots(M):
@@ -2848,10 +2891,7 @@ def reg_upsample(R, ipeak, shape, upsample, radius=None, out=None, workspace=Non
     if N and (not R[0].is_contiguous() or (N > 1 and R.stride(0) < H * K)):
         R = R.contiguous()
     fs = R.stride(0) if N > 1 else H * K
-    if out is None:
-        out = torch.empty((N, U, U), dtype=torch.float64, device=R.device)
-    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float64 or tuple(out.shape) != (N, U, U) or not out.is_contiguous():
-        raise ValueError(f"{what}: out must be a contiguous float64 {(N, U, U)} device tensor")
+    out = _reg_out(out, (N, U, U), torch.float64, "float64", what, R, alias=False)
     if N == 0:
         return out
     L = _lib.lib()
@@ -2898,24 +2938,25 @@ def reg_fine_peak(C, ipeak, upsample, out=None):
     return shifts, peak
 
 
+def _reg_shift(stack, shifts, mode, fill, out, rank, what):
+    """``reg_shift`` (``rank`` 2) and ``reg_shift3d`` (3): the checks and the call; the kernels are two (the z walk is the volumes')."""
+    L = _lib.lib()
+    stack, dt, N, shape, fs = _reg_stack(stack, rank, what)
+    if mode not in _lib.SHIFT_MODE:
+        raise ValueError(f"{what}: mode is one of {sorted(_lib.SHIFT_MODE)}, got {mode!r}")
+    shifts = _vec(shifts, rank * N, "shifts", what)
+    out = _reg_out(out, (N, *shape), stack.dtype, stack.dtype if rank == 2 else "float32", what, stack)
+    args = (fs, _p(shifts), _lib.SHIFT_MODE[mode], float(fill), _p(out), _stream())
+    check(L.cwfa_reg_shift(_p(stack), dt, N, *shape, *args) if rank == 2 else L.cwfa_reg_shift3d_f32(_p(stack), N, *shape, *args), what)
+    return out
+
+
 def reg_shift(stack, shifts, mode="bilinear", fill=0.0, out=None):
     """out[n,y,x] = stack[n, y + dy, x + dx] with (dy, dx) = shifts[n] read on the device (float32 [N,2]): bilinear with separately
     rounded fp32 weights and products, or ``mode="nearest"`` (rintf of the shift).  A tap of weight exactly 0 is neither read nor
     added, so an integer shift copies bits; a tap outside the frame reads ``fill``; a non-finite shift fills the frame.  The result
     has the stack's dtype.  ``out``: a contiguous tensor of the stack's shape and dtype that shares no memory with it."""
-    L = _lib.lib()
-    stack, dt, N, H, W, fs = _frames(stack, "reg_shift")
-    if mode not in _lib.SHIFT_MODE:
-        raise ValueError(f"reg_shift: mode is one of {sorted(_lib.SHIFT_MODE)}, got {mode!r}")
-    shifts = _vec(shifts, 2 * N, "shifts", "reg_shift")
-    if out is None:
-        out = torch.empty((N, H, W), dtype=stack.dtype, device=stack.device)
-    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != stack.dtype or tuple(out.shape) != (N, H, W) or not out.is_contiguous():
-        raise ValueError(f"reg_shift: out must be a contiguous {stack.dtype} {(N, H, W)} device tensor")
-    elif _overlap(out, stack):
-        raise ValueError("reg_shift: out must not alias the stack")
-    check(L.cwfa_reg_shift(_p(stack), dt, N, H, W, fs, _p(shifts), _lib.SHIFT_MODE[mode], float(fill), _p(out), _stream()), "reg_shift")
-    return out
+    return _reg_shift(stack, shifts, mode, fill, out, 2, "reg_shift")
 
 
 # ------------------------------------------------------------------------------------------------ per-lenslet registration
@@ -2951,17 +2992,11 @@ def reg_window_views(stack, centers, view_shape, wy, wx, out=None):
     shape that shares no memory with the stack."""
     what = "reg_window_views"
     c, ph, pw = _view_centers(centers, view_shape, what)
-    stack, dt, N, H, W, fs = _frames(stack, what)
+    stack, dt, N, (H, W), fs = _reg_stack(stack, 2, what)
     if H < 1 or W < 1:
         raise ValueError(f"{what}: a frame of {H} x {W}")
     wy, wx = _vec(wy, ph, "wy", what), _vec(wx, pw, "wx", what)
-    shape = (N, len(c), ph, pw)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=stack.device)
-    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError(f"{what}: out must be a contiguous float32 {shape} device tensor")
-    elif _overlap(out, stack):
-        raise ValueError(f"{what}: out must not alias the stack")
+    out = _reg_out(out, (N, len(c), ph, pw), torch.float32, "float32", what, stack)
     if N == 0:
         return out
     check(_lib.lib().cwfa_reg_window_views(_p(stack), dt, N, H, W, fs, _host(c), len(c), ph, pw, _p(wy), _p(wx), _p(out), _stream()), what)
@@ -3022,7 +3057,7 @@ def reg_shift_labeled(stack, table, labels, mode="bilinear", fill=0.0, out=None)
     ``reg_shift``, bit for bit; the source is the whole frame, so a tap that leaves its view's box reads what lies there.  ``out``: a
     contiguous tensor of the stack's shape and dtype that shares no memory with it."""
     what = "reg_shift_labeled"
-    stack, dt, N, H, W, fs = _frames(stack, what)
+    stack, dt, N, (H, W), fs = _reg_stack(stack, 2, what)
     if mode not in _lib.SHIFT_MODE:
         raise ValueError(f"{what}: mode is one of {sorted(_lib.SHIFT_MODE)}, got {mode!r}")
     if not torch.is_tensor(table) or table.dim() != 3 or int(table.shape[0]) != N or table.shape[2] != 2 or not 2 <= table.shape[1] <= _lib.REG_MAX_VIEWS + 1:
@@ -3032,12 +3067,7 @@ def reg_shift_labeled(stack, table, labels, mode="bilinear", fill=0.0, out=None)
     labels = _vec(labels, H * W, "labels", what, torch.uint8)
     if H < 1 or W < 1:
         raise ValueError(f"{what}: a frame of {H} x {W}")
-    if out is None:
-        out = torch.empty((N, H, W), dtype=stack.dtype, device=stack.device)
-    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != stack.dtype or tuple(out.shape) != (N, H, W) or not out.is_contiguous():
-        raise ValueError(f"{what}: out must be a contiguous {stack.dtype} {(N, H, W)} device tensor")
-    elif _overlap(out, stack):
-        raise ValueError(f"{what}: out must not alias the stack")
+    out = _reg_out(out, (N, H, W), stack.dtype, stack.dtype, what, stack)
     if N == 0:
         return out
     check(_lib.lib().cwfa_reg_shift_labeled(_p(stack), dt, N, H, W, fs, _p(table), _p(labels), Lv, _lib.SHIFT_MODE[mode], float(fill), _p(out),
@@ -3046,48 +3076,11 @@ def reg_shift_labeled(stack, table, labels, mode="bilinear", fill=0.0, out=None)
 
 
 # ------------------------------------------------------------------------------------------------ registration of volumes
-def _volume_stack(x, what):
-    """A [N, D, H, W] float32 stack as ``_stack`` returns it, with D, H and W."""
-    x, dt, N, P, vs = _stack(x, what)
-    if dt != 0:
-        raise TypeError(f"{what}: float32 volumes are expected, got {x.dtype}")
-    if x.dim() != 4:
-        raise ValueError(f"{what}: a stack [N, D, H, W] is expected, got {tuple(x.shape)}")
-    D, H, W = (int(s) for s in x.shape[1:])
-    if D * H * W >= 1 << 31:
-        raise ValueError(f"{what}: a volume of {D} x {H} x {W} is too large")
-    return x, N, D, H, W, vs
-
-
-def _max_shift3(max_shift, D, H, W, what):
-    """``_max_shift`` for volumes: an int or a (mz, my, mx) triple."""
-    try:
-        m = (max_shift,) * 3 if isinstance(max_shift, int) else tuple(max_shift)
-        if len(m) != 3:
-            raise TypeError
-        mz, my, mx = (int(v) for v in m)
-    except TypeError:
-        raise ValueError(f"{what}: max_shift is an int or (mz, my, mx), got {max_shift!r}") from None
-    if min(mz, my, mx) < 0 or (D and H and W and (2 * mz + 1 > D or 2 * my + 1 > H or 2 * mx + 1 > W)):
-        raise ValueError(f"{what}: max_shift ({mz}, {my}, {mx}) needs 0 <= 2 m + 1 <= the volume's {D} x {H} x {W}")
-    return mz, my, mx
-
-
 def reg_window3d(stack, wz, wy, wx, out=None):
     """float32 [N,D,H,W]: fl(stack * fl(fl(wz[z] * wy[y]) * wx[x])) for a [N,D,H,W] float32 device stack and float32 device vectors
     ``wz`` [D], ``wy`` [H], ``wx`` [W] -- the edge taper in front of the forward transform, in one read and one write.  ``out``: a
     contiguous float32 tensor of the stack's shape that shares no memory with it."""
-    L = _lib.lib()
-    stack, N, D, H, W, vs = _volume_stack(stack, "reg_window3d")
-    wz, wy, wx = _vec(wz, D, "wz", "reg_window3d"), _vec(wy, H, "wy", "reg_window3d"), _vec(wx, W, "wx", "reg_window3d")
-    if out is None:
-        out = torch.empty((N, D, H, W), dtype=torch.float32, device=stack.device)
-    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (N, D, H, W) or not out.is_contiguous():
-        raise ValueError(f"reg_window3d: out must be a contiguous float32 {(N, D, H, W)} device tensor")
-    elif _overlap(out, stack):
-        raise ValueError("reg_window3d: out must not alias the stack")
-    check(L.cwfa_reg_window3d_f32(_p(stack), N, D, H, W, vs, _p(wz), _p(wy), _p(wx), _p(out), _stream()), "reg_window3d")
-    return out
+    return _reg_window(stack, (wz, wy, wx), out, "reg_window3d")
 
 
 def reg_peak3d(corr, max_shift, subpixel=True, out=None):
@@ -3095,18 +3088,7 @@ def reg_peak3d(corr, max_shift, subpixel=True, out=None):
     [N,D,H,W]: ``reg_peak`` with one more axis -- the maximum over the signed window |sz| <= mz, |sy| <= my, |sx| <= mx (read modulo
     the volume; ``max_shift``: an int or (mz, my, mx)), ties to the lowest window index, NaN below everything, and with ``subpixel``
     a float64 parabola per axis.  A window without a finite value gives shift 0 and peak NaN.  ``out``: the three tensors."""
-    L = _lib.lib()
-    corr, N, D, H, W, vs = _volume_stack(corr, "reg_peak3d")
-    mz, my, mx = _max_shift3(max_shift, D, H, W, "reg_peak3d")
-    if out is None:
-        out = (torch.empty((N, 3), dtype=torch.float32, device=corr.device), torch.empty((N, 3), dtype=torch.int32, device=corr.device),
-               torch.empty((N,), dtype=torch.float32, device=corr.device))
-    shifts, ipeak, peak = out
-    for t, dtype, shape, name in ((shifts, torch.float32, (N, 3), "shifts"), (ipeak, torch.int32, (N, 3), "ipeak"), (peak, torch.float32, (N,), "peak")):
-        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f"reg_peak3d: {name} must be a contiguous {dtype} {shape} device tensor")
-    check(L.cwfa_reg_peak3d_f32(_p(corr), N, D, H, W, vs, mz, my, mx, int(bool(subpixel)), _p(shifts), _p(ipeak), _p(peak), _stream()), "reg_peak3d")
-    return shifts, ipeak, peak
+    return _reg_peak(corr, max_shift, subpixel, out, 3, "reg_peak3d")
 
 
 def reg_shift3d(stack, shifts, mode="bilinear", fill=0.0, out=None):
@@ -3115,19 +3097,7 @@ def reg_shift3d(stack, shifts, mode="bilinear", fill=0.0, out=None):
     ``mode="nearest"``: rintf of the shift.  A plane or tap of weight exactly 0 is neither read nor added, so an integer shift
     copies bits; whatever lies outside the volume reads ``fill``; a non-finite shift fills the volume.  ``out``: a contiguous
     float32 tensor of the stack's shape that shares no memory with it."""
-    L = _lib.lib()
-    stack, N, D, H, W, vs = _volume_stack(stack, "reg_shift3d")
-    if mode not in _lib.SHIFT_MODE:
-        raise ValueError(f"reg_shift3d: mode is one of {sorted(_lib.SHIFT_MODE)}, got {mode!r}")
-    shifts = _vec(shifts, 3 * N, "shifts", "reg_shift3d")
-    if out is None:
-        out = torch.empty((N, D, H, W), dtype=torch.float32, device=stack.device)
-    elif not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (N, D, H, W) or not out.is_contiguous():
-        raise ValueError(f"reg_shift3d: out must be a contiguous float32 {(N, D, H, W)} device tensor")
-    elif _overlap(out, stack):
-        raise ValueError("reg_shift3d: out must not alias the stack")
-    check(L.cwfa_reg_shift3d_f32(_p(stack), N, D, H, W, vs, _p(shifts), _lib.SHIFT_MODE[mode], float(fill), _p(out), _stream()), "reg_shift3d")
-    return out
+    return _reg_shift(stack, shifts, mode, fill, out, 3, "reg_shift3d")
 
 
 # ------------------------------------------------------------------------------------------------ neuron footprints

@@ -201,6 +201,22 @@ def test_peak_accepts_an_int_and_writes_into_out():
     assert all(same_bits(a, b) for a, b in zip(got, R.peak(c, 3)))
 
 
+def test_more_frames_than_a_grid_axis_holds():
+    """N = 70 000 maps of 1 x 4, more than a grid's y or z axis holds and more than the 65 536 workgroups the volumes' peak kernel
+    launches: every frame gets its peak, the last one included.  Dense, and with a frame stride larger than the frame: the frame
+    index, the item stride and the stride of the two-component outputs together."""
+    from cwfa_amd import ops
+    N = 70000
+    c = np.random.default_rng(5).standard_normal((N, 1, 4)).astype(np.float32)
+    win = c[:, 0, [3, 0, 1]]                                                # the window reads x = 3, 0, 1: shifts -1, 0, 1
+    wi = np.argmax(win, axis=1)                                             # the first maximum: the lowest index
+    want_i = np.stack([np.zeros(N), wi - 1], axis=1).astype(np.int32)
+    for cd in (device_stack(c), device_stack(c, pad=3, offset=1, gap=9.0)):
+        s, i, p = ops.reg_peak(cd, (0, 1), subpixel=False)
+        assert np.array_equal(i.cpu().numpy(), want_i) and np.array_equal(s.cpu().numpy(), want_i.astype(np.float32))
+        assert same_bits(p, win[np.arange(N), wi]), "every frame, the last one included"
+
+
 # ------------------------------------------------------------------------------------------------ the resampling
 def integer_shift_reference(x, d, fill):
     out = np.full(x.shape, fill, dtype=x.dtype)

@@ -165,6 +165,9 @@ def test_peak_accepts_an_int_and_writes_into_out():
 # ------------------------------------------------------------------------------------------------ D = 1: the 2-D kernels
 @pytest.mark.parametrize("N,H,W,pad,offset", [(1, 1, 1, 0, 0), (3, 5, 7, 0, 0), (2, 12, 16, 0, 0), (2, 12, 16, 4, 0), (3, 10, 13, 2, 1)])
 def test_depth_one_is_the_two_dimensional_kernel_bit_for_bit(N, H, W, pad, offset):
+    """The window is one kernel for frames and volumes, so the window part here compares that kernel with itself through its two
+    entry points (each entry point is held against its own restatement in ``test_window_bit_for_bit`` of this file and of
+    test_gpu_register.py).  The peak and the resampling parts still compare two kernels."""
     from cwfa_amd import ops
     x = volume_data(N, 1, H, W)
     xd = device_stack(x, pad, offset)
