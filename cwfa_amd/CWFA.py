@@ -24,7 +24,9 @@ __all__ = ["sample_z_truncated", "check_empty_depths", "evaluate_INN_forward", "
            "corr_coeff_3D", "truncated_normal_variance", "posterior_moments", "posterior_samples", "posterior_roi_means",
            "ActivityMap", "find_neurons", "read_neural_coordinates_from_file", "write_neural_coordinates_to_file",
            "NeuronFootprints", "Footprints", "extract_traces", "demix_plan", "demix_traces", "trace_baseline", "delta_f_over_f", "trace_noise", "infer_spikes",
-           "estimate_volume_shifts", "shift_volumes", "register_volumes", "VolumeRegistration", "VolumeRegistrar", "valid_box"]
+           "estimate_volume_shifts", "shift_volumes", "register_volumes", "VolumeRegistration", "VolumeRegistrar", "valid_box",
+           "block_grid", "BlockGrid", "estimate_block_shifts", "warp_volumes", "register_volumes_piecewise", "PiecewiseRegistration",
+           "PiecewiseVolumeRegistrar"]
 
 
 def _no_grad_trunc_normal_(tensor, mean=0., std=1., a=-1., b=1.):
@@ -1067,6 +1069,240 @@ def valid_box(shifts, shape):
             return (0,) * 6
         box += [b0, b1]
     return tuple(box)
+
+
+# ---------------------------------------------------------------------------------------------------- piecewise-rigid registration
+# For a sample whose parts move differently: the volume is cut into a grid of blocks, every block is registered
+# like a volume of section 30, the table of block shifts is cleaned once and interpolated between the block centres, and the volume
+# is resampled once under a displacement per voxel.
+PiecewiseRegistration = namedtuple("PiecewiseRegistration", ["volumes", "field", "peak", "inlier", "shifts", "template"])
+
+
+class BlockGrid:
+    """The geometry ``block_grid`` makes, on the host: ``shape`` (D, H, W), ``block`` (bz, by, bx), ``grid`` (gz, gy, gx), ``B`` their
+    product, and per axis ``origins`` (int32 [g]), ``centers`` (float64 [g]) and the interpolation tables ``idx`` (int32 [S]) and
+    ``t`` (float32 [S]).  ``tables(device)``: (idxz, tz, idxy, ty, idxx, tx) on the device, copied once per device."""
+
+    def __init__(self, shape, block, grid, origins, centers, idx, t):
+        self.shape, self.block, self.grid, self.origins, self.centers, self.idx, self.t = shape, block, grid, origins, centers, idx, t
+        self.B = grid[0] * grid[1] * grid[2]
+        self._dev = {}
+
+    def tables(self, device):
+        key = str(torch.device(device))
+        if key not in self._dev:
+            self._dev[key] = tuple(torch.from_numpy(a).to(device) for pair in zip(self.idx, self.t) for a in pair)
+        return self._dev[key]
+
+    def windows(self, taper, device):
+        """The three raised-cosine tapers of a block on the device, copied once per (taper, device)."""
+        key = (tuple(taper), str(torch.device(device)))
+        if key not in self._dev:
+            self._dev[key] = tuple(taper_window(n, t).to(device) for n, t in zip(self.block, taper))
+        return self._dev[key]
+
+
+def block_grid(shape, block=(32, 128, 128), grid=None, device=None):
+    """The ``BlockGrid`` of a volume of ``shape`` (D, H, W) cut into ``grid`` = (gz, gy, gx) blocks of ``block`` = (bz, by, bx) voxels
+    (clipped to the volume; ``grid`` None: ceil(S / b) per axis; at most 4096 blocks) -- DESIGN.md section 32, all on the host in
+    integers and float64.  Along an axis of S voxels the origins are (i (S - b)) // (g - 1), i = 0 .. g - 1 (one block: (S - b) // 2),
+    so the first and last block touch the faces and blocks overlap or leave gaps as the sizes ask; a centre is origin + (b - 1) / 2;
+    coordinate p interpolates between the centres around it -- node idx[p], the last centre at or below p, and the fraction
+    t[p] = float32((p - c[idx]) / (c[idx + 1] - c[idx])) -- and takes the end centre's vector beyond it (t = 0).  ``device``: copy the
+    tables there now; otherwise they are copied at their first use."""
+    import numpy as np
+    what = "block_grid"
+    if not isinstance(shape, (tuple, list, torch.Size)) or len(shape) != 3:
+        raise ValueError(f"{what}: shape is (D, H, W), got {shape!r}")
+    shape = tuple(ops._count(s, "shape", what) for s in shape)
+    if not isinstance(block, (tuple, list, torch.Size)) or len(block) != 3:
+        raise ValueError(f"{what}: block is (bz, by, bx), got {block!r}")
+    block = tuple(min(ops._count(b, "block", what), s) for b, s in zip(block, shape))
+    grid = ops._block_grid3(tuple(-(-s // b) for s, b in zip(shape, block)) if grid is None else grid, what)
+    origins, centers, idx, t = [], [], [], []
+    for S, b, g in zip(shape, block, grid):
+        o = np.array([(i * (S - b)) // (g - 1) for i in range(g)] if g > 1 else [(S - b) // 2], dtype=np.int64)
+        c = o.astype(np.float64) + (b - 1) / 2.0
+        p = np.arange(S, dtype=np.float64)
+        i = np.clip(np.searchsorted(c, p, side="right") - 1, 0, g - 1)
+        inner = (p > c[0]) & (p < c[g - 1])
+        nxt = np.minimum(i + 1, g - 1)
+        with np.errstate(all="ignore"):
+            frac = ((p - c[i]) / (c[nxt] - c[i])).astype(np.float32)
+        origins.append(o.astype(np.int32))
+        centers.append(c)
+        idx.append(np.where(p <= c[0], 0, np.where(p >= c[g - 1], g - 1, i)).astype(np.int32))
+        t.append(np.where(inner, frac, np.float32(0)).astype(np.float32))
+    bg = BlockGrid(shape, block, grid, tuple(origins), tuple(centers), tuple(idx), tuple(t))
+    if device is not None:
+        bg.tables(device)
+    return bg
+
+
+def _block_reg_args(volumes, template, grid, max_shift, taper, smooth, eps, chunk, subpixel, what):
+    """The checks of ``estimate_block_shifts`` that need no device: those of ``estimate_volume_shifts`` for the stack and the template,
+    and max_shift and taper against the BLOCK's sides: ((mz, my, mx), (tz, ty, tx), chunk)."""
+    _vol_reg_args(volumes, template, 0, 0, smooth, eps, chunk, subpixel, what)
+    if not isinstance(grid, BlockGrid):
+        raise ValueError(f"{what}: grid is the BlockGrid of block_grid")
+    if tuple(int(n) for n in volumes.shape[1:]) != grid.shape:
+        raise ValueError(f"{what}: the grid was made for volumes of {grid.shape}, got {tuple(volumes.shape[1:])}")
+    probe = torch.empty((0, *grid.block), dtype=torch.float32)
+    try:
+        return _reg_args(probe, None, max_shift, taper, smooth, eps, chunk, what, "volume")[:3]
+    except ValueError as e:
+        raise ValueError(f"{e} (the volume here is a block of the grid)") from None
+
+
+def _min_peak_args(min_peak, max_dev, what):
+    min_peak = float(min_peak)
+    if min_peak != min_peak:
+        raise ValueError(f"{what}: min_peak is NaN")
+    if max_dev is not None:
+        try:
+            max_dev = tuple(float(v) for v in ((max_dev,) * 3 if isinstance(max_dev, (int, float)) else max_dev))
+        except (TypeError, ValueError):
+            max_dev = ()
+        if len(max_dev) != 3 or not all(v >= 0.0 for v in max_dev):
+            raise ValueError(f"{what}: max_dev is None, a number or (dz, dy, dx), not negative and not NaN")
+    return min_peak, max_dev
+
+
+def _block_estimate(volumes, template, grid, max_shift, taper, smooth, eps, subpixel, min_peak, max_dev, base, chunk, what):
+    """(field, peak, inlier, raw shifts), [N,gz,gy,gx,..]: ``estimate_block_shifts`` and the table before its clean-up."""
+    m, taper, chunk = _block_reg_args(volumes, template, grid, max_shift, taper, smooth, eps, chunk, subpixel, what)
+    min_peak, max_dev = _min_peak_args(min_peak, max_dev, what)
+    if template is None:
+        raise ValueError(f"{what}: a template is needed")
+    N = int(volumes.shape[0])
+    if base is not None and (not torch.is_tensor(base) or tuple(base.shape) != (N, 3) or base.dtype != torch.float32):
+        raise ValueError(f"{what}: base is a float32 [{N}, 3] tensor")
+    ops._dev(volumes, "volumes")
+    w = grid.windows(taper, volumes.device)
+    shifts, peak = _estimate(lambda s, e, out: ops.reg_window_blocks3d(volumes[s:e], grid.origins, grid.block, *w, out=out),
+                             ops.reg_window_blocks3d(template.contiguous()[None], grid.origins, grid.block, *w)[0], N, grid.block, m, smooth, eps,
+                             bool(subpixel), False, None, chunk)
+    if base is None:
+        base = estimate_volume_shifts(volumes, template, max_shift=m, taper=taper, smooth=smooth, eps=eps, subpixel=subpixel, chunk=chunk)[0]
+    field, inlier = ops.reg_field_fill(shifts.view(N, grid.B, 3), peak.view(N, grid.B), base, grid.grid, min_peak, max_dev)
+    g = grid.grid
+    return field.view(N, *g, 3), peak.view(N, *g), inlier.view(N, *g), shifts.view(N, *g, 3)
+
+
+@amp_region
+def estimate_block_shifts(volumes, template, grid, max_shift=(2, 8, 8), taper=None, smooth=0.0, eps=1e-5, subpixel=True, min_peak=0.0, max_dev=None,
+                          base=None, chunk=1):
+    """(field float32 [N,gz,gy,gx,3], peak float32 [N,gz,gy,gx], inlier uint8 [N,gz,gy,gx]) on the device: the displacement (dz, dy,
+    dx) of every block of ``grid`` (a ``BlockGrid``) of every volume of a contiguous [N,D,H,W] float32 device stack against the same
+    block of the float32 ``template`` [D,H,W].  The blocks are cut and tapered in one read (``taper``: that of
+    ``estimate_volume_shifts`` at the BLOCK's size) and go through the transforms, the whitening, the peak search over |d| <=
+    ``max_shift`` and the parabola of ``estimate_volume_shifts`` as a batch, ``chunk`` volumes (chunk x B blocks) at a time;
+    ``subpixel="dft"`` is refused as there.  The shifts are TOTAL displacements of the original volume, not residuals after a rigid
+    pass, so ``warp_volumes`` interpolates a volume once.
+
+    The table is then cleaned once: a block is an inlier when its peak is finite and >= ``min_peak``, its shift is finite and, with
+    ``max_dev`` (a number or (dz, dy, dx)), within that of ``base`` per component; an outlier takes the mean of the inliers among
+    its 26 grid neighbours, or ``base`` where it has none.  ``base`` float32 [N,3]: None is the whole-volume rigid estimate of
+    ``estimate_volume_shifts`` under the same arguments.  Nothing is read back."""
+    return _block_estimate(volumes, template, grid, max_shift, taper, smooth, eps, subpixel, min_peak, max_dev, base, chunk, "estimate_block_shifts")[:3]
+
+
+def _field_arg(volumes, field, grid, what):
+    if not isinstance(grid, BlockGrid):
+        raise ValueError(f"{what}: grid is the BlockGrid of block_grid")
+    N = int(volumes.shape[0])
+    if tuple(int(n) for n in volumes.shape[1:]) != grid.shape:
+        raise ValueError(f"{what}: the grid was made for volumes of {grid.shape}, got {tuple(volumes.shape[1:])}")
+    if not torch.is_tensor(field) or field.dtype != torch.float32 or tuple(field.shape) not in ((N, *grid.grid, 3), (N, grid.B, 3)):
+        raise ValueError(f"{what}: field is a float32 {[N, *grid.grid, 3]} tensor")
+    return field.reshape(N, grid.B, 3)
+
+
+@amp_region
+def warp_volumes(volumes, field, grid, mode="bilinear", fill=0.0, out=None):
+    """out[n,z,y,x] = volumes[n, z + dz, y + dy, x + dx] with (dz, dy, dx) the trilinear interpolation of ``field`` (float32
+    [N,gz,gy,gx,3] on the device, as ``estimate_block_shifts`` returns it) between the block centres of ``grid`` at that voxel, the
+    end centre's vector beyond it; the resampling of a voxel is ``shift_volumes``' under its vector ("bilinear" or "nearest", ``fill``
+    outside the volume, a non-finite vector fills the voxel), so a field of equal nodes gives ``shift_volumes`` bit for bit and a
+    region of constant integer field copies bits.  ``out`` must not share memory with ``volumes``.
+
+    The interpolated vector is a convex combination of node vectors (up to rounding), so ``valid_box(field.reshape(-1, 3), shape)``
+    bounds the box that holds data in every volume."""
+    _shift_volume_args(volumes, None, mode, out, "warp_volumes")
+    return ops.reg_warp3d(volumes, _field_arg(volumes, field, grid, "warp_volumes"), grid.grid, grid.tables(volumes.device), mode=mode, fill=fill, out=out)
+
+
+@amp_region
+def register_volumes_piecewise(volumes, template=None, grid=None, block=(32, 128, 128), n_iter=1, max_shift=(2, 8, 8), subpixel=True, mode="bilinear",
+                               taper=None, smooth=0.0, eps=1e-5, min_peak=0.0, max_dev=None, chunk=1, fill=0.0, out=None):
+    """Piecewise-rigid registration of a contiguous [N,D,H,W] float32 device stack:
+    ``PiecewiseRegistration(volumes, field, peak, inlier, shifts, template)`` with volumes[n] = the input's volume n moved back under
+    the interpolated ``field`` [N,gz,gy,gx,3]; ``shifts`` is the table as measured, before the clean-up.  ``grid``: a ``BlockGrid``, or
+    (gz, gy, gx) / None for ``block_grid(shape, block, grid)``.  ``template`` None: the per-voxel lower temporal median; ``n_iter`` > 1:
+    the template becomes the median of the registered stack and the field is estimated again FROM THE ORIGINAL VOLUMES.  The other
+    arguments are those of ``estimate_block_shifts`` and ``warp_volumes``; ``valid_box(field.reshape(-1, 3), shape)`` is the box that
+    holds data in every volume.  Nothing is read back."""
+    what = "register_volumes_piecewise"
+    _vol_reg_args(volumes, template, 0, 0, smooth, eps, chunk, subpixel, what)
+    if not isinstance(grid, BlockGrid):
+        grid = block_grid(tuple(int(n) for n in volumes.shape[1:]), block, grid)
+    _block_reg_args(volumes, template, grid, max_shift, taper, smooth, eps, chunk, subpixel, what)
+    _min_peak_args(min_peak, max_dev, what)
+    _register_args(volumes, n_iter, mode, out, what, "volume")
+    estimate = lambda tmpl: _block_estimate(volumes, tmpl, grid, max_shift, taper, smooth, eps, subpixel, min_peak, max_dev, None, chunk, what)
+    out, (field, peak, inlier, shifts), tmpl = _register(volumes, template, n_iter, _volume_median, estimate,
+                                                         lambda est, out: warp_volumes(volumes, est[0], grid, mode=mode, fill=fill, out=out), out)
+    return PiecewiseRegistration(out, field, peak, inlier, shifts, tmpl)
+
+
+class PiecewiseVolumeRegistrar:
+    """The streaming twin of ``VolumeRegistrar`` for piecewise-rigid motion: ``reg(chunk)`` returns the registered [T',D,H,W] chunk (or
+    volume, for one [D,H,W] volume) against the fixed float32 ``template`` [D,H,W] on the ``BlockGrid`` ``grid`` and appends the
+    chunk's field, peaks and inlier map to the device lists ``reg.field``, ``reg.peak`` and ``reg.inlier``; nothing is read back inside
+    the call.  ``all_fields()`` concatenates the fields ([N,gz,gy,gx,3]); ``estimate_args``: those of ``estimate_block_shifts``;
+    ``mode`` and ``fill``: those of ``warp_volumes``::
+
+        reg = PiecewiseVolumeRegistrar(template, block_grid(template.shape, (32, 128, 128)), max_shift=(2, 8, 8))
+        for cond in batches:
+            am.update(reg(inverse_pass(conv_inn, cond_nets, cond, mean_vols_cache)[:, 0]))
+        box = valid_box(reg.all_fields().reshape(-1, 3), template.shape)      # the one read-back, after the loop
+    """
+
+    def __init__(self, template, grid, mode="bilinear", fill=0.0, **estimate_args):
+        what = "PiecewiseVolumeRegistrar"
+        ops._dev(template, "template")
+        if template.dim() != 3:
+            raise ValueError(f"{what}: the template is a float32 [D,H,W] tensor, got {tuple(template.shape)}")
+        if mode not in ("bilinear", "nearest"):
+            raise ValueError(f"{what}: mode is 'bilinear' or 'nearest', got {mode!r}")
+        self.template, self.grid, self.mode, self.fill, self.estimate_args = template.contiguous(), grid, mode, float(fill), dict(estimate_args)
+        a = self.estimate_args
+        probe = torch.empty((0,) + tuple(template.shape), dtype=torch.float32, device=template.device)
+        _block_reg_args(probe, self.template, grid, a.get("max_shift", (2, 8, 8)), a.get("taper"), a.get("smooth", 0.0), a.get("eps", 1e-5),
+                        a.get("chunk", 1), a.get("subpixel", True), what)
+        _min_peak_args(a.get("min_peak", 0.0), a.get("max_dev"), what)
+        self.field, self.peak, self.inlier = [], [], []
+
+    def __call__(self, volumes, out=None):
+        single = torch.is_tensor(volumes) and volumes.dim() == 3
+        if single:
+            volumes = volumes.unsqueeze(0)
+        field, peak, inlier = estimate_block_shifts(volumes, self.template, self.grid, **self.estimate_args)
+        moved = warp_volumes(volumes, field, self.grid, mode=self.mode, fill=self.fill, out=out)
+        self.field.append(field)
+        self.peak.append(peak)
+        self.inlier.append(inlier)
+        return moved[0] if single else moved
+
+    def all_fields(self):
+        """float32 [N,gz,gy,gx,3] on the device: the field of every volume seen so far."""
+        if self.field:
+            return torch.cat(self.field)
+        return torch.empty((0, *self.grid.grid, 3), dtype=torch.float32, device=self.template.device)
+
+    def all_peaks(self):
+        """float32 [N,gz,gy,gx] on the device: the correlation peak of every block seen so far."""
+        return torch.cat(self.peak) if self.peak else torch.empty((0, *self.grid.grid), dtype=torch.float32, device=self.template.device)
 
 
 # ---------------------------------------------------------------------------------------------------- neuron footprints

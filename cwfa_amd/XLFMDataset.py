@@ -179,8 +179,8 @@ def _subpixel_arg(subpixel, upsample, what):
 
 def _estimate(window, tapered, N, shape, max_shift, smooth, eps, subpixel, dft, upsample, chunk):
     """(shifts float32 [n, rank], peak float32 [n]), n = N x the items of a stack element: the phase correlation the three estimators
-    share.  ``tapered``: the tapered float32 template, [*items, *shape] with ``shape`` the 2 or 3 transformed axes (items: nothing, or
-    L views); ``window(s, e, out)`` writes the tapered float32 elements s .. e - 1 of the stack into ``out`` [e - s, *items, *shape] and
+    share.  ``tapered``: the tapered float32 template, [*items, *shape] with ``shape`` the 2 or 3 transformed axes (items: nothing,
+    L views, or the B blocks of a volume's grid); ``window(s, e, out)`` writes the tapered float32 elements s .. e - 1 of the stack into ``out`` [e - s, *items, *shape] and
     returns it.  The template is transformed, whitened and conjugated, low-passed where ``smooth`` > 0, its DC bin zeroed; a chunk
     is windowed, transformed, whitened against that plane, transformed back, and searched for its peak."""
     rank, dev = len(shape), tapered.device

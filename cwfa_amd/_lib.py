@@ -91,6 +91,7 @@ SELECT_FORM = {"auto": 0, "lds": 1, "stream": 2}                                
 SHIFT_MODE = {"bilinear": 0, "nearest": 1}                                      # cwfa_reg_shift's `mode`
 VIEW_MODEL = {"axial": 0, "free": 1}                                            # cwfa_reg_fit_views_f64's `model`
 REG_MAX_VIEWS = 254               # a label is a byte; label L is the rest of the frame
+REG_MAX_BLOCKS = 4096             # RB_MAX_BLOCKS of register_blocks_ops.hip: the blocks of a piecewise grid
 FOOTPRINT_SELECT_MAX = 1 << 15   # CWFA_FOOTPRINT_SELECT_MAX
 DEMIX_PAIR_BYTES = 48             # CWFA_DEMIX_PAIR_BYTES
 
@@ -235,6 +236,9 @@ SIGNATURES = {
     "cwfa_reg_window3d_f32": (i, [p, i, i, i, i, i64, p, p, p, p, p]),
     "cwfa_reg_peak3d_f32": (i, [p, i, i, i, i, i64, i, i, i, i, p, p, p, p]),
     "cwfa_reg_shift3d_f32": (i, [p, i, i, i, i, i64, p, i, f, p, p]),
+    "cwfa_reg_window_blocks3d_f32": (i, [p, i, i, i, i, i64, p, i, i, i, i, i, i, p, p, p, p, p]),
+    "cwfa_reg_field_fill": (i, [p, p, p, i, i, i, i, d, p, p, p, p]),
+    "cwfa_reg_warp3d_f32": (i, [p, i, i, i, i, i64, p, i, i, i, p, p, p, p, p, p, i, f, p, p]),
     "cwfa_roi_mark_u8": (i, [p, i, p, i, i, i, p]),
     "cwfa_roi_weighted_sums_f32": (i, [p, p, p, p, p, i, i, i, i, i, i64, p]),
     "cwfa_roi_shell_sums_f32": (i, [p, p, p, p, p, p, i, i, i, i, i, i64, p]),

@@ -1,4 +1,4 @@
-// What the registration kernels share (register_ops.hip: frames; register_views_ops.hip: lenslet views; register3d_ops.hip: volumes).
+// What the registration kernels share (register_ops.hip: frames; register_views_ops.hip: lenslet views; register3d_ops.hip: volumes; register_blocks_ops.hip: blocks of volumes).
 // One definition of each, so that a frame is a volume of one plane by construction and not by a copy kept in step:
 //   the grid rule of the kernels whose threads walk the items                                         reg_grid_y
 //   the edge taper over [N, D, H, W], D = 1 and no wz for frames                                      reg_window_kernel

@@ -3100,6 +3100,133 @@ def reg_shift3d(stack, shifts, mode="bilinear", fill=0.0, out=None):
     return _reg_shift(stack, shifts, mode, fill, out, 3, "reg_shift3d")
 
 
+# ------------------------------------------------------------------------------------------------ piecewise-rigid registration of volumes
+def _block_grid3(grid, what):
+    """(gz, gy, gx): three counts of at least 1 whose product is at most ``REG_MAX_BLOCKS``."""
+    if not isinstance(grid, (tuple, list, torch.Size)) or len(grid) != 3:
+        raise ValueError(f"{what}: grid is (gz, gy, gx), got {grid!r}")
+    g = tuple(_count(v, "grid", what) for v in grid)
+    if g[0] * g[1] * g[2] > _lib.REG_MAX_BLOCKS:
+        raise ValueError(f"{what}: a grid of {_by(g)} has more than {_lib.REG_MAX_BLOCKS} blocks")
+    return g
+
+
+def _block_origins(origins, block, shape, what):
+    """(int32 host table [gz + gy + gx], (gz, gy, gx), (bz, by, bx)): the origins per axis, every block inside the volume."""
+    import numpy as np
+    if not isinstance(block, (tuple, list, torch.Size)) or len(block) != 3:
+        raise ValueError(f"{what}: block is (bz, by, bx), got {block!r}")
+    b = tuple(_count(v, "block", what) for v in block)
+    if any(v > s for v, s in zip(b, shape)):
+        raise ValueError(f"{what}: a block of {_by(b)} does not fit the {_by(shape)} volume")
+    if not isinstance(origins, (tuple, list)) or len(origins) != 3:
+        raise ValueError(f"{what}: origins is three integer sequences, one per axis")
+    rows = []
+    for a, o in enumerate(origins):
+        try:
+            o = np.asarray(o.detach().cpu().numpy() if torch.is_tensor(o) else o)
+            ok = o.ndim == 1 and o.size >= 1 and np.issubdtype(o.dtype, np.integer)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{what}: origins[{a}] is a sequence of at least one integer")
+        if (o < 0).any() or (o.astype(np.int64) > shape[a] - b[a]).any():
+            raise ValueError(f"{what}: an origin of axis {a} puts the block outside the volume")
+        rows.append(o.astype(np.int32))
+    g = _block_grid3(tuple(len(r) for r in rows), what)
+    return np.ascontiguousarray(np.concatenate(rows)), g, b
+
+
+def reg_window_blocks3d(stack, origins, block, wz, wy, wx, out=None):
+    """float32 [N,B,bz,by,bx]: the gz x gy x gx blocks of every volume of a [N,D,H,W] float32 device stack, cut and tapered in one
+    read: fl(stack[n, oz + z, oy + y, ox + x] * fl(fl(wz[z] * wy[y]) * wx[x])), block (iz gy + iy) gx + ix.  ``origins``: three HOST
+    integer sequences (z, y, x; their lengths are the grid, at most 4096 blocks) that keep every block of ``block`` = (bz, by, bx)
+    inside the volume; ``wz`` [bz], ``wy`` [by], ``wx`` [bx] fp32 device vectors.  ``out``: a contiguous float32 tensor of that
+    shape that shares no memory with the stack."""
+    what = "reg_window_blocks3d"
+    if not torch.is_tensor(stack) or stack.dim() != 4:
+        raise ValueError(f"{what}: a stack {_REG_AXES[3][0]} is expected")
+    o, g, b = _block_origins(origins, block, tuple(int(s) for s in stack.shape[1:]), what)      # the host table first: no device needed
+    stack, _, N, shape, fs = _reg_stack(stack, 3, what)
+    w = [_vec(v, n, name, what) for v, n, name in zip((wz, wy, wx), b, ("wz", "wy", "wx"))]
+    out = _reg_out(out, (N, g[0] * g[1] * g[2], *b), torch.float32, "float32", what, stack)
+    if N == 0:
+        return out
+    check(_lib.lib().cwfa_reg_window_blocks3d_f32(_p(stack), N, *shape, fs, _host(o), *g, *b, _p(w[0]), _p(w[1]), _p(w[2]), _p(out), _stream()), what)
+    return out
+
+
+def reg_field_fill(shifts, peak, base, grid, min_peak=0.0, max_dev=None, out=None):
+    """(field float32 [N,B,3], inlier uint8 [N,B]) on the device: the one clean-up pass over the table of block shifts (float32
+    [N,B,3], B = gz gy gx of ``grid``) with their peaks (float32 [N,B]) and a base shift per volume (float32 [N,3]).  A node is an
+    inlier when its peak is finite and >= ``min_peak``, its components are finite and |s_c - base_c| <= ``max_dev``[c] (three
+    numbers; None: no such test), compared in float64; an inlier keeps its bits, an outlier takes per component the float64 mean of
+    the inliers among its 26 grid neighbours (fixed order, status read from the input) rounded once, or ``base`` where it has none.
+    ``out``: the two tensors; ``field`` must not be ``shifts``."""
+    import ctypes
+    what = "reg_field_fill"
+    g = _block_grid3(grid, what)
+    B = g[0] * g[1] * g[2]
+    min_peak = float(min_peak)
+    if min_peak != min_peak:
+        raise ValueError(f"{what}: min_peak is NaN")
+    md = None
+    if max_dev is not None:
+        try:
+            md = tuple(float(v) for v in max_dev)
+        except (TypeError, ValueError):
+            md = ()
+        if len(md) != 3 or not all(v >= 0.0 for v in md):
+            raise ValueError(f"{what}: max_dev is None or three numbers that are not negative and not NaN, got {max_dev!r}")
+    if not torch.is_tensor(shifts) or shifts.dim() != 3 or int(shifts.shape[1]) != B or shifts.shape[2] != 3:
+        raise ValueError(f"{what}: shifts is a float32 [N, {B}, 3] tensor")
+    N = int(shifts.shape[0])
+    shifts, peak, base = _vec(shifts, 3 * N * B, "shifts", what), _vec(peak, N * B, "peak", what), _vec(base, 3 * N, "base", what)
+    dev = shifts.device
+    if out is None:
+        out = (torch.empty((N, B, 3), dtype=torch.float32, device=dev), torch.empty((N, B), dtype=torch.uint8, device=dev))
+    field, inlier = out
+    for t, dtype, tshape, name in ((field, torch.float32, (N, B, 3), "field"), (inlier, torch.uint8, (N, B), "inlier")):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != tshape or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous {dtype} {tshape} device tensor")
+    if _overlap(field, shifts):
+        raise ValueError(f"{what}: field must not alias shifts")
+    if N == 0:
+        return field, inlier
+    mdp = None if md is None else (ctypes.c_double * 3)(*md)
+    check(_lib.lib().cwfa_reg_field_fill(_p(shifts), _p(peak), _p(base), N, *g, min_peak, mdp, _p(field), _p(inlier), _stream()), what)
+    return field, inlier
+
+
+def reg_warp3d(stack, field, grid, tables, mode="bilinear", fill=0.0, out=None):
+    """out[n,z,y,x] = stack[n, z + dz, y + dy, x + dx] with (dz, dy, dx) the trilinear interpolation of the node table ``field``
+    (float32 [N,B,3], B = gz gy gx of ``grid``) at the voxel: ``tables`` = (idxz, tz, idxy, ty, idxx, tx), device vectors over the
+    coordinates of each axis (int32 node at or below, float32 fraction towards the next, as ``CWFA.block_grid`` makes them), lerp
+    a + t (b - a) along x, then y, then z, every operation rounded, t == 0 taking a itself.  The resampling of a voxel is that of
+    ``reg_shift3d`` under its vector, bit for bit, so a field whose nodes are equal gives ``reg_shift3d``.  ``out``: a contiguous
+    float32 tensor of the stack's shape that shares no memory with it."""
+    what = "reg_warp3d"
+    if mode not in _lib.SHIFT_MODE:
+        raise ValueError(f"{what}: mode is one of {sorted(_lib.SHIFT_MODE)}, got {mode!r}")
+    g = _block_grid3(grid, what)
+    if not isinstance(tables, (tuple, list)) or len(tables) != 6:
+        raise ValueError(f"{what}: tables is (idxz, tz, idxy, ty, idxx, tx)")
+    stack, _, N, shape, fs = _reg_stack(stack, 3, what)
+    B = g[0] * g[1] * g[2]
+    if not torch.is_tensor(field) or field.dim() != 3 or tuple(field.shape) != (N, B, 3):
+        raise ValueError(f"{what}: field is a float32 [{N}, {B}, 3] tensor")
+    field = _vec(field, 3 * N * B, "field", what)
+    tabs = []
+    for k, (t, name) in enumerate(zip(tables, ("idxz", "tz", "idxy", "ty", "idxx", "tx"))):
+        tabs.append(_vec(t, shape[k // 2], name, what, torch.float32 if k & 1 else torch.int32))
+    out = _reg_out(out, (N, *shape), torch.float32, "float32", what, stack)
+    if N == 0:
+        return out
+    check(_lib.lib().cwfa_reg_warp3d_f32(_p(stack), N, *shape, fs, _p(field), *g, *(_p(t) for t in tabs), _lib.SHIFT_MODE[mode], float(fill), _p(out),
+                                         _stream()), what)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ neuron footprints
 def _nonneg_triple(v, name, what):
     t = _triple(v, name, what)

@@ -1113,6 +1113,36 @@ int cwfa_reg_peak3d_f32(const float* c, int N, int D, int H, int W, int64_t vol_
 int cwfa_reg_shift3d_f32(const float* in, int N, int D, int H, int W, int64_t vol_stride, const float* shifts, int mode, float fill,
                          float* out, void* stream);
 
+/* ---- piecewise-rigid registration of volumes: a volume is cut into gz x gy x gx blocks (B = gz gy gx <= 4096,
+ * block b = (iz gy + iy) gx + ix), every block is registered by the passes above on the batch of N B blocks, the table of block shifts
+ * is cleaned, interpolated between the block centres and the volume resampled once under a displacement per voxel.  Arguments are
+ * checked before any device work (CWFA_E_INVAL / _SHAPE / _ALIGN as above), offsets are 64-bit, nothing is allocated or read back,
+ * no atomics, N == 0 launches nothing, no grid axis grows with N.
+ *   reg_window_blocks3d_f32: out[n,b,z,y,x] = fl32(x[n, oz+z, oy+y, ox+x] * fl32(fl32(wz[z] wy[y]) wx[x])), fp32 [N, B, bz, by, bx]
+ *                     contiguous.  `origins`: a HOST int32 table, the gz origins of axis z, then gy of y, then gx of x, each checked
+ *                     to keep the block inside the volume (0 <= o <= side - b) and carried to the kernel in its arguments.  One
+ *                     read of each block, one write; 16-byte stores where bx and out's base allow, loads of element alignment.
+ *   reg_field_fill:   shifts fp32 [N, B, 3], peak fp32 [N, B], base fp32 [N, 3] on the device; `max_dev`: three HOST doubles or null.
+ *                     A node is an inlier when its peak is finite and >= min_peak, its components are finite and (max_dev given)
+ *                     |s_c - base_c| <= max_dev[c], compared in float64.  field [N, B, 3]: an inlier's bits; for an outlier, per
+ *                     component, the float64 mean of the inliers among its 26 grid neighbours (row-major over {-1,0,1}^3, z slowest,
+ *                     status read from the input) rounded once to fp32, or base[n] where it has none.  inlier uint8 [N, B].
+ *                     field != shifts.  One thread per node, bitwise repeatable.
+ *   reg_warp3d_f32:   field fp32 [N, B, 3] and the six axis tables on the device (idx int32, t fp32, one entry per coordinate: the
+ *                     node at or below and the fraction towards the next; an idx is clamped to the grid, and node idx + 1 is never
+ *                     read where t == 0 or idx is the last node).  (dz, dy, dx) of a voxel: lerp(a, b, t) = a where t == 0, else
+ *                     fl32(a + fl32(t fl32(b - a))), along x, then y, then z.  out[n,z,y,x] = reg_shift3d_f32's rule under that vector,
+ *                     voxel by voxel: a field whose nodes are equal gives reg_shift3d_f32's bits.  out != in.  A thread writes four
+ *                     consecutive voxels in one 16-byte store where W and out's base allow, one otherwise, and walks up to 16
+ *                     planes, keeping the (y, x) interpolation of its two node planes. */
+int cwfa_reg_window_blocks3d_f32(const float* x, int N, int D, int H, int W, int64_t vol_stride, const int32_t* origins, int gz, int gy, int gx,
+                                 int bz, int by, int bx, const float* wz, const float* wy, const float* wx, float* out, void* stream);
+int cwfa_reg_field_fill(const float* shifts, const float* peak, const float* base, int N, int gz, int gy, int gx, double min_peak,
+                        const double* max_dev, float* field, unsigned char* inlier, void* stream);
+int cwfa_reg_warp3d_f32(const float* in, int N, int D, int H, int W, int64_t vol_stride, const float* field, int gz, int gy, int gx,
+                        const int32_t* idxz, const float* tz, const int32_t* idxy, const float* ty, const int32_t* idxx, const float* tx, int mode,
+                        float fill, float* out, void* stream);
+
 /* ---- neuron footprints: behind the detector, which voxels of a neuron's ROI box move with its centre once the
  * signal shared with the surroundings is taken out, and the traces weighted by that.  x: volumes [T, D, H, W] fp32, contiguous
  * volumes, t_stride >= D * H * W elements between them.  Box tables are HOST int32 [N][6] = {z0,z1,y0,y1,x0,x1}, half-open, inside the
