@@ -26,7 +26,8 @@ __all__ = ["sample_z_truncated", "check_empty_depths", "evaluate_INN_forward", "
            "NeuronFootprints", "Footprints", "extract_traces", "demix_plan", "demix_traces", "trace_baseline", "delta_f_over_f", "trace_noise", "infer_spikes",
            "estimate_volume_shifts", "shift_volumes", "register_volumes", "VolumeRegistration", "VolumeRegistrar", "valid_box",
            "block_grid", "BlockGrid", "estimate_block_shifts", "warp_volumes", "register_volumes_piecewise", "PiecewiseRegistration",
-           "PiecewiseVolumeRegistrar"]
+           "PiecewiseVolumeRegistrar", "fit_rigid_motion", "RigidFit", "rigid_move_volumes", "estimate_rigid_motion", "register_volumes_rigid",
+           "RigidRegistration", "RigidVolumeRegistrar", "rigid_angles", "rigid_corner_shifts"]
 
 
 def _no_grad_trunc_normal_(tensor, mean=0., std=1., a=-1., b=1.):
@@ -1168,6 +1169,16 @@ def _min_peak_args(min_peak, max_dev, what):
     return min_peak, max_dev
 
 
+def _block_table(volumes, template, grid, m, taper, smooth, eps, subpixel, chunk, chunk_of=None):
+    """(shifts float32 [N B, 3], peak float32 [N B]): the table of block shifts as measured -- no clean-up, no whole-volume estimate.
+    ``chunk_of(s, e)``: the volumes s .. e - 1 the blocks are cut from, where they are not ``volumes[s:e]`` themselves."""
+    w = grid.windows(taper, volumes.device)
+    source = (lambda s, e: volumes[s:e]) if chunk_of is None else chunk_of
+    return _estimate(lambda s, e, out: ops.reg_window_blocks3d(source(s, e), grid.origins, grid.block, *w, out=out),
+                     ops.reg_window_blocks3d(template.contiguous()[None], grid.origins, grid.block, *w)[0], int(volumes.shape[0]), grid.block, m, smooth,
+                     eps, bool(subpixel), False, None, chunk)
+
+
 def _block_estimate(volumes, template, grid, max_shift, taper, smooth, eps, subpixel, min_peak, max_dev, base, chunk, what):
     """(field, peak, inlier, raw shifts), [N,gz,gy,gx,..]: ``estimate_block_shifts`` and the table before its clean-up."""
     m, taper, chunk = _block_reg_args(volumes, template, grid, max_shift, taper, smooth, eps, chunk, subpixel, what)
@@ -1178,10 +1189,7 @@ def _block_estimate(volumes, template, grid, max_shift, taper, smooth, eps, subp
     if base is not None and (not torch.is_tensor(base) or tuple(base.shape) != (N, 3) or base.dtype != torch.float32):
         raise ValueError(f"{what}: base is a float32 [{N}, 3] tensor")
     ops._dev(volumes, "volumes")
-    w = grid.windows(taper, volumes.device)
-    shifts, peak = _estimate(lambda s, e, out: ops.reg_window_blocks3d(volumes[s:e], grid.origins, grid.block, *w, out=out),
-                             ops.reg_window_blocks3d(template.contiguous()[None], grid.origins, grid.block, *w)[0], N, grid.block, m, smooth, eps,
-                             bool(subpixel), False, None, chunk)
+    shifts, peak = _block_table(volumes, template, grid, m, taper, smooth, eps, subpixel, chunk)
     if base is None:
         base = estimate_volume_shifts(volumes, template, max_shift=m, taper=taper, smooth=smooth, eps=eps, subpixel=subpixel, chunk=chunk)[0]
     field, inlier = ops.reg_field_fill(shifts.view(N, grid.B, 3), peak.view(N, grid.B), base, grid.grid, min_peak, max_dev)
@@ -1303,6 +1311,238 @@ class PiecewiseVolumeRegistrar:
     def all_peaks(self):
         """float32 [N,gz,gy,gx] on the device: the correlation peak of every block seen so far."""
         return torch.cat(self.peak) if self.peak else torch.empty((0, *self.grid.grid), dtype=torch.float32, device=self.template.device)
+
+
+# ---------------------------------------------------------------------------------------------------- rigid registration with rotation
+# For a sample that turns about the optical axis (DESIGN.md section 33): the table of block shifts of section 32 is fitted by
+# "rotation about z + 3-D shift", five float64 numbers (dz, dy, dx, c, s) per volume, and the volume is resampled once under them.
+RigidFit = namedtuple("RigidFit", ["params", "inlier"])
+RigidRegistration = namedtuple("RigidRegistration", ["volumes", "params", "peak", "inlier", "shifts", "template"])
+
+
+def _rigid_center(center, shape, what):
+    """(cy, cx) as the resampling kernel takes them: two finite numbers rounded to float32, the centre of the plane where None."""
+    cy, cx = ops._rigid_center(center, shape, what)
+    c = torch.tensor([cy, cx], dtype=torch.float32)
+    return float(c[0]), float(c[1])
+
+
+def _rigid_arms(grid, center, device):
+    """float64 [B,2] on the device: block centre minus rotation centre, (y, x), block b = (iz gy + iy) gx + ix."""
+    gz, gy, gx = grid.grid
+    ay = torch.from_numpy(grid.centers[1]).to(torch.float64) - center[0]
+    ax = torch.from_numpy(grid.centers[2]).to(torch.float64) - center[1]
+    arms = torch.stack((ay[None, :, None].expand(gz, gy, gx), ax[None, None, :].expand(gz, gy, gx)), dim=-1)
+    return arms.reshape(grid.B, 2).contiguous().to(device)
+
+
+def _rigid_fit_args(min_peak, reject, what):
+    min_peak, reject = float(min_peak), float(reject)
+    if not min_peak >= 0.0 or not reject >= 0.0:
+        raise ValueError(f"{what}: min_peak and reject are not negative and not NaN, got {min_peak}, {reject}")
+    return min_peak, reject
+
+
+def _rigid_params_arg(params, N, what, name="params"):
+    if not torch.is_tensor(params) or tuple(params.shape) != (N, 5) or params.dtype != torch.float64:
+        raise ValueError(f"{what}: {name} is a float64 [{N}, 5] tensor of (dz, dy, dx, c, s)")
+
+
+def fit_rigid_motion(shifts, peak, grid, center=None, min_peak=0.0, reject=1.0, prior=None):
+    """``RigidFit(params, inlier)`` from a table of block shifts (float32 [N,gz,gy,gx,3] or [N,B,3], as measured on the ``BlockGrid``
+    ``grid``) and its peaks: per volume the motion (dz, dy, dx, c, s) -- a rotation about z by the angle of cosine c and sine s around
+    ``center`` (cy, cx; None: the centre of the plane) plus a 3-D shift -- that explains the table best, a Procrustes fit in float64
+    over the blocks whose peak is finite and >= ``min_peak`` with one rejection pass at ``reject`` voxels.  All
+    blocks of a grid with gz > 1 vote for one in-plane rotation and one dz.  ``params`` float64 [N,5]; ``inlier`` uint8 [N,gz,gy,gx].
+    ``prior`` float64 [N,5]: the motion already applied to the volumes that were measured; the result is the total motion of the
+    original.  Everything stays on the device."""
+    what = "fit_rigid_motion"
+    if not isinstance(grid, BlockGrid):
+        raise ValueError(f"{what}: grid is the BlockGrid of block_grid")
+    min_peak, reject = _rigid_fit_args(min_peak, reject, what)
+    center = _rigid_center(center, grid.shape, what)
+    if not torch.is_tensor(shifts) or shifts.dim() < 3 or tuple(shifts.shape[1:]) not in ((*grid.grid, 3), (grid.B, 3)) or shifts.dtype != torch.float32:
+        raise ValueError(f"{what}: shifts is a float32 {['N', *grid.grid, 3]} tensor")
+    N = int(shifts.shape[0])
+    if not torch.is_tensor(peak) or peak.numel() != N * grid.B or peak.dtype != torch.float32:
+        raise ValueError(f"{what}: peak is a float32 {['N', *grid.grid]} tensor")
+    if prior is not None:
+        _rigid_params_arg(prior, N, what, "prior")
+    if not shifts.is_cuda:
+        raise RuntimeError(f"{what}: cwfa_amd runs on MI355X only -- shifts must be a device tensor (no CPU fallback exists)")
+    params, inlier = ops.reg_fit_rigid(shifts.reshape(N, grid.B, 3), peak.reshape(N, grid.B), _rigid_arms(grid, center, shifts.device), min_peak, reject,
+                                       prior)
+    return RigidFit(params, inlier.view(N, *grid.grid))
+
+
+@amp_region
+def rigid_move_volumes(volumes, params, center=None, mode="bilinear", fill=0.0, out=None):
+    """out[n,z,y,x] = volumes[n, z + dz, c0 + R ((y, x) - c0) + (dy, dx)] with (dz, dy, dx, c, s) = params[n] (float64 [N,5] on the
+    device, as ``fit_rigid_motion`` returns them), R = [[c, -s], [s, c]] and c0 = ``center`` (None: the centre of the plane): the
+    sign convention of ``shift_volumes``, which it equals bit for bit at (c, s) = (1, 0).  Trilinear or ``mode="nearest"``; voxels
+    from outside the volume are ``fill``.  ``out`` must not share memory with ``volumes``.
+    ``valid_box(rigid_corner_shifts(params, shape, center), shape)`` bounds the box that holds data in every volume."""
+    what = "rigid_move_volumes"
+    _shift_volume_args(volumes, None, mode, out, what)
+    _rigid_params_arg(params, int(volumes.shape[0]), what)
+    return ops.reg_rigid3d(volumes, params, _rigid_center(center, tuple(volumes.shape[1:]), what), mode=mode, fill=fill, out=out)
+
+
+def _rigid_estimate(volumes, template, grid, n_refine, center, max_shift, taper, smooth, eps, subpixel, min_peak, reject, chunk, what):
+    """(params, peak, inlier, shifts) of ``estimate_rigid_motion``."""
+    m, taper, chunk = _block_reg_args(volumes, template, grid, max_shift, taper, smooth, eps, chunk, subpixel, what)
+    min_peak, reject = _rigid_fit_args(min_peak, reject, what)
+    if int(n_refine) < 0:
+        raise ValueError(f"{what}: n_refine is not negative, got {n_refine}")
+    center = _rigid_center(center, grid.shape, what)
+    if template is None:
+        raise ValueError(f"{what}: a template is needed")
+    ops._dev(volumes, "volumes")
+    N, g = int(volumes.shape[0]), grid.grid
+    arms = _rigid_arms(grid, center, volumes.device)
+
+    def table(chunk_of=None):
+        shifts, peak = _block_table(volumes, template, grid, m, taper, smooth, eps, subpixel, chunk, chunk_of)
+        return shifts.view(N, grid.B, 3), peak.view(N, grid.B)
+
+    shifts, peak = table()
+    params, inlier = ops.reg_fit_rigid(shifts, peak, arms, min_peak, reject)
+    if N and int(n_refine):
+        scratch = torch.empty((min(chunk, N), *grid.shape), dtype=torch.float32, device=volumes.device)
+        for _ in range(int(n_refine)):
+            moved = lambda s, e, cur=params: ops.reg_rigid3d(volumes[s:e], cur[s:e], center, out=scratch[:e - s])
+            shifts, peak = table(moved)
+            params, inlier = ops.reg_fit_rigid(shifts, peak, arms, min_peak, reject, prior=params)
+    return params, peak.view(N, *g), inlier.view(N, *g), shifts.view(N, *g, 3)
+
+
+@amp_region
+def estimate_rigid_motion(volumes, template, grid, n_refine=2, center=None, max_shift=(2, 8, 8), taper=None, smooth=0.0, eps=1e-5, subpixel=True,
+                          min_peak=0.0, reject=1.0, chunk=1):
+    """(params float64 [N,5], peak float32 [N,gz,gy,gx], inlier uint8 [N,gz,gy,gx], shifts float32 [N,gz,gy,gx,3]) on the device: the
+    rigid motion (dz, dy, dx, c, s) of every volume of a contiguous [N,D,H,W] float32 device stack against the float32 ``template``
+    [D,H,W] -- a rotation about the optical axis around ``center`` plus a 3-D shift.  Pass 0 measures the table
+    of block shifts of the ``BlockGrid`` ``grid`` as ``estimate_block_shifts`` measures it (its arguments; no clean-up and no
+    whole-volume estimate) and fits it (``fit_rigid_motion``: ``min_peak``, ``reject``).  A block that is still rotated against its
+    template reports a biased shift, so each of the ``n_refine`` further passes moves the ORIGINAL chunk under the current motion
+    into a scratch chunk, measures that, and fits with the current motion as ``prior``: the result stays the total motion of the
+    original and a volume is never interpolated twice.  ``peak``, ``inlier`` and ``shifts`` are those of the last pass.  The angles
+    must be small enough for a block to correlate with its template (a few degrees).  Nothing is read back."""
+    return _rigid_estimate(volumes, template, grid, n_refine, center, max_shift, taper, smooth, eps, subpixel, min_peak, reject, chunk,
+                           "estimate_rigid_motion")
+
+
+@amp_region
+def register_volumes_rigid(volumes, template=None, grid=None, block=(32, 128, 128), n_iter=1, n_refine=2, center=None, max_shift=(2, 8, 8),
+                           subpixel=True, mode="bilinear", taper=None, smooth=0.0, eps=1e-5, min_peak=0.0, reject=1.0, chunk=1, fill=0.0, out=None):
+    """Rigid registration with a rotation about the optical axis of a contiguous [N,D,H,W] float32 device stack:
+    ``RigidRegistration(volumes, params, peak, inlier, shifts, template)`` with volumes[n] = the input's volume n moved back under
+    params[n] = (dz, dy, dx, c, s).  ``grid``: a ``BlockGrid``, or (gz, gy, gx) / None for ``block_grid(shape, block, grid)``.
+    ``template`` None: the per-voxel lower temporal median; ``n_iter`` > 1: the template becomes the median of the registered stack
+    and the motion is estimated again FROM THE ORIGINAL VOLUMES.  The other arguments are those of ``estimate_rigid_motion`` and
+    ``rigid_move_volumes``; ``valid_box(rigid_corner_shifts(params, shape, center), shape)`` is the box that holds data in every
+    volume.  Nothing is read back."""
+    what = "register_volumes_rigid"
+    _vol_reg_args(volumes, template, 0, 0, smooth, eps, chunk, subpixel, what)
+    if not isinstance(grid, BlockGrid):
+        grid = block_grid(tuple(int(n) for n in volumes.shape[1:]), block, grid)
+    _block_reg_args(volumes, template, grid, max_shift, taper, smooth, eps, chunk, subpixel, what)
+    _rigid_fit_args(min_peak, reject, what)
+    _rigid_center(center, grid.shape, what)
+    if int(n_refine) < 0:
+        raise ValueError(f"{what}: n_refine is not negative, got {n_refine}")
+    _register_args(volumes, n_iter, mode, out, what, "volume")
+    estimate = lambda tmpl: _rigid_estimate(volumes, tmpl, grid, n_refine, center, max_shift, taper, smooth, eps, subpixel, min_peak, reject, chunk, what)
+    out, (params, peak, inlier, shifts), tmpl = _register(volumes, template, n_iter, _volume_median, estimate,
+                                                          lambda est, out: rigid_move_volumes(volumes, est[0], center, mode=mode, fill=fill, out=out), out)
+    return RigidRegistration(out, params, peak, inlier, shifts, tmpl)
+
+
+class RigidVolumeRegistrar:
+    """The streaming twin of ``PiecewiseVolumeRegistrar`` for rigid motion with rotation: ``reg(chunk)`` returns the registered
+    [T',D,H,W] chunk (or volume, for one [D,H,W] volume) against the fixed float32 ``template`` [D,H,W] on the ``BlockGrid`` ``grid``
+    and appends the chunk's parameters, peaks and inlier map to the device lists ``reg.params``, ``reg.peak`` and ``reg.inlier``;
+    nothing is read back inside the call.  ``all_params()`` concatenates the parameters (float64 [N,5]); ``estimate_args``: those of
+    ``estimate_rigid_motion``; ``mode`` and ``fill``: those of ``rigid_move_volumes``::
+
+        reg = RigidVolumeRegistrar(template, block_grid(template.shape, (32, 128, 128)), max_shift=(2, 8, 8))
+        for cond in batches:
+            am.update(reg(inverse_pass(conv_inn, cond_nets, cond, mean_vols_cache)[:, 0]))
+        box = valid_box(rigid_corner_shifts(reg.all_params(), template.shape), template.shape)      # the one read-back, after the loop
+    """
+
+    def __init__(self, template, grid, mode="bilinear", fill=0.0, **estimate_args):
+        what = "RigidVolumeRegistrar"
+        ops._dev(template, "template")
+        if template.dim() != 3:
+            raise ValueError(f"{what}: the template is a float32 [D,H,W] tensor, got {tuple(template.shape)}")
+        if mode not in ("bilinear", "nearest"):
+            raise ValueError(f"{what}: mode is 'bilinear' or 'nearest', got {mode!r}")
+        self.template, self.grid, self.mode, self.fill, self.estimate_args = template.contiguous(), grid, mode, float(fill), dict(estimate_args)
+        a = self.estimate_args
+        probe = torch.empty((0,) + tuple(template.shape), dtype=torch.float32, device=template.device)
+        _block_reg_args(probe, self.template, grid, a.get("max_shift", (2, 8, 8)), a.get("taper"), a.get("smooth", 0.0), a.get("eps", 1e-5),
+                        a.get("chunk", 1), a.get("subpixel", True), what)
+        _rigid_fit_args(a.get("min_peak", 0.0), a.get("reject", 1.0), what)
+        self.center = _rigid_center(a.get("center"), grid.shape, what)
+        if int(a.get("n_refine", 2)) < 0:
+            raise ValueError(f"{what}: n_refine is not negative, got {a['n_refine']}")
+        self.params, self.peak, self.inlier = [], [], []
+
+    def __call__(self, volumes, out=None):
+        single = torch.is_tensor(volumes) and volumes.dim() == 3
+        if single:
+            volumes = volumes.unsqueeze(0)
+        params, peak, inlier, _ = estimate_rigid_motion(volumes, self.template, self.grid, **self.estimate_args)
+        moved = rigid_move_volumes(volumes, params, self.center, mode=self.mode, fill=self.fill, out=out)
+        self.params.append(params)
+        self.peak.append(peak)
+        self.inlier.append(inlier)
+        return moved[0] if single else moved
+
+    def all_params(self):
+        """float64 [N,5] on the device: the motion of every volume seen so far."""
+        return torch.cat(self.params) if self.params else torch.empty((0, 5), dtype=torch.float64, device=self.template.device)
+
+    def all_peaks(self):
+        """float32 [N,gz,gy,gx] on the device: the correlation peak of every block seen so far (last pass)."""
+        return torch.cat(self.peak) if self.peak else torch.empty((0, *self.grid.grid), dtype=torch.float32, device=self.template.device)
+
+
+def rigid_angles(params):
+    """float64 [N]: the rotation angles of ``params`` (float64 [N,5]) in degrees, atan2(s, c), on the tensor's device."""
+    if not torch.is_tensor(params) or params.dim() != 2 or params.shape[1] != 5:
+        raise ValueError("rigid_angles: params is a [N, 5] tensor of (dz, dy, dx, c, s)")
+    p = params.to(torch.float64)
+    return torch.atan2(p[:, 4], p[:, 3]) * (180.0 / math.pi)
+
+
+def rigid_corner_shifts(params, shape, center=None):
+    """float32 [4 N, 3] on the host: the displacement (dz, vy, vx) that ``rigid_move_volumes`` applies at the four corners of the plane
+    of a volume of ``shape`` (D, H, W), for every row of ``params`` (float64 [N,5]), in the resampling's own fp32 arithmetic.  The
+    displacement is affine in the position and every rounded operation is monotone, so its extremes over the plane are at the
+    corners: ``valid_box(rigid_corner_shifts(params, shape, center), shape)`` bounds the box in which every registered volume holds
+    data and no ``fill`` -- the box to hand to ``find_neurons(margin=)``.  A host helper: it reads the parameters back."""
+    what = "rigid_corner_shifts"
+    dims = tuple(int(v) for v in shape)
+    if len(dims) != 3:
+        raise ValueError(f"{what}: shape is (D, H, W), got {shape!r}")
+    if not torch.is_tensor(params) or params.dim() != 2 or params.shape[1] != 5:
+        raise ValueError(f"{what}: params is a [N, 5] tensor of (dz, dy, dx, c, s)")
+    cy, cx = _rigid_center(center, dims, what)
+    p = params.detach().to("cpu", torch.float64)
+    f32 = lambda t: t.to(torch.float32)
+    dz, dy, dx, s = f32(p[:, 0]), f32(p[:, 1]), f32(p[:, 2]), f32(p[:, 4])
+    cm1 = f32(-(p[:, 4] * p[:, 4]) / (1.0 + p[:, 3]))
+    cm1 = torch.where(torch.isfinite(p[:, 3]), cm1, torch.full_like(cm1, float("nan")))
+    rows = []
+    for y in (0, dims[1] - 1):
+        for x in (0, dims[2] - 1):
+            py = torch.tensor(float(y), dtype=torch.float32) - torch.tensor(cy, dtype=torch.float32)
+            px = torch.tensor(float(x), dtype=torch.float32) - torch.tensor(cx, dtype=torch.float32)
+            # (dz + 0 cm1: a rotation that is not finite fills the volume, so it makes the row non-finite in every component)
+            rows.append(torch.stack((dz + 0.0 * cm1, dy + (cm1 * py - s * px), dx + (s * py + cm1 * px)), dim=1))
+    return torch.stack(rows, dim=1).reshape(-1, 3)
 
 
 # ---------------------------------------------------------------------------------------------------- neuron footprints

@@ -239,6 +239,8 @@ SIGNATURES = {
     "cwfa_reg_window_blocks3d_f32": (i, [p, i, i, i, i, i64, p, i, i, i, i, i, i, p, p, p, p, p]),
     "cwfa_reg_field_fill": (i, [p, p, p, i, i, i, i, d, p, p, p, p]),
     "cwfa_reg_warp3d_f32": (i, [p, i, i, i, i, i64, p, i, i, i, p, p, p, p, p, p, i, f, p, p]),
+    "cwfa_reg_fit_rigid_f64": (i, [p, p, p, i, i, d, d, p, p, p, p]),
+    "cwfa_reg_rigid3d_f32": (i, [p, i, i, i, i, i64, p, f, f, i, f, p, p]),
     "cwfa_roi_mark_u8": (i, [p, i, p, i, i, i, p]),
     "cwfa_roi_weighted_sums_f32": (i, [p, p, p, p, p, i, i, i, i, i, i64, p]),
     "cwfa_roi_shell_sums_f32": (i, [p, p, p, p, p, p, i, i, i, i, i, i64, p]),

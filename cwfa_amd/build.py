@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libcwfa_hip.so")
-SOURCES = ["elementwise.hip", "conv2d.hip", "conv_wino.hip", "conv_wino2d.hip", "conv_split_layer.hip", "conv_split_out.hip", "conv_split3x3.hip", "conv3d.hip", "conv3d_split.hip", "lrnn_ops.hip", "conv_bwd.hip", "eval_ops.hip", "prep_ops.hip", "optim_ops.hip", "loss_ops.hip", "deconv_ops.hip", "neuron_ops.hip", "noise_ops.hip", "sparse_ops.hip", "register_ops.hip", "register_views_ops.hip", "register3d_ops.hip", "register_blocks_ops.hip", "footprint_ops.hip", "trace_ops.hip", "demix_ops.hip"]
+SOURCES = ["elementwise.hip", "conv2d.hip", "conv_wino.hip", "conv_wino2d.hip", "conv_split_layer.hip", "conv_split_out.hip", "conv_split3x3.hip", "conv3d.hip", "conv3d_split.hip", "lrnn_ops.hip", "conv_bwd.hip", "eval_ops.hip", "prep_ops.hip", "optim_ops.hip", "loss_ops.hip", "deconv_ops.hip", "neuron_ops.hip", "noise_ops.hip", "sparse_ops.hip", "register_ops.hip", "register_views_ops.hip", "register3d_ops.hip", "register_blocks_ops.hip", "register_rigid_ops.hip", "footprint_ops.hip", "trace_ops.hip", "demix_ops.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-I", INCLUDE, "-I", CSRC,
          "-Wall", "-Wno-unused-function"]

@@ -3227,6 +3227,73 @@ def reg_warp3d(stack, field, grid, tables, mode="bilinear", fill=0.0, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ rigid registration with a rotation about z
+def _rigid_center(center, shape, what):
+    """(cy, cx): two finite floats, the centre of the plane where ``center`` is None."""
+    if center is None:
+        return (shape[-2] - 1) / 2.0, (shape[-1] - 1) / 2.0
+    try:
+        c = tuple(float(v) for v in center)
+    except (TypeError, ValueError):
+        c = ()
+    if len(c) != 2 or not all(abs(v) < float("inf") for v in c):
+        raise ValueError(f"{what}: center is None or two finite numbers (cy, cx), got {center!r}")
+    return c
+
+
+def reg_fit_rigid(shifts, peak, arms, min_peak=0.0, reject=1.0, prior=None):
+    """(params float64 [N,5], inlier uint8 [N,B]) on the device from a table of block shifts (float32 [N,B,3]), their peaks (float32
+    [N,B]) and the arms (float64 [B,2]: block centre minus rotation centre, (y, x)): per volume the rigid motion (dz, dy, dx, c, s),
+    rotation about z by the angle of cosine c and sine s plus a 3-D shift, fitted in float64 with a fixed summation order over the
+    blocks whose peak is finite and >= ``min_peak`` and whose shift is finite, one rejection pass at ``reject`` voxels (inf: none) and
+    a second fit.  ``prior`` float64 [N,5]: the motion already applied to the measured volumes; the result
+    is then the total motion of the original."""
+    what = "reg_fit_rigid"
+    min_peak, reject = float(min_peak), float(reject)
+    if not min_peak >= 0.0 or not reject >= 0.0:
+        raise ValueError(f"{what}: min_peak and reject are not negative and not NaN, got {min_peak}, {reject}")
+    if not torch.is_tensor(shifts) or shifts.dim() != 3 or shifts.shape[2] != 3:
+        raise ValueError(f"{what}: shifts is a float32 [N,B,3] tensor")
+    N, B = int(shifts.shape[0]), int(shifts.shape[1])
+    if not 1 <= B <= _lib.REG_MAX_BLOCKS:
+        raise ValueError(f"{what}: 1 to {_lib.REG_MAX_BLOCKS} blocks are expected, got {B}")
+    shifts, peak = _vec(shifts, 3 * N * B, "shifts", what), _vec(peak, N * B, "peak", what)
+    arms = _vec(arms, 2 * B, "arms", what, torch.float64)
+    if prior is not None:
+        prior = _vec(prior, 5 * N, "prior", what, torch.float64)
+    dev = shifts.device
+    params = torch.empty((N, 5), dtype=torch.float64, device=dev)
+    inlier = torch.empty((N, B), dtype=torch.uint8, device=dev)
+    if N == 0:
+        return params, inlier
+    check(_lib.lib().cwfa_reg_fit_rigid_f64(_p(shifts), _p(peak), _p(arms), N, B, min_peak, reject, _p(prior), _p(params), _p(inlier), _stream()), what)
+    return params, inlier
+
+
+def reg_rigid3d(volumes, params, center=None, mode="bilinear", fill=0.0, out=None):
+    """out[n,z,y,x] = volumes[n, z + dz, c0 + R ((y, x) - c0) + (dy, dx)] with (dz, dy, dx, c, s) = params[n] read on the device
+    (float64 [N,5]), R = [[c, -s], [s, c]] and c0 = ``center`` (cy, cx), None: ((H - 1) / 2, (W - 1) / 2).  The in-plane displacement
+    of a voxel is formed in fp32 from (c - 1, s), c - 1 as -(s s) / (1 + c) in float64, and the voxel is resampled as ``reg_shift3d``
+    resamples under that vector, bit for bit: (c, s) = (1, 0) gives ``reg_shift3d``, a quarter turn about the centre of a square
+    plane copies bits.  A non-finite parameter fills the volume.  ``out``: a contiguous float32 tensor of the stack's shape that
+    shares no memory with it."""
+    what = "reg_rigid3d"
+    if mode not in _lib.SHIFT_MODE:
+        raise ValueError(f"{what}: mode is one of {sorted(_lib.SHIFT_MODE)}, got {mode!r}")
+    if not torch.is_tensor(volumes) or volumes.dim() != 4:
+        raise ValueError(f"{what}: a stack {_REG_AXES[3][0]} is expected")
+    cy, cx = _rigid_center(center, tuple(int(s) for s in volumes.shape), what)
+    stack, _, N, shape, fs = _reg_stack(volumes, 3, what)
+    if not torch.is_tensor(params) or tuple(params.shape) != (N, 5):
+        raise ValueError(f"{what}: params is a float64 [{N}, 5] tensor")
+    params = _vec(params, 5 * N, "params", what, torch.float64)
+    out = _reg_out(out, (N, *shape), torch.float32, "float32", what, stack)
+    if N == 0:
+        return out
+    check(_lib.lib().cwfa_reg_rigid3d_f32(_p(stack), N, *shape, fs, _p(params), cy, cx, _lib.SHIFT_MODE[mode], float(fill), _p(out), _stream()), what)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ neuron footprints
 def _nonneg_triple(v, name, what):
     t = _triple(v, name, what)

@@ -1143,6 +1143,41 @@ int cwfa_reg_warp3d_f32(const float* in, int N, int D, int H, int W, int64_t vol
                         const int32_t* idxz, const float* tz, const int32_t* idxy, const float* ty, const int32_t* idxx, const float* tx, int mode,
                         float fill, float* out, void* stream);
 
+/* ---- rigid registration of volumes with a rotation about the optical axis: the block-shift table of section 32
+ * is fitted by "rotation about z + 3-D shift" and the volume is resampled once under it.  A motion is five float64 numbers
+ * (dz, dy, dx, c, s), c = cos, s = sin of the angle, and moves a volume as
+ *   out(z, y, x) = in(z + dz, c0 + R ((y, x) - c0) + (dy, dx)),  R = [[c, -s], [s, c]] on (y, x),  c0 = (cy, cx);
+ * c - 1 is always formed as cm1 = -(s s) / (1 + c); no trigonometric function is evaluated.  Arguments are checked before any device
+ * work (CWFA_E_INVAL / _SHAPE / _ALIGN as above), offsets are 64-bit, nothing is allocated or read back, no atomics, N == 0 launches
+ * nothing.  Every floating-point operation is rounded separately.
+ *   reg_fit_rigid_f64: per volume n from shifts fp32 [N, B, 3], peak fp32 [N, B] and arms a float64 [B, 2] (block centre - c0, (y, x);
+ *                     all device), 1 <= B <= 4096, one thread per volume, float64, sums over b = 0 .. B - 1 in order from 0.0
+ *                     skipping blocks of weight 0: w_b = 1 where peak is finite and >= min_peak and the three components are finite;
+ *                     m = sum w; for m >= 1: am = (sum w a) / m, sm = (sum w s) / m, e = a_b - am, f = e + (s_b,yx - sm_yx),
+ *                     P = sum w (ey fy + ex fx), Q = sum w (ey fx - ex fy), r = sqrt(P P + Q Q); (c, s) = (P / r, Q / r) where r > 0,
+ *                     P > 0 and both are finite, else (1, 0); dz = sm_z, dy = sm_y - (cm1 am_y - s am_x),
+ *                     dx = sm_x - (s am_y + cm1 am_x).  Then r_b = max(|s_z - dz|, |s_y - (dy + (cm1 a_y - s a_x))|,
+ *                     |s_x - (dx + (s a_y + cm1 a_x))|) and w_b = 0 where r_b > reject; if a weight is left the fit is repeated
+ *                     once, if none is the first fit and weights stand.  m == 0: (0, 0, 0, 1, 0).  prior [N, 5] float64 or null: the
+ *                     motion (dz', dy', dx', c', s') already applied to the measured volumes; the result is then the total motion,
+ *                     C = c' c - s' s, S = s' c + c' s, h = sqrt(C C + S S), rotation (C / h, S / h),
+ *                     dy = (dy + (cm1' dy - s' dx)) + dy', dx = (dx + (s' dy + cm1' dx)) + dx', dz = dz + dz'.  params [N, 5]
+ *                     float64, inlier [N, B] bytes = the final w.  min_peak, reject >= 0 (reject may be +inf), CWFA_E_INVAL otherwise
+ *                     (NaN included); arms, params, prior 8-byte aligned; params != prior.  Bitwise repeatable.
+ *   reg_rigid3d_f32:  params [N, 5] float64 read on the device; cy, cx two finite host floats.  Per volume dzf, dyf, dxf, sf = the fp32
+ *                     roundings of dz, dy, dx, s and cm1f = (float)cm1 (cm1 in float64); a c that is not finite or a non-finite one
+ *                     of those five fills the volume with `fill`.  Per voxel py = fl32((float)y - cy), px = fl32((float)x - cx),
+ *                     vy = fl32(dyf + fl32(fl32(cm1f py) - fl32(sf px))), vx = fl32(dxf + fl32(fl32(sf py) + fl32(cm1f px))) and
+ *                     out[n,z,y,x] = reg_shift3d_f32's rule under (dzf, vy, vx), `fill` where vy or vx overflowed: (c, s) = (1, 0) gives reg_shift3d_f32's bits, an
+ *                     integer shift without rotation copies source bits, (0, +-1) about the centre of a square plane is a quarter
+ *                     turn of every plane, bit for bit.  out [N, D, H, W] contiguous, out != in.  A thread writes four consecutive
+ *                     voxels of a row in one 16-byte store where W and out's base allow, one voxel otherwise, forms their (vy, vx)
+ *                     once per volume and walks up to 16 planes keeping p_1 as the next plane's p_0. */
+int cwfa_reg_fit_rigid_f64(const float* shifts, const float* peak, const double* arms, int N, int B, double min_peak, double reject,
+                           const double* prior, double* params, uint8_t* inlier, void* stream);
+int cwfa_reg_rigid3d_f32(const float* in, int N, int D, int H, int W, int64_t vol_stride, const double* params, float cy, float cx, int mode,
+                         float fill, float* out, void* stream);
+
 /* ---- neuron footprints: behind the detector, which voxels of a neuron's ROI box move with its centre once the
  * signal shared with the surroundings is taken out, and the traces weighted by that.  x: volumes [T, D, H, W] fp32, contiguous
  * volumes, t_stride >= D * H * W elements between them.  Box tables are HOST int32 [N][6] = {z0,z1,y0,y1,x0,x1}, half-open, inside the
