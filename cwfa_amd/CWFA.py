@@ -962,8 +962,7 @@ def _shift_volume_args(volumes, shifts, mode, out, what):
         raise ValueError(f"{what}: a contiguous [N,D,H,W] stack is expected")
     if volumes.dtype != torch.float32:
         raise ValueError(f"{what}: a float32 stack is expected, got {volumes.dtype}")
-    if mode not in ("bilinear", "nearest"):
-        raise ValueError(f"{what}: mode is 'bilinear' or 'nearest', got {mode!r}")
+    ops._shift_mode(mode, what, plain=True)
     if shifts is not None and (not torch.is_tensor(shifts) or tuple(shifts.shape) != (int(volumes.shape[0]), 3) or shifts.dtype != torch.float32):
         raise ValueError(f"{what}: shifts is a float32 [{int(volumes.shape[0])}, 3] tensor")
     if out is not None and (out is volumes or (torch.is_tensor(out) and ops._overlap(out, volumes))):
@@ -1003,7 +1002,41 @@ def register_volumes(volumes, template=None, n_iter=1, max_shift=(2, 8, 8), subp
     return VolumeRegistration(out, shifts, peak, tmpl)
 
 
-class VolumeRegistrar:
+class _StreamingRegistrar:
+    """What the streaming registrars share: the checks of the template, ``mode`` and the estimate's arguments on a probe of no volumes,
+    the call on a chunk or on one [D,H,W] volume, and the accessors.  A subclass names its device lists (``_lists``: what its
+    estimate returns, in that order; the first is what moves the volumes) and states ``_check``, ``_estimate`` and ``_move``."""
+
+    def __init__(self, template, mode, fill, estimate_args):
+        what = type(self).__name__
+        ops._dev(template, "template")
+        if template.dim() != 3:
+            raise ValueError(f"{what}: the template is a float32 [D,H,W] tensor, got {tuple(template.shape)}")
+        ops._shift_mode(mode, what, plain=True)
+        self.template, self.mode, self.fill, self.estimate_args = template.contiguous(), mode, float(fill), dict(estimate_args)
+        a = self.estimate_args.get
+        probe = torch.empty((0,) + tuple(template.shape), dtype=torch.float32, device=template.device)
+        self._check(probe, (a("max_shift", (2, 8, 8)), a("taper"), a("smooth", 0.0), a("eps", 1e-5), a("chunk", 1), a("subpixel", True)), a, what)
+        for name in self._lists:
+            setattr(self, name, [])
+
+    def __call__(self, volumes, out=None):
+        single = torch.is_tensor(volumes) and volumes.dim() == 3
+        if single:
+            volumes = volumes.unsqueeze(0)
+        est = self._estimate(volumes)
+        moved = self._move(volumes, est[0], out)
+        for name, t in zip(self._lists, est):
+            getattr(self, name).append(t)
+        return moved[0] if single else moved
+
+    def _all(self, name, tail, dtype=torch.float32):
+        """The list ``name`` concatenated, or the empty [0, *tail] tensor of ``dtype`` where no volume has been seen."""
+        got = getattr(self, name)
+        return torch.cat(got) if got else torch.empty((0, *tail), dtype=dtype, device=self.template.device)
+
+
+class VolumeRegistrar(_StreamingRegistrar):
     """Registration of a series that is never resident, against a fixed float32 ``template`` [D,H,W]: ``reg(chunk)`` returns the
     registered [T',D,H,W] chunk (or volume, for one [D,H,W] volume) and appends the chunk's shifts and peaks to the device lists
     ``reg.shifts`` and ``reg.peak``; nothing is read back inside the call.  ``all_shifts()`` / ``all_peaks()`` concatenate them
@@ -1016,36 +1049,27 @@ class VolumeRegistrar:
         box = valid_box(reg.all_shifts(), template.shape)      # the one read-back, after the loop
     """
 
-    def __init__(self, template, mode="bilinear", fill=0.0, **estimate_args):
-        ops._dev(template, "template")
-        if template.dim() != 3:
-            raise ValueError(f"VolumeRegistrar: the template is a float32 [D,H,W] tensor, got {tuple(template.shape)}")
-        if mode not in ("bilinear", "nearest"):
-            raise ValueError(f"VolumeRegistrar: mode is 'bilinear' or 'nearest', got {mode!r}")
-        self.template, self.mode, self.fill, self.estimate_args = template.contiguous(), mode, float(fill), dict(estimate_args)
-        probe = torch.empty((0,) + tuple(template.shape), dtype=torch.float32, device=template.device)
-        _vol_reg_args(probe, self.template, self.estimate_args.get("max_shift", (2, 8, 8)), self.estimate_args.get("taper"),
-                      self.estimate_args.get("smooth", 0.0), self.estimate_args.get("eps", 1e-5), self.estimate_args.get("chunk", 1),
-                      self.estimate_args.get("subpixel", True), "VolumeRegistrar")
-        self.shifts, self.peak = [], []
+    _lists = ("shifts", "peak")
 
-    def __call__(self, volumes, out=None):
-        single = torch.is_tensor(volumes) and volumes.dim() == 3
-        if single:
-            volumes = volumes.unsqueeze(0)
-        shifts, peak = estimate_volume_shifts(volumes, self.template, **self.estimate_args)
-        moved = shift_volumes(volumes, shifts, mode=self.mode, fill=self.fill, out=out)
-        self.shifts.append(shifts)
-        self.peak.append(peak)
-        return moved[0] if single else moved
+    def __init__(self, template, mode="bilinear", fill=0.0, **estimate_args):
+        super().__init__(template, mode, fill, estimate_args)
+
+    def _check(self, probe, common, a, what):
+        _vol_reg_args(probe, self.template, *common, what)
+
+    def _estimate(self, volumes):
+        return estimate_volume_shifts(volumes, self.template, **self.estimate_args)
+
+    def _move(self, volumes, shifts, out):
+        return shift_volumes(volumes, shifts, mode=self.mode, fill=self.fill, out=out)
 
     def all_shifts(self):
         """float32 [N,3] on the device: the shifts of every volume seen so far."""
-        return torch.cat(self.shifts) if self.shifts else torch.empty((0, 3), dtype=torch.float32, device=self.template.device)
+        return self._all("shifts", (3,))
 
     def all_peaks(self):
         """float32 [N] on the device: the correlation peaks of every volume seen so far."""
-        return torch.cat(self.peak) if self.peak else torch.empty((0,), dtype=torch.float32, device=self.template.device)
+        return self._all("peak", ())
 
 
 def valid_box(shifts, shape):
@@ -1140,14 +1164,19 @@ def block_grid(shape, block=(32, 128, 128), grid=None, device=None):
     return bg
 
 
+def _grid_arg(grid, what, volumes=None):
+    """``grid`` is a ``BlockGrid``, made for the shape of ``volumes`` [N,D,H,W] where they are given."""
+    if not isinstance(grid, BlockGrid):
+        raise ValueError(f"{what}: grid is the BlockGrid of block_grid")
+    if volumes is not None and tuple(int(n) for n in volumes.shape[1:]) != grid.shape:
+        raise ValueError(f"{what}: the grid was made for volumes of {grid.shape}, got {tuple(volumes.shape[1:])}")
+
+
 def _block_reg_args(volumes, template, grid, max_shift, taper, smooth, eps, chunk, subpixel, what):
     """The checks of ``estimate_block_shifts`` that need no device: those of ``estimate_volume_shifts`` for the stack and the template,
     and max_shift and taper against the BLOCK's sides: ((mz, my, mx), (tz, ty, tx), chunk)."""
     _vol_reg_args(volumes, template, 0, 0, smooth, eps, chunk, subpixel, what)
-    if not isinstance(grid, BlockGrid):
-        raise ValueError(f"{what}: grid is the BlockGrid of block_grid")
-    if tuple(int(n) for n in volumes.shape[1:]) != grid.shape:
-        raise ValueError(f"{what}: the grid was made for volumes of {grid.shape}, got {tuple(volumes.shape[1:])}")
+    _grid_arg(grid, what, volumes)
     probe = torch.empty((0, *grid.block), dtype=torch.float32)
     try:
         return _reg_args(probe, None, max_shift, taper, smooth, eps, chunk, what, "volume")[:3]
@@ -1216,11 +1245,8 @@ def estimate_block_shifts(volumes, template, grid, max_shift=(2, 8, 8), taper=No
 
 
 def _field_arg(volumes, field, grid, what):
-    if not isinstance(grid, BlockGrid):
-        raise ValueError(f"{what}: grid is the BlockGrid of block_grid")
+    _grid_arg(grid, what, volumes)
     N = int(volumes.shape[0])
-    if tuple(int(n) for n in volumes.shape[1:]) != grid.shape:
-        raise ValueError(f"{what}: the grid was made for volumes of {grid.shape}, got {tuple(volumes.shape[1:])}")
     if not torch.is_tensor(field) or field.dtype != torch.float32 or tuple(field.shape) not in ((N, *grid.grid, 3), (N, grid.B, 3)):
         raise ValueError(f"{what}: field is a float32 {[N, *grid.grid, 3]} tensor")
     return field.reshape(N, grid.B, 3)
@@ -1263,7 +1289,7 @@ def register_volumes_piecewise(volumes, template=None, grid=None, block=(32, 128
     return PiecewiseRegistration(out, field, peak, inlier, shifts, tmpl)
 
 
-class PiecewiseVolumeRegistrar:
+class PiecewiseVolumeRegistrar(_StreamingRegistrar):
     """The streaming twin of ``VolumeRegistrar`` for piecewise-rigid motion: ``reg(chunk)`` returns the registered [T',D,H,W] chunk (or
     volume, for one [D,H,W] volume) against the fixed float32 ``template`` [D,H,W] on the ``BlockGrid`` ``grid`` and appends the
     chunk's field, peaks and inlier map to the device lists ``reg.field``, ``reg.peak`` and ``reg.inlier``; nothing is read back inside
@@ -1276,41 +1302,29 @@ class PiecewiseVolumeRegistrar:
         box = valid_box(reg.all_fields().reshape(-1, 3), template.shape)      # the one read-back, after the loop
     """
 
-    def __init__(self, template, grid, mode="bilinear", fill=0.0, **estimate_args):
-        what = "PiecewiseVolumeRegistrar"
-        ops._dev(template, "template")
-        if template.dim() != 3:
-            raise ValueError(f"{what}: the template is a float32 [D,H,W] tensor, got {tuple(template.shape)}")
-        if mode not in ("bilinear", "nearest"):
-            raise ValueError(f"{what}: mode is 'bilinear' or 'nearest', got {mode!r}")
-        self.template, self.grid, self.mode, self.fill, self.estimate_args = template.contiguous(), grid, mode, float(fill), dict(estimate_args)
-        a = self.estimate_args
-        probe = torch.empty((0,) + tuple(template.shape), dtype=torch.float32, device=template.device)
-        _block_reg_args(probe, self.template, grid, a.get("max_shift", (2, 8, 8)), a.get("taper"), a.get("smooth", 0.0), a.get("eps", 1e-5),
-                        a.get("chunk", 1), a.get("subpixel", True), what)
-        _min_peak_args(a.get("min_peak", 0.0), a.get("max_dev"), what)
-        self.field, self.peak, self.inlier = [], [], []
+    _lists = ("field", "peak", "inlier")
 
-    def __call__(self, volumes, out=None):
-        single = torch.is_tensor(volumes) and volumes.dim() == 3
-        if single:
-            volumes = volumes.unsqueeze(0)
-        field, peak, inlier = estimate_block_shifts(volumes, self.template, self.grid, **self.estimate_args)
-        moved = warp_volumes(volumes, field, self.grid, mode=self.mode, fill=self.fill, out=out)
-        self.field.append(field)
-        self.peak.append(peak)
-        self.inlier.append(inlier)
-        return moved[0] if single else moved
+    def __init__(self, template, grid, mode="bilinear", fill=0.0, **estimate_args):
+        self.grid = grid
+        super().__init__(template, mode, fill, estimate_args)
+
+    def _check(self, probe, common, a, what):
+        _block_reg_args(probe, self.template, self.grid, *common, what)
+        _min_peak_args(a("min_peak", 0.0), a("max_dev"), what)
+
+    def _estimate(self, volumes):
+        return estimate_block_shifts(volumes, self.template, self.grid, **self.estimate_args)
+
+    def _move(self, volumes, field, out):
+        return warp_volumes(volumes, field, self.grid, mode=self.mode, fill=self.fill, out=out)
 
     def all_fields(self):
         """float32 [N,gz,gy,gx,3] on the device: the field of every volume seen so far."""
-        if self.field:
-            return torch.cat(self.field)
-        return torch.empty((0, *self.grid.grid, 3), dtype=torch.float32, device=self.template.device)
+        return self._all("field", (*self.grid.grid, 3))
 
     def all_peaks(self):
         """float32 [N,gz,gy,gx] on the device: the correlation peak of every block seen so far."""
-        return torch.cat(self.peak) if self.peak else torch.empty((0, *self.grid.grid), dtype=torch.float32, device=self.template.device)
+        return self._all("peak", self.grid.grid)
 
 
 # ---------------------------------------------------------------------------------------------------- rigid registration with rotation
@@ -1357,8 +1371,7 @@ def fit_rigid_motion(shifts, peak, grid, center=None, min_peak=0.0, reject=1.0, 
     ``prior`` float64 [N,5]: the motion already applied to the volumes that were measured; the result is the total motion of the
     original.  Everything stays on the device."""
     what = "fit_rigid_motion"
-    if not isinstance(grid, BlockGrid):
-        raise ValueError(f"{what}: grid is the BlockGrid of block_grid")
+    _grid_arg(grid, what)
     min_peak, reject = _rigid_fit_args(min_peak, reject, what)
     center = _rigid_center(center, grid.shape, what)
     if not torch.is_tensor(shifts) or shifts.dim() < 3 or tuple(shifts.shape[1:]) not in ((*grid.grid, 3), (grid.B, 3)) or shifts.dtype != torch.float32:
@@ -1458,7 +1471,7 @@ def register_volumes_rigid(volumes, template=None, grid=None, block=(32, 128, 12
     return RigidRegistration(out, params, peak, inlier, shifts, tmpl)
 
 
-class RigidVolumeRegistrar:
+class RigidVolumeRegistrar(_StreamingRegistrar):
     """The streaming twin of ``PiecewiseVolumeRegistrar`` for rigid motion with rotation: ``reg(chunk)`` returns the registered
     [T',D,H,W] chunk (or volume, for one [D,H,W] volume) against the fixed float32 ``template`` [D,H,W] on the ``BlockGrid`` ``grid``
     and appends the chunk's parameters, peaks and inlier map to the device lists ``reg.params``, ``reg.peak`` and ``reg.inlier``;
@@ -1471,42 +1484,32 @@ class RigidVolumeRegistrar:
         box = valid_box(rigid_corner_shifts(reg.all_params(), template.shape), template.shape)      # the one read-back, after the loop
     """
 
-    def __init__(self, template, grid, mode="bilinear", fill=0.0, **estimate_args):
-        what = "RigidVolumeRegistrar"
-        ops._dev(template, "template")
-        if template.dim() != 3:
-            raise ValueError(f"{what}: the template is a float32 [D,H,W] tensor, got {tuple(template.shape)}")
-        if mode not in ("bilinear", "nearest"):
-            raise ValueError(f"{what}: mode is 'bilinear' or 'nearest', got {mode!r}")
-        self.template, self.grid, self.mode, self.fill, self.estimate_args = template.contiguous(), grid, mode, float(fill), dict(estimate_args)
-        a = self.estimate_args
-        probe = torch.empty((0,) + tuple(template.shape), dtype=torch.float32, device=template.device)
-        _block_reg_args(probe, self.template, grid, a.get("max_shift", (2, 8, 8)), a.get("taper"), a.get("smooth", 0.0), a.get("eps", 1e-5),
-                        a.get("chunk", 1), a.get("subpixel", True), what)
-        _rigid_fit_args(a.get("min_peak", 0.0), a.get("reject", 1.0), what)
-        self.center = _rigid_center(a.get("center"), grid.shape, what)
-        if int(a.get("n_refine", 2)) < 0:
-            raise ValueError(f"{what}: n_refine is not negative, got {a['n_refine']}")
-        self.params, self.peak, self.inlier = [], [], []
+    _lists = ("params", "peak", "inlier")
 
-    def __call__(self, volumes, out=None):
-        single = torch.is_tensor(volumes) and volumes.dim() == 3
-        if single:
-            volumes = volumes.unsqueeze(0)
-        params, peak, inlier, _ = estimate_rigid_motion(volumes, self.template, self.grid, **self.estimate_args)
-        moved = rigid_move_volumes(volumes, params, self.center, mode=self.mode, fill=self.fill, out=out)
-        self.params.append(params)
-        self.peak.append(peak)
-        self.inlier.append(inlier)
-        return moved[0] if single else moved
+    def __init__(self, template, grid, mode="bilinear", fill=0.0, **estimate_args):
+        self.grid = grid
+        super().__init__(template, mode, fill, estimate_args)
+
+    def _check(self, probe, common, a, what):
+        _block_reg_args(probe, self.template, self.grid, *common, what)
+        _rigid_fit_args(a("min_peak", 0.0), a("reject", 1.0), what)
+        self.center = _rigid_center(a("center"), self.grid.shape, what)
+        if int(a("n_refine", 2)) < 0:
+            raise ValueError(f"{what}: n_refine is not negative, got {a('n_refine')}")
+
+    def _estimate(self, volumes):
+        return estimate_rigid_motion(volumes, self.template, self.grid, **self.estimate_args)
+
+    def _move(self, volumes, params, out):
+        return rigid_move_volumes(volumes, params, self.center, mode=self.mode, fill=self.fill, out=out)
 
     def all_params(self):
         """float64 [N,5] on the device: the motion of every volume seen so far."""
-        return torch.cat(self.params) if self.params else torch.empty((0, 5), dtype=torch.float64, device=self.template.device)
+        return self._all("params", (5,), torch.float64)
 
     def all_peaks(self):
         """float32 [N,gz,gy,gx] on the device: the correlation peak of every block seen so far (last pass)."""
-        return torch.cat(self.peak) if self.peak else torch.empty((0, *self.grid.grid), dtype=torch.float32, device=self.template.device)
+        return self._all("peak", self.grid.grid)
 
 
 def rigid_angles(params):

@@ -249,8 +249,7 @@ def shift_frames(frames, shifts, mode="bilinear", fill=0.0, out=None):
     has the dtype of ``frames``; ``out`` must not share memory with ``frames``."""
     if not torch.is_tensor(frames) or frames.dim() != 3 or not frames.is_contiguous():
         raise ValueError("shift_frames: a contiguous [N,H,W] stack is expected")
-    if mode not in ("bilinear", "nearest"):
-        raise ValueError(f"shift_frames: mode is 'bilinear' or 'nearest', got {mode!r}")
+    ops._shift_mode(mode, "shift_frames", plain=True)
     if not torch.is_tensor(shifts) or tuple(shifts.shape) != (int(frames.shape[0]), 2) or shifts.dtype != torch.float32:
         raise ValueError(f"shift_frames: shifts is a float32 [{int(frames.shape[0])}, 2] tensor")
     if out is not None and (out is frames or (torch.is_tensor(out) and ops._overlap(out, frames))):
@@ -262,8 +261,7 @@ def _register_args(stack, n_iter, mode, out, what, item="frame"):
     """The checks the three ``register_*`` add to their estimator's."""
     if int(n_iter) < 1:
         raise ValueError(f"{what}: n_iter must be at least 1, got {n_iter}")
-    if mode not in ("bilinear", "nearest"):
-        raise ValueError(f"{what}: mode is 'bilinear' or 'nearest', got {mode!r}")
+    ops._shift_mode(mode, what, plain=True)
     if out is not None and (out is stack or (torch.is_tensor(out) and ops._overlap(out, stack))):
         raise ValueError(f"{what}: out must not alias {item}s")
     if int(stack.shape[0]) < 1:
@@ -399,8 +397,7 @@ def shift_views(frames, table, labels, mode="bilinear", fill=0.0, out=None):
     does).  An integer shift copies bits; ``out`` must not share memory with ``frames``."""
     if not torch.is_tensor(frames) or frames.dim() != 3 or not frames.is_contiguous():
         raise ValueError("shift_views: a contiguous [N,H,W] stack is expected")
-    if mode not in ("bilinear", "nearest"):
-        raise ValueError(f"shift_views: mode is 'bilinear' or 'nearest', got {mode!r}")
+    ops._shift_mode(mode, "shift_views", plain=True)
     N, H, W = (int(s) for s in frames.shape)
     if not torch.is_tensor(table) or table.dim() != 3 or int(table.shape[0]) != N or table.shape[2] != 2 or table.dtype != torch.float32:
         raise ValueError(f"shift_views: table is a float32 [{N}, L + 1, 2] tensor")

@@ -91,7 +91,7 @@ SELECT_FORM = {"auto": 0, "lds": 1, "stream": 2}                                
 SHIFT_MODE = {"bilinear": 0, "nearest": 1}                                      # cwfa_reg_shift's `mode`
 VIEW_MODEL = {"axial": 0, "free": 1}                                            # cwfa_reg_fit_views_f64's `model`
 REG_MAX_VIEWS = 254               # a label is a byte; label L is the rest of the frame
-REG_MAX_BLOCKS = 4096             # RB_MAX_BLOCKS of register_blocks_ops.hip: the blocks of a piecewise grid
+REG_MAX_BLOCKS = 4096             # REG_MAX_BLOCKS of register_internal.h: the blocks of a grid
 FOOTPRINT_SELECT_MAX = 1 << 15   # CWFA_FOOTPRINT_SELECT_MAX
 DEMIX_PAIR_BYTES = 48             # CWFA_DEMIX_PAIR_BYTES
 

@@ -4,7 +4,8 @@
 // trilinearly between the block centres and the volume is resampled once under a displacement that differs per voxel.  Here:
 //   rbwin_*    cuts and tapers the blocks of every volume in one read of each block
 //   rbfill_*   the clean-up of the shift table, one thread per node, float64, fixed order, no atomics
-//   rbwarp_*   the resampling: the node interpolation per voxel and step 7 of section 30.1 through rshift_pixels<1>
+//   rbwarp_*   the resampling: the node interpolation per voxel and step 7 of section 30.1 through rshift_pixels<1>, over the tile, the
+//              z split, the blend and the launch geometry of register_internal.h
 // The block origins are a HOST table, checked here and handed to the kernel in its arguments (the form of the centre table of
 // register_views_ops.hip): what a kernel indexes with is what was checked.  All offsets into a stack are 64-bit.  Built with
 // -ffp-contract=off; the counted operations use the __f*_rn intrinsics all the same.  tests/register_blocks_ref.py is the numpy
@@ -13,16 +14,11 @@
 #include "common.h"
 #include "register_internal.h"
 
-#define RB_MAX_BLOCKS 4096            // nodes of a grid: a volume's node table is then at most 48 KB
 #define RB_ORIGINS 256                // origins per axis that one launch carries in its arguments
 
-static inline bool rb_sizes_ok(int D, int H, int W) {
-    return D < (1 << 30) && H < (1 << 30) && W < (1 << 30) && (int64_t)D * H < ((int64_t)1 << 31) && (int64_t)D * H * W < ((int64_t)1 << 31);
-}
-
-// g_a >= 1 and gz gy gx <= RB_MAX_BLOCKS, without overflow
+// g_a >= 1 and gz gy gx <= REG_MAX_BLOCKS, without overflow
 static inline bool rb_grid_ok(int gz, int gy, int gx) {
-    return gz >= 1 && gy >= 1 && gx >= 1 && gz <= RB_MAX_BLOCKS && gy <= RB_MAX_BLOCKS && gx <= RB_MAX_BLOCKS && (int64_t)gz * gy * gx <= RB_MAX_BLOCKS;
+    return gz >= 1 && gy >= 1 && gx >= 1 && gz <= REG_MAX_BLOCKS && gy <= REG_MAX_BLOCKS && gx <= REG_MAX_BLOCKS && (int64_t)gz * gy * gx <= REG_MAX_BLOCKS;
 }
 
 // ------------------------------------------------------------------------------------------------ the cut and the taper
@@ -72,10 +68,9 @@ extern "C" int cwfa_reg_window_blocks3d_f32(const float* x, int N, int D, int H,
                                             void* stream) {
     const char* fn = "cwfa_reg_window_blocks3d_f32";
     CWFA_REQUIRE(x && origins && wz && wy && wx && out, CWFA_E_INVAL, "%s: null pointer", fn);
-    CWFA_REQUIRE(N >= 0 && D >= 0 && H >= 0 && W >= 0, CWFA_E_SHAPE, "%s: negative size", fn);
-    CWFA_REQUIRE(rb_sizes_ok(D, H, W), CWFA_E_SHAPE, "%s: a volume of %d x %d x %d is too large", fn, D, H, W);
+    REG3_REQUIRE_SIZES(fn, N, D, H, W);
     CWFA_REQUIRE(rb_grid_ok(gz, gy, gx), CWFA_E_SHAPE, "%s: a grid of %d x %d x %d: every axis at least 1, at most %d blocks", fn, gz, gy, gx,
-                 RB_MAX_BLOCKS);
+                 REG_MAX_BLOCKS);
     CWFA_REQUIRE(bz >= 1 && by >= 1 && bx >= 1 && bz <= D && by <= H && bx <= W, CWFA_E_SHAPE,
                  "%s: a block of %d x %d x %d does not fit the %d x %d x %d volume", fn, bz, by, bx, D, H, W);
     const int g[3] = {gz, gy, gx}, b[3] = {bz, by, bx}, S[3] = {D, H, W};
@@ -105,7 +100,7 @@ extern "C" int cwfa_reg_window_blocks3d_f32(const float* x, int N, int D, int H,
                     og.o[1][i] = i < cy ? origins[gz + fy + i] : 0;
                     og.o[2][i] = i < cx ? origins[gz + gy + fx + i] : 0;
                 }
-                const int64_t nb = (int64_t)cz * cy * cx;             // <= RB_MAX_BLOCKS
+                const int64_t nb = (int64_t)cz * cy * cx;             // <= REG_MAX_BLOCKS
                 const dim3 grid((unsigned)nx, (unsigned)nb, reg_grid_y(nx * nb, N, 65536));
                 if (v4)
                     hipLaunchKernelGGL((rbwin_kernel<4>), grid, dim3(256), 0, st, x, N, H, W, vol_stride, og, cz, cy, cx, fz, fy, fx, gy, gx, B, bz, by, bx,
@@ -180,7 +175,7 @@ extern "C" int cwfa_reg_field_fill(const float* shifts, const float* peak, const
     CWFA_REQUIRE(shifts && peak && base && field && inlier, CWFA_E_INVAL, "%s: null pointer", fn);
     CWFA_REQUIRE(N >= 0, CWFA_E_SHAPE, "%s: negative size", fn);
     CWFA_REQUIRE(rb_grid_ok(gz, gy, gx), CWFA_E_SHAPE, "%s: a grid of %d x %d x %d: every axis at least 1, at most %d blocks", fn, gz, gy, gx,
-                 RB_MAX_BLOCKS);
+                 REG_MAX_BLOCKS);
     CWFA_REQUIRE(min_peak == min_peak, CWFA_E_INVAL, "%s: min_peak is NaN", fn);
     RbDev md = {{0.0, 0.0, 0.0}};
     if (max_dev)
@@ -204,16 +199,15 @@ extern "C" int cwfa_reg_field_fill(const float* shifts, const float* peak, const
 // ------------------------------------------------------------------------------------------------ the warp
 // out[n,z,y,x] = step 7 of section 30.1 under the voxel's own (dz, dy, dx), the trilinear interpolation of the node table
 // field[n] [gz, gy, gx, 3] with the axis tables (idx, t): lerp(a, b, t) = a where t == 0, else fl(a + fl(t * fl(b - a))), along x first
-// (four times), then y (twice), then z; node i + 1 is not read where t == 0.  The resampling of a voxel is rshift_pixels<1>
-// (register_internal.h) on planes z + floor(dz) and the next one, blended as rshift3_kernel (register3d_ops.hip) blends them.
+// (four times), then y (twice), then z; node i + 1 is not read where t == 0.  The resampling of a voxel is rshift_pixels<1> on planes
+// z + floor(dz) and the next one under the z split and the blend of register_internal.h, whose tile and launch geometry the kernel
+// takes too.
 //
-// A thread owns V consecutive voxels of a row and a segment of at most RBWARP_ZSEG planes, and walks z.  The x and y lerps of a node
-// plane do not depend on z, so a thread keeps them for node planes iz and iz + 1 (2 x 3 V registers) and forms them again only where
-// idxz steps; per output plane only the z lerp and the resampling are left.  The node table (at most 48 KB a volume) is read through
-// the caches: the 8 nodes around a thread's voxels are shared by the whole workgroup almost everywhere.  Table indices are clamped to
-// the grid before they index anything.  The volumes are walked inside the kernel (blockIdx.y, + gridDim.y, ..).
-#define RBWARP_ZSEG 16
-
+// The vector changes with z, so no resampled plane can be carried and the kernel walks its segment itself.  The x and y lerps of a
+// node plane do not depend on z, so a thread keeps them for node planes iz and iz + 1 (2 x 3 V registers) and forms them again only
+// where idxz steps; per output plane only the z lerp and the resampling are left.  The node table (at most 48 KB a volume) is read
+// through the caches: the 8 nodes around a thread's voxels are shared by the whole workgroup almost everywhere.  Table indices are
+// clamped to the grid before they index anything.
 __device__ __forceinline__ float rb_lerp(float a, float b, float t) { return t == 0.f ? a : __fadd_rn(a, __fmul_rn(t, __fsub_rn(b, a))); }
 
 // the (y, x) interpolation of node plane nz at the V voxels: Y[j][c]
@@ -251,12 +245,9 @@ __global__ __launch_bounds__(256) void rbwarp_kernel(const float* __restrict__ i
                                                      const float* __restrict__ txt, int nearest, float fill, int nseg, int zseg,
                                                      float* __restrict__ out) {
     typedef float fvec __attribute__((ext_vector_type(V)));
-    const int Wv = W / V;                                             // V > 1: W is a multiple of V
-    const int seg = (int)(blockIdx.x % (unsigned)nseg);
-    const int64_t q = (int64_t)(blockIdx.x / (unsigned)nseg) * blockDim.x + threadIdx.x;
-    if (q >= (int64_t)H * Wv) return;
-    const int y = (int)(q / Wv), x0 = (int)(q - (int64_t)y * Wv) * V;
-    const int z0 = seg * zseg, z1 = z0 + zseg < D ? z0 + zseg : D;
+    reg3_tile t;
+    if (!reg3_tile_of<V>(D, H, W, nseg, zseg, t)) return;
+    const int y = t.y, x0 = t.x0;
     const int64_t HW = (int64_t)H * W;
     // the tables' entries of this thread, clamped to the grid; where idx is the last node, t is 0 by construction and is made so
     int iy = idxy[y];
@@ -274,11 +265,11 @@ __global__ __launch_bounds__(256) void rbwarp_kernel(const float* __restrict__ i
     for (int n = blockIdx.y; n < N; n += gridDim.y) {
         const float* fn = field + (int64_t)n * B3;
         const float* vol = in + (int64_t)n * vs;
-        float* o = out + (int64_t)n * D * HW + (int64_t)y * W + x0;
+        float* o = out + (int64_t)n * D * HW + t.p;
         float Y0[V][3], Y1[V][3];
         int cur = -1;
         bool have1 = false;
-        for (int z = z0; z < z1; ++z) {
+        for (int z = t.z0; z < t.z1; ++z) {
             int iz = idxz[z];
             iz = iz < 0 ? 0 : (iz > gz - 1 ? gz - 1 : iz);
             const float tz = iz == gz - 1 ? 0.f : tzt[z];
@@ -293,23 +284,18 @@ __global__ __launch_bounds__(256) void rbwarp_kernel(const float* __restrict__ i
             fvec r;
 #pragma unroll
             for (int j = 0; j < V; ++j) {
-                float dz = tz == 0.f ? Y0[j][0] : rb_lerp(Y0[j][0], Y1[j][0], tz);
+                const float dz = tz == 0.f ? Y0[j][0] : rb_lerp(Y0[j][0], Y1[j][0], tz);
                 const float dy = tz == 0.f ? Y0[j][1] : rb_lerp(Y0[j][1], Y1[j][1], tz);
                 const float dx = tz == 0.f ? Y0[j][2] : rb_lerp(Y0[j][2], Y1[j][2], tz);
                 if (!(fabsf(dz) < INFINITY) || !(fabsf(dy) < INFINITY) || !(fabsf(dx) < INFINITY)) {
                     r[j] = fill;
                     continue;
                 }
-                if (nearest) dz = rintf(dz);                          // rshift_pixels rounds (dy, dx) itself
-                const float izf = floorf(dz);
-                const float fz = __fsub_rn(dz, izf);
-                const int sz = (int)fminf(fmaxf(izf, -(float)(D + 1)), (float)(D + 1));   // beyond: every plane is outside whatever the value
-                const float w0 = __fsub_rn(1.f, fz), w1 = fz;
-                const bool use0 = w0 != 0.f, use1 = w1 != 0.f;        // never both false: fz == 0 gives w0 == 1
-                float t0 = 0.f, t1 = 0.f;
-                if (use0) t0 = __fmul_rn(w0, rbwarp_tap(vol, D, H, W, z + sz, y, x0 + j, dy, dx, nearest, fill));
-                if (use1) t1 = __fmul_rn(w1, rbwarp_tap(vol, D, H, W, z + sz + 1, y, x0 + j, dy, dx, nearest, fill));
-                r[j] = use0 ? (use1 ? __fadd_rn(t0, t1) : t0) : t1;
+                const reg3_zsplit s = reg3_zsplit_of(dz, nearest, D);
+                float p0 = 0.f, p1 = 0.f;
+                if (s.use0) p0 = rbwarp_tap(vol, D, H, W, z + s.iz, y, x0 + j, dy, dx, nearest, fill);
+                if (s.use1) p1 = rbwarp_tap(vol, D, H, W, z + s.iz + 1, y, x0 + j, dy, dx, nearest, fill);
+                r[j] = reg3_blend(s, p0, p1);
             }
             *reinterpret_cast<fvec*>(o + (int64_t)z * HW) = r;
         }
@@ -321,31 +307,17 @@ extern "C" int cwfa_reg_warp3d_f32(const float* in, int N, int D, int H, int W, 
                                    int mode, float fill, float* out, void* stream) {
     const char* fn = "cwfa_reg_warp3d_f32";
     CWFA_REQUIRE(in && field && idxz && tz && idxy && ty && idxx && tx && out, CWFA_E_INVAL, "%s: null pointer", fn);
-    CWFA_REQUIRE(mode == 0 || mode == 1, CWFA_E_INVAL, "%s: mode is 0 (bilinear) or 1 (nearest), got %d", fn, mode);
-    CWFA_REQUIRE(N >= 0 && D >= 0 && H >= 0 && W >= 0, CWFA_E_SHAPE, "%s: negative size", fn);
-    CWFA_REQUIRE(rb_sizes_ok(D, H, W), CWFA_E_SHAPE, "%s: a volume of %d x %d x %d is too large", fn, D, H, W);
+    REG3_REQUIRE_MODE(fn, mode);
+    REG3_REQUIRE_SIZES(fn, N, D, H, W);
     CWFA_REQUIRE(rb_grid_ok(gz, gy, gx), CWFA_E_SHAPE, "%s: a grid of %d x %d x %d: every axis at least 1, at most %d blocks", fn, gz, gy, gx,
-                 RB_MAX_BLOCKS);
+                 REG_MAX_BLOCKS);
     CWFA_REQUIRE(((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(field) | reinterpret_cast<uintptr_t>(idxz) | reinterpret_cast<uintptr_t>(tz) |
                    reinterpret_cast<uintptr_t>(idxy) | reinterpret_cast<uintptr_t>(ty) | reinterpret_cast<uintptr_t>(idxx) | reinterpret_cast<uintptr_t>(tx) |
                    reinterpret_cast<uintptr_t>(out)) & 3u) == 0,
                  CWFA_E_ALIGN, "%s: the volumes, the field and the tables must be 4-byte aligned", fn);
-    CWFA_REQUIRE(out != in, CWFA_E_INVAL, "%s: out must not alias the stack", fn);
-    if (N == 0 || D == 0 || H == 0 || W == 0) return CWFA_OK;
-    const int64_t HW = (int64_t)H * W;
-    CWFA_REQUIRE(vol_stride >= (int64_t)D * HW, CWFA_E_INVAL, "%s: volume stride smaller than a volume", fn);
-    // 16-byte stores where W and out's base allow (every row of every volume then starts on 16 bytes); the loads take any alignment
-    const bool v4 = (W & 3) == 0 && cwfa_aligned16(out);
-    const int nseg = (D + RBWARP_ZSEG - 1) / RBWARP_ZSEG, zseg = (D + nseg - 1) / nseg;
-    const int64_t gridx = (((v4 ? HW >> 2 : HW) + 255) / 256) * nseg;
-    const dim3 grid((unsigned)gridx, reg_grid_y(gridx, N, 65536));
-    hipStream_t st = (hipStream_t)stream;
-    if (v4)
-        hipLaunchKernelGGL((rbwarp_kernel<4>), grid, dim3(256), 0, st, in, N, D, H, W, vol_stride, field, gz, gy, gx, idxz, tz, idxy, ty, idxx, tx, mode,
-                           fill, nseg, zseg, out);
-    else
-        hipLaunchKernelGGL((rbwarp_kernel<1>), grid, dim3(256), 0, st, in, N, D, H, W, vol_stride, field, gz, gy, gx, idxz, tz, idxy, ty, idxx, tx, mode,
-                           fill, nseg, zseg, out);
-    CWFA_LAUNCH_CHECK("cwfa_reg_warp3d_f32");
+    REG3_REQUIRE_STACK(fn, in, out, N, D, H, W, vol_stride);
+    REG3_LAUNCH(rbwarp_kernel, N, D, H, W, out, (hipStream_t)stream, in, N, D, H, W, vol_stride, field, gz, gy, gx, idxz, tz, idxy, ty, idxx, tx, mode, fill);
+    CWFA_LAUNCH_CHECK(fn);
     return CWFA_OK;
 }
+

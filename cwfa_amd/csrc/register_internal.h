@@ -1,10 +1,15 @@
-// What the registration kernels share (register_ops.hip: frames; register_views_ops.hip: lenslet views; register3d_ops.hip: volumes; register_blocks_ops.hip: blocks of volumes).
+// What the registration kernels share (register_ops.hip: frames; register_views_ops.hip: lenslet views; register3d_ops.hip: volumes;
+// register_blocks_ops.hip: blocks of volumes; register_rigid_ops.hip: volumes that turn).
 // One definition of each, so that a frame is a volume of one plane by construction and not by a copy kept in step:
 //   the grid rule of the kernels whose threads walk the items                                         reg_grid_y
 //   the edge taper over [N, D, H, W], D = 1 and no wz for frames                                      reg_window_kernel
 //   the order of the integer peak's keys and the float64 parabola                                     reg_peak_key, reg_parabola
 //   the arithmetic of step 7 of DESIGN.md section 26.1 for V consecutive pixels of a row              rshift_pixels
 //   the store form of the two 2-D resampling entry points                                             reg_store_width
+//   the size rule of a volume and the block limit of a grid                                           reg3_sizes_ok, REG_MAX_BLOCKS
+//   the checks and the launch geometry of the three entry points that resample volumes                REG3_REQUIRE_*, REG3_LAUNCH
+//   a thread's voxels and z segment, the split of dz, the blend of two planes, the segment fill       reg3_tile_of, reg3_zsplit_of, ..
+//   the walk over a segment that carries a resampled plane from one output plane to the next          reg3_walk
 #pragma once
 #include <math.h>
 #include <type_traits>
@@ -187,3 +192,133 @@ static inline int reg_store_width(int dtype, int W, const void* out) {
         else if (dtype) hipLaunchKernelGGL((KERNEL<1, true>), grid_, dim3(256), 0, st, __VA_ARGS__);                       \
         else hipLaunchKernelGGL((KERNEL<1, false>), grid_, dim3(256), 0, st, __VA_ARGS__);                                 \
     } while (0)
+
+// ------------------------------------------------------------------------------------------------ the resampling of volumes
+// What rshift3_kernel (register3d_ops.hip), rbwarp_kernel (register_blocks_ops.hip) and rrigid3_kernel (register_rigid_ops.hip) are
+// made of.  out[n,z] = fl(w0 * p_0) + fl(w1 * p_1) with iz = floorf(dz), fz = fl(dz - iz), (w0, w1) = (fl(1 - fz), fz) and p_r the
+// plane z + iz + r of volume n resampled in-plane by rshift_pixels (the bits of cwfa_reg_shift); a plane outside the volume holds
+// `fill`; a plane of weight exactly 0 is neither read nor added (w0 == 0 happens: a tiny negative dz has fl(dz - iz) == 1); a
+// non-finite component fills.
+//
+// A thread owns V consecutive voxels of a row and a segment of at most REG3_ZSEG planes, and walks z.  The segments of one (y, x) band
+// have consecutive block indices, so they are in flight together and the plane two of them share is still in a cache.  The volumes
+// are walked inside the kernels (blockIdx.y, + gridDim.y, ..).
+#define REG_MAX_BLOCKS 4096           // blocks (nodes) of a grid: a volume's node table is then at most 48 KB
+#define REG3_ZSEG 16
+
+// what every entry point asks of a volume: sides that stay ints with a margin (z + iz + 1 with |iz| <= D + 1 stays an int, and so
+// along y and x in rshift_pixels), fewer than 2^31 voxels
+static inline bool reg3_sizes_ok(int D, int H, int W) {
+    return D < (1 << 30) && H < (1 << 30) && W < (1 << 30) && (int64_t)D * H < ((int64_t)1 << 31) && (int64_t)D * H * W < ((int64_t)1 << 31);
+}
+
+// The checks the three resampling entry points share, in the order they make them (an entry point puts its own in between); `fn` is
+// its name.  The windows' entry points make the one of the sizes too.  REG3_REQUIRE_STACK returns CWFA_OK for an empty stack.
+#define REG3_REQUIRE_MODE(fn, mode) CWFA_REQUIRE((mode) == 0 || (mode) == 1, CWFA_E_INVAL, "%s: mode is 0 (bilinear) or 1 (nearest), got %d", fn, mode)
+#define REG3_REQUIRE_SIZES(fn, N, D, H, W)                                                                                  \
+    do {                                                                                                                   \
+        CWFA_REQUIRE((N) >= 0 && (D) >= 0 && (H) >= 0 && (W) >= 0, CWFA_E_SHAPE, "%s: negative size", fn);                 \
+        CWFA_REQUIRE(reg3_sizes_ok(D, H, W), CWFA_E_SHAPE, "%s: a volume of %d x %d x %d is too large", fn, D, H, W);      \
+    } while (0)
+#define REG3_REQUIRE_STACK(fn, in, out, N, D, H, W, vol_stride)                                                             \
+    do {                                                                                                                   \
+        CWFA_REQUIRE((out) != (in), CWFA_E_INVAL, "%s: out must not alias the stack", fn);                                 \
+        if ((N) == 0 || (D) == 0 || (H) == 0 || (W) == 0) return CWFA_OK;                                                  \
+        CWFA_REQUIRE((vol_stride) >= (int64_t)(D) * (H) * (W), CWFA_E_INVAL, "%s: volume stride smaller than a volume", fn); \
+    } while (0)
+
+// Launches KERNEL<V>(.., nseg, zseg, out): 16-byte stores where W and out's base allow (every row of every volume then starts on 16
+// bytes; the loads take any alignment), even segments (96 planes are 6 x 16), ceil(H W / V / 256) * nseg <= D H W / 256 + D + nseg
+// < 2^31 blocks along x by reg_grid_y blocks.
+#define REG3_LAUNCH(KERNEL, N, D, H, W, out, st, ...)                                                                       \
+    do {                                                                                                                   \
+        const bool v4_ = ((W) & 3) == 0 && cwfa_aligned16(out);                                                            \
+        const int nseg_ = ((D) + REG3_ZSEG - 1) / REG3_ZSEG, zseg_ = ((D) + nseg_ - 1) / nseg_;                            \
+        const int64_t gx_ = ((((int64_t)(H) * (W) >> (v4_ ? 2 : 0)) + 255) / 256) * nseg_;                                 \
+        const dim3 grid_((unsigned)gx_, reg_grid_y(gx_, N, 65536));                                                        \
+        if (v4_) hipLaunchKernelGGL((KERNEL<4>), grid_, dim3(256), 0, st, __VA_ARGS__, nseg_, zseg_, out);                 \
+        else hipLaunchKernelGGL((KERNEL<1>), grid_, dim3(256), 0, st, __VA_ARGS__, nseg_, zseg_, out);                     \
+    } while (0)
+
+// a thread's voxels (y, x0 .. x0 + V - 1), its offset p into a plane and its planes z0 .. z1 - 1; false for a thread past the plane
+struct reg3_tile {
+    int y, x0, z0, z1;
+    int64_t p;
+};
+template <int V>
+__device__ __forceinline__ bool reg3_tile_of(int D, int H, int W, int nseg, int zseg, reg3_tile& t) {
+    const int Wv = W / V;                                             // V > 1: W is a multiple of V
+    const int seg = (int)(blockIdx.x % (unsigned)nseg);
+    const int64_t q = (int64_t)(blockIdx.x / (unsigned)nseg) * blockDim.x + threadIdx.x;
+    if (q >= (int64_t)H * Wv) return false;
+    t.y = (int)(q / Wv), t.x0 = (int)(q - (int64_t)t.y * Wv) * V;
+    t.z0 = seg * zseg, t.z1 = t.z0 + zseg < D ? t.z0 + zseg : D;
+    t.p = (int64_t)t.y * W + t.x0;
+    return true;
+}
+
+// the split of a finite dz: plane offset iz (beyond +-(D + 1) every plane is outside whatever the value: clamped before the
+// conversion to int) and the weights of planes z + iz and z + iz + 1; use0 and use1 are never both false: fz == 0 gives w0 == 1
+struct reg3_zsplit {
+    int iz;
+    float w0, w1;
+    bool use0, use1;
+};
+__device__ __forceinline__ reg3_zsplit reg3_zsplit_of(float dz, int nearest, int D) {
+    if (nearest) dz = rintf(dz);                                      // rshift_pixels rounds (dy, dx) itself
+    const float izf = floorf(dz);
+    const float fz = __fsub_rn(dz, izf);
+    reg3_zsplit s;
+    s.iz = (int)fminf(fmaxf(izf, -(float)(D + 1)), (float)(D + 1));
+    s.w0 = __fsub_rn(1.f, fz), s.w1 = fz;
+    s.use0 = s.w0 != 0.f, s.use1 = s.w1 != 0.f;
+    return s;
+}
+// the blend of the two resampled planes; the value of an unused one is not looked at
+__device__ __forceinline__ float reg3_blend(const reg3_zsplit& s, float p0, float p1) {
+    const float t0 = __fmul_rn(s.w0, p0), t1 = __fmul_rn(s.w1, p1);
+    return s.use0 ? (s.use1 ? __fadd_rn(t0, t1) : t0) : t1;
+}
+
+// `fill` over a thread's segment: the volume's parameters are not finite.  o: the thread's voxels in plane 0 of the output volume
+template <int V>
+__device__ __forceinline__ void reg3_fill(float* __restrict__ o, int64_t HW, int z0, int z1, float fill) {
+    typedef float fvec __attribute__((ext_vector_type(V)));
+    fvec r;
+#pragma unroll
+    for (int j = 0; j < V; ++j) r[j] = fill;
+    for (int z = z0; z < z1; ++z) *reinterpret_cast<fvec*>(o + (int64_t)z * HW) = r;
+}
+
+// The walk over z0 .. z1 - 1 for a displacement that does not change with z.  plane(zz, acc) resamples source plane zz, inside the
+// volume, for the thread's V voxels; voxel j is `fill` where bad[j].  p_1 of plane z IS p_0 of plane z + 1 (the same function of the
+// same source plane), so it is kept in registers and a source plane is read once per segment -- (ZSEG + 1) / ZSEG of the stack in
+// all, whichever XCD's L2 a workgroup lands on.
+template <int V, class Plane>
+__device__ __forceinline__ void reg3_walk(float* __restrict__ o, int D, int64_t HW, int z0, int z1, const reg3_zsplit s, const bool (&bad)[V], float fill,
+                                          Plane plane) {
+    typedef float fvec __attribute__((ext_vector_type(V)));
+    auto at = [&](int zz, float(&acc)[V]) {
+        if (zz < 0 || zz >= D) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) acc[j] = fill;
+        } else {
+            plane(zz, acc);
+        }
+    };
+    float a[V] = {}, b[V] = {};                                       // the unused one of the two stays 0 and is not read
+    if (s.use0) at(z0 + s.iz, a);
+    for (int z = z0; z < z1; ++z) {
+        if (s.use1) at(z + s.iz + 1, b);
+        fvec r;
+#pragma unroll
+        for (int j = 0; j < V; ++j) r[j] = bad[j] ? fill : reg3_blend(s, a[j], b[j]);
+        *reinterpret_cast<fvec*>(o + (int64_t)z * HW) = r;
+        if (s.use0 && s.use1) {                                       // plane z + iz + 1 is the next step's first plane
+#pragma unroll
+            for (int j = 0; j < V; ++j) a[j] = b[j];
+        } else if (s.use0 && z + 1 < z1) {
+            at(z + 1 + s.iz, a);
+        }
+    }
+}

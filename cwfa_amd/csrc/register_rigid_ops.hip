@@ -2,19 +2,14 @@
 // of section 32 is fitted by "rotation about z + 3-D shift" and the volume is resampled once under that motion.  Here:
 //   rrfit_*    the rigid fit of a block-shift table, float64, one thread per volume, fixed order, no atomics, and its composition
 //              with the motion already applied to the measured volumes
-//   rrigid3_*  the resampling: the in-plane displacement of a voxel from (c - 1, s) and step 7 of section 30.1 through rshift_pixels<1>
+//   rrigid3_*  the resampling: the in-plane displacement of a voxel from (c - 1, s), then the z walk of register_internal.h over
+//              rshift_pixels<1>
 // No trigonometric function is evaluated: (c, s) come out of the fit by a square root and two divisions, and c - 1 is always formed
 // as -(s s) / (1 + c).  All offsets into a stack are 64-bit.  Built with -ffp-contract=off; the counted fp32 operations use the
 // __f*_rn intrinsics all the same.  tests/register_rigid_ref.py is the numpy restatement.
 #include <math.h>
 #include "common.h"
 #include "register_internal.h"
-
-#define RR_MAX_BLOCKS 4096            // RB_MAX_BLOCKS of register_blocks_ops.hip: the blocks of a grid
-
-static inline bool rr_sizes_ok(int D, int H, int W) {
-    return D < (1 << 30) && H < (1 << 30) && W < (1 << 30) && (int64_t)D * H < ((int64_t)1 << 31) && (int64_t)D * H * W < ((int64_t)1 << 31);
-}
 
 // ------------------------------------------------------------------------------------------------ the fit
 // One thread per volume, everything float64, every sum over the blocks in order b = 0 .. B - 1 from 0.0 (a block of weight 0 is
@@ -113,7 +108,7 @@ extern "C" int cwfa_reg_fit_rigid_f64(const float* shifts, const float* peak, co
     const char* fn = "cwfa_reg_fit_rigid_f64";
     CWFA_REQUIRE(shifts && peak && arms && params && inlier, CWFA_E_INVAL, "%s: null pointer", fn);
     CWFA_REQUIRE(N >= 0, CWFA_E_SHAPE, "%s: negative size", fn);
-    CWFA_REQUIRE(B >= 1 && B <= RR_MAX_BLOCKS, CWFA_E_SHAPE, "%s: 1 to %d blocks are expected, got %d", fn, RR_MAX_BLOCKS, B);
+    CWFA_REQUIRE(B >= 1 && B <= REG_MAX_BLOCKS, CWFA_E_SHAPE, "%s: 1 to %d blocks are expected, got %d", fn, REG_MAX_BLOCKS, B);
     CWFA_REQUIRE(min_peak >= 0.0 && reject >= 0.0, CWFA_E_INVAL, "%s: min_peak and reject are not negative and not NaN", fn);
     CWFA_REQUIRE(((reinterpret_cast<uintptr_t>(arms) | reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(prior)) & 7u) == 0 &&
                      ((reinterpret_cast<uintptr_t>(shifts) | reinterpret_cast<uintptr_t>(peak)) & 3u) == 0,
@@ -130,94 +125,50 @@ extern "C" int cwfa_reg_fit_rigid_f64(const float* shifts, const float* peak, co
 // Per volume (dzf, dyf, dxf, sf) = the fp32 roundings of (dz, dy, dx, s) and cm1f = (float)(-(s s) / (1 + c)), formed in float64; per
 // voxel py = (float)y - cy, px = (float)x - cx,
 //   vy = fl(dyf + fl(fl(cm1f py) - fl(sf px))),  vx = fl(dxf + fl(fl(sf py) + fl(cm1f px)))
-// and out[n,z,y,x] = step 7 of section 30.1 under (dzf, vy, vx): rshift_pixels<1> (register_internal.h) on planes z + floor(dzf) and the
-// next one, blended as rshift3_kernel (register3d_ops.hip) blends them.  A parameter that is not finite fills the volume.
+// and out[n,z,y,x] = step 7 of section 30.1 under (dzf, vy, vx).  A parameter that is not finite fills the volume.
 //
 // (vy, vx) does not depend on z, nor does anything rshift_pixels derives from it -- the floors, the four weights, the tap offsets,
-// the inside / outside decisions.  A thread owns V consecutive voxels of a row and a segment of at most RRIGID3_ZSEG planes; it forms
-// the V vectors once per volume and walks z, the plane resampling being the same function of the same arguments on every plane,
-// with p_1 of plane z kept as p_0 of plane z + 1.  The volumes are walked inside the kernel (blockIdx.y, + gridDim.y, ..).
-#define RRIGID3_ZSEG 16
-
-template <int V>
-__device__ __forceinline__ void rrigid3_plane(const float* __restrict__ vol, int D, int H, int W, int zz, int y, int x0, const float (&vy)[V],
-                                              const float (&vx)[V], int nearest, float fill, float (&acc)[V]) {
-    if (zz < 0 || zz >= D) {
-#pragma unroll
-        for (int j = 0; j < V; ++j) acc[j] = fill;
-    } else {
-        const float* plane = vol + (int64_t)zz * H * W;
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            float a[1];
-            rshift_pixels<1, float>(plane, H, W, y, x0 + j, vy[j], vx[j], nearest, fill, a);
-            acc[j] = a[0];
-        }
-    }
-}
-
+// the inside / outside decisions.  So this is the walk of register_internal.h: a thread forms its V vectors once per volume, a source
+// plane is resampled by rshift_pixels<1> per voxel under (vy[j], vx[j]), and a voxel whose vector overflowed is masked (it fills, as
+// in rbwarp_kernel).
 template <int V>
 __global__ __launch_bounds__(256) void rrigid3_kernel(const float* __restrict__ in, int N, int D, int H, int W, int64_t vs, const double* __restrict__ params,
                                                       float cy, float cx, int nearest, float fill, int nseg, int zseg, float* __restrict__ out) {
-    typedef float fvec __attribute__((ext_vector_type(V)));
-    const int Wv = W / V;                                             // V > 1: W is a multiple of V
-    const int seg = (int)(blockIdx.x % (unsigned)nseg);
-    const int64_t q = (int64_t)(blockIdx.x / (unsigned)nseg) * blockDim.x + threadIdx.x;
-    if (q >= (int64_t)H * Wv) return;
-    const int y = (int)(q / Wv), x0 = (int)(q - (int64_t)y * Wv) * V;
-    const int z0 = seg * zseg, z1 = z0 + zseg < D ? z0 + zseg : D;
+    reg3_tile t;
+    if (!reg3_tile_of<V>(D, H, W, nseg, zseg, t)) return;
     const int64_t HW = (int64_t)H * W;
-    const float py = __fsub_rn((float)y, cy);
+    const float py = __fsub_rn((float)t.y, cy);
     float px[V];
 #pragma unroll
-    for (int j = 0; j < V; ++j) px[j] = __fsub_rn((float)(x0 + j), cx);
+    for (int j = 0; j < V; ++j) px[j] = __fsub_rn((float)(t.x0 + j), cx);
     for (int n = blockIdx.y; n < N; n += gridDim.y) {
         const double* p = params + 5 * (int64_t)n;
         const double c = p[3], s = p[4];
-        float dz = (float)p[0];
-        const float dyf = (float)p[1], dxf = (float)p[2], sf = (float)s, cm1f = (float)(-(s * s) / (1.0 + c));
+        const float dz = (float)p[0], dyf = (float)p[1], dxf = (float)p[2], sf = (float)s, cm1f = (float)(-(s * s) / (1.0 + c));
         const float* vol = in + (int64_t)n * vs;
-        float* o = out + (int64_t)n * D * HW + (int64_t)y * W + x0;
+        float* o = out + (int64_t)n * D * HW + t.p;
         if (!(fabs(c) < (double)INFINITY) || !(fabsf(dz) < INFINITY) || !(fabsf(dyf) < INFINITY) || !(fabsf(dxf) < INFINITY) || !(fabsf(sf) < INFINITY) ||
             !(fabsf(cm1f) < INFINITY)) {
-            fvec r;
-#pragma unroll
-            for (int j = 0; j < V; ++j) r[j] = fill;
-            for (int z = z0; z < z1; ++z) *reinterpret_cast<fvec*>(o + (int64_t)z * HW) = r;
+            reg3_fill<V>(o, HW, t.z0, t.z1, fill);
             continue;
         }
         float vy[V], vx[V];
-        bool bad[V];                                                  // a vector that overflowed fills its voxel, as in rbwarp_kernel
+        bool bad[V];
 #pragma unroll
         for (int j = 0; j < V; ++j) {
             vy[j] = __fadd_rn(dyf, __fsub_rn(__fmul_rn(cm1f, py), __fmul_rn(sf, px[j])));
             vx[j] = __fadd_rn(dxf, __fadd_rn(__fmul_rn(sf, py), __fmul_rn(cm1f, px[j])));
             bad[j] = !(fabsf(vy[j]) < INFINITY) || !(fabsf(vx[j]) < INFINITY);
         }
-        if (nearest) dz = rintf(dz);                                  // rshift_pixels rounds (vy, vx) itself
-        const float izf = floorf(dz);
-        const float fz = __fsub_rn(dz, izf);
-        const int iz = (int)fminf(fmaxf(izf, -(float)(D + 1)), (float)(D + 1));   // beyond: every plane is outside whatever the value
-        const float w0 = __fsub_rn(1.f, fz), w1 = fz;
-        const bool use0 = w0 != 0.f, use1 = w1 != 0.f;                // never both false: fz == 0 gives w0 == 1
-        float a[V] = {}, b[V] = {};                                   // the unused one of the two stays 0 and is not read
-        if (use0) rrigid3_plane<V>(vol, D, H, W, z0 + iz, y, x0, vy, vx, nearest, fill, a);
-        for (int z = z0; z < z1; ++z) {
-            if (use1) rrigid3_plane<V>(vol, D, H, W, z + iz + 1, y, x0, vy, vx, nearest, fill, b);
-            fvec r;
+        reg3_walk<V>(o, D, HW, t.z0, t.z1, reg3_zsplit_of(dz, nearest, D), bad, fill, [&](int zz, float(&acc)[V]) {
+            const float* plane = vol + (int64_t)zz * H * W;
 #pragma unroll
             for (int j = 0; j < V; ++j) {
-                const float t0 = __fmul_rn(w0, a[j]), t1 = __fmul_rn(w1, b[j]);
-                r[j] = bad[j] ? fill : (use0 ? (use1 ? __fadd_rn(t0, t1) : t0) : t1);
+                float a[1];
+                rshift_pixels<1, float>(plane, H, W, t.y, t.x0 + j, vy[j], vx[j], nearest, fill, a);
+                acc[j] = a[0];
             }
-            *reinterpret_cast<fvec*>(o + (int64_t)z * HW) = r;
-            if (use0 && use1) {                                       // plane z + iz + 1 is the next step's first plane
-#pragma unroll
-                for (int j = 0; j < V; ++j) a[j] = b[j];
-            } else if (use0 && z + 1 < z1) {
-                rrigid3_plane<V>(vol, D, H, W, z + 1 + iz, y, x0, vy, vx, nearest, fill, a);
-            }
-        }
+        });
     }
 }
 
@@ -225,25 +176,14 @@ extern "C" int cwfa_reg_rigid3d_f32(const float* in, int N, int D, int H, int W,
                                     float fill, float* out, void* stream) {
     const char* fn = "cwfa_reg_rigid3d_f32";
     CWFA_REQUIRE(in && params && out, CWFA_E_INVAL, "%s: null pointer", fn);
-    CWFA_REQUIRE(mode == 0 || mode == 1, CWFA_E_INVAL, "%s: mode is 0 (bilinear) or 1 (nearest), got %d", fn, mode);
+    REG3_REQUIRE_MODE(fn, mode);
     CWFA_REQUIRE(fabsf(cy) < INFINITY && fabsf(cx) < INFINITY, CWFA_E_INVAL, "%s: the centre (%g, %g) is not finite", fn, (double)cy, (double)cx);
-    CWFA_REQUIRE(N >= 0 && D >= 0 && H >= 0 && W >= 0, CWFA_E_SHAPE, "%s: negative size", fn);
-    // z + iz + 1 with |iz| <= D + 1 stays an int (and so along y and x, in rshift_pixels)
-    CWFA_REQUIRE(rr_sizes_ok(D, H, W), CWFA_E_SHAPE, "%s: a volume of %d x %d x %d is too large", fn, D, H, W);
+    REG3_REQUIRE_SIZES(fn, N, D, H, W);
     CWFA_REQUIRE(((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 3u) == 0 && (reinterpret_cast<uintptr_t>(params) & 7u) == 0,
                  CWFA_E_ALIGN, "%s: the volumes must be 4-byte aligned, params 8-byte aligned", fn);
-    CWFA_REQUIRE(out != in, CWFA_E_INVAL, "%s: out must not alias the stack", fn);
-    if (N == 0 || D == 0 || H == 0 || W == 0) return CWFA_OK;
-    const int64_t HW = (int64_t)H * W;
-    CWFA_REQUIRE(vol_stride >= (int64_t)D * HW, CWFA_E_INVAL, "%s: volume stride smaller than a volume", fn);
-    // 16-byte stores where W and out's base allow (every row of every volume then starts on 16 bytes); the loads take any alignment
-    const bool v4 = (W & 3) == 0 && cwfa_aligned16(out);
-    const int nseg = (D + RRIGID3_ZSEG - 1) / RRIGID3_ZSEG, zseg = (D + nseg - 1) / nseg;     // even segments: 96 planes are 6 x 16
-    const int64_t gx = (((v4 ? HW >> 2 : HW) + 255) / 256) * nseg;    // <= D H W / 256 + D + nseg < 2^31
-    const dim3 grid((unsigned)gx, reg_grid_y(gx, N, 65536));
-    hipStream_t st = (hipStream_t)stream;
-    if (v4) hipLaunchKernelGGL((rrigid3_kernel<4>), grid, dim3(256), 0, st, in, N, D, H, W, vol_stride, params, cy, cx, mode, fill, nseg, zseg, out);
-    else hipLaunchKernelGGL((rrigid3_kernel<1>), grid, dim3(256), 0, st, in, N, D, H, W, vol_stride, params, cy, cx, mode, fill, nseg, zseg, out);
-    CWFA_LAUNCH_CHECK("cwfa_reg_rigid3d_f32");
+    REG3_REQUIRE_STACK(fn, in, out, N, D, H, W, vol_stride);
+    REG3_LAUNCH(rrigid3_kernel, N, D, H, W, out, (hipStream_t)stream, in, N, D, H, W, vol_stride, params, cy, cx, mode, fill);
+    CWFA_LAUNCH_CHECK(fn);
     return CWFA_OK;
 }
+

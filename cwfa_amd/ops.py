@@ -2938,15 +2938,22 @@ def reg_fine_peak(C, ipeak, upsample, out=None):
     return shifts, peak
 
 
+def _shift_mode(mode, what, plain=False):
+    """The entry points' code of ``mode``.  ``plain``: the message names the modes as the functions of CWFA.py and XLFMDataset.py do."""
+    if mode not in _lib.SHIFT_MODE:
+        names = " or ".join(repr(m) for m in sorted(_lib.SHIFT_MODE)) if plain else f"one of {sorted(_lib.SHIFT_MODE)}"
+        raise ValueError(f"{what}: mode is {names}, got {mode!r}")
+    return _lib.SHIFT_MODE[mode]
+
+
 def _reg_shift(stack, shifts, mode, fill, out, rank, what):
     """``reg_shift`` (``rank`` 2) and ``reg_shift3d`` (3): the checks and the call; the kernels are two (the z walk is the volumes')."""
     L = _lib.lib()
     stack, dt, N, shape, fs = _reg_stack(stack, rank, what)
-    if mode not in _lib.SHIFT_MODE:
-        raise ValueError(f"{what}: mode is one of {sorted(_lib.SHIFT_MODE)}, got {mode!r}")
+    mode = _shift_mode(mode, what)
     shifts = _vec(shifts, rank * N, "shifts", what)
     out = _reg_out(out, (N, *shape), stack.dtype, stack.dtype if rank == 2 else "float32", what, stack)
-    args = (fs, _p(shifts), _lib.SHIFT_MODE[mode], float(fill), _p(out), _stream())
+    args = (fs, _p(shifts), mode, float(fill), _p(out), _stream())
     check(L.cwfa_reg_shift(_p(stack), dt, N, *shape, *args) if rank == 2 else L.cwfa_reg_shift3d_f32(_p(stack), N, *shape, *args), what)
     return out
 
@@ -3058,8 +3065,7 @@ def reg_shift_labeled(stack, table, labels, mode="bilinear", fill=0.0, out=None)
     contiguous tensor of the stack's shape and dtype that shares no memory with it."""
     what = "reg_shift_labeled"
     stack, dt, N, (H, W), fs = _reg_stack(stack, 2, what)
-    if mode not in _lib.SHIFT_MODE:
-        raise ValueError(f"{what}: mode is one of {sorted(_lib.SHIFT_MODE)}, got {mode!r}")
+    mode = _shift_mode(mode, what)
     if not torch.is_tensor(table) or table.dim() != 3 or int(table.shape[0]) != N or table.shape[2] != 2 or not 2 <= table.shape[1] <= _lib.REG_MAX_VIEWS + 1:
         raise ValueError(f"{what}: table is a float32 [{N}, L + 1, 2] tensor, 1 <= L <= {_lib.REG_MAX_VIEWS}")
     Lv = int(table.shape[1]) - 1
@@ -3070,7 +3076,7 @@ def reg_shift_labeled(stack, table, labels, mode="bilinear", fill=0.0, out=None)
     out = _reg_out(out, (N, H, W), stack.dtype, stack.dtype, what, stack)
     if N == 0:
         return out
-    check(_lib.lib().cwfa_reg_shift_labeled(_p(stack), dt, N, H, W, fs, _p(table), _p(labels), Lv, _lib.SHIFT_MODE[mode], float(fill), _p(out),
+    check(_lib.lib().cwfa_reg_shift_labeled(_p(stack), dt, N, H, W, fs, _p(table), _p(labels), Lv, mode, float(fill), _p(out),
                                             _stream()), what)
     return out
 
@@ -3206,8 +3212,7 @@ def reg_warp3d(stack, field, grid, tables, mode="bilinear", fill=0.0, out=None):
     ``reg_shift3d`` under its vector, bit for bit, so a field whose nodes are equal gives ``reg_shift3d``.  ``out``: a contiguous
     float32 tensor of the stack's shape that shares no memory with it."""
     what = "reg_warp3d"
-    if mode not in _lib.SHIFT_MODE:
-        raise ValueError(f"{what}: mode is one of {sorted(_lib.SHIFT_MODE)}, got {mode!r}")
+    mode = _shift_mode(mode, what)
     g = _block_grid3(grid, what)
     if not isinstance(tables, (tuple, list)) or len(tables) != 6:
         raise ValueError(f"{what}: tables is (idxz, tz, idxy, ty, idxx, tx)")
@@ -3222,7 +3227,7 @@ def reg_warp3d(stack, field, grid, tables, mode="bilinear", fill=0.0, out=None):
     out = _reg_out(out, (N, *shape), torch.float32, "float32", what, stack)
     if N == 0:
         return out
-    check(_lib.lib().cwfa_reg_warp3d_f32(_p(stack), N, *shape, fs, _p(field), *g, *(_p(t) for t in tabs), _lib.SHIFT_MODE[mode], float(fill), _p(out),
+    check(_lib.lib().cwfa_reg_warp3d_f32(_p(stack), N, *shape, fs, _p(field), *g, *(_p(t) for t in tabs), mode, float(fill), _p(out),
                                          _stream()), what)
     return out
 
@@ -3278,8 +3283,7 @@ def reg_rigid3d(volumes, params, center=None, mode="bilinear", fill=0.0, out=Non
     plane copies bits.  A non-finite parameter fills the volume.  ``out``: a contiguous float32 tensor of the stack's shape that
     shares no memory with it."""
     what = "reg_rigid3d"
-    if mode not in _lib.SHIFT_MODE:
-        raise ValueError(f"{what}: mode is one of {sorted(_lib.SHIFT_MODE)}, got {mode!r}")
+    mode = _shift_mode(mode, what)
     if not torch.is_tensor(volumes) or volumes.dim() != 4:
         raise ValueError(f"{what}: a stack {_REG_AXES[3][0]} is expected")
     cy, cx = _rigid_center(center, tuple(int(s) for s in volumes.shape), what)
@@ -3290,7 +3294,7 @@ def reg_rigid3d(volumes, params, center=None, mode="bilinear", fill=0.0, out=Non
     out = _reg_out(out, (N, *shape), torch.float32, "float32", what, stack)
     if N == 0:
         return out
-    check(_lib.lib().cwfa_reg_rigid3d_f32(_p(stack), N, *shape, fs, _p(params), cy, cx, _lib.SHIFT_MODE[mode], float(fill), _p(out), _stream()), what)
+    check(_lib.lib().cwfa_reg_rigid3d_f32(_p(stack), N, *shape, fs, _p(params), cy, cx, mode, float(fill), _p(out), _stream()), what)
     return out
 
 
