@@ -22,7 +22,7 @@ __all__ = ["sample_z_truncated", "check_empty_depths", "evaluate_INN_forward", "
            "forward_nll_pass", "mean_volume_cache", "save_mean_volume_cache", "load_mean_volume_cache",
            "denormalise_prediction", "denormalise_ground_truth", "compute_INN_step_performance", "evaluate_step", "roi_boxes",
            "corr_coeff_3D", "truncated_normal_variance", "posterior_moments", "posterior_samples", "posterior_roi_means",
-           "ActivityMap", "find_neurons", "read_neural_coordinates_from_file", "write_neural_coordinates_to_file",
+           "ActivityMap", "RegressionMap", "RegressionMaps", "calcium_regressors", "find_neurons", "read_neural_coordinates_from_file", "write_neural_coordinates_to_file",
            "NeuronFootprints", "Footprints", "extract_traces", "demix_plan", "demix_traces", "trace_baseline", "delta_f_over_f", "trace_noise", "infer_spikes",
            "estimate_volume_shifts", "shift_volumes", "register_volumes", "VolumeRegistration", "VolumeRegistrar", "valid_box",
            "block_grid", "BlockGrid", "estimate_block_shifts", "warp_volumes", "register_volumes_piecewise", "PiecewiseRegistration",
@@ -884,11 +884,104 @@ class ActivityMap:
         return score, mean, std, self.state[3], self.state[4]
 
 
-def find_neurons(score, r12=5, r3=3, n_max=None, thr=None, rel_thr=0.1, start_plane_offset=-25 // 2, margin=None, dist=None, kind="std"):
+RegressionMaps = namedtuple("RegressionMaps", ["corr", "beta", "t", "r2"])
+
+
+class RegressionMap:
+    """The per-voxel linear regression of a series of [D,H,W] volumes against ``n_regressors`` known time courses (1 .. 16, beside an
+    implicit intercept), accumulated as the volumes are produced: which voxels follow the stimulus, the
+    behaviour or a seed neuron.  A regressor is a stimulus or behaviour trace through the calcium kernel (``calcium_regressors``)
+    or a neuron's own trace.  Beside the state of an ``ActivityMap`` -- kept by the same operations, so ``activity`` returns that
+    object's maps from the same pass -- a voxel keeps one float64 sum per regressor: 28 + 8 K bytes per voxel, 2.3 GB at
+    96 x 512 x 512 for K = 8.  Any chunking of the series gives the same bits."""
+
+    def __init__(self, shape, device, n_regressors):
+        self.shape = tuple(int(s) for s in shape)
+        if len(self.shape) != 3 or min(self.shape) < 0:
+            raise ValueError(f"RegressionMap: shape is (D, H, W), got {shape!r}")
+        self.reg = ops.regression_state(self.shape, device, n_regressors)
+        self.n_regressors = int(n_regressors)
+        self.state = self.reg.plain
+        self.count = 0
+
+    def update(self, volumes, rows):
+        """Add ``volumes``: [T',D,H,W] or one [D,H,W] volume, float32 on the device, with their regressor values ``rows``: float64
+        [T',K] on the device ([K] for one volume)."""
+        K = self.n_regressors
+        if not torch.is_tensor(volumes) or not torch.is_tensor(rows):
+            raise TypeError("RegressionMap.update: volumes and rows are torch tensors")
+        if volumes.dim() == 3 and rows.dim() == 1:
+            volumes, rows = volumes.unsqueeze(0), rows.unsqueeze(0)
+        if volumes.dim() != 4 or tuple(volumes.shape[1:]) != self.shape:
+            raise ValueError(f"RegressionMap.update: volumes of shape {self.shape} are expected, got {tuple(volumes.shape)}")
+        if rows.dim() != 2 or rows.shape[1] != K or rows.dtype != torch.float64:
+            raise ValueError(f"RegressionMap.update: rows is a float64 tensor [T', {K}], got {tuple(rows.shape)} {rows.dtype}")
+        if rows.shape[0] != volumes.shape[0]:
+            raise ValueError(f"RegressionMap.update: {rows.shape[0]} rows for {volumes.shape[0]} volumes")
+        ops._dev(volumes, "volumes")
+        if volumes.shape[0]:
+            first = self.count == 0
+            ops.activity_update_regress(volumes, rows, self.reg, first=first)
+            ops.regress_rows(rows, self.reg, first=first)
+            self.count += volumes.shape[0]
+        return self
+
+    def finish(self, want=("corr", "beta", "t", "r2"), rcond=1e-10):
+        """``RegressionMaps(corr, beta, t, r2)``, float32: per regressor [K,D,H,W] the correlation of the series with it, its
+        coefficient in the joint fit and that coefficient's t-statistic (N - K - 1 degrees of freedom, white residuals), and
+        [D,H,W] the fit's R^2; ``None`` for what ``want`` does not name.  A voxel whose series is constant or holds NaN or inf is 0
+        in every map.  Raises ``ValueError`` when a regressor is constant, a combination of the others (a Cholesky pivot not above
+        ``rcond`` times its diagonal entry) or not finite.  The state is kept: more volumes may follow."""
+        if self.count < 1:
+            raise ValueError("RegressionMap.finish: no volume has been added")
+        ops.regress_want(want, self.count, self.n_regressors, "RegressionMap.finish")
+        design = ops.regress_design(self.reg, self.count, rcond)
+        code, k = (int(v) for v in design.status.cpu())
+        if code:
+            raise ValueError(f"RegressionMap.finish: collinear or constant regressor {k} "
+                             f"({ops._lib.REGRESS_STATUS.get(code, code)}; rcond = {rcond:g})")
+        return RegressionMaps(*ops.regress_finish(self.reg, design, self.count, want))
+
+    def activity(self, kind="std"):
+        """What ``ActivityMap.finish(kind)`` returns from the same state: (score, mean, std, vmax, vmin)."""
+        if kind == "corr":
+            raise ValueError("RegressionMap.activity: the local correlation image is an ActivityMap(neighbours=...)'s")
+        if self.count < 1:
+            raise ValueError("RegressionMap.activity: no volume has been added")
+        score, mean, std = ops.activity_finish(self.state, self.count, kind)
+        return score, mean, std, self.state[3], self.state[4]
+
+
+@amp_region
+def calcium_regressors(events, gamma, device="cuda"):
+    """The regressors of a ``RegressionMap`` from event or stimulus time courses: every column of ``events`` ([T,K], or [T] for one)
+    through the AR(1) calcium kernel ``infer_spikes`` assumes, c[t] = gamma c[t-1] + e[t] in float64 from c[-1] = 0.  Returns the
+    float64 [T,K] tensor on ``device`` whose row slices go to ``RegressionMap.update``.  A host helper: T K values need no kernel."""
+    import numpy as np
+    e = np.asarray(events.detach().cpu().numpy() if torch.is_tensor(events) else events, dtype=np.float64)
+    if e.ndim == 1:
+        e = e[:, None]
+    if e.ndim != 2:
+        raise ValueError(f"calcium_regressors: events is [T] or [T,K], got {e.shape}")
+    g = float(gamma)
+    if not 0.0 <= g < 1.0:
+        raise ValueError(f"calcium_regressors: gamma is in [0, 1), got {gamma!r}")
+    c = np.empty_like(e)
+    prev = np.zeros(e.shape[1])
+    for t in range(e.shape[0]):
+        prev = g * prev + e[t]
+        c[t] = prev
+    return torch.from_numpy(c).to(device)
+
+
+def find_neurons(score, r12=5, r3=3, n_max=None, thr=None, rel_thr=0.1, start_plane_offset=-25 // 2, margin=None, dist=None, kind="std",
+                 *, regressor=None):
     """Neuron positions as the 3-D local maxima of an activity map: ``(coords, scores)``.
 
     ``score``: a float32 device map [D,H,W], or an ``ActivityMap``, which is finished with ``kind`` (used in that case only; "corr"
-    for the local correlation image of an ``ActivityMap(neighbours=...)``).  A voxel is kept when it is at
+    for the local correlation image of an ``ActivityMap(neighbours=...)``), or a ``RegressionMap``: ``kind`` = "t", "corr" or "beta"
+    then takes that map of regressor ``regressor`` (the neurons tuned to it; an absolute ``thr`` is the natural argument for "t"
+    and "corr"), any other ``kind`` the activity map of the same state.  A voxel is kept when it is at
     least ``thr`` (default ``rel_thr`` times the map's maximum), at least ``margin`` (default ``(r3, r12, r12)``) from every face and
     the maximum of the box of half-widths ``dist`` (default ``(2 r3 - 1, 2 r12 - 1, 2 r12 - 1)``) around it, ties going to the
     lowest linear index (``ops.local_maxima``); the ``n_max`` highest are returned, by descending score.  With the default ``dist`` two
@@ -906,6 +999,15 @@ def find_neurons(score, r12=5, r3=3, n_max=None, thr=None, rel_thr=0.1, start_pl
     dist, margin, n_max, _ = ops.local_maxima_args(dist, margin, n_max, 0, "find_neurons")
     if thr is None and not 0.0 <= float(rel_thr) <= 1.0:
         raise ValueError(f"find_neurons: rel_thr = {rel_thr} is not in [0, 1]")
+    if isinstance(score, RegressionMap):
+        if kind in ("t", "corr", "beta"):
+            if isinstance(regressor, bool) or not isinstance(regressor, int) or not 0 <= regressor < score.n_regressors:
+                raise ValueError(f"find_neurons: regressor is 0 .. {score.n_regressors - 1} for kind {kind!r}, got {regressor!r}")
+            score = getattr(score.finish(want=(kind,)), kind)[regressor]
+        else:
+            score = score.activity(kind)[0]
+    elif regressor is not None:
+        raise ValueError("find_neurons: regressor is for a RegressionMap")
     if isinstance(score, ActivityMap):
         score = score.finish(kind)[0]
     ops._dev(score, "score")

@@ -94,6 +94,9 @@ REG_MAX_VIEWS = 254               # a label is a byte; label L is the rest of th
 REG_MAX_BLOCKS = 4096             # REG_MAX_BLOCKS of register_internal.h: the blocks of a grid
 FOOTPRINT_SELECT_MAX = 1 << 15   # CWFA_FOOTPRINT_SELECT_MAX
 DEMIX_PAIR_BYTES = 48             # CWFA_DEMIX_PAIR_BYTES
+REGRESS_MAX_K = 16                # CWFA_REGRESS_MAX_K
+REGRESS_WANT = {"corr": 1, "beta": 2, "t": 4, "r2": 8}                          # CWFA_REGRESS_CORR .. CWFA_REGRESS_R2
+REGRESS_STATUS = {1: "collinear or constant", 2: "non-finite", 3: "row count"}  # CWFA_REGRESS_COLLINEAR ..
 
 # name -> (restype, argtypes); must list EVERY function declared in include/cwfa_hip.h (tests/test_boundary.py checks)
 i, i64, f, d, p = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_void_p
@@ -257,6 +260,10 @@ SIGNATURES = {
     "cwfa_demix_plan_destroy": (i, [p]),
     "cwfa_demix_coeffs_f64": (i, [p, p, i64, p, p, i, p, p]),
     "cwfa_demix_solve_f64": (i, [p, i64, p, i, i, p, i, d, i, p, p]),
+    "cwfa_activity_update_regress_f32": (i, [p, p, p, p, p, p, p, p, i, i, i64, i64, i, p]),
+    "cwfa_regress_rows_f64": (i, [p, i, i, p, p, p, i, p]),
+    "cwfa_regress_design_f64": (i, [p, p, p, i64, i, d, p, p, p, p]),
+    "cwfa_regress_finish_f32": (i, [p, p, p, p, p, p, i64, i, i64, i, p, p, p, p, p]),
 }
 del i, i64, f, d, p
 

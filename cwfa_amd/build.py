@@ -9,15 +9,16 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libcwfa_hip.so")
-SOURCES = ["elementwise.hip", "conv2d.hip", "conv_wino.hip", "conv_wino2d.hip", "conv_split_layer.hip", "conv_split_out.hip", "conv_split3x3.hip", "conv3d.hip", "conv3d_split.hip", "lrnn_ops.hip", "conv_bwd.hip", "eval_ops.hip", "prep_ops.hip", "optim_ops.hip", "loss_ops.hip", "deconv_ops.hip", "neuron_ops.hip", "noise_ops.hip", "sparse_ops.hip", "register_ops.hip", "register_views_ops.hip", "register3d_ops.hip", "register_blocks_ops.hip", "register_rigid_ops.hip", "footprint_ops.hip", "trace_ops.hip", "demix_ops.hip"]
+SOURCES = ["elementwise.hip", "conv2d.hip", "conv_wino.hip", "conv_wino2d.hip", "conv_split_layer.hip", "conv_split_out.hip", "conv_split3x3.hip", "conv3d.hip", "conv3d_split.hip", "lrnn_ops.hip", "conv_bwd.hip", "eval_ops.hip", "prep_ops.hip", "optim_ops.hip", "loss_ops.hip", "deconv_ops.hip", "neuron_ops.hip", "noise_ops.hip", "sparse_ops.hip", "register_ops.hip", "register_views_ops.hip", "register3d_ops.hip", "register_blocks_ops.hip", "register_rigid_ops.hip", "footprint_ops.hip", "trace_ops.hip", "demix_ops.hip", "regress_ops.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-I", INCLUDE, "-I", CSRC,
          "-Wall", "-Wno-unused-function"]
 
 
 # per-file flags.  conv3d_split.hip: paired into v_pk_add_f32 the residual subtractions of its three-way split are slow beside MFMAs
-# demix_ops.hip: its float64 operations are rounded one by one (what FLAGS sets for every file, restated where the bits rest on it)
-EXTRA = {"conv3d_split.hip": ["-fno-slp-vectorize"], "demix_ops.hip": ["-ffp-contract=off"]}
+# demix_ops.hip, regress_ops.hip: their float64 operations are rounded one by one (what FLAGS sets for every file, restated where the
+# bits rest on it)
+EXTRA = {"conv3d_split.hip": ["-fno-slp-vectorize"], "demix_ops.hip": ["-ffp-contract=off"], "regress_ops.hip": ["-ffp-contract=off"]}
 
 
 def _newer(src, dst):

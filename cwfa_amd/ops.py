@@ -2,6 +2,7 @@
 HIP stream; every computation happens in libcwfa_hip.so.  Inputs must be fp32 tensors on a HIP device -- a CPU tensor
 raises (there is no CPU path in the product; the CPU restatement lives in oracle/ and is test infrastructure)."""
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
@@ -2486,6 +2487,137 @@ def correlation_finish(state, cc, count, neighbours):
     check(L.cwfa_activity_corr_finish_f32(_p(state[1]), _p(state[2]), _p(cc), int(count), *state[0].shape, int(neighbours), _p(score),
                                           _stream()), "correlation_finish")
     return score
+
+
+# ------------------------------------------------------------------------------------------------ regression maps
+RegressionState = namedtuple("RegressionState", ["plain", "p", "sr", "srr", "rows"])
+RegressionDesign = namedtuple("RegressionDesign", ["gdiag", "ginv", "status"])
+
+
+def regression_state(shape, device, k):
+    """The state of a streaming regression of [D,H,W] volumes of ``shape`` on ``k`` regressors:
+    ``plain`` = ``activity_state`` (28 bytes per voxel), ``p`` float64 [k,D,H,W] (8 k bytes per voxel), and the regressors' own sums
+    ``sr`` float64 [k], ``srr`` float64 [k,k] and row count ``rows`` int64 [1], all uninitialised -- the first
+    ``activity_update_regress`` / ``regress_rows`` (``first=True``) write all of it."""
+    shape = tuple(int(s) for s in shape)
+    if len(shape) != 3 or min(shape) < 0:
+        raise ValueError(f"regression_state: shape is (D, H, W), got {shape!r}")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _lib.REGRESS_MAX_K:
+        raise ValueError(f"regression_state: 1 .. {_lib.REGRESS_MAX_K} regressors, got {k!r}")
+    f = lambda *s: torch.empty(s, dtype=torch.float64, device=device)
+    return RegressionState(activity_state(shape, device), f(k, *shape), f(k), f(k, k), torch.empty(1, dtype=torch.int64, device=device))
+
+
+def _regress(st, what):
+    if not isinstance(st, RegressionState):
+        raise ValueError(f"{what}: the state is an ops.RegressionState (ops.regression_state)")
+    m = _activity(st.plain, what)
+    if st.plain[0].dim() != 3:
+        raise ValueError(f"{what}: the state of [D,H,W] volumes is expected, got {tuple(st.plain[0].shape)}")
+    k = st.p.shape[0] if torch.is_tensor(st.p) and st.p.dim() == 4 else 0
+    for t, dt, shape in ((st.p, torch.float64, (k, *st.plain[0].shape)), (st.sr, torch.float64, (k,)), (st.srr, torch.float64, (k, k)),
+                         (st.rows, torch.int64, (1,))):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError(f"{what}: p [K,D,H,W], sr [K], srr [K,K] (float64) and rows [1] (int64) are contiguous tensors on the HIP "
+                             f"device (ops.regression_state)")
+    if not 1 <= k <= _lib.REGRESS_MAX_K:
+        raise ValueError(f"{what}: 1 .. {_lib.REGRESS_MAX_K} regressors, got {k}")
+    return m, k
+
+
+def _regress_rows(rows, T, k, what):
+    if not torch.is_tensor(rows) or rows.dtype != torch.float64 or rows.dim() != 2 or rows.shape[1] != k:
+        raise ValueError(f"{what}: rows is a float64 tensor [T', {k}], got "
+                         f"{(tuple(rows.shape), rows.dtype) if torch.is_tensor(rows) else type(rows)}")
+    if T is not None and rows.shape[0] != T:
+        raise ValueError(f"{what}: {rows.shape[0]} rows for {T} volumes")
+    if not rows.is_cuda:
+        raise RuntimeError(f"{what}: cwfa_amd runs on MI355X only -- got {rows.device} rows (no CPU fallback exists)")
+    return rows.contiguous()
+
+
+def activity_update_regress(x, rows, st, first):
+    """``activity_update`` of the chunk ``x`` [T',D,H,W] -- ``st.plain`` comes out bit for bit as that writes it -- which in the same
+    read of the chunk adds d(t) r[t,k] (d = x - x0 in float64) to ``st.p[k]`` per voxel, in time order; ``rows``: the chunk's float64
+    [T',K] on the device.  Any chunking gives the same bits.  The regressors' own sums are ``regress_rows``'."""
+    L = _lib.lib()
+    _dev(x, "x")
+    m, k = _regress(st, "activity_update_regress")
+    if x.dim() != 4 or tuple(x.shape[1:]) != tuple(st.plain[0].shape):
+        raise ValueError(f"activity_update_regress: a chunk [T', {', '.join(str(s) for s in st.plain[0].shape)}] is expected, "
+                         f"got {tuple(x.shape)}")
+    T = x.shape[0]
+    rows = _regress_rows(rows, T, k, "activity_update_regress")
+    if first and T < 1:
+        raise ValueError("activity_update_regress: the first chunk needs at least one volume")
+    if T and m and (not x[0].is_contiguous() or (T > 1 and x.stride(0) < m)):
+        x = x.contiguous()
+    ss = x.stride(0) if T > 1 else m
+    check(L.cwfa_activity_update_regress_f32(_p(x), _p(rows), *(_p(t) for t in st.plain), _p(st.p), T, k, m, ss, int(bool(first)),
+                                             _stream()), "activity_update_regress")
+    return st
+
+
+def regress_rows(rows, st, first):
+    """Add the float64 ``rows`` [T',K] to ``st.sr`` (sums), ``st.srr`` (sums of products) and ``st.rows`` (their number), in time
+    order; ``first`` starts them from 0."""
+    L = _lib.lib()
+    _, k = _regress(st, "regress_rows")
+    rows = _regress_rows(rows, None, k, "regress_rows")
+    check(L.cwfa_regress_rows_f64(_p(rows), rows.shape[0], k, _p(st.sr), _p(st.srr), _p(st.rows), int(bool(first)), _stream()),
+          "regress_rows")
+    return st
+
+
+def regress_design(st, count, rcond=1e-10):
+    """``RegressionDesign(gdiag [K], ginv [K,K], status int32 [2])`` on the device from the regressors' sums after ``count`` samples:
+    the diagonal of G = Srr - Sr Sr' / N and G's inverse by a Cholesky factorisation in one thread.  ``status[0]`` != 0 (a key of
+    ``_lib.REGRESS_STATUS``; ``status[1]``: the regressor) when a pivot is not above ``rcond`` times its diagonal entry, an entry is
+    not finite or ``st.rows`` != ``count``.  Nothing is read back: the caller reads the status."""
+    L = _lib.lib()
+    _, k = _regress(st, "regress_design")
+    if int(count) < 1:
+        raise ValueError("regress_design: needs at least one sample")
+    if not 0.0 <= float(rcond) < 1.0:
+        raise ValueError(f"regress_design: rcond is in [0, 1), got {rcond!r}")
+    dev = st.sr.device
+    des = RegressionDesign(torch.empty(k, dtype=torch.float64, device=dev), torch.empty(k, k, dtype=torch.float64, device=dev),
+                           torch.empty(2, dtype=torch.int32, device=dev))
+    check(L.cwfa_regress_design_f64(_p(st.sr), _p(st.srr), _p(st.rows), int(count), k, float(rcond), _p(des.gdiag), _p(des.ginv),
+                                    _p(des.status), _stream()), "regress_design")
+    return des
+
+
+def regress_want(want, count, k, what):
+    """The mask of ``want`` (names out of "corr", "beta", "t", "r2"), refusing an unknown name, an empty set and ``t`` without a
+    degree of freedom."""
+    names = (want,) if isinstance(want, str) else tuple(want)
+    if not names or any(n not in _lib.REGRESS_WANT for n in names):
+        raise ValueError(f"{what}: want is a non-empty subset of {tuple(_lib.REGRESS_WANT)}, got {want!r}")
+    if "t" in names and int(count) - k - 1 < 1:
+        raise ValueError(f"{what}: t needs N - K - 1 >= 1 degrees of freedom, got {int(count)} samples for {k} regressors")
+    return sum(_lib.REGRESS_WANT[n] for n in set(names))
+
+
+def regress_finish(st, design, count, want=("corr", "beta", "t", "r2")):
+    """(corr [K,D,H,W], beta [K,D,H,W], t [K,D,H,W], r2 [D,H,W]) float32 from the state after ``count`` samples and ``design``
+    (``regress_design``), ``None`` for what ``want`` does not name; the formulae of DESIGN.md section 34.1 in float64.  A voxel whose
+    series is constant or holds NaN or inf is 0 in every map.  The state is only read."""
+    L = _lib.lib()
+    m, k = _regress(st, "regress_finish")
+    if int(count) < 1:
+        raise ValueError("regress_finish: needs at least one sample")
+    mask = regress_want(want, count, k, "regress_finish")
+    if (not isinstance(design, RegressionDesign) or any(not torch.is_tensor(t) or not t.is_cuda or not t.is_contiguous() for t in design)
+            or tuple(design.gdiag.shape) != (k,) or tuple(design.ginv.shape) != (k, k) or design.gdiag.dtype != torch.float64
+            or design.ginv.dtype != torch.float64):
+        raise ValueError(f"regress_finish: design is the ops.RegressionDesign of {k} regressors (ops.regress_design)")
+    shape = tuple(st.plain[0].shape)
+    out = [torch.empty((k, *shape) if n != "r2" else shape, dtype=torch.float32, device=st.p.device) if mask & bit else None
+           for n, bit in _lib.REGRESS_WANT.items()]
+    check(L.cwfa_regress_finish_f32(_p(st.plain[1]), _p(st.plain[2]), _p(st.p), _p(st.sr), _p(design.gdiag), _p(design.ginv), int(count),
+                                    k, m, mask, *(_p(t) for t in out), _stream()), "regress_finish")
+    return tuple(out)
 
 
 def _triple(v, name, what):

@@ -924,6 +924,46 @@ int cwfa_activity_update_corr_f32(const float* x, float* x0, double* s1, double*
 int cwfa_activity_corr_finish_f32(const double* s1, const double* s2, const double* cc, int64_t N, int D, int H, int W, int neighbours,
                                   float* score, void* stream);
 
+/* ---- stimulus and seed regression maps: the per-voxel linear regression of the streamed series against K known
+ * time courses r[t][0 .. K) (float64 rows, 1 <= K <= CWFA_REGRESS_MAX_K; the intercept is implicit), from sums kept beside the state
+ * of activity_update.  Every float64 operation is rounded separately, in the order written here.
+ *
+ *   activity_update_regress: everything activity_update does (x0, s1, s2, vmax, vmin come out bit for bit what that entry point
+ *                    writes), and in the same read of the chunk  p[k][i] += d_i(t) * r[t][k],  d = (double)x - (double)x0,  in time
+ *                    order from 0.0 over the samples after the first (d of the first is exactly 0); p is float64 [K, m], rows the
+ *                    chunk's [T, K] on the device.  K <= 8: one launch; beyond, a second launch over x adds the regressors from the
+ *                    ninth on and writes p only.  16-byte accesses where m % 4 == 0, x_ss % 4 == 0 and every pointer allow, element
+ *                    by element otherwise.  T == 0 (first == 0) or m == 0: no launch.
+ *   regress_rows:    Sr[k] += r[t][k], Srr[k][l] += r[t][k] * r[t][l] (float64 [K], [K, K]) and *count += T over the chunk's rows in
+ *                    time order -- over all samples, the first included; first != 0 starts them from 0.  One thread per (k, l).
+ *   regress_design:  from the sums of N samples, by one thread:  G[k][l] = Srr[k][l] - Sr[k] * Sr[l] / N;  gdiag[k] = G[k][k];
+ *                    G = L L' (Cholesky, row by row: pivot s = G[j][j] - L[j][0]^2 - .. - L[j][j-1]^2 subtracted in that order,
+ *                    L[j][j] = sqrt(s), L[i][j] = (G[i][j] - L[i][0] L[j][0] - ..) / L[j][j]);  Linv column by column
+ *                    (Linv[c][c] = 1 / L[c][c], Linv[i][c] = (0 - L[i][c] Linv[c][c] - .. - L[i][i-1] Linv[i-1][c]) / L[i][i]);
+ *                    ginv[k][l] = Linv[q][k] * Linv[q][l] added from 0.0 over q = max(k, l) .. K - 1.
+ *                    status[0] (int32 pair on the device, written always): 0, or REGRESS_COLLINEAR when a pivot is not above
+ *                    rcond * G[j][j] or G[j][j] is not above rcond * Srr[j][j] (a constant regressor), REGRESS_NONFINITE when
+ *                    an entry of Sr / Srr is NaN or inf, REGRESS_COUNT when *count != N; status[1]: the regressor.  On a non-zero
+ *                    status gdiag and ginv are 0.
+ *   regress_finish:  per voxel, with a = s1, vx = s2 - a * a / N, c[k] = p[k] - a * Sr[k] / N:
+ *                        corr[k] = c[k] / sqrt(vx * gdiag[k]);   beta[k] = ginv[k][0] * c[0] + .. added from 0.0 in this order;
+ *                        rss = max(vx - (c[0] * beta[0] + ..), 0);   t[k] = beta[k] / sqrt(rss / (N - K - 1) * ginv[k][k]), 0 where
+ *                        that root is 0;   r2 = 1 - rss / vx
+ *                    rounded to fp32 at the store; every map is 0 where vx is not > 0 or s1, s2 or a p[k] is not finite.  `want`
+ *                    is a mask of REGRESS_CORR .. REGRESS_R2: only those are computed and stored, the other pointers may be null.
+ *                    t needs N - K - 1 >= 1 (CWFA_E_SHAPE).  The state is only read.  m == 0: no launch. */
+#define CWFA_REGRESS_MAX_K 16
+enum { CWFA_REGRESS_CORR = 1, CWFA_REGRESS_BETA = 2, CWFA_REGRESS_T = 4, CWFA_REGRESS_R2 = 8 };
+enum { CWFA_REGRESS_COLLINEAR = 1, CWFA_REGRESS_NONFINITE = 2, CWFA_REGRESS_COUNT = 3 };
+int cwfa_activity_update_regress_f32(const float* x, const double* rows, float* x0, double* s1, double* s2, float* vmax, float* vmin,
+                                     double* p, int T, int K, int64_t m, int64_t x_ss, int first, void* stream);
+int cwfa_regress_rows_f64(const double* rows, int T, int K, double* Sr, double* Srr, int64_t* count, int first, void* stream);
+int cwfa_regress_design_f64(const double* Sr, const double* Srr, const int64_t* count, int64_t N, int K, double rcond, double* gdiag,
+                            double* ginv, int* status, void* stream);
+int cwfa_regress_finish_f32(const double* s1, const double* s2, const double* p, const double* Sr, const double* gdiag,
+                            const double* ginv, int64_t N, int K, int64_t m, int want, float* corr, float* beta, float* t, float* r2,
+                            void* stream);
+
 /* ---- shot noise: a Poisson draw per element, in one launch, nothing read back.
  *   out[s][e] = fl32(fl32(k) * post[s]),   k ~ Poisson(rate),   rate = fl32(lam[s * lam_ss + e] * pre[s])
  * for s < N, e < n.  pre / post: nullable DEVICE float [N], NULL means 1.  lam_ss = 0: all N samples draw from one rate plane;
